@@ -306,6 +306,23 @@ def spawn_ranks(n):
     raise SystemExit(r.returncode)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, poses, rank=None):
+    """--dump-outputs: the poses of the last timed step, [B, K, 4, 4] float32.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the instances is
+    written instead, with their batch indices next to it (poses_instances.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank is None else f"_rank{rank}"
+    per_instance = poses[0].nbytes if len(poses) else 1
+    if poses.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(poses), DUMP_LIMIT_BYTES // 2 // per_instance, replace=False))
+        np.save(os.path.join(out_dir, f"poses_instances{suffix}.npy"), keep.astype(np.float64))
+        poses = poses[keep]
+    np.save(os.path.join(out_dir, f"poses{suffix}.npy"), np.ascontiguousarray(poses, dtype=np.float32))
+    note(f"wrote {poses.shape} poses to {out_dir}")
+
+
 _T0 = time.perf_counter()
 
 
@@ -337,7 +354,11 @@ def main():
                                                                     "5 warm-up steps (7 ms) do not ramp them -- the same command measured 5 %% slower at --steps 20 than at --steps 250 (0 disables)")
     ap.add_argument("--no-incl-pack", action="store_true", help="skip the second timed region (value_incl_pack): profiling passes, whose per-kernel averages must be those of the first region")
     ap.add_argument("--baseline-n1", type=float, default=None, help="the N = 1 value of the same command: rank 0 then also reports efficiency = value / (N x this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned (the solved poses, float32) "
+                                                                         "as DIR/poses.npy (DIR/poses_rank<r>.npy per rank when N > 1), so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # --gpus N without a launcher: become the launcher (one rank per GPU under torch.distributed.run, RCCL via backend nccl)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -435,6 +456,8 @@ def main():
     note(f"timed region done: {seconds:.3f} s")
     st = ws.collect_stats()
     out_poses = poses_d.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out_poses, rank if world > 1 else None)
     # (non-finite poses: caught below through the gathered pose checksums, so that every rank leaves together instead of one rank hanging the gather)
     # What a tracker pays: its correspondences are NEW on every call, so nothing about them can be prepared outside the call.  Same steps again,
     # handing the solve the EntryJ array (already in HBM) as it is -- the library's default for fresh matches reads the 32-byte wire format in

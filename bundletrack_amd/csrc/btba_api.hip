@@ -349,9 +349,9 @@ int btba_workspace_set_option(btba_workspace *ws, int option, int64_t value)
     case BTBA_OPT_COUNT_LIVE:
         ws->count_live = value != 0;
         if (ws->count_live) {
-            int rc = ws->live_blocks.ensure(8 * sizeof(unsigned long long));       // [0] walked blocks; [1 .. 8): the lane census of developer builds (-DBTBA_CENSUS)
+            int rc = ws->live_blocks.ensure(sizeof(unsigned long long));       // the walked blocks
             if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(ws->live_blocks.p, 0, 8 * sizeof(unsigned long long), ws->stream));
+            HIP_TRY(hipMemsetAsync(ws->live_blocks.p, 0, sizeof(unsigned long long), ws->stream));
         }
         break;
     case 1000:      // not part of the ABI.  64 = the watchdog's self-test (solve items never publish: the launch runs into the watchdog, the solve is REPORTED failed,
@@ -392,21 +392,6 @@ int btba_workspace_live_blocks(btba_workspace *ws, uint64_t *blocks)
     *blocks = v;
     return BTBA_OK;
 }
-
-#ifdef BTBA_CENSUS
-// Developer builds only (scripts/sweep_census.py): the lane census of the dense block walk since BTBA_OPT_COUNT_LIVE was set --
-// out[0] walked blocks (= wave trips), [1] lanes with a usable source depth, [2] lanes whose projection lands in the target image (`valid`),
-// [3] wave trips that end at ballot(valid) == 0, [4] lanes in the trips that go on (64 per trip), [5] lanes accepted after the tap tests,
-// [6] lanes valid but rejected by the target depth range, [7] lanes valid, depth fine, rejected by the normal / distance tests.
-extern "C" BTBA_API int btba_dev_census(btba_workspace *ws, uint64_t *out)
-{
-    DeviceGuard device_guard(ws);
-    if (!ws || !out || !ws->live_blocks.p) return BTBA_EINVAL;
-    HIP_TRY(hipStreamSynchronize(ws->stream));
-    HIP_TRY(hipMemcpy(out, ws->live_blocks.p, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return BTBA_OK;
-}
-#endif
 
 int btba_workspace_sync(btba_workspace *ws)
 {
@@ -995,7 +980,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     }
     const size_t pairsum_floats = lds_pairs / sizeof(float);
     S.chain_iterations = 0;
-    const size_t lut_bytes = sizeof(float) * (size_t)((Wd + Hd + 3) & ~3) + (zn_layout == 1 ? sizeof(float4) * (size_t)(Wd + Hd + 4) : 0) + blist_bytes + (size_t)ws->tune.debug_lds_pad;         // coordinate look-up tables of the compact dense sweep (+ its list of live blocks)
+    const size_t lut_bytes = sizeof(float) * (size_t)((Wd + Hd + 3) & ~3) + (zn_layout == 1 ? sizeof(float4) * (size_t)(Wd + Hd) : 0) + blist_bytes + (size_t)ws->tune.debug_lds_pad;         // coordinate look-up tables of the compact dense sweep (+ its list of live blocks)
     if (chain) {
         // ONE launch: 8 XCD sequences x n_gn iterations x (instances of the XCD) x (sweep items + 1 solve item)
         const size_t chain_lds = std::max(lut_bytes, lds_rest + 16 + sizeof(float) * chain_region_floats(N));
@@ -1103,16 +1088,6 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
             Dh.corr_entry0 = (c24_it || relayout) ? (int64_t)b0 * corr_stride : 0;
             Dh.corr24_out = (relayout && it == 0) ? ws->corr24_tmp.as<float2>() : nullptr;
             if (Dh.block_ranges) Dh.block_ranges += b0 * N * (size_t)((Wd / 8) * (Hd / 8));
-#ifdef BTBA_WG_TRACE
-            static DevBuf wg_trace_buf;
-            const char *wg_trace_file = std::getenv("BTBA_WG_TRACE_FILE");
-            const size_t wg_trace_n = (size_t)tiles * D.n_dense_pairs * H.nb + (size_t)chunks * P * H.nb;
-            if (wg_trace_file && it == prm->n_gn_iters - 1 && h == 0) {
-                if ((rc = wg_trace_buf.ensure(32 * wg_trace_n))) return rc;
-                HIP_TRY(hipMemsetAsync(wg_trace_buf.p, 0, 32 * wg_trace_n, H.st));
-                Dh.wg_trace = wg_trace_buf.as<unsigned long long>();
-            }
-#endif
             const unsigned n_d = (unsigned)tiles * D.n_dense_pairs * H.nb, n_s = (unsigned)chunks * P * H.nb;
             // one interleaved launch of both sweeps: the dense workgroups are VALU-bound, the sparse ones stream HBM, and the
             // two fill each other's idle pipes -- measured at c3 (scripts/ab_dense.py, fused vs separate step time):
@@ -1150,14 +1125,6 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
                     if ((rc = time_end(ws, slot, H.st))) return rc;
                 }
             }
-#ifdef BTBA_WG_TRACE
-            if (Dh.wg_trace) {                                   // dump the last iteration's workgroup timeline
-                std::vector<unsigned long long> host(4 * wg_trace_n);
-                HIP_TRY(hipStreamSynchronize(H.st));
-                HIP_TRY(hipMemcpy(host.data(), wg_trace_buf.p, 32 * wg_trace_n, hipMemcpyDeviceToHost));
-                if (FILE *f = std::fopen(wg_trace_file, "wb")) { std::fwrite(host.data(), 8, host.size(), f); std::fclose(f); }
-            }
-#endif
             if ((rc = time_begin(ws, timing_it, 2, &slot, H.st))) return rc;
             float *A_h = (a_global || D.pre_assembled) ? ws->big_A.as<float>() + b0 * (n + 2) * ld : nullptr;
             float *out_h = (it == prm->n_gn_iters - 1) ? poses + 16 * b0 * N : nullptr;     // the last iterate's matrices go straight to the caller's buffer

@@ -72,9 +72,6 @@ struct SolveDims {
     int pairsum_in_lds;  // 1: stage reduced pair sums in LDS, 0: in global scratch
     int pre_assembled;   // large windows: k_big_reduce + k_big_assemble have built the system, k_system_solve only solves and updates
     int walk_blocks;     // pinhole sweep on the compact cache: waves walk 8 x 8 pixel blocks (width and height multiples of 8)
-#ifdef BTBA_WG_TRACE
-    unsigned long long *wg_trace; // developer build (scripts/wg_trace.py): per workgroup of the fused sweep (start, end) in 100 MHz ticks, hardware id, kind
-#endif
     const int4 *dense_work;       // work position q -> (target, source, dense pair, -): the order the sweeps work the pairs off, heaviest first
     int work_formula;             // 1 / 2: the table is the closed form "all pairs by ascending |i - j|, then ascending i" with target = lower / higher
                                   // frame -- the pinhole sweeps then compute their item instead of loading it (one memory round trip less)
@@ -976,9 +973,6 @@ __device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 
 //   * depth-range tests are one unsigned compare of the bit patterns: for positive floats order is bit order, negative
 //     values, zeros and NaN fall outside after the subtraction wraps;
 //   * wave-uniform operands of 2-cycle operations (relative pose, intrinsics) live in VGPRs.
-#ifdef BTBA_WG_TRACE
-__shared__ unsigned long long wg_dbg[12];       // developer build: (end of prologue, end of pixel loop, live blocks) of the workgroup's dense item
-#endif
 struct PinholeCtx {
     float R[9], t[3];                 // relative pose source camera -> target camera (scalar registers)
     float fx, fy, cx, cy, wm1, hm1, wm2, hm2, w16, normal_thresh, dist2_thresh, wdelta, w_dense, ybase4;
@@ -986,33 +980,9 @@ struct PinholeCtx {
     unsigned zmin_bits, zrange_bits;  // depth_min < z < depth_max  <=>  bits(z) - (bits(depth_min) + 1) < zrange_bits (unsigned)
 };
 
-__device__ __forceinline__ float lds_f32_at(const float *base, unsigned byte_off) { return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + byte_off); }
-__device__ __forceinline__ float2 lds_f32x2_at(const float *base, unsigned byte_off) { const char *q = reinterpret_cast<const char *>(base) + byte_off; return make_float2(*reinterpret_cast<const float *>(q), *reinterpret_cast<const float *>(q + 4)); }
-__device__ __forceinline__ float4 gather16(const float4 *base, unsigned byte_off) { return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(base) + byte_off); }
-// ... with the constant part of the address as the load's immediate offset (base + zext(byte_off) + IMM in 64 bits: a 32-bit `byte_off + IMM` may wrap, so the
-// compiler cannot fold it and spends a vector add per tap)
+// 16 bytes at a byte offset, with the constant part of the address as the load's immediate offset (base + zext(byte_off) + IMM in 64 bits: a 32-bit
+// `byte_off + IMM` may wrap, so the compiler cannot fold it and spends a vector add per tap)
 template <int IMM> __device__ __forceinline__ float4 gather16_imm(const char *base, unsigned byte_off) { return *reinterpret_cast<const float4 *>(base + (size_t)byte_off + IMM); }
-#ifndef BTBA_POSE_LDS
-#define BTBA_POSE_LDS 0      // measured, round 6 (profiles/r06/sweep_diet.json): 16 fewer scalar-operand instructions per trip, 4 more broadcast LDS reads: 161 -> 169 us per launch.  Off.
-#endif
-#ifndef BTBA_POSE_VGPR
-#define BTBA_POSE_VGPR 0
-#endif
-#ifndef BTBA_TAP_BASES
-#define BTBA_TAP_BASES 1
-#endif
-#ifndef BTBA_STREAM_SADDR
-#define BTBA_STREAM_SADDR 1
-#endif
-#ifndef BTBA_LUT_ABS
-#define BTBA_LUT_ABS 1
-#endif
-#ifndef BTBA_LIST_LANES
-#define BTBA_LIST_LANES 1
-#endif
-#ifndef BTBA_TAPS_EXEC
-#define BTBA_TAPS_EXEC 1     // round 6 (profiles/r06/bound_probes.json, taps_exec.json): the four tap gathers only for lanes that passed the in-image / source-depth tests; same bits, -1.5 % on the launch
-#endif
 // LDS byte address of a pointer into the workgroup's LDS, and two consecutive floats at an absolute LDS byte address: the table base rides in the fp32 address
 // arithmetic (exact below 2^24) instead of costing a vector add behind every float -> int conversion
 __device__ __forceinline__ unsigned lds_address(const void *p) { return (unsigned)(unsigned long)(const __attribute__((address_space(3))) char *)p; }
@@ -1185,17 +1155,7 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         else rowB[e - D.width] = make_float4(C.R[1] * l + C.R[2], C.R[4] * l + C.R[5], C.R[7] * l + C.R[8], 0.0f);
     }
     if (tid >= 64 && tid < 64 + 36) red[4 * kDenseVals + kDenseVals + 4 + ((int)tid - 64)] = m_stage;
-    // Round 6: the pair's wave-uniform operands of the pixel loop -- relative pose and intrinsics -- ALSO in LDS, four 16-byte entries [R row | t] x 3,
-    // (fx, fy, cx, cy).  A VALU instruction with a scalar-register source issues at HALF rate on gfx950 (profiles/r02/valu_calibration.md, rows `y:`), and
-    // the loop has 16 of them per trip (3 translation FMAs, 4 projection multiply-adds, 9 for the normal rotation: 32 of a trip's 388 issue cycles); holding
-    // the 16 values in VGPRs for the whole loop costs a wave per SIMD (archive 4.2: 101 VGPRs, slower).  Read back per trip as broadcast LDS loads
-    // (LDS issue is not VALU issue) they live in VGPRs for a few instructions only.  Same operations on the same values: same bits.
-    float4 *pose_l = rowB + D.height;
-    if (tid == 0) {
-        pose_l[0] = make_float4(C.R[0], C.R[1], C.R[2], C.t[0]); pose_l[1] = make_float4(C.R[3], C.R[4], C.R[5], C.t[1]);
-        pose_l[2] = make_float4(C.R[6], C.R[7], C.R[8], C.t[2]); pose_l[3] = make_float4(D.fx, D.fy, D.cx, D.cy);
-    }
-    int *hdr = reinterpret_cast<int *>(pose_l + 4);                       // [0 .. 8) wave totals of the list compaction (two blocks per lane and pass: [0 .. 4) first halves, [4 .. 8) second)
+    int *hdr = reinterpret_cast<int *>(rowB + D.height);                  // [0 .. 8) wave totals of the list compaction (two blocks per lane and pass: [0 .. 4) first halves, [4 .. 8) second)
     unsigned *blist = reinterpret_cast<unsigned *>(hdr + 8);
     int n_live = 0;
     if (WALK == 2) {
@@ -1255,103 +1215,44 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
 #pragma unroll
     for (int k = 0; k < kDenseVals; k++) acc[k] = 0.0f;
 
-    // one source pixel: zs = its (gated depth, normal), ox / oy = LDS byte offsets of its column / row entries in the ray tables (from colA)
-#ifdef BTBA_TRIP_TRACE
-    unsigned long long tt_a = 0, tt_b = 0, tt_c = 0, tt_live = 0, tt_dead = 0;       // shader-clock sums of this wave: top of the trip / taps in flight / blend + accumulate
-    auto stamp_after = [](float dep) { unsigned long long t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(dep) : "memory"); return t; };
-#endif
-#ifdef BTBA_CENSUS
-    unsigned cen[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };      // wave-uniform lane counts (scripts/sweep_census.py)
-#endif
-    typedef const volatile __attribute__((address_space(3))) btba_f4v lds_cv4;        // (an explicit LDS pointer: a volatile access through a generic one stays a flat_load)
-    lds_cv4 *pose_v = (lds_cv4 *)pose_l;
-#if BTBA_POSE_VGPR
-    btba_f4v pv0 = (btba_f4v){ C.R[0], C.R[1], C.R[2], C.t[0] }, pv1 = (btba_f4v){ C.R[3], C.R[4], C.R[5], C.t[1] }, pv2 = (btba_f4v){ C.R[6], C.R[7], C.R[8], C.t[2] }, pvk = (btba_f4v){ D.fx, D.fy, D.cx, D.cy };
-    asm volatile("" : "+v"(pv0), "+v"(pv1), "+v"(pv2), "+v"(pvk));
-#endif
     const char *tap_row0 = reinterpret_cast<const char *>(zn_t), *tap_row1 = tap_row0 + C.row16;
     const float lut_addr_f = (float)lds_address(lut), ybase4_abs = C.ybase4 + lut_addr_f;
+    // one source pixel: zs = its (gated depth, normal), ox / oy = LDS byte offsets of its column / row entries in the ray tables (from colA)
     auto pixel = [&](const float4 &zs, unsigned ox, unsigned oy) {
-#ifdef BTBA_TRIP_TRACE
-        unsigned long long tt0; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt0) :: "memory");
-#endif
         // source pixel -> camera space (gated depth: 0 where invalid), depth-range test on the bit pattern
         const float d = zs.x;
         const bool src_ok = (__float_as_uint(d) - C.zmin_bits) < C.zrange_bits;
         // transform the point, project
         const float4 ra = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(colA) + ox), rb = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(colA) + oy);
-#if BTBA_POSE_VGPR
-        const btba_f4v P0 = pv0, P1 = pv1, P2 = pv2, PK = pvk;                              // developer experiment: the sixteen operands in VGPRs for the whole loop (needs 5 waves per SIMD: -DBTBA_FUSED_WAVES=5)
-        const float qx = fma_nd(ra.x + rb.x, d, P0.w), qy = fma_nd(ra.y + rb.y, d, P1.w), qz = fma_nd(ra.z + rb.z, d, P2.w);
-        const float rqz = fast_rcp(qz);
-        const float u = __builtin_fmaf(qx * PK.x, rqz, PK.z), v = __builtin_fmaf(qy * PK.y, rqz, PK.w);      // NOT fma_nd: see below
-#elif BTBA_POSE_LDS
-        const btba_f4v P0 = pose_v[0], P1 = pose_v[1], P2 = pose_v[2], PK = pose_v[3];      // volatile: re-read every trip, never hoisted into loop-long registers
-        // (fma_nd: with every operand in a VGPR the compiler overwrites the addend's register, and such a read-modify-write FMA issues at half rate when its
-        // two multiplicands share a register parity -- the allocator's luck; a fresh destination is full rate whatever it gets)
-        const float qx = fma_nd(ra.x + rb.x, d, P0.w), qy = fma_nd(ra.y + rb.y, d, P1.w), qz = fma_nd(ra.z + rb.z, d, P2.w);
-        const float rqz = fast_rcp(qz);
-        // (u, v through the compiler's own FMA, not fma_nd: an inline-asm consumer directly behind v_rcp_f32 is invisible to the hazard recognizer, which then
-        // does not insert the wait state gfx950 needs between a transcendental and a VALU use of its result -- round 6's first build of this switch read a
-        // stale reciprocal now and then: non-deterministic poses, 2e-4 off, caught by tests/test_cpp_bundler.py and scripts/r06/determinism.py)
-        const float u = __builtin_fmaf(qx * PK.x, rqz, PK.z), v = __builtin_fmaf(qy * PK.y, rqz, PK.w);
-#else
         const float qx = (ra.x + rb.x) * d + C.t[0], qy = (ra.y + rb.y) * d + C.t[1], qz = (ra.z + rb.z) * d + C.t[2];
         const float rqz = fast_rcp(qz);
+        // (u, v through the compiler's own FMAs, not fma_nd: an inline-asm consumer directly behind v_rcp_f32 is invisible to the hazard recognizer, which then
+        // does not insert the wait state gfx950 needs between a transcendental and a VALU use of its result -- a round-6 build that did so read a stale
+        // reciprocal now and then: non-deterministic poses, 2e-4 off, caught by tests/test_cpp_bundler.py and scripts/r06/determinism.py)
         const float u = qx * C.fx * rqz + C.cx, v = qy * C.fy * rqz + C.cy;
-#endif
         const float uc = clamp0_s(u, C.wm1), vc = clamp0_s(v, C.hm1);      // NaN -> 0: addresses stay in the frame
         const bool valid = src_ok & (fabsf(u - uc) < 0.5f) & (fabsf(v - vc) < 0.5f);
-#ifdef BTBA_CENSUS
-        cen[1] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(src_ok)); cen[2] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid));
-        if (__builtin_amdgcn_ballot_w64(valid) == 0ull) cen[3] += 1u; else cen[4] += 64u;
-#endif
-#ifdef BTBA_TRIP_TRACE
-        const unsigned long long tt1 = stamp_after(valid ? uc : vc);
-        tt_a += tt1 - tt0;
-        if (__builtin_amdgcn_ballot_w64(valid) == 0ull) { tt_dead++; return; }
-#else
         if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return;
-#endif
         // rotate the normal (only the waves that go on need it: half of the block trips end above)
-#if BTBA_POSE_LDS || BTBA_POSE_VGPR
-        const float nqx = fma_nd(P0.z, zs.w, fma_nd(P0.y, zs.z, P0.x * zs.y));
-        const float nqy = fma_nd(P1.z, zs.w, fma_nd(P1.y, zs.z, P1.x * zs.y));
-        const float nqz = fma_nd(P2.z, zs.w, fma_nd(P2.y, zs.z, P2.x * zs.y));
-#else
         const float nqx = C.R[0] * zs.y + C.R[1] * zs.z + C.R[2] * zs.w;
         const float nqy = C.R[3] * zs.y + C.R[4] * zs.z + C.R[5] * zs.w;
         const float nqz = C.R[6] * zs.y + C.R[7] * zs.z + C.R[8] * zs.w;
-#endif
         // taps (x0, x0 + 1) x (y0, y0 + 1) with x0 = min(floor(uc), W - 2): at the right / bottom edge (uc = W - 1) the weights are (0, 1)
         // instead of (1, -) -- the same blend, and the four taps are always the 2 x 2 block at ONE computed address
         const float fx0 = min_raw_s(floorf(uc), C.wm2), fy0 = min_raw_s(floorf(vc), C.hm2);
         const float alpha = uc - fx0, beta = vc - fy0;
-#if BTBA_TAP_BASES
         // one computed byte offset for the 2 x 2 block: the second row's base is a scalar add (wave-uniform), the + 16 the load's immediate offset field
         const unsigned o00 = (unsigned)(fy0 * C.w16 + 16.0f * fx0);                             // byte offset, fp32-exact below 2^24
-#if BTBA_TAPS_EXEC
         // Lanes that already failed the in-image / source-depth tests (8.8 % in the trips that go on, clustered along block edges: profiles/r06/sweep_census.json) issue no
         // taps.  The texture addresser's service time per gather is exposed almost in full (profiles/r06/bound_probes.json: one more 16-byte gather per trip = +13.4 us
-        // per launch, linear) and it skips idle quads.  The registers of those lanes stay undefined and are never used: `ok` contains `valid`, and `keep` zeroes
-        // everything a rejected lane contributes (an AND: NaN-safe).
+        // per launch, linear) and it skips idle quads (profiles/r06/taps_exec.json: same bits, -1.5 % on the launch).  The registers of those lanes stay undefined
+        // and are never used: `ok` contains `valid`, and `keep` zeroes everything a rejected lane contributes (an AND: NaN-safe).
         float4 z00, z10, z01, z11;
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wconditional-uninitialized"
         if (valid) { z00 = gather16_imm<0>(tap_row0, o00); z10 = gather16_imm<16>(tap_row0, o00); z01 = gather16_imm<0>(tap_row1, o00); z11 = gather16_imm<16>(tap_row1, o00); }
 #pragma clang diagnostic pop
-#else
-        const float4 z00 = gather16_imm<0>(tap_row0, o00), z10 = gather16_imm<16>(tap_row0, o00), z01 = gather16_imm<0>(tap_row1, o00), z11 = gather16_imm<16>(tap_row1, o00);
-#endif
-#else
-        const unsigned o00 = (unsigned)(fy0 * C.w16 + 16.0f * fx0), o01 = o00 + C.row16;      // byte offsets, fp32-exact below 2^24
-        const float4 z00 = gather16(zn_t, o00), z10 = gather16(zn_t, o00 + 16u), z01 = gather16(zn_t, o01), z11 = gather16(zn_t, o01 + 16u);
-#endif
-#if BTBA_LUT_ABS
         const float2 xi2 = lds_f32x2_abs((unsigned)(4.0f * fx0 + lut_addr_f)), yi2 = lds_f32x2_abs((unsigned)(4.0f * fy0 + ybase4_abs));
-#else
-        const float2 xi2 = lds_f32x2_at(lut, (unsigned)(4.0f * fx0)), yi2 = lds_f32x2_at(lut, (unsigned)(4.0f * fy0 + C.ybase4));
-#endif
         const float a0 = 1.0f - alpha, b0 = 1.0f - beta;
         // blend of the taps' camera-space points (x = column term * z, y = row term * z, z = gated depth) and normals; the
         // column / row terms are shared by the taps of a column / row, so they multiply the partial sums:
@@ -1370,21 +1271,10 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         const float nix = fma_nd(c11, z11.y, fma_nd(c01, z01.y, fma_nd(c00, z00.y, c10 * z10.y)));
         const float niy = fma_nd(c11, z11.z, fma_nd(c01, z01.z, fma_nd(c00, z00.z, c10 * z10.z)));
         const float niz = fma_nd(c11, z11.w, fma_nd(c01, z01.w, fma_nd(c00, z00.w, c10 * z10.w)));
-#ifdef BTBA_TRIP_TRACE
-        const unsigned long long tt3 = stamp_after(z00.x + z10.x + z01.x + z11.x);
-        tt_b += tt3 - tt1;
-#endif
         const float dx = qx - cix, dy = qy - ciy, dz = qz - ciz;
         const float dist2 = fma_nd(dz, dz, fma_nd(dx, dx, dy * dy));
         const float dn = fma_nd(nqz, niz, fma_nd(nqx, nix, nqy * niy));
         const bool ok = valid & ((__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits) & (dn >= C.normal_thresh) & (dist2 <= C.dist2_thresh);
-#ifdef BTBA_CENSUS
-        {
-            const bool depth_ok = (__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits;
-            cen[5] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(ok)); cen[6] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid & !depth_ok));
-            cen[7] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid & depth_ok & !ok));
-        }
-#endif
         // rejected pixels contribute exact zeros: AND with 0 / ~0 (one select, then 2-cycle v_and_b32; NaN-safe, unlike a multiply)
         const unsigned keep = opaque_vgpr(ok ? 0xFFFFFFFFu : 0u);
         auto masked = [keep](float x) { return __uint_as_float(__float_as_uint(x) & keep); };
@@ -1414,9 +1304,6 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
             acc[21 + r] += pr[r].x * rr.y;
         }
         acc[27] += masked(1.0f);
-#ifdef BTBA_TRIP_TRACE
-        tt_c += stamp_after(acc[27] + acc[0] + acc[20] + acc[26]) - tt3; tt_live++;
-#endif
     };
 
     if (WALK == 2) {
@@ -1426,9 +1313,6 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         const int lane = (int)tid & 63, wave = __builtin_amdgcn_readfirstlane((int)tid >> 6);
         n_live = __builtin_amdgcn_readfirstlane(n_live);
         if (D.live_blocks && tid == 0) atomicAdd(D.live_blocks, (unsigned long long)n_live);
-#ifdef BTBA_WG_TRACE
-        if (tid == 0) { wg_dbg[0] = wall_clock64(); wg_dbg[2] = (unsigned long long)n_live; }
-#endif
         const unsigned lx = (unsigned)lane & 7u, ly = (unsigned)lane >> 3;
         const unsigned lane_px = ly * (unsigned)D.width + lx;          // pixel offset of the lane inside its block
         const unsigned ox_l = 16u * lx, oy_l = 16u * ly + 16u * (unsigned)D.width;
@@ -1443,29 +1327,19 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         // Two trips per loop iteration with the two register sets swapping roles: a single-trip loop rotates (next -> current) through
         // eight v_mov per trip, 5 % of its instructions.
         const int nt = (n_live > wave) ? (n_live - wave + kBlock / 64 - 1) / (kBlock / 64) : 0;
-#if BTBA_LIST_LANES
         // this wave's list entries ride in a register, 64 at a time (lane l: entry 64 c + l of the wave), and a trip takes its entry with v_readlane_b32:
         // no LDS round trip (address move, ds_read, wait, readfirstlane) at the top of every trip
         int list_chunk = 0;
         unsigned list_reg = nt > 0 ? blist[wave + (kBlock / 64) * min(lane, nt - 1)] : 0u;
-#endif
         auto fetch = [&](int i, unsigned &code, float4 &zs) {
-#if BTBA_LIST_LANES
             const int idx = min(i, nt - 1);
             if ((idx >> 6) != list_chunk) { list_chunk = idx >> 6; list_reg = blist[wave + (kBlock / 64) * min(64 * list_chunk + lane, nt - 1)]; }
             code = (unsigned)__builtin_amdgcn_readlane((int)list_reg, idx & 63);
-#else
-            code = (unsigned)__builtin_amdgcn_readfirstlane((int)blist[wave + (kBlock / 64) * min(i, nt - 1)]);
-#endif
-#if BTBA_STREAM_SADDR
             // block base in the scalar address (wave-uniform), the lane's pixel inside the block as the constant vector offset: no vector add per trip
             // (the lane offset goes through an opaque copy: seen as loop-invariant, `frame base + lane offset` is hoisted as a 64-bit VECTOR address and the block
             // offset becomes a 64-bit vector add per trip)
             asm volatile("" : "+v"(lane_off16));          // (in place: no copy)
             zs = gather16_imm<0>(reinterpret_cast<const char *>(zn_s) + (size_t)(16u * ((code >> 16) * 8u * (unsigned)D.width + (code & 0xFFFFu) * 8u)), lane_off16);
-#else
-            zs = gather16(zn_s, 16u * ((code >> 16) * 8u * (unsigned)D.width + (code & 0xFFFFu) * 8u + lane_px));
-#endif
         };
         auto work = [&](const float4 &zs, unsigned code) { pixel(zs, ox_l + kBlockStep * (code & 0xFFFFu), oy_l + kBlockStep * (code >> 16)); };
         if (nt > 0) {
@@ -1481,15 +1355,6 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
                 if (++i >= nt) break;
             }
         }
-#ifdef BTBA_CENSUS
-        if (D.live_blocks && lane == 0) for (int k = 1; k < 8; k++) atomicAdd(D.live_blocks + k, (unsigned long long)cen[k]);
-#endif
-#ifdef BTBA_WG_TRACE
-        if (tid == 0) wg_dbg[1] = wall_clock64();
-#endif
-#ifdef BTBA_TRIP_TRACE
-        if (tid == 0) { wg_dbg[4] = tt_a; wg_dbg[5] = tt_b; wg_dbg[6] = tt_c; wg_dbg[7] = tt_live | (tt_dead << 32); }
-#endif
     } else {
         const int n_src = LISTS ? valid_counts[slot_s] : D.npix;
         const uint32_t *list = LISTS ? valid_lists + slot_s * (size_t)D.npix : nullptr;
@@ -1592,9 +1457,6 @@ __device__ __forceinline__ void fused_item(const SolveDims &D, unsigned n_d, uns
     const bool in_tail = slot >= Gi;
     const bool is_sparse = in_tail || (nsi && (slot % Rx == 0u) && (slot / Rx < nsi));
     const unsigned sparse_local = in_tail ? nsi + (slot - Gi) : slot / Rx;
-#ifdef BTBA_WG_TRACE
-    const unsigned long long wg_t0 = wall_clock64();
-#endif
     if (is_sparse) {
         const unsigned i = sparse_base + sparse_local;           // (chunk fastest, then pair, then instance)
         const int chunk = (int)(i % (unsigned)D.sparse_chunks);
@@ -1623,18 +1485,6 @@ __device__ __forceinline__ void fused_item(const SolveDims &D, unsigned n_d, uns
             else dense_block_zn<false, true>(D, campos, ij, T, Tinv, dense_partials, tile, p, b, red, valid_lists, valid_counts, zn_lut);
         }
     }
-#ifdef BTBA_WG_TRACE
-    if (D.wg_trace && threadIdx.x == 0) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n s_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
-        unsigned long long *q = D.wg_trace + 4 * (size_t)g;
-        q[0] = wg_t0; q[1] = wall_clock64(); q[2] = (unsigned long long)(hw & 0xFFFFu) | ((unsigned long long)(xcc & 0xFu) << 16) | ((is_sparse ? 0ull : (wg_dbg[2] & 0xFFFFull)) << 32);
-        q[3] = is_sparse ? 1ull : (((wg_dbg[0] - wg_t0) & 0xFFFFFFull) << 8) | (((wg_dbg[1] - wg_t0) & 0xFFFFFFull) << 32);      // kind | prologue end | loop end (ticks from start)
-#ifdef BTBA_TRIP_TRACE
-        if (!is_sparse) { q[0] = wg_dbg[4]; q[1] = wg_dbg[5]; q[3] = wg_dbg[6] << 8; q[2] = (q[2] & 0xFFFFFFFFull) | (wg_dbg[7] << 32); }       // wave 0's phase sums instead of the timeline (scripts/trip_trace.py)
-#endif
-    }
-#endif
 }
 
 #define BTBA_FUSED_ITEM_ARGS D, n_d, n_s, g, campos, normals, dense_pairs, T, Tinv, dense_partials, corr, pair_offsets, sparse_partials, valid_lists, valid_counts, red, zn_lut

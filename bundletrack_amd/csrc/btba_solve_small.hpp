@@ -41,9 +41,6 @@
 #ifndef BTBA_SOLVE_FAST_SE3
 #define BTBA_SOLVE_FAST_SE3 true     // the update phase's divisions and square roots as x * v_rcp_f32(y) / v_sqrt_f32 (btba_device.hpp: se3_div, se3_sqrt); false = IEEE, rounds 5's kernel
 #endif
-#ifndef BTBA_SOLVE_REPEAT
-#define BTBA_SOLVE_REPEAT 1          // developer experiment (> 1: the whole body again, stamps of the last pass -- what a warm instruction cache is worth; wrong results)
-#endif
 
 namespace btba {
 
@@ -118,16 +115,8 @@ __global__ void __launch_bounds__(kSmallBlock) k_solve_small(const SmallSolveArg
     float *ps = lds + L::ops, *pd = ps + __umul24(P, kSparseVals);
 
     float *tr = S.trace ? S.trace + (size_t)b * (size_t)S.trace_instance + (size_t)S.iter * S.trace_record : nullptr;
-#if BTBA_SOLVE_REPEAT > 1
-    for (int rep = 0; rep < BTBA_SOLVE_REPEAT; rep++) {
-    __syncthreads();
-#endif
     const long long clk0 = tr ? (long long)clock64() : 0;
-#ifdef BTBA_SOLVE_PCG_STAMPS
-#define BTBA_SSTAMP(slot) do { } while (0)
-#else
 #define BTBA_SSTAMP(slot) do { if (tr && tid == 0) tr[S.tr_clk + (slot)] = (float)((long long)clock64() - clk0); } while (0)
-#endif
 
     // ---- phase 1: everything this solve reads from global memory, issued at once (every load is a fabric-latency miss: the sweeps
     // of other XCDs wrote the partials, the previous launch the poses).  Loads and stores WITHOUT conditions around them (see above):
@@ -364,13 +353,7 @@ __global__ void __launch_bounds__(kSmallBlock) k_solve_small(const SmallSolveArg
             }
             rz = wave_sum_all(part);
         }
-#ifdef BTBA_SOLVE_PCG_STAMPS      // developer experiment: the trace's eight clock slots = seven points inside PCG step 1 (wave 0's view)
-#define BTBA_PSTAMP(slot) do { if (tr && tid == 0 && li == 1) tr[S.tr_clk + (slot)] = (float)((long long)clock64() - clk0); } while (0)
-#else
-#define BTBA_PSTAMP(slot) do { } while (0)
-#endif
         for (int li = 0; li < S.n_pcg; li++) {
-            BTBA_PSTAMP(0);
             if (pw) {
                 const float4 *p4 = reinterpret_cast<const float4 *>(vp + h * CPL);
                 f2 qa = (f2){ 0.f, 0.f }, qb = qa, qc = qa, qd = qa;
@@ -387,16 +370,13 @@ __global__ void __launch_bounds__(kSmallBlock) k_solve_small(const SmallSolveArg
                 s = dpp_add<0x141, 0xf>(s);                                 //   row_half_mirror
                 if (h == 0 && row_live) vAp[a_row] = s;
             }
-            BTBA_PSTAMP(1);
             __syncthreads();
-            BTBA_PSTAMP(2);
             if (wave == 0) {
                 float ap_[2], z_[2];
                 float part = 0.0f;
 #pragma unroll
                 for (int j = 0; j < 2; j++) { const int idx = lane + 64 * j; ap_[j] = idx < na ? vAp[idx] : 0.0f; part += p_[j] * ap_[j]; }
                 const float pAp = wave_sum_all(part);
-                BTBA_PSTAMP(3);
                 const float alpha = (pAp > kEps) ? rz * __builtin_amdgcn_rcpf(pAp) : 0.0f;
                 part = 0.0f;
 #pragma unroll
@@ -407,18 +387,14 @@ __global__ void __launch_bounds__(kSmallBlock) k_solve_small(const SmallSolveArg
                     part += z_[j] * r_[j];
                 }
                 const float rz_new = wave_sum_all(part);
-                BTBA_PSTAMP(4);
                 const float beta = (rz > kEps) ? rz_new * __builtin_amdgcn_rcpf(rz) : 0.0f;
                 if (tr && tid == 0) { float *sc = tr + S.tr_pcg + 4 * li; sc[0] = pAp; sc[1] = alpha; sc[2] = rz_new; sc[3] = beta; }
                 rz = rz_new;
 #pragma unroll
                 for (int j = 0; j < 2; j++) { p_[j] = z_[j] + beta * p_[j]; if (lane + 64 * j < na) vp[lane + 64 * j] = p_[j]; }
             }
-            BTBA_PSTAMP(5);
             __syncthreads();
-            BTBA_PSTAMP(6);
         }
-#undef BTBA_PSTAMP
         if (wave == 0) {
 #pragma unroll
             for (int j = 0; j < 2; j++) if (lane + 64 * j < na) vd[lane + 64 * j] = d_[j];
@@ -476,9 +452,6 @@ __global__ void __launch_bounds__(kSmallBlock) k_solve_small(const SmallSolveArg
     }
     BTBA_SSTAMP(7);
 #undef BTBA_SSTAMP
-#if BTBA_SOLVE_REPEAT > 1
-    }
-#endif
 }
 
 }  // namespace btba

@@ -1,4 +1,5 @@
-"""Where the dense workgroup's prologue goes (developer tool; needs a library built with -DBTBA_WG_TRACE -DBTBA_PROLOGUE_TRACE from the sources with scripts/dev/prologue_trace.patch applied: two more stamps).
+"""Where the dense workgroup's prologue goes (developer tool; needs a library built with -DBTBA_WG_TRACE -DBTBA_PROLOGUE_TRACE from the sources with
+`git apply scripts/dev/wg_trace.patch scripts/dev/prologue_trace.patch` applied: two more stamps).
     BTBA_LIB_PATH=build/ab/protrace.so python scripts/prologue_trace.py"""
 import json, os, sys, tempfile
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT)

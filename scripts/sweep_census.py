@@ -1,5 +1,6 @@
-"""Lane census of the dense block walk (developer tool; needs a library built with -DBTBA_CENSUS: `scripts/ab_build.sh census -DBTBA_CENSUS` or
-build/ab/census.so):   BTBA_LIB_PATH=build/ab/census.so python scripts/sweep_census.py [--config c3|c4] [--masked] > profiles/r06/sweep_census.json
+"""Lane census of the dense block walk (developer tool; needs a library built with -DBTBA_CENSUS from the sources with the probe applied:
+`git apply scripts/dev/sweep_census.patch`, then `scripts/ab_build.sh census -DBTBA_CENSUS` or build/ab/census.so):
+    BTBA_LIB_PATH=build/ab/census.so python scripts/sweep_census.py [--config c3|c4] [--masked] > profiles/r06/sweep_census.json
 Where do the lanes of a walked 8 x 8 block die?  Per solve (7 launches) of the bench batch: wave trips, lanes with a usable source depth, lanes whose
 projection lands in the target image, trips that end at ballot(valid) == 0, lanes in the heavy half (taps, blend, 27-FMA accumulation), lanes accepted.
 Decides whether compacting the survivors of two blocks before the accumulation can pay (round 5's verdict, item 4a/c)."""

@@ -1,5 +1,5 @@
 """Where a wave's time goes inside one block trip of the fused sweep (developer tool; needs a library built with
--DBTBA_WG_TRACE -DBTBA_TRIP_TRACE).
+-DBTBA_WG_TRACE -DBTBA_TRIP_TRACE from the sources with `git apply scripts/dev/wg_trace.patch` applied).
     BTBA_LIB_PATH=build/ab/triptrace.so python scripts/trip_trace.py > gpurun_out/trip_trace.json
 Wave 0 of every dense workgroup sums, in shader-clock cycles (s_memtime), over its trips:
     top    from the start of a trip to the validity ballot: wait for the block's pixels (prefetched), ray tables from LDS, projection

@@ -1,4 +1,5 @@
-"""Workgroup timeline of one k_fused_sweeps launch (developer tool; needs a library built with -DBTBA_WG_TRACE, scripts/ab_build.sh).
+"""Workgroup timeline of one k_fused_sweeps launch (developer tool; needs a library built with -DBTBA_WG_TRACE from the sources
+with `git apply scripts/dev/wg_trace.patch` applied, scripts/ab_build.sh).
     BTBA_LIB_PATH=build/ab/trace.so python scripts/wg_trace.py [--tiles T] > gpurun_out/wg_trace.json
 Every workgroup records (start, end) in 100 MHz ticks and the CU it ran on; the summary answers: how long are dense / sparse
 workgroups, how much of the launch is the drain at the end (slots idle while the last workgroups finish), how even is the load."""

@@ -40,7 +40,13 @@ EXPORTED_SYMBOLS = [
     "btba_matrices_to_poses", "btba_poses_to_matrices",
     "btba_process_depth", "btba_depth_to_normals",
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
+    "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
 ]
+
+# btba_match (include/btba.h): one descriptor match, 40 bytes
+MATCH_DTYPE = np.dtype(
+    [("idx_a", "<i4"), ("idx_b", "<i4"), ("dist", "<f4"), ("dir", "<i4"), ("ptA_cam", "<f4", (3,)), ("ptB_cam", "<f4", (3,))]
+)
 
 
 class Params(C.Structure):
@@ -53,6 +59,12 @@ class Params(C.Structure):
         ("weights_sparse_per_iter", C.c_void_p), ("weights_dense_per_iter", C.c_void_p),      # host float[n_gn_iters] or NULL (the scalars)
         ("n_weights_per_iter", C.c_int32),                                                     # their length (must equal n_gn_iters when either is set)
     ]
+
+
+class MatchParams(C.Structure):
+    """btba_match_params (include/btba.h)."""
+    _fields_ = [("k", C.c_int32), ("mutual", C.c_int32), ("max_dist_neighbor", C.c_float), ("cos_max_normal_neighbor", C.c_float),
+                ("max_dist_no_neighbor", C.c_float), ("cos_max_normal_no_neighbor", C.c_float), ("min_z", C.c_float)]
 
 
 class Stats(C.Structure):
@@ -203,6 +215,12 @@ def lib() -> C.CDLL:
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.btba_process_depth.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float]
         L.btba_depth_to_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_match_params_default.argtypes = [C.POINTER(MatchParams)]
+        L.btba_match_params_default.restype = None
+        L.btba_match_capacity.argtypes = [C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
+        L.btba_match_pairs.argtypes = [C.c_void_p, C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -215,6 +233,17 @@ def check(status: int, where: str) -> None:
 def default_params(**kw) -> Params:
     p = Params()
     lib().btba_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def match_params(**kw) -> MatchParams:
+    """btba_match_params_default with fields overridden by keyword."""
+    p = MatchParams()
+    lib().btba_match_params_default(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)

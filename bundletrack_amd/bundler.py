@@ -49,6 +49,8 @@ class FrameRef:
     depth_gpu: object = None
     normal_gpu: object = None
     color_gpu: object = None
+    kpts_gpu: object = None              # [n, 2] float32 CUDA tensor: keypoints (x, y) in full-resolution pixels (Frame::_keypts)
+    desc_gpu: object = None              # [n, D] float32 CUDA tensor: their descriptors (Frame::_feat_des_gpu)
 
     def __hash__(self):
         return hash(self.id)

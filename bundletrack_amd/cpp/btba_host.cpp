@@ -317,6 +317,71 @@ void FeatureManager::runRansacMultiPairGPU(btba_workspace *ws, const std::vector
     }
 }
 
+void FeatureManager::findCorresbyNNMultiPair(btba_workspace *ws, const std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> &pairs)
+{
+    if (pairs.empty()) return;
+    const Config cfg = yml ? *yml : Config{};
+    btba_match_params prm;
+    btba_match_params_default(&prm);
+    prm.mutual = cfg.feature_corres_mutual ? 1 : 0;
+    prm.max_dist_neighbor = cfg.feature_corres_max_dist_neighbor;
+    prm.cos_max_normal_neighbor = (float)std::cos(cfg.feature_corres_max_normal_neighbor / 180.0 * M_PI);     // :252-255
+    prm.max_dist_no_neighbor = cfg.feature_corres_max_dist_no_neighbor;
+    prm.cos_max_normal_no_neighbor = (float)std::cos(cfg.feature_corres_max_normal_no_neighbor / 180.0 * M_PI);
+    std::vector<Frame *> frames;                                                  // every frame once, in order of first appearance
+    std::map<const Frame *, int> index;
+    std::vector<int32_t> pr;
+    for (const auto &p : pairs)
+        for (const Frame *f : { p.first.get(), p.second.get() }) {
+            auto it = index.find(f);
+            if (it == index.end()) { it = index.emplace(f, (int)frames.size()).first; frames.push_back(const_cast<Frame *>(f)); }
+            pr.push_back(it->second);
+        }
+    const int n = (int)frames.size();
+    const Frame &f0 = *frames[0];
+    int D = 4;
+    std::vector<const float *> desc(n), kpts(n), depth(n), normal(n);
+    std::vector<int32_t> n_kpts(n), ids(n);
+    std::vector<float> poses(16 * (size_t)n);
+    for (int k = 0; k < n; k++) {
+        const Frame &f = *frames[k];
+        if (f._H != f0._H || f._W != f0._W) throw Error(BTBA_EINVAL, "findCorresbyNNMultiPair: frames of different sizes");
+        if (f._n_keypts > 0) D = f._feat_dim;
+        desc[k] = f._feat_des_gpu; kpts[k] = reinterpret_cast<const float *>(f._kpts_gpu);
+        depth[k] = f._depth_gpu; normal[k] = reinterpret_cast<const float *>(f._normal_gpu);
+        n_kpts[k] = f._n_keypts; ids[k] = f._id;
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) poses[16 * (size_t)k + 4 * r + c] = f._pose_in_model(r, c);
+    }
+    float K[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) K[3 * r + c] = f0._K(r, c);
+    int64_t cap = 0;
+    int rc = btba_match_capacity(&prm, n, f0._H, f0._W, D, n_kpts.data(), (int)pairs.size(), pr.data(), &cap);
+    if (rc != BTBA_OK) throw Error(rc, "btba_match_capacity");
+    std::vector<btba_match> out(std::max<int64_t>(cap, 1));
+    std::vector<int32_t> n_out(pairs.size());
+    rc = btba_match_pairs(ws, &prm, /*device_resident=*/0, n, f0._H, f0._W, K, desc.data(), D, kpts.data(), n_kpts.data(), depth.data(), normal.data(),
+                          poses.data(), ids.data(), (int)pairs.size(), pr.data(), out.data(), nullptr, nullptr, n_out.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_match_pairs");
+    size_t o = 0;
+    for (size_t p = 0; p < pairs.size(); p++) {                                  // collectMutualMatches (:341-368): appended in the library's order
+        Correspondences &m = _matches[{ pairs[p].first->_id, pairs[p].second->_id }];
+        for (int i = 0; i < n_out[p]; i++, o++) {
+            m.ptA_cam.insert(m.ptA_cam.end(), out[o].ptA_cam, out[o].ptA_cam + 3);
+            m.ptB_cam.insert(m.ptB_cam.end(), out[o].ptB_cam, out[o].ptB_cam + 3);
+        }
+    }
+}
+
+void FeatureManager::findCorresbyNN(btba_workspace *ws, const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB)
+{
+    if (frameA->_n_keypts == 0 || frameB->_n_keypts == 0) return;               // :250
+    findCorresbyNNMultiPair(ws, { { frameA, frameB } });
+    const bool is_neighbor = std::abs(frameA->_id - frameB->_id) == 1;
+    if (is_neighbor && countInlierCorres(frameA, frameB) < 5) frameA->_status = Frame::FAIL;      // :280-285
+}
+
 // ---- Bundler ---------------------------------------------------------------------------------------------------
 Bundler::Bundler(std::shared_ptr<Config> yml1, std::shared_ptr<FeatureManager> fm, const Matrix3f &K1, int H1, int W1, OptimizeFn optimize)
     : yml(yml1 ? std::move(yml1) : std::make_shared<Config>()), _fm(std::move(fm)), memory(yml), K(K1), H(H1), W(W1), optimize_(std::move(optimize))

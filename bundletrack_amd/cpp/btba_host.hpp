@@ -58,6 +58,9 @@ struct Config {
     int window_size = 2;                          // bundle.window_size :26 ("exclude keyframes, include new frame")
     int ransac_max_iter = 2000;                   // ransac.* :53-56
     float ransac_inlier_dist = 0.01f;
+    bool feature_corres_mutual = true;            // feature_corres.* :46-51
+    float feature_corres_max_dist_no_neighbor = 0.02f, feature_corres_max_normal_no_neighbor = 45.0f;
+    float feature_corres_max_dist_neighbor = 0.03f, feature_corres_max_normal_neighbor = 45.0f;
     std::string pose_dir;                         // debug_dir + "/poses/" (:5; Bundler.cpp:366); empty = do not write pose files
 };
 
@@ -105,6 +108,11 @@ struct Frame {                                   // the fields of Frame (src/Fra
     float *_depth_gpu = nullptr;
     float4 *_normal_gpu = nullptr;
     uchar4 *_color_gpu = nullptr;
+    int _H = 0, _W = 0;                          // image size and full-resolution intrinsics (Frame.h: _H, _W, _K): the matcher's pixel lookup
+    Matrix3f _K{};
+    float2 *_kpts_gpu = nullptr;                 // [_n_keypts] keypoints (x, y) on the device (the reference keeps cv::KeyPoint on the host)
+    float *_feat_des_gpu = nullptr;              // [_n_keypts][_feat_dim] descriptors on the device (Frame::_feat_des_gpu)
+    int _feat_dim = 0;
 };
 
 // Utils::solveRigidTransformBetweenPoints (Utils.cpp:180-214): the rigid transform points1 -> points2 (n x 3 each, xyz
@@ -158,6 +166,13 @@ public:
     // every pair's matches are replaced by their RANSAC inliers, or emptied when fewer than 5 survive.  Needs the GPU.
     void runRansacMultiPairGPU(btba_workspace *ws, const std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> &pairs,
                                int max_iter, float inlier_dist);
+    // :370-437 on btba_match_pairs (one call for all pairs, in place of OpenCV's CUDA brute-force matcher): every pair's matches --
+    // A -> B, then B -> A with feature_corres.mutual -- are APPENDED to _matches[{A, B}].  Needs the GPU and yml (the shipping
+    // values when it is null); frames need _kpts_gpu, _feat_des_gpu, _feat_dim, _depth_gpu, _normal_gpu, _H, _W, _K.
+    std::shared_ptr<Config> yml;
+    void findCorresbyNNMultiPair(btba_workspace *ws, const std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> &pairs);
+    // :247-288: one pair (A newer); a neighbouring pair left with fewer than 5 matches marks A FAIL
+    void findCorresbyNN(btba_workspace *ws, const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB);
 };
 
 // Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its mask, depth and normals on the device:

@@ -24,6 +24,7 @@
 #include "btba_image.hpp"
 #include "btba_ransac.hpp"
 #include "btba_xorwow.hpp"
+#include "btba_match.hpp"
 
 using namespace btba;
 
@@ -164,6 +165,7 @@ struct btba_workspace {
     DevBuf ransac;                                          // btba_ransac_pairs staging (points, samples, per-trial poses and counts, results)
     DevBuf ransac_u;                                        // the reference's sample stream: n_trials x 3 uniforms (btba_xorwow.hpp), kept per (seed, n_trials)
     std::vector<float> ransac_u_host;
+    DevBuf match;                                           // btba_match_pairs: tables, norms, candidate lists, selections, counts, host-form staging
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;
@@ -303,7 +305,7 @@ void btba_workspace_destroy(btba_workspace *ws)
     for (auto e : ws->event_pool) (void)hipEventDestroy(e);
     DevBuf *bufs[] = { &ws->x, &ws->T, &ws->Tinv, &ws->sparse_part, &ws->dense_part, &ws->pairsum, &ws->dense_pairs, &ws->ptrs, &ws->big_A, &ws->solve_tab,
                        &ws->corr, &ws->offsets, &ws->poses, &ws->campos, &ws->normals, &ws->nvalid, &ws->valid_lists, &ws->valid_counts, &ws->block_ranges,
-                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens };
+                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens };
     for (auto b : bufs) b->release();
     if (ws->corr_stage) (void)hipHostFree(ws->corr_stage);
     if (ws->chain_error) (void)hipHostFree(ws->chain_error);
@@ -2046,6 +2048,141 @@ int btba_ransac_reference_uniforms(uint64_t seed, int n_trials, float *u_out)
 {
     if (n_trials < 0 || (n_trials && !u_out)) return BTBA_EINVAL;
     xorwow::ransac_uniform_table(seed, n_trials, u_out);
+    return BTBA_OK;
+}
+
+void btba_match_params_default(btba_match_params *p)
+{
+    if (!p) return;
+    p->k = 5;                                                         // FeatureManager.cpp:262 (k_near)
+    p->mutual = 1;                                                    // config_ycbineoat.yml:47
+    p->max_dist_neighbor = 0.03f;
+    p->cos_max_normal_neighbor = (float)std::cos(45.0f / 180.0 * M_PI);
+    p->max_dist_no_neighbor = 0.02f;
+    p->cos_max_normal_no_neighbor = (float)std::cos(45.0f / 180.0 * M_PI);
+    p->min_z = 0.1f;                                                  // FeatureManager.cpp:319
+}
+
+int btba_match_capacity(const btba_match_params *prm, int n_frames, int H, int W, int D, const int32_t *n_kpts,
+                        int n_pairs, const int32_t *pairs, int64_t *capacity_out)
+{
+    if (!prm || prm->k < 1 || prm->k > kMatchKMax || n_frames < 1 || H < 1 || W < 1 || D < 4 || D > kMatchMaxD || D % 4 || !n_kpts || n_pairs < 0 ||
+        (n_pairs && !pairs) || !capacity_out)
+        return BTBA_EINVAL;
+    for (int f = 0; f < n_frames; f++)
+        if (n_kpts[f] < 0 || n_kpts[f] > kMatchMaxKpts) return BTBA_EINVAL;
+    int64_t cap = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        const int a = pairs[2 * p], b = pairs[2 * p + 1];
+        if (a < 0 || a >= n_frames || b < 0 || b >= n_frames || a == b) return BTBA_EINVAL;
+        cap += n_kpts[a] + (prm->mutual ? n_kpts[b] : 0);
+    }
+    if (cap > INT_MAX) return BTBA_EINVAL;                            // query and output positions are int32 on the device
+    *capacity_out = cap;
+    return BTBA_OK;
+}
+
+int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int device_resident, int n_frames, int H, int W,
+                     const float *K, const float *const *desc_dev, int D, const float *const *kpts_dev,
+                     const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev, const float *poses,
+                     const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
+                     btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, int32_t *n_out)
+{
+    // every argument is checked before the first HIP call
+    int64_t cap = 0;
+    int rc = btba_match_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, &cap);
+    if (rc) return rc;
+    if (!ws || !K || !desc_dev || !kpts_dev || !depth_dev || !normal_dev || !poses || !frame_ids || (n_pairs && !n_out) || (cap && !matches_out))
+        return BTBA_EINVAL;
+    std::vector<char> used(n_frames, 0);
+    for (int p = 0; p < n_pairs; p++) used[pairs[2 * p]] = used[pairs[2 * p + 1]] = 1;
+    auto misaligned = [](const void *q, size_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
+    for (int f = 0; f < n_frames; f++)
+        if (used[f] && n_kpts[f] > 0 &&
+            (!desc_dev[f] || !kpts_dev[f] || !depth_dev[f] || !normal_dev[f] || misaligned(desc_dev[f], 16) || misaligned(kpts_dev[f], 8) || misaligned(normal_dev[f], 16)))
+            return BTBA_EINVAL;
+    if (n_pairs == 0) return BTBA_OK;
+    DeviceGuard device_guard(ws);
+
+    // host tables: frames, pairs (thresholds chosen by frame ids, FeatureManager.cpp:259)
+    std::vector<MatchFrame> fr(n_frames);
+    int n_norms = 0, max_n = 0;
+    for (int f = 0; f < n_frames; f++) {
+        MatchFrame &m = fr[f];
+        m = MatchFrame{};
+        m.n = used[f] ? n_kpts[f] : 0;
+        m.desc = desc_dev[f]; m.kpts = reinterpret_cast<const float2 *>(kpts_dev[f]);
+        m.depth = depth_dev[f]; m.normal = reinterpret_cast<const float4 *>(normal_dev[f]);
+        m.norm_off = n_norms;
+        n_norms += m.n;
+        max_n = std::max(max_n, m.n);
+        for (int k = 0; k < 12; k++) m.pose[k] = poses[16 * f + k];
+    }
+    std::vector<MatchPair> pt(n_pairs);
+    int qbase = 0, max_q = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        const int a = pairs[2 * p], b = pairs[2 * p + 1];
+        const bool neighbor = std::abs((long long)frame_ids[a] - (long long)frame_ids[b]) == 1;
+        pt[p] = MatchPair{ a, b, qbase, 0, neighbor ? prm->max_dist_neighbor : prm->max_dist_no_neighbor,
+                           neighbor ? prm->cos_max_normal_neighbor : prm->cos_max_normal_no_neighbor, 0.0f, 0.0f };
+        const int nq = fr[a].n + (prm->mutual ? fr[b].n : 0);
+        qbase += nq;
+        max_q = std::max(max_q, nq);
+    }
+    const size_t Q = (size_t)qbase;
+    const bool dev = device_resident != 0;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t o = 0;
+    const size_t o_fr = o; o += al(sizeof(MatchFrame) * n_frames);
+    const size_t o_pr = o; o += al(sizeof(MatchPair) * n_pairs);
+    const size_t o_nrm = o; o += al(sizeof(float) * (n_norms ? n_norms : 1));
+    const size_t o_cand = o; o += al(sizeof(MatchCand) * prm->k * (Q ? Q : 1));
+    const size_t o_sel = o; o += al(sizeof(int) * (Q ? Q : 1));
+    const size_t o_pos = o; o += al(sizeof(int) * (Q ? Q : 1));
+    const size_t o_cnt = o; o += al(sizeof(int) * n_pairs);
+    const size_t o_off = o; o += al(sizeof(int) * n_pairs);
+    const size_t o_out = o; o += dev ? 0 : al(sizeof(btba_match) * (Q ? Q : 1));
+    const size_t o_pa = o; o += (dev || !ptsA_model_out) ? 0 : al(16 * (Q ? Q : 1));
+    const size_t o_pb = o; o += (dev || !ptsB_model_out) ? 0 : al(16 * (Q ? Q : 1));
+    if ((rc = ws->match.ensure(o))) return rc;
+    unsigned char *base = ws->match.as<unsigned char>();
+    HIP_TRY(hipMemcpyAsync(base + o_fr, fr.data(), sizeof(MatchFrame) * n_frames, hipMemcpyHostToDevice, ws->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_pr, pt.data(), sizeof(MatchPair) * n_pairs, hipMemcpyHostToDevice, ws->stream));
+
+    MatchDims M{};
+    M.W = W; M.H = H; M.D = D; M.k = prm->k; M.mutual = prm->mutual ? 1 : 0; M.min_z = prm->min_z;
+    float intr[4];
+    scaled_intrinsics(H, W, H, W, K, intr, &M.Kinv);                 // btba_depth_to_normals' inverse: the same camera-space points
+    const MatchFrame *dF = reinterpret_cast<const MatchFrame *>(base + o_fr);
+    const MatchPair *dP = reinterpret_cast<const MatchPair *>(base + o_pr);
+    float *d_nrm = reinterpret_cast<float *>(base + o_nrm);
+    MatchCand *d_cand = reinterpret_cast<MatchCand *>(base + o_cand);
+    int *d_sel = reinterpret_cast<int *>(base + o_sel), *d_pos = reinterpret_cast<int *>(base + o_pos);
+    int *d_cnt = reinterpret_cast<int *>(base + o_cnt), *d_off = reinterpret_cast<int *>(base + o_off);
+    btba_match *d_out = dev ? matches_out : reinterpret_cast<btba_match *>(base + o_out);
+    float4 *d_pa = dev ? reinterpret_cast<float4 *>(ptsA_model_out) : (ptsA_model_out ? reinterpret_cast<float4 *>(base + o_pa) : nullptr);
+    float4 *d_pb = dev ? reinterpret_cast<float4 *>(ptsB_model_out) : (ptsB_model_out ? reinterpret_cast<float4 *>(base + o_pb) : nullptr);
+    if (max_n > 0) {
+        k_match_norms<<<dim3((max_n + 255) / 256, n_frames), 256, 0, ws->stream>>>(dF, D, d_nrm);
+        k_match_topk<<<dim3(n_pairs, (max_n + kMatchRows - 1) / kMatchRows, 1 + M.mutual), 256, 0, ws->stream>>>(M, dF, dP, d_nrm, d_cand);
+    }
+    k_match_select<<<n_pairs, 256, 0, ws->stream>>>(M, dF, dP, d_cand, d_sel, d_pos, d_cnt);
+    k_match_offsets<<<1, 256, 0, ws->stream>>>(n_pairs, d_cnt, d_off);
+    if (max_q > 0)
+        k_match_pack<<<dim3(n_pairs, (max_q + 255) / 256), 256, 0, ws->stream>>>(M, dF, dP, d_cand, d_sel, d_pos, d_off, d_out, d_pa, d_pb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(n_out, d_cnt, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, ws->stream));
+    HIP_TRY(hipStreamSynchronize(ws->stream));                       // n_out valid; the host tables above may go
+    if (!dev) {
+        size_t total = 0;
+        for (int p = 0; p < n_pairs; p++) total += (size_t)n_out[p];
+        if (total) {
+            HIP_TRY(hipMemcpyAsync(matches_out, d_out, sizeof(btba_match) * total, hipMemcpyDeviceToHost, ws->stream));
+            if (d_pa) HIP_TRY(hipMemcpyAsync(ptsA_model_out, d_pa, 16 * total, hipMemcpyDeviceToHost, ws->stream));
+            if (d_pb) HIP_TRY(hipMemcpyAsync(ptsB_model_out, d_pb, 16 * total, hipMemcpyDeviceToHost, ws->stream));
+            HIP_TRY(hipStreamSynchronize(ws->stream));
+        }
+    }
     return BTBA_OK;
 }
 

@@ -374,3 +374,60 @@ class SyntheticFeatureManager:
         if 5 <= keep.sum() < len(keep):
             pose = solve_rigid_transform_between_points(src[keep], dst[keep])
         return pose
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Keypoints and descriptors on a make_problem scene: the input of btba_match_pairs (bundletrack_amd/matching.py).
+# ---------------------------------------------------------------------------------------------------------
+
+@dataclass
+class KeypointScene:
+    kpts: list                    # per frame float32 [n_k, 2]: (x, y) full-resolution pixels
+    desc: list                    # per frame float32 [n_k, D]: unit descriptors
+    landmark: list                # per frame int32 [n_k]: planted landmark of every keypoint, -1 for a distractor
+    landmarks_model: np.ndarray   # [L, 3] model-frame landmark positions
+
+
+def make_keypoints(pb: Problem, n_landmarks: int = 600, n_distractors: int = 100, *, D: int = 256, desc_noise: float = 0.03,
+                   px_noise: float = 0.2, seed: int = 0, frames=None) -> KeypointScene:
+    """Plant `n_landmarks` surface points of the scene's object and observe them in every frame that sees them: a keypoint at the
+    projection (+ N(0, px_noise) pixels) whose descriptor is the landmark's random unit vector + N(0, desc_noise) per component,
+    renormalised (D = 256 is LF-Net's desc_dim).  `n_distractors` keypoints at random pixels with random unit descriptors are added
+    per frame, and every frame's keypoints are shuffled.  Uses its own generator: make_problem's streams are untouched."""
+    if pb.depth is None:
+        raise ValueError("make_keypoints needs a full-resolution scene (make_problem(..., full_res=True))")
+    rng = np.random.default_rng([seed, 0x6b70])
+    frames = range(pb.n_frames) if frames is None else frames
+    K = pb.K.astype(np.float64)
+    pts, nrm = _sample_surface(rng, n_landmarks)
+    base = rng.normal(size=(n_landmarks, D))
+    base /= np.linalg.norm(base, axis=1, keepdims=True)
+    out = KeypointScene([], [], [], pts)
+    for k in frames:
+        T = pb.poses_gt[k]
+        centre = T[:3, 3]
+        cam = (pts - centre) @ T[:3, :3]                               # model -> camera: R^T (p - t)
+        z = cam[:, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            uv = np.stack([K[0, 0] * cam[:, 0] / z + K[0, 2], K[1, 1] * cam[:, 1] / z + K[1, 2]], 1)
+        uv += rng.normal(scale=px_noise, size=uv.shape)
+        facing = ((centre - pts) * nrm).sum(1) > 0.02
+        inside = (z > 0.1) & (uv[:, 0] >= 1) & (uv[:, 0] <= pb.W - 2) & (uv[:, 1] >= 1) & (uv[:, 1] <= pb.H - 2)
+        vis = facing & inside
+        ui = np.clip(np.round(uv[:, 0]), 0, pb.W - 1).astype(int)
+        vi = np.clip(np.round(uv[:, 1]), 0, pb.H - 1).astype(int)
+        vis &= np.abs(pb.depth[k][vi, ui] - z) < 0.005                 # the rendered surface is there (not an edge pixel)
+        ids = np.nonzero(vis)[0]
+        d = base[ids] + rng.normal(scale=desc_noise, size=(len(ids), D))
+        xy = uv[ids]
+        dd = rng.normal(size=(n_distractors, D))
+        dxy = np.stack([rng.uniform(0, pb.W - 1, n_distractors), rng.uniform(0, pb.H - 1, n_distractors)], 1)
+        d = np.concatenate([d, dd])
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        xy = np.concatenate([xy, dxy])
+        lm = np.concatenate([ids, -np.ones(n_distractors, np.int64)])
+        perm = rng.permutation(len(lm))
+        out.kpts.append(xy[perm].astype(np.float32))
+        out.desc.append(d[perm].astype(np.float32))
+        out.landmark.append(lm[perm].astype(np.int32))
+    return out

@@ -476,6 +476,68 @@ BTBA_API int btba_ransac_pairs(btba_workspace *ws, int n_pairs, const float *pts
  * 2^67-step subsequence jump as a GF(2) matrix power (bundletrack_amd/csrc/btba_xorwow.hpp).  BTBA_EINVAL on bad arguments. */
 BTBA_API int btba_ransac_reference_uniforms(uint64_t seed, int n_trials, float *u_out);
 
+/* ---- descriptor matching (the step before RANSAC) ---------------------------------------------------------------
+ * Replaces SiftManager::findCorresbyNN / findCorresbyNNMultiPair (src/FeatureManager.cpp:247-437: OpenCV's brute-force
+ * kNN matcher, pruneMatches, collectMutualMatches) for many frame pairs in one call.  For every pair (A, B), A first:
+ *   1. kNN A -> B: for every keypoint i of A the min(k, nB) keypoints of B nearest in L2, ascending (d2, index in B).
+ *   2. Gate: walk i's neighbours in that order and keep the FIRST j that passes, then stop.  Both keypoints are rounded
+ *      with roundf (halves away from zero) and must land in 0 <= u < W, 0 <= v < H; the camera-space points there (the
+ *      ones btba_depth_to_normals writes to xyz_dev, bit for bit) must both have z >= 0.1 (params.min_z); points
+ *      (R p + t) and normals (R n) move into the model frame with the frames' poses; reject when |PA - PB| > max_dist
+ *      or dot(normalize(nA), normalize(nB)) < cos_max_normal (a zero normal stays zero).  Pairs with |idA - idB| == 1
+ *      use the *_neighbor thresholds, all others the *_no_neighbor ones.
+ *   3. With params.mutual: the same with the roles swapped (B -> A).
+ *   4. Output: the A -> B matches in ascending A index, then the B -> A matches in ascending B index.  No consistency
+ *      filter and no de-duplication (the reference's collectMutualMatches has neither): RANSAC's triples index this list.
+ * Distance arithmetic (fixed, so that a CPU restatement reproduces the output bit for bit):
+ *   na = sum_k a_k^2 and dot = sum_k a_k b_k are each ONE sequential fmaf chain over k = 0 .. D-1 from +0;
+ *   d2 = fmaf(-2, dot, na + nb), replaced by +0 unless it is > 0 (negative, -0 and NaN become +0);
+ *   rank on (d2, train index); dist = sqrtf(d2).  d2 is symmetric, B -> A ranks the same numbers.
+ * Gate arithmetic: uncontracted fp32 in the order written: P_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3,
+ * N_r = (T_r0 nx + T_r1 ny) + T_r2 nz, |PA - PB| = sqrtf((dx dx + dy dy) + dz dz), normalize = n / sqrtf(|n|^2) when |n|^2 > 0.
+ *
+ *   desc_dev[f]   : device float [n_kpts[f]][D] descriptors, D a multiple of 4, 4 .. 512
+ *   kpts_dev[f]   : device float2 [n_kpts[f]] keypoints (x, y) in full-resolution pixels
+ *   n_kpts[f]     : 0 .. 8192 (host)
+ *   depth_dev[f], normal_dev[f] : device float [H*W] and float4 [H*W] maps of the frame (btba_depth_to_normals' format)
+ *   poses         : host float [n_frames][16] row-major camera -> model;  frame_ids: host int32 [n_frames] (Frame::_id)
+ *   pairs         : host int32 [n_pairs][2] frame indices (A first, A != B); frames may belong to many windows
+ *   matches_out   : btba_match records of all pairs back to back: pair p starts at sum_{q<p} n_out[q].  Capacity: the
+ *                   bound of btba_match_capacity, sum (nA + nB) (sum nA without mutual)
+ *   ptsA_model_out / ptsB_model_out : NULL, or float4 (x, y, z, 1) model-frame points of every match, in the same layout:
+ *                   exactly what btba_ransac_pairs_ex takes (the arithmetic of the host transform around it)
+ *   n_out         : host int32 [n_pairs], valid on return
+ * device_resident = 1: matches_out and ptsA/B_model_out are device pointers; 0: host pointers.  Synchronous on the
+ * workspace stream.  Scratch is grow-only in the workspace. */
+typedef struct btba_match_params {
+    int32_t k;                              /* neighbours per query, 1 .. 8 (default 5) */
+    int32_t mutual;                         /* 1 (default): also match B -> A */
+    float max_dist_neighbor;                /* 0.03 m  (config_ycbineoat.yml feature_corres) */
+    float cos_max_normal_neighbor;          /* (float)cos(45 / 180 pi) */
+    float max_dist_no_neighbor;             /* 0.02 m */
+    float cos_max_normal_no_neighbor;       /* (float)cos(45 / 180 pi) */
+    float min_z;                            /* 0.1 m: camera-space z a matched point needs */
+} btba_match_params;
+
+typedef struct btba_match {                 /* 40 bytes */
+    int32_t idx_a, idx_b;                   /* keypoint indices in A and in B */
+    float dist;                             /* descriptor distance sqrtf(d2) */
+    int32_t dir;                            /* 0: found A -> B, 1: found B -> A */
+    float ptA_cam[3], ptB_cam[3];           /* camera-space points at the rounded keypoints */
+} btba_match;
+
+BTBA_API void btba_match_params_default(btba_match_params *p);
+/* Validates every host-side argument of btba_match_pairs (BTBA_EINVAL: params NULL, k outside 1..8, n_frames < 1, H or W < 1,
+ * D not a multiple of 4 or outside 4..512, n_kpts NULL or a count outside 0..8192, n_pairs < 0, pairs NULL, a pair with A == B or
+ * an index out of range) and returns the output capacity the call needs in *capacity_out.  Host-only: no GPU, no workspace. */
+BTBA_API int btba_match_capacity(const btba_match_params *params, int n_frames, int H, int W, int D, const int32_t *n_kpts,
+                                 int n_pairs, const int32_t *pairs, int64_t *capacity_out);
+BTBA_API int btba_match_pairs(btba_workspace *ws, const btba_match_params *params, int device_resident, int n_frames, int H, int W,
+                              const float *K_rowmajor, const float *const *desc_dev, int D, const float *const *kpts_dev,
+                              const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev, const float *poses,
+                              const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
+                              btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, int32_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "btba_process_depth", "btba_depth_to_normals",
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
+    "btba_mask_params_default", "btba_apply_masks",
 ]
 
 # btba_match (include/btba.h): one descriptor match, 40 bytes
@@ -65,6 +66,11 @@ class MatchParams(C.Structure):
     """btba_match_params (include/btba.h)."""
     _fields_ = [("k", C.c_int32), ("mutual", C.c_int32), ("max_dist_neighbor", C.c_float), ("cos_max_normal_neighbor", C.c_float),
                 ("max_dist_no_neighbor", C.c_float), ("cos_max_normal_no_neighbor", C.c_float), ("min_z", C.c_float)]
+
+
+class MaskParams(C.Structure):
+    """btba_mask_params (include/btba.h)."""
+    _fields_ = [("largest_component_hull", C.c_int32), ("dilate", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -221,6 +227,10 @@ def lib() -> C.CDLL:
         L.btba_match_pairs.argtypes = [C.c_void_p, C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_mask_params_default.argtypes = [C.POINTER(MaskParams)]
+        L.btba_mask_params_default.restype = None
+        L.btba_apply_masks.argtypes = [C.c_void_p, C.POINTER(MaskParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -244,6 +254,17 @@ def match_params(**kw) -> MatchParams:
     """btba_match_params_default with fields overridden by keyword."""
     p = MatchParams()
     lib().btba_match_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def mask_params(**kw) -> MaskParams:
+    """btba_mask_params_default with fields overridden by keyword."""
+    p = MaskParams()
+    lib().btba_mask_params_default(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)

@@ -51,6 +51,8 @@ class FrameRef:
     color_gpu: object = None
     kpts_gpu: object = None              # [n, 2] float32 CUDA tensor: keypoints (x, y) in full-resolution pixels (Frame::_keypts)
     desc_gpu: object = None              # [n, D] float32 CUDA tensor: their descriptors (Frame::_feat_des_gpu)
+    mask_gpu: object = None              # [H, W] uint8 CUDA tensor: the raw object mask, nonzero = foreground (the mask PNG)
+    fg_mask_gpu: object = None           # [H, W] uint8 CUDA tensor: the final 0 / 1 mask segmentation made of it (Frame::_fg_mask)
 
     def __hash__(self):
         return hash(self.id)
@@ -206,8 +208,9 @@ def load_pose_txt(path: str) -> np.ndarray:
 
 
 class Bundler:
-    """Bundler::processNewFrame (src/Bundler.cpp:52-183) from the point where a frame has a mask and features:
-    pose initialisation from the previous frame, sliding window, keyframe subset, bundle adjustment through
+    """Bundler::processNewFrame (src/Bundler.cpp:52-183) from the point where a frame has depth, normals and features:
+    the segmentation by its mask when `mask_gpu` is set (segmentation.apply_masks on `mask_workspace` or the optimiser's
+    workspace; the ROI gate then sees the real ROI), pose initialisation from the previous frame, sliding window, keyframe subset, bundle adjustment through
     an injected `optimizer` (anything with OptimizerGpu.optimizeFrames' signature) and keyframe insertion.
 
     feature_manager must offer (the slice of SiftManager the caller uses):
@@ -218,8 +221,12 @@ class Bundler:
     """
 
     def __init__(self, optimizer, feature_manager, K, H, W, *, window_size=2, max_BA_frames=15, min_rot_deg=10.0,
-                 min_feat_num=0, min_fm_edges_newframe=5, pose_dir=None, persistent_frame_cache=False):
+                 min_feat_num=0, min_fm_edges_newframe=5, pose_dir=None, persistent_frame_cache=False,
+                 mask_largest_component_hull=False, mask_dilate=5, mask_workspace=None):
         self.opt, self.fm = optimizer, feature_manager
+        self.mask_largest_component_hull = bool(mask_largest_component_hull)     # the reference's `data_dir contains "NOCS"` (Frame.cpp:255,280)
+        self.mask_dilate = int(mask_dilate)                                      # MORPH_RECT 5 x 5 (Frame.cpp:310)
+        self.mask_workspace = mask_workspace                                     # None: the optimiser's workspace
         self.K, self.H, self.W = np.asarray(K, np.float32), int(H), int(W)
         self.window_size = int(window_size)                        # bundle.window_size (config_ycbineoat.yml:26 ships 2)
         self.min_fm_edges_newframe = int(min_fm_edges_newframe)    # bundle.min_fm_edges_newframe
@@ -246,6 +253,8 @@ class Bundler:
         if last is not None:
             frame.id = last.id + 1
             frame.pose_in_model = np.array(last.pose_in_model, np.float32)             # :78-79
+        if frame.mask_gpu is not None:                                                 # :80/:84 segmentationByMaskFile (minus the PNG read)
+            self.segment(frame)
         if frame.roi[1] - frame.roi[0] < 10 or frame.roi[3] - frame.roi[2] < 10:        # :88-93: empty cloud -> FAIL and a plain return
             frame.status = "FAIL"
             return
@@ -280,6 +289,15 @@ class Bundler:
         self.memory.check_and_add_keyframe(frame)
         if self.pose_dir is not None:
             self.save_newframe_result()
+
+    def segment(self, frame: FrameRef) -> None:
+        """Frame::segmentationByMaskFile on the GPU (btba_apply_masks): frame.depth_gpu, normal_gpu, color_gpu zeroed outside
+        the final mask in place, frame.roi and frame.fg_mask_gpu set."""
+        from .segmentation import apply_masks
+        ws = self.mask_workspace if self.mask_workspace is not None else getattr(self.opt, "workspace", None)
+        if ws is None:
+            raise RuntimeError("Bundler.segment needs a workspace: pass mask_workspace= or an optimizer with one")
+        apply_masks(ws, [frame], [frame.mask_gpu], largest_component_hull=self.mask_largest_component_hull, dilate=self.mask_dilate)
 
     def _evict_cached(self, frame) -> None:
         """A frame dropped after BA has cached it must not leave its (z, n) cache behind under an id the next frame reuses."""

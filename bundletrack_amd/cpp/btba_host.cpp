@@ -382,6 +382,38 @@ void FeatureManager::findCorresbyNN(btba_workspace *ws, const std::shared_ptr<Fr
     if (is_neighbor && countInlierCorres(frameA, frameB) < 5) frameA->_status = Frame::FAIL;      // :280-285
 }
 
+void segmentationByMaskMultiFrame(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, bool largest_component_hull, int dilate)
+{
+    if (frames.empty()) return;
+    const int n = (int)frames.size(), H = frames[0]->_H, W = frames[0]->_W;
+    std::vector<const uint8_t *> mask(n);
+    std::vector<float *> depth(n), normal(n);
+    std::vector<uint8_t *> color(n), out(n);
+    for (int k = 0; k < n; k++) {
+        const Frame &f = *frames[k];
+        if (f._H != H || f._W != W) throw Error(BTBA_EINVAL, "segmentationByMask: frames of different sizes");
+        mask[k] = f._mask_gpu;
+        depth[k] = f._depth_gpu;
+        normal[k] = reinterpret_cast<float *>(f._normal_gpu);
+        color[k] = reinterpret_cast<uint8_t *>(f._color_gpu);
+        out[k] = f._fg_mask_gpu;
+    }
+    btba_mask_params prm;
+    btba_mask_params_default(&prm);
+    prm.largest_component_hull = largest_component_hull ? 1 : 0;
+    prm.dilate = dilate;
+    std::vector<float> roi(4 * (size_t)n);
+    const int rc = btba_apply_masks(ws, &prm, n, H, W, mask.data(), depth.data(), normal.data(), color.data(), out.data(), roi.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_apply_masks");
+    for (int k = 0; k < n; k++)
+        for (int q = 0; q < 4; q++) frames[k]->_roi[q] = roi[4 * k + q];
+}
+
+void segmentationByMask(btba_workspace *ws, const std::shared_ptr<Frame> &frame, bool largest_component_hull, int dilate)
+{
+    segmentationByMaskMultiFrame(ws, { frame }, largest_component_hull, dilate);
+}
+
 // ---- Bundler ---------------------------------------------------------------------------------------------------
 Bundler::Bundler(std::shared_ptr<Config> yml1, std::shared_ptr<FeatureManager> fm, const Matrix3f &K1, int H1, int W1, OptimizeFn optimize)
     : yml(yml1 ? std::move(yml1) : std::make_shared<Config>()), _fm(std::move(fm)), memory(yml), K(K1), H(H1), W(W1), optimize_(std::move(optimize))
@@ -397,6 +429,15 @@ void Bundler::processNewFrame(std::shared_ptr<Frame> frame)
         last_frame = _frames.back();
         frame->_id = last_frame->_id + 1;
         frame->_pose_in_model = last_frame->_pose_in_model;
+    }
+    if (frame->_mask_gpu) {                                                      // :80/:84 segmentationByMaskFile
+        if (frame->_H == 0 && frame->_W == 0) { frame->_H = H; frame->_W = W; }
+        btba_workspace *ws = mask_ws;
+        if (!ws) {
+            if (!own_opt_) own_opt_ = std::make_unique<OptimizerGpu>(yml);
+            ws = own_opt_->workspace();
+        }
+        segmentationByMask(ws, frame, yml->mask_largest_component_hull, yml->mask_dilate);
     }
     if (frame->_roi[1] - frame->_roi[0] < 10 || frame->_roi[3] - frame->_roi[2] < 10) {      // :88-93: "cloud is empty, marked FAIL" -- a plain return:
         frame->_status = Frame::FAIL;                                            // no forgetFrame, no re-initialisation request

@@ -61,6 +61,8 @@ struct Config {
     bool feature_corres_mutual = true;            // feature_corres.* :46-51
     float feature_corres_max_dist_no_neighbor = 0.02f, feature_corres_max_normal_no_neighbor = 45.0f;
     float feature_corres_max_dist_neighbor = 0.03f, feature_corres_max_normal_neighbor = 45.0f;
+    bool mask_largest_component_hull = false;     // the reference's `data_dir contains "NOCS"` (Frame.cpp:255,280): largest component -> hull -> fill
+    int mask_dilate = 5;                          // MORPH_RECT 5 x 5 (Frame.cpp:310)
     std::string pose_dir;                         // debug_dir + "/poses/" (:5; Bundler.cpp:366); empty = do not write pose files
 };
 
@@ -113,7 +115,16 @@ struct Frame {                                   // the fields of Frame (src/Fra
     float2 *_kpts_gpu = nullptr;                 // [_n_keypts] keypoints (x, y) on the device (the reference keeps cv::KeyPoint on the host)
     float *_feat_des_gpu = nullptr;              // [_n_keypts][_feat_dim] descriptors on the device (Frame::_feat_des_gpu)
     int _feat_dim = 0;
+    uint8_t *_mask_gpu = nullptr;                // [_H * _W] the raw object mask on the device, nonzero = foreground (the mask PNG); null = none
+    uint8_t *_fg_mask_gpu = nullptr;             // [_H * _W] caller-owned: receives the final 0 / 1 mask (Frame::_fg_mask); null = not kept
 };
+
+// Frame::segmentationByMaskFile (Frame.cpp:236-373) minus the PNG read, on btba_apply_masks: optionally the largest 8-connected
+// component's filled convex hull, a dilate x dilate dilation, colour / depth / normals zeroed outside the mask in place, _roi set and
+// the final mask written to _fg_mask_gpu when that is set.  Frames need _mask_gpu, _depth_gpu, _normal_gpu, _H, _W (one size per
+// call); _color_gpu may be null.  Needs the GPU; synchronous (the ROIs come back to the host).
+void segmentationByMask(btba_workspace *ws, const std::shared_ptr<Frame> &frame, bool largest_component_hull, int dilate = 5);
+void segmentationByMaskMultiFrame(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, bool largest_component_hull, int dilate = 5);
 
 // Utils::solveRigidTransformBetweenPoints (Utils.cpp:180-214): the rigid transform points1 -> points2 (n x 3 each, xyz
 // triples), identity when fewer than 3 points, a non-orthonormal V U^T or a non-finite result.
@@ -175,8 +186,9 @@ public:
     void findCorresbyNN(btba_workspace *ws, const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB);
 };
 
-// Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its mask, depth and normals on the device:
-// pose initialisation from the previous frame, the sliding window, the keyframe subset, bundle adjustment, keyframe insertion,
+// Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its depth and normals on the device: the
+// segmentation by its mask when _mask_gpu is set (segmentationByMask on mask_ws, or on the workspace of the Bundler's own
+// OptimizerGpu when mask_ws is null), pose initialisation from the previous frame, the sliding window, the keyframe subset, bundle adjustment, keyframe insertion,
 // the pose file.  `optimize` defaults to one persistent OptimizerGpu (the reference constructs a new one per call, :349);
 // tests inject a CPU stand-in with the same signature.
 class Bundler {
@@ -194,6 +206,7 @@ public:
     int H = 0, W = 0;
     int n_ba_calls = 0;
     Window last_window;                                             // what the last optimizeGPU marshalled
+    btba_workspace *mask_ws = nullptr;                              // the caller's workspace for the segmentation (not owned)
 
     Bundler(std::shared_ptr<Config> yml1, std::shared_ptr<FeatureManager> fm, const Matrix3f &K1, int H1, int W1, OptimizeFn optimize = {});
     void processNewFrame(std::shared_ptr<Frame> frame);             // :56-183

@@ -25,6 +25,7 @@
 #include "btba_ransac.hpp"
 #include "btba_xorwow.hpp"
 #include "btba_match.hpp"
+#include "btba_mask.hpp"
 
 using namespace btba;
 
@@ -166,6 +167,7 @@ struct btba_workspace {
     DevBuf ransac_u;                                        // the reference's sample stream: n_trials x 3 uniforms (btba_xorwow.hpp), kept per (seed, n_trials)
     std::vector<float> ransac_u_host;
     DevBuf match;                                           // btba_match_pairs: tables, norms, candidate lists, selections, counts, host-form staging
+    DevBuf mask;                                            // btba_apply_masks: labels, counts, argmax keys, row extents, spans, hull stacks, ROI slots
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;
@@ -305,7 +307,7 @@ void btba_workspace_destroy(btba_workspace *ws)
     for (auto e : ws->event_pool) (void)hipEventDestroy(e);
     DevBuf *bufs[] = { &ws->x, &ws->T, &ws->Tinv, &ws->sparse_part, &ws->dense_part, &ws->pairsum, &ws->dense_pairs, &ws->ptrs, &ws->big_A, &ws->solve_tab,
                        &ws->corr, &ws->offsets, &ws->poses, &ws->campos, &ws->normals, &ws->nvalid, &ws->valid_lists, &ws->valid_counts, &ws->block_ranges,
-                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens };
+                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->mask, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens };
     for (auto b : bufs) b->release();
     if (ws->corr_stage) (void)hipHostFree(ws->corr_stage);
     if (ws->chain_error) (void)hipHostFree(ws->chain_error);
@@ -2181,6 +2183,89 @@ int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int devic
             if (d_pa) HIP_TRY(hipMemcpyAsync(ptsA_model_out, d_pa, 16 * total, hipMemcpyDeviceToHost, ws->stream));
             if (d_pb) HIP_TRY(hipMemcpyAsync(ptsB_model_out, d_pb, 16 * total, hipMemcpyDeviceToHost, ws->stream));
             HIP_TRY(hipStreamSynchronize(ws->stream));
+        }
+    }
+    return BTBA_OK;
+}
+
+void btba_mask_params_default(btba_mask_params *p)
+{
+    if (!p) return;
+    p->largest_component_hull = 0;                                    // config_ycbineoat.yml: data_dir without "NOCS"
+    p->dilate = 5;                                                    // Frame.cpp:310 (MORPH_RECT 5 x 5)
+}
+
+int btba_apply_masks(btba_workspace *ws, const btba_mask_params *prm, int n_frames, int H, int W,
+                     const uint8_t *const *mask_dev, float *const *depth_dev, float *const *normal_dev,
+                     uint8_t *const *color_dev, uint8_t *const *mask_out_dev, float *roi_out)
+{
+    // every argument is checked before the first HIP call
+    if (!ws || !prm || prm->dilate < 1 || prm->dilate > 2 * kMaskMaxR + 1 || prm->dilate % 2 == 0 || n_frames < 1 || H < 1 || W < 1 ||
+        (int64_t)H * W >= ((int64_t)1 << 31) || !mask_dev || !depth_dev || !normal_dev)
+        return BTBA_EINVAL;
+    for (int f = 0; f < n_frames; f++)
+        if (!mask_dev[f] || !depth_dev[f] || !normal_dev[f] || (reinterpret_cast<uintptr_t>(normal_dev[f]) & 15) ||
+            (color_dev && color_dev[f] && (reinterpret_cast<uintptr_t>(color_dev[f]) & 3)) ||
+            (mask_out_dev && mask_out_dev[f] && static_cast<const void *>(mask_out_dev[f]) == static_cast<const void *>(mask_dev[f])))
+            return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+    const bool hull = prm->largest_component_hull != 0;
+    const int r = prm->dilate / 2, chunk = std::min(n_frames, kMaskChunk);
+    const size_t HW = (size_t)H * W;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t o = 0;
+    const size_t o_roi = o; o += roi_out ? al(sizeof(int) * 4 * n_frames) : 0;
+    const size_t o_lab = o; o += hull ? al(sizeof(int) * chunk * HW) : 0;
+    const size_t o_cnt = o; o += hull ? al(sizeof(int) * chunk * HW) : 0;
+    const size_t o_best = o; o += hull ? al(sizeof(unsigned long long) * chunk) : 0;
+    const size_t o_rows = o; o += hull ? al(sizeof(int2) * chunk * (size_t)H) : 0;
+    const size_t o_span = o; o += hull ? al(sizeof(int2) * chunk * (size_t)H) : 0;
+    const size_t o_stk = o; o += (hull && H > kHullLdsMaxH) ? al(sizeof(int2) * chunk * (4 * (size_t)H + 2)) : 0;
+    int rc;
+    if ((rc = ws->mask.ensure(o ? o : 256))) return rc;
+    unsigned char *base = ws->mask.as<unsigned char>();
+    int *d_roi = roi_out ? reinterpret_cast<int *>(base + o_roi) : nullptr;
+    int *d_lab = reinterpret_cast<int *>(base + o_lab), *d_cnt = reinterpret_cast<int *>(base + o_cnt);
+    unsigned long long *d_best = reinterpret_cast<unsigned long long *>(base + o_best);
+    int2 *d_rows = reinterpret_cast<int2 *>(base + o_rows), *d_span = reinterpret_cast<int2 *>(base + o_span), *d_stk = reinterpret_cast<int2 *>(base + o_stk);
+    if (d_roi) HIP_TRY(hipMemsetAsync(d_roi, 0, sizeof(int) * 4 * n_frames, ws->stream));      // the zero start of k_mask_apply's ROI encoding
+    const dim3 lgrid((W + kLabelTile - 1) / kLabelTile, (H + kLabelTile - 1) / kLabelTile, 1), lblock(kLabelTile, kLabelTile);
+    const dim3 agrid((W + kMaskTileW - 1) / kMaskTileW, (H + kMaskTileH - 1) / kMaskTileH, 1), ablock(kMaskTileW, 4);
+    const size_t hull_lds = H <= kHullLdsMaxH ? sizeof(int2) * (5 * (size_t)H + 2) : 0;
+    for (int b0 = 0; b0 < n_frames; b0 += kMaskChunk) {
+        const int nf = std::min(kMaskChunk, n_frames - b0);
+        MaskFrames F{};
+        for (int z = 0; z < nf; z++) {
+            F.mask[z] = mask_dev[b0 + z];
+            F.depth[z] = depth_dev[b0 + z];
+            F.normal[z] = reinterpret_cast<float4 *>(normal_dev[b0 + z]);
+            F.color[z] = color_dev ? reinterpret_cast<uchar4 *>(color_dev[b0 + z]) : nullptr;
+            F.mask_out[z] = mask_out_dev ? mask_out_dev[b0 + z] : nullptr;
+        }
+        dim3 lg = lgrid, ag = agrid;
+        lg.z = ag.z = nf;
+        if (hull) {
+            k_mask_label_local<<<lg, lblock, 0, ws->stream>>>(W, H, F, d_lab, d_cnt, d_best);
+            k_mask_label_merge<<<lg, lblock, 0, ws->stream>>>(W, H, d_lab);
+            k_mask_label_count<<<lg, lblock, 0, ws->stream>>>(W, H, d_lab, d_cnt);
+            k_mask_argmax<<<dim3((unsigned)((HW + 255) / 256), nf), 256, 0, ws->stream>>>((int)HW, d_cnt, d_best);
+            k_mask_rows<<<dim3((H + 3) / 4, nf), 256, 0, ws->stream>>>(W, H, d_lab, d_best, d_rows);
+            k_mask_hull<<<nf, 256, hull_lds, ws->stream>>>(W, H, d_rows, d_stk, d_span);
+            k_mask_apply<true><<<ag, ablock, 0, ws->stream>>>(W, H, r, F, d_span, d_roi, b0);
+        } else {
+            k_mask_apply<false><<<ag, ablock, 0, ws->stream>>>(W, H, r, F, nullptr, d_roi, b0);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (roi_out) {
+        std::vector<int> h(4 * (size_t)n_frames);
+        HIP_TRY(hipMemcpyAsync(h.data(), d_roi, sizeof(int) * h.size(), hipMemcpyDeviceToHost, ws->stream));
+        HIP_TRY(hipStreamSynchronize(ws->stream));
+        for (int f = 0; f < n_frames; f++) {
+            roi_out[4 * f + 0] = (float)(9999 - h[4 * f + 0]);
+            roi_out[4 * f + 1] = (float)h[4 * f + 1];
+            roi_out[4 * f + 2] = (float)(9999 - h[4 * f + 2]);
+            roi_out[4 * f + 3] = (float)h[4 * f + 3];
         }
     }
     return BTBA_OK;

@@ -431,3 +431,44 @@ def make_keypoints(pb: Problem, n_landmarks: int = 600, n_distractors: int = 100
         out.desc.append(d[perm].astype(np.float32))
         out.landmark.append(lm[perm].astype(np.int32))
     return out
+
+
+def make_mask(T_cam2model: np.ndarray, K: np.ndarray, H: int = 480, W: int = 640, *, seed: int = 0, n_blobs: int = 0,
+              n_holes: int = 0, bridge: bool = False) -> np.ndarray:
+    """A segmentation mask the way a tracker's mask file gives it: uint8 [H, W], 255 on the object silhouette (render without
+    background, depth > 0), 0 elsewhere.  Optionally n_blobs disjoint spurious discs away from the object, n_holes small holes
+    punched into it, and a 1-pixel diagonal bridge from the object to one more blob (8-connected only: it joins the two in the
+    8-connected labelling).  Use it with a background=True render of the same pose as the depth the mask is applied to."""
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    depth, _ = render(T_cam2model, K, xs, ys, background=False)
+    m = depth > 0
+    rng = np.random.default_rng(seed)
+    oy, ox = np.nonzero(m)
+    if n_holes and oy.size:
+        for k in rng.choice(oy.size, n_holes):
+            m[max(oy[k] - 1, 0):oy[k] + 2, max(ox[k] - 1, 0):ox[k] + 2] = False
+    near = np.zeros_like(m)
+    if oy.size:
+        near[max(oy.min() - 12, 0):oy.max() + 13, max(ox.min() - 12, 0):ox.max() + 13] = True
+    placed = 0
+    for _ in range(200 * max(n_blobs, 1)):
+        if placed >= n_blobs:
+            break
+        r = int(rng.integers(3, 12))
+        cy, cx = int(rng.integers(r, H - r)), int(rng.integers(r, W - r))
+        disc = (ys - cy) ** 2 + (xs - cx) ** 2 <= r * r
+        grown = (ys - cy) ** 2 + (xs - cx) ** 2 <= (r + 3) ** 2
+        if (grown & (near | m)).any():
+            continue
+        m |= disc
+        near |= grown
+        placed += 1
+    if bridge and oy.size:
+        k = int(np.argmax(ox - oy))                  # the object's pixel furthest towards the top right
+        y, x = int(oy[k]), int(ox[k])
+        n = int(min(40, y - 4, W - 5 - x))
+        for s in range(1, max(n, 0) + 1):            # diagonal steps up and to the right: pixels touch only at corners
+            m[y - s, x + s] = True
+        if n > 0:
+            m[max(y - n - 4, 0):y - n, x + n + 1:x + n + 5] = True
+    return np.where(m, 255, 0).astype(np.uint8)

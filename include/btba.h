@@ -538,6 +538,51 @@ BTBA_API int btba_match_pairs(btba_workspace *ws, const btba_match_params *param
                               const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
                               btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, int32_t *n_out);
 
+/* ---- foreground-mask segmentation (the first step of every frame) ------------------------------------------------
+ * Replaces Frame::segmentationByMaskFile minus the PNG read (src/Frame.cpp:236-373, called first by Bundler::processNewFrame,
+ * src/Bundler.cpp:80,84) for many frames in one call.  Every rule is exact integer logic, so a CPU restatement reproduces the
+ * output bit for bit:
+ *   M0, plain path (largest_component_hull = 0, the shipping YCBInEOAT configuration): M0 = (mask != 0).
+ *   M0, hull path (largest_component_hull = 1, the reference's "data_dir contains NOCS"): the 8-connected components of
+ *       (mask != 0); the one with the most pixels wins, ties to the one whose first pixel in raster (row-major) order comes first
+ *       (how OpenCV and scipy.ndimage.label number components; the reference breaks ties by the iteration order of an
+ *       unordered_map, which is unspecified).  M0(x, y) = 1 iff the integer point (x, y) lies in the CLOSED convex hull of the
+ *       winner's pixel coordinates, decided with integer cross products; a one-point hull or a segment sets its lattice points.
+ *       An empty mask gives M0 = 0.
+ *   Dilation: M(x, y) = OR of M0 over the dilate x dilate square centred at (x, y); pixels outside the image count as 0 (OpenCV's
+ *       default dilation border).
+ *   Invalidation: where M = 0, depth = 0, normal = (0, 0, 0, 0), colour = (0, 0, 0, 0); where M = 1 every map stays bit for bit
+ *       as it was.  (The reference's updateNormalGPU also zeroes normals inside the mask where (double) z <= 0.1.  For a float z
+ *       that holds exactly when z < 0.1f, 0.1f being the smallest float above 0.1: the pixels btba_depth_to_normals already
+ *       gives zero normals, CC.z < 0.1f.)
+ *   ROI: roi_out[f] = (umin, umax, vmin, vmax) over the pixels with M = 1 as floats, started from the reference's
+ *       (9999, 0, 9999, 0) (Frame.cpp:359): (9999, 0, 9999, 0) for an empty mask.
+ * Deliberate differences from the reference:
+ *   - cv::fillConvexPoly rounds span ends and rasterises the outline, so it may also paint pixels whose centres lie up to half
+ *     a pixel outside the hull; the rule above does not.  Unmeasured (no OpenCV to compare with); after the dilation any
+ *     difference can only sit on the outer boundary of the final mask.
+ *   - the reference's _fg_mask keeps dilated grey values; mask_out is 0 / 1.  Only zero against non-zero is ever read
+ *     (Frame.cpp:349,364; Bundler.cpp:389).
+ *
+ *   mask_dev[f]     : device uint8 [H*W], nonzero = foreground (as imread gives it)
+ *   depth_dev[f]    : device float [H*W], zeroed outside the final mask, in place
+ *   normal_dev[f]   : device float4 [H*W] (btba_depth_to_normals' format, 16-byte aligned), zeroed outside, in place
+ *   color_dev       : NULL, or [f] device uchar4 [H*W] (entries may be NULL), zeroed outside, in place
+ *   mask_out_dev    : NULL, or [f] device uint8 [H*W] (entries may be NULL): the final mask as 0 / 1; must not alias mask_dev
+ *   roi_out         : NULL, or host float [n_frames][4].  With roi_out the call is synchronous; without, it is asynchronous
+ *                     on the workspace stream (no host memory is read after it returns).
+ * Scratch (labels, counts, row extents, hull) is grow-only in the workspace.  BTBA_EINVAL: ws or params NULL, dilate even or
+ * outside 1..15, n_frames < 1, H or W < 1, H * W >= 2^31 (the argmax key packs a 32-bit pixel index), NULL mask_dev /
+ * depth_dev / normal_dev or any of their entries, a misaligned normal map, a mask_out entry equal to its mask entry. */
+typedef struct btba_mask_params {
+    int32_t largest_component_hull;  /* 0 (default): YCBInEOAT path; 1: NOCS path (largest 8-connected component -> convex hull -> fill) */
+    int32_t dilate;                  /* side of the square dilation element, odd, 1 .. 15 (default 5; 1 = no dilation) */
+} btba_mask_params;
+BTBA_API void btba_mask_params_default(btba_mask_params *p);
+BTBA_API int btba_apply_masks(btba_workspace *ws, const btba_mask_params *params, int n_frames, int H, int W,
+                              const uint8_t *const *mask_dev, float *const *depth_dev, float *const *normal_dev,
+                              uint8_t *const *color_dev, uint8_t *const *mask_out_dev, float *roi_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_mask_params_default", "btba_apply_masks",
+    "btba_detector_params_default", "btba_detector_transform", "btba_detector_inputs", "btba_detector_keypoints_to_image",
 ]
 
 # btba_match (include/btba.h): one descriptor match, 40 bytes
@@ -71,6 +72,11 @@ class MatchParams(C.Structure):
 class MaskParams(C.Structure):
     """btba_mask_params (include/btba.h)."""
     _fields_ = [("largest_component_hull", C.c_int32), ("dilate", C.c_int32)]
+
+
+class DetectorParams(C.Structure):
+    """btba_detector_params (include/btba.h)."""
+    _fields_ = [("out_size", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -231,6 +237,13 @@ def lib() -> C.CDLL:
         L.btba_mask_params_default.restype = None
         L.btba_apply_masks.argtypes = [C.c_void_p, C.POINTER(MaskParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_detector_params_default.argtypes = [C.POINTER(DetectorParams)]
+        L.btba_detector_params_default.restype = None
+        L.btba_detector_transform.argtypes = [C.POINTER(DetectorParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_detector_inputs.argtypes = [C.c_void_p, C.POINTER(DetectorParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+        L.btba_detector_keypoints_to_image.argtypes = [C.c_void_p, C.POINTER(DetectorParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
         _lib = L
     return _lib
 
@@ -265,6 +278,17 @@ def mask_params(**kw) -> MaskParams:
     """btba_mask_params_default with fields overridden by keyword."""
     p = MaskParams()
     lib().btba_mask_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def detector_params(**kw) -> DetectorParams:
+    """btba_detector_params_default with fields overridden by keyword."""
+    p = DetectorParams()
+    lib().btba_detector_params_default(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)

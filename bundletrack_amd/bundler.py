@@ -210,8 +210,10 @@ def load_pose_txt(path: str) -> np.ndarray:
 class Bundler:
     """Bundler::processNewFrame (src/Bundler.cpp:52-183) from the point where a frame has depth, normals and features:
     the segmentation by its mask when `mask_gpu` is set (segmentation.apply_masks on `mask_workspace` or the optimiser's
-    workspace; the ROI gate then sees the real ROI), pose initialisation from the previous frame, sliding window, keyframe subset, bundle adjustment through
-    an injected `optimizer` (anything with OptimizerGpu.optimizeFrames' signature) and keyframe insertion.
+    workspace; the ROI gate then sees the real ROI), feature detection when a `detector` is given (Bundler.detect: the
+    detector's input and the keypoints' way back on the GPU, the detector itself a callable; an exception from it marks the
+    frame FAIL), pose initialisation from the previous frame, sliding window, keyframe subset, bundle adjustment through an
+    injected `optimizer` (anything with OptimizerGpu.optimizeFrames' signature) and keyframe insertion.
 
     feature_manager must offer (the slice of SiftManager the caller uses):
         find_corres(frameA, frameB)        -> None; fills matches[(frameA.id, frameB.id)] = (ptA_cam, ptB_cam), A newer
@@ -222,8 +224,10 @@ class Bundler:
 
     def __init__(self, optimizer, feature_manager, K, H, W, *, window_size=2, max_BA_frames=15, min_rot_deg=10.0,
                  min_feat_num=0, min_fm_edges_newframe=5, pose_dir=None, persistent_frame_cache=False,
-                 mask_largest_component_hull=False, mask_dilate=5, mask_workspace=None):
+                 mask_largest_component_hull=False, mask_dilate=5, mask_workspace=None, detector=None, detector_out_size=400):
         self.opt, self.fm = optimizer, feature_manager
+        self.detector = detector                                                 # None: frames arrive with kpts_gpu / desc_gpu set
+        self.detector_out_size = int(detector_out_size)                          # Lfnet::detectFeature's H_input = W_input = 400
         self.mask_largest_component_hull = bool(mask_largest_component_hull)     # the reference's `data_dir contains "NOCS"` (Frame.cpp:255,280)
         self.mask_dilate = int(mask_dilate)                                      # MORPH_RECT 5 x 5 (Frame.cpp:310)
         self.mask_workspace = mask_workspace                                     # None: the optimiser's workspace
@@ -262,6 +266,14 @@ class Bundler:
             self.fm.forget_frame(frame)
             self.need_reinit = True
             return
+        if self.detector is not None:                                                  # :103-117 detectFeature; an exception marks FAIL
+            try:
+                self.detect(frame)
+            except Exception:
+                frame.status = "FAIL"
+                self.need_reinit = True
+                self.fm.forget_frame(frame)
+                return
         if last is not None:
             self.fm.find_corres(frame, last)                                           # :122
             if frame.status == "FAIL":
@@ -294,10 +306,29 @@ class Bundler:
         """Frame::segmentationByMaskFile on the GPU (btba_apply_masks): frame.depth_gpu, normal_gpu, color_gpu zeroed outside
         the final mask in place, frame.roi and frame.fg_mask_gpu set."""
         from .segmentation import apply_masks
+        ws = self._workspace("segment")
+        apply_masks(ws, [frame], [frame.mask_gpu], largest_component_hull=self.mask_largest_component_hull, dilate=self.mask_dilate)
+
+    def detect(self, frame: FrameRef) -> None:
+        """Lfnet::detectFeature with rot_deg = 0 around the injected detector: the detector's input made on the GPU
+        (detection.prepare_detector_inputs on frame.color_gpu and frame.roi), detector(bgr [1,S,S,3] uint8, gray [1,1,S,S] float32)
+        -> (kpts [m,2], desc [m,D]) float32 CUDA tensors in detector pixels, the keypoints mapped back to full-resolution pixels
+        (detection.keypoints_to_image).  Sets frame.kpts_gpu, desc_gpu and n_keypts."""
+        import torch
+        from .detection import keypoints_to_image, prepare_detector_inputs
+        ws = self._workspace("detect")
+        bgr, gray = prepare_detector_inputs(ws, [frame], out_size=self.detector_out_size)
+        kpts, desc = self.detector(bgr, gray)
+        kpts = kpts.to(device=bgr.device, dtype=torch.float32).reshape(-1, 2).contiguous()
+        desc = desc.to(device=bgr.device, dtype=torch.float32).reshape(kpts.shape[0], -1).contiguous()
+        keypoints_to_image(ws, [frame], [kpts], out_size=self.detector_out_size)
+        frame.desc_gpu = desc
+
+    def _workspace(self, what: str):
         ws = self.mask_workspace if self.mask_workspace is not None else getattr(self.opt, "workspace", None)
         if ws is None:
-            raise RuntimeError("Bundler.segment needs a workspace: pass mask_workspace= or an optimizer with one")
-        apply_masks(ws, [frame], [frame.mask_gpu], largest_component_hull=self.mask_largest_component_hull, dilate=self.mask_dilate)
+            raise RuntimeError(f"Bundler.{what} needs a workspace: pass mask_workspace= or an optimizer with one")
+        return ws
 
     def _evict_cached(self, frame) -> None:
         """A frame dropped after BA has cached it must not leave its (z, n) cache behind under an id the next frame reuses."""

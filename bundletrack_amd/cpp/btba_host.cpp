@@ -414,6 +414,48 @@ void segmentationByMask(btba_workspace *ws, const std::shared_ptr<Frame> &frame,
     segmentationByMaskMultiFrame(ws, { frame }, largest_component_hull, dilate);
 }
 
+void prepareDetectorInputs(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, uint8_t *bgr_out, float *gray_out, int out_size)
+{
+    if (frames.empty()) return;
+    const int n = (int)frames.size(), H = frames[0]->_H, W = frames[0]->_W;
+    std::vector<const uint8_t *> color(n);
+    std::vector<float> roi(4 * (size_t)n);
+    for (int k = 0; k < n; k++) {
+        const Frame &f = *frames[k];
+        if (f._H != H || f._W != W) throw Error(BTBA_EINVAL, "prepareDetectorInputs: frames of different sizes");
+        color[k] = reinterpret_cast<const uint8_t *>(f._color_gpu);
+        for (int q = 0; q < 4; q++) roi[4 * k + q] = f._roi[q];
+    }
+    btba_detector_params prm;
+    btba_detector_params_default(&prm);
+    prm.out_size = out_size;
+    const int rc = btba_detector_inputs(ws, &prm, n, H, W, color.data(), roi.data(), bgr_out, gray_out);
+    if (rc != BTBA_OK) throw Error(rc, "btba_detector_inputs");
+}
+
+void keypointsToImage(btba_workspace *ws, const std::shared_ptr<Frame> &frame, const float2 *kpts_in, int n, float2 *kpts_out, int out_size)
+{
+    btba_detector_params prm;
+    btba_detector_params_default(&prm);
+    prm.out_size = out_size;
+    const float *in = reinterpret_cast<const float *>(kpts_in);
+    float *out = reinterpret_cast<float *>(kpts_out);
+    const int32_t cnt = n;
+    const int rc = btba_detector_keypoints_to_image(ws, &prm, 1, frame->_roi, &in, &cnt, &out);
+    if (rc != BTBA_OK) throw Error(rc, "btba_detector_keypoints_to_image");
+    frame->_kpts_gpu = kpts_out;
+    frame->_n_keypts = n;
+}
+
+void DetectorFeatureManager::detectFeature(const std::shared_ptr<Frame> &frame)              // FeatureManager.cpp:811-908
+{
+    prepareDetectorInputs(ws_, { frame }, bgr_, gray_, out_size_);
+    const DetectedFeatures got = detect_(bgr_, gray_, out_size_);
+    keypointsToImage(ws_, frame, got.kpts_dev, got.n, got.kpts_dev, out_size_);
+    frame->_feat_des_gpu = got.desc_dev;
+    frame->_feat_dim = got.dim;
+}
+
 // ---- Bundler ---------------------------------------------------------------------------------------------------
 Bundler::Bundler(std::shared_ptr<Config> yml1, std::shared_ptr<FeatureManager> fm, const Matrix3f &K1, int H1, int W1, OptimizeFn optimize)
     : yml(yml1 ? std::move(yml1) : std::make_shared<Config>()), _fm(std::move(fm)), memory(yml), K(K1), H(H1), W(W1), optimize_(std::move(optimize))

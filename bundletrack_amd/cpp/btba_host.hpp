@@ -126,6 +126,14 @@ struct Frame {                                   // the fields of Frame (src/Fra
 void segmentationByMask(btba_workspace *ws, const std::shared_ptr<Frame> &frame, bool largest_component_hull, int dilate = 5);
 void segmentationByMaskMultiFrame(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, bool largest_component_hull, int dilate = 5);
 
+// Lfnet::detectFeature (FeatureManager.cpp:811-908, rot_deg = 0) minus the detector, on btba_detector_inputs and
+// btba_detector_keypoints_to_image.  prepareDetectorInputs: the frames' masked _color_gpu cropped to _roi, zero-padded to a square
+// and resized to out_size x out_size, into caller-owned device buffers bgr_out [n][S][S][3] uint8 and gray_out [n][S][S] float (either
+// may be null).  keypointsToImage: n keypoints in detector pixels (device float2) mapped back to full-resolution pixels into kpts_out
+// (may equal kpts_in), which becomes the frame's _kpts_gpu; _n_keypts = n.  Both asynchronous on the workspace stream.
+void prepareDetectorInputs(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, uint8_t *bgr_out, float *gray_out, int out_size = 400);
+void keypointsToImage(btba_workspace *ws, const std::shared_ptr<Frame> &frame, const float2 *kpts_in, int n, float2 *kpts_out, int out_size = 400);
+
 // Utils::solveRigidTransformBetweenPoints (Utils.cpp:180-214): the rigid transform points1 -> points2 (n x 3 each, xyz
 // triples), identity when fewer than 3 points, a non-orthonormal V U^T or a non-finite result.
 void solveRigidTransformBetweenPoints(const std::vector<float> &points1, const std::vector<float> &points2, Matrix4f &pose);
@@ -184,6 +192,32 @@ public:
     void findCorresbyNNMultiPair(btba_workspace *ws, const std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> &pairs);
     // :247-288: one pair (A newer); a neighbouring pair left with fewer than 5 matches marks A FAIL
     void findCorresbyNN(btba_workspace *ws, const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB);
+};
+
+// Lfnet (src/FeatureManager.h:124-136) with the zmq round trip replaced by an in-process detector: detectFeature makes the
+// detector's input on the device (prepareDetectorInputs into the caller's bgr / gray buffers), calls `detect` and maps the returned
+// keypoints back in place (keypointsToImage); _kpts_gpu, _n_keypts, _feat_des_gpu and _feat_dim come from what `detect` returns,
+// whose device memory it owns.  The buffers are written, and the keypoints read, on the workspace stream: a detector on another
+// stream orders itself with it (btba_workspace_wait_stream / _signal_stream).  An exception from `detect` reaches Bundler::processNewFrame, which marks the frame FAIL (:108-117).
+// findCorres stays the caller's hook, as in FeatureManager.
+struct DetectedFeatures {
+    float2 *kpts_dev = nullptr;                  // [n] keypoints (x, y) in detector pixels; overwritten with full-resolution pixels
+    float *desc_dev = nullptr;                   // [n][dim] descriptors
+    int n = 0, dim = 0;
+};
+class DetectorFeatureManager : public FeatureManager {
+public:
+    using DetectFn = std::function<DetectedFeatures(const uint8_t *bgr_dev, const float *gray_dev, int out_size)>;
+    // bgr_dev: device uint8 [S][S][3], gray_dev: device float [S][S] (either may be null; the detector gets what is set)
+    DetectorFeatureManager(btba_workspace *ws, DetectFn detect, uint8_t *bgr_dev, float *gray_dev, int out_size = 400)
+        : ws_(ws), detect_(std::move(detect)), bgr_(bgr_dev), gray_(gray_dev), out_size_(out_size) {}
+    void detectFeature(const std::shared_ptr<Frame> &frame) override;
+private:
+    btba_workspace *ws_;
+    DetectFn detect_;
+    uint8_t *bgr_;
+    float *gray_;
+    int out_size_;
 };
 
 // Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its depth and normals on the device: the

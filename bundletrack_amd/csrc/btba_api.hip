@@ -26,6 +26,7 @@
 #include "btba_xorwow.hpp"
 #include "btba_match.hpp"
 #include "btba_mask.hpp"
+#include "btba_detect.hpp"
 
 using namespace btba;
 
@@ -2267,6 +2268,125 @@ int btba_apply_masks(btba_workspace *ws, const btba_mask_params *prm, int n_fram
             roi_out[4 * f + 2] = (float)(9999 - h[4 * f + 2]);
             roi_out[4 * f + 3] = (float)h[4 * f + 3];
         }
+    }
+    return BTBA_OK;
+}
+
+}  // extern "C"
+
+// ---- detector front end (btba_detect.hpp) ----------------------------------------------------------------------
+namespace {
+struct DetRoi { int umin, vmin, wc, hc; };
+
+// the ROI rules shared by the three entry points: integral, non-negative, below 2^24 (exact in float), at least 1 x 1 after the
+// crop, and inside the H x W image when that is known (H > 0)
+bool det_roi(const float *r, int H, int W, DetRoi &o)
+{
+    for (int q = 0; q < 4; q++)
+        if (!(r[q] >= 0.0f && r[q] < 16777216.0f) || r[q] != std::floor(r[q])) return false;
+    o.umin = (int)r[0];
+    o.vmin = (int)r[2];
+    o.wc = (int)(r[1] - r[0]);
+    o.hc = (int)(r[3] - r[2]);
+    if (o.wc < 1 || o.hc < 1) return false;
+    return H <= 0 || ((int64_t)o.umin + o.wc <= W && (int64_t)o.vmin + o.hc <= H);
+}
+
+bool det_params_ok(const btba_detector_params *p)
+{
+    return p && p->out_size >= 4 && p->out_size <= kDetMaxSize && p->out_size % 4 == 0;
+}
+
+// Lfnet::detectFeature's forward_transform (scale * translation, formed by Eigen's 3 x 3 product) and Eigen's cofactor inverse
+// of it, in fp32 (include/btba.h)
+void det_transform(int S, const float *roi, const DetRoi &r, float *fwd, float *bwd)
+{
+#pragma clang fp contract(off)
+    const float s = (float)S / (float)std::max(r.wc, r.hc);
+    const float su = s * roi[0], sv = s * roi[2];
+    const float F[9] = { s, 0.0f, 0.0f - su, 0.0f, s, 0.0f - sv, 0.0f, 0.0f, 1.0f };
+    const float det = s * s, invdet = 1.0f / det, r00 = s * invdet;
+    const float B[9] = { r00, 0.0f, (su * s) * invdet, 0.0f, r00, (sv * s) * invdet, 0.0f, 0.0f, det * invdet };
+    if (fwd) std::memcpy(fwd, F, sizeof F);
+    if (bwd) std::memcpy(bwd, B, sizeof B);
+}
+}  // namespace
+
+extern "C" {
+
+void btba_detector_params_default(btba_detector_params *p)
+{
+    if (!p) return;
+    p->out_size = 400;                                                // Lfnet::detectFeature's H_input = W_input (FeatureManager.cpp:851-852)
+}
+
+int btba_detector_transform(const btba_detector_params *prm, const float *roi, float *fwd, float *bwd)
+{
+    DetRoi r;
+    if (!det_params_ok(prm) || !roi || !fwd || !bwd || !det_roi(roi, 0, 0, r)) return BTBA_EINVAL;
+    det_transform(prm->out_size, roi, r, fwd, bwd);
+    return BTBA_OK;
+}
+
+int btba_detector_inputs(btba_workspace *ws, const btba_detector_params *prm, int n_frames, int H, int W,
+                         const uint8_t *const *color_dev, const float *roi_host, uint8_t *bgr_out_dev, float *gray_out_dev)
+{
+    // every argument is checked before the first HIP call
+    if (!ws || !det_params_ok(prm) || n_frames < 1 || H < 1 || W < 1 || !color_dev || !roi_host ||
+        (reinterpret_cast<uintptr_t>(bgr_out_dev) & 3) || (reinterpret_cast<uintptr_t>(gray_out_dev) & 15))
+        return BTBA_EINVAL;
+    std::vector<DetRoi> rois(n_frames);
+    for (int f = 0; f < n_frames; f++)
+        if (!color_dev[f] || (reinterpret_cast<uintptr_t>(color_dev[f]) & 3) || !det_roi(roi_host + 4 * f, H, W, rois[f])) return BTBA_EINVAL;
+    if (!bgr_out_dev && !gray_out_dev) return BTBA_OK;
+    DeviceGuard device_guard(ws);
+    const int S = prm->out_size;
+    const dim3 block(64, 4), grid((S + 255) / 256, S / 4, 1);
+    for (int b0 = 0; b0 < n_frames; b0 += kDetChunk) {
+        const int nf = std::min(kDetChunk, n_frames - b0);
+        DetectFrames F{};
+        for (int z = 0; z < nf; z++) {
+            const DetRoi &r = rois[b0 + z];
+            F.color[z] = reinterpret_cast<const uchar4 *>(color_dev[b0 + z]) + ((size_t)r.vmin * W + r.umin);
+            F.wc[z] = r.wc;
+            F.hc[z] = r.hc;
+        }
+        dim3 g = grid;
+        g.z = nf;
+        k_detect_inputs<<<g, block, 0, ws->stream>>>(W, S, F, b0, bgr_out_dev, gray_out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return BTBA_OK;
+}
+
+int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_params *prm, int n_frames, const float *roi_host,
+                                     const float *const *kpts_in_dev, const int32_t *n_kpts, float *const *kpts_out_dev)
+{
+    if (!ws || !det_params_ok(prm) || n_frames < 1 || !roi_host || !kpts_in_dev || !n_kpts || !kpts_out_dev) return BTBA_EINVAL;
+    std::vector<float> bwd(9 * (size_t)n_frames);
+    for (int f = 0; f < n_frames; f++) {
+        DetRoi r;
+        if (n_kpts[f] < 0 || n_kpts[f] > kDetMaxKpts || (n_kpts[f] > 0 && (!kpts_in_dev[f] || !kpts_out_dev[f])) ||
+            (reinterpret_cast<uintptr_t>(kpts_in_dev[f]) & 7) || (reinterpret_cast<uintptr_t>(kpts_out_dev[f]) & 7) || !det_roi(roi_host + 4 * f, 0, 0, r))
+            return BTBA_EINVAL;
+        det_transform(prm->out_size, roi_host + 4 * f, r, nullptr, bwd.data() + 9 * f);
+    }
+    DeviceGuard device_guard(ws);
+    for (int b0 = 0; b0 < n_frames; b0 += kDetChunk) {
+        const int nf = std::min(kDetChunk, n_frames - b0);
+        KptFrames F{};
+        int n_max = 0;
+        for (int z = 0; z < nf; z++) {
+            const float *B = bwd.data() + 9 * (b0 + z);
+            F.in[z] = reinterpret_cast<const float2 *>(kpts_in_dev[b0 + z]);
+            F.out[z] = reinterpret_cast<float2 *>(kpts_out_dev[b0 + z]);
+            F.n[z] = n_kpts[b0 + z];
+            F.r00[z] = B[0]; F.r02[z] = B[2]; F.r11[z] = B[4]; F.r12[z] = B[5];
+            n_max = std::max(n_max, F.n[z]);
+        }
+        if (n_max == 0) continue;
+        k_detect_keypoints<<<dim3((n_max + 255) / 256, nf), 256, 0, ws->stream>>>(F);
+        HIP_TRY(hipGetLastError());
     }
     return BTBA_OK;
 }

@@ -472,3 +472,28 @@ def make_mask(T_cam2model: np.ndarray, K: np.ndarray, H: int = 480, W: int = 640
         if n > 0:
             m[max(y - n - 4, 0):y - n, x + n + 1:x + n + 5] = True
     return np.where(m, 255, 0).astype(np.uint8)
+
+
+def make_color(T_cam2model: np.ndarray, K: np.ndarray, H: int = 480, W: int = 640, *, seed: int = 0, background: bool = True) -> np.ndarray:
+    """A colour map the way Frame::updateColorGPU lays it out: uint8 [H, W, 4], bytes B, G, R and 0.  The object carries a
+    deterministic texture fixed to its surface (sinusoids and a checker in model coordinates, so every view of a point has the
+    same colour, with edges at all angles for the resize to blend); the background (with background=True: the render's far
+    sphere, else every pixel off the object) is seeded noise blurred over 3 x 3 pixels."""
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    depth, _ = render(T_cam2model, K, xs, ys, background=False)
+    d_cam = np.stack([(xs - K[0, 2]) / K[0, 0], (ys - K[1, 2]) / K[1, 1], np.ones_like(xs)], -1)
+    p = (d_cam @ T_cam2model[:3, :3].T) * depth[..., None].astype(np.float64) + T_cam2model[:3, 3]    # model-frame surface point
+    q = p / SEMI_AXES
+    chk = ((np.floor(q[..., 0] * 6) + np.floor(q[..., 1] * 6) + np.floor(q[..., 2] * 6)) % 2) * 60
+    b = 100 + 80 * np.sin(17 * q[..., 0] + 5 * q[..., 2]) + chk
+    g = 110 + 70 * np.sin(13 * q[..., 1] - 7 * q[..., 0]) + 0.5 * chk
+    r = 120 + 90 * np.sin(11 * q[..., 2] + 9 * q[..., 1]) - 0.5 * chk
+    obj = np.clip(np.rint(np.stack([b, g, r], -1)), 0, 255)
+    rng = np.random.default_rng(seed)
+    noise = rng.integers(0, 256, (H + 2, W + 2, 3)).astype(np.float64)
+    bg = sum(noise[dy:dy + H, dx:dx + W] for dy in range(3) for dx in range(3)) / 9.0
+    if not background:
+        bg[:] = 0
+    out = np.zeros((H, W, 4), np.uint8)
+    out[..., :3] = np.where((depth > 0)[..., None], obj, np.rint(bg)).astype(np.uint8)
+    return out

@@ -583,6 +583,64 @@ BTBA_API int btba_apply_masks(btba_workspace *ws, const btba_mask_params *params
                               const uint8_t *const *mask_dev, float *const *depth_dev, float *const *normal_dev,
                               uint8_t *const *color_dev, uint8_t *const *mask_out_dev, float *roi_out);
 
+/* ---- detector front end (the step between the mask and the matcher) ----------------------------------------------
+ * Replaces the image and point arithmetic of Lfnet::detectFeature (src/FeatureManager.cpp:811-908, called by
+ * Bundler::processNewFrame, src/Bundler.cpp:103-117) with rot_deg = 0 (the only value the reference passes): the masked colour
+ * image cropped to the ROI, zero-padded into a square and resized to S x S (S = out_size, 400 in the reference), the grey float
+ * image the LF-Net server makes of it (lf-net-release/run_server.py:160-165), and the detector's keypoints mapped back to
+ * full-resolution pixels.  The detector itself stays with the caller.  Every rule is exact integer or fp32 arithmetic, so a CPU
+ * restatement reproduces the output bit for bit:
+ *   Crop: roi = (umin, umax, vmin, vmax) as btba_apply_masks writes it (integral floats).  Wc = (int)(umax - umin),
+ *       Hc = (int)(vmax - vmin) (column umax and row vmax are left out, as in the reference), side = max(Wc, Hc).
+ *       I(y, x) = colour(vmin + y, umin + x) for x < Wc, y < Hc, else (0, 0, 0): the padding goes right and below.  Channels are
+ *       the B, G, R bytes of the uchar4 colour map (Frame::updateColorGPU's layout); the fourth byte is ignored.
+ *   Resize (cv::resize INTER_LINEAR, OpenCV's fixed-point path for 8-bit images), inv = (double)S / side, scale = 1.0 / inv:
+ *       per output column dx: fx = (float)((dx + 0.5) * scale - 0.5) in double, uncontracted; sx = floor(fx); fx -= sx in float;
+ *       sx < 0 -> fx = 0, sx = 0; sx >= side - 1 -> fx = 0, sx = side - 1.  a0 = rint_even((1.f - fx) * 2048),
+ *       a1 = rint_even(fx * 2048); h = I[sx] * a0 + I[sx + 1] * a1 (int; the second tap is not read when sx = side - 1, a1 = 0).
+ *       Per output row dy: fy, sy the same, but fy is NOT zeroed at the border: the two source rows are clamp(sy, 0, side - 1) and
+ *       clamp(sy + 1, 0, side - 1), b0 = rint_even((1.f - fy) * 2048), b1 = rint_even(fy * 2048).
+ *       Vertical combine, the SIMD form (VResizeLinearVec_32s8u, which an x86 build applies to nearly every pixel):
+ *           out = sat_u8((((h0 >> 4) * b0 >> 16) + ((h1 >> 4) * b1 >> 16) + 2) >> 2).
+ *       OpenCV's scalar form, (h0 * b0 + h1 * b1 + (1 << 21)) >> 22, can differ from it by one level; which form the reference's
+ *       OpenCV applies to a given pixel depends on its version and SIMD dispatch.  UNMEASURED (no OpenCV to compare with).
+ *       side == S is a plain copy (the rule gives one).  side == 2 S is INTER_AREA, as cv::resize switches it:
+ *           out = (I(2y, 2x) + I(2y, 2x + 1) + I(2y + 1, 2x) + I(2y + 1, 2x + 1) + 2) >> 2   (only a ROI 2 S wide or high).
+ *   Grey: OpenCV 4's RGB2GRAY on the BGR bytes, as the server calls it: g = (9798 * B + 19235 * G + 3735 * R + 16384) >> 15, then
+ *       g / 255.0f correctly rounded.  OpenCV 3 used 14-bit weights (4899, 9617, 1868); which one the reference's server ran is
+ *       unknown.
+ *   Transform (btba_detector_transform): s = (float)S / (float)side; forward F = [[s, 0, 0 - fl(s * umin)], [0, s, 0 - fl(s * vmin)],
+ *       [0, 0, 1]] (the product Eigen forms of the scale and translation matrices: -fl(s * umin), +0 for umin = 0).  Backward: Eigen's
+ *       3 x 3 cofactor inverse of F in fp32: det = fl(s * s), invdet = fl(1 / det), r00 = r11 = fl(s * invdet),
+ *       r02 = fl(fl(fl(s * umin) * s) * invdet), r12 likewise with vmin, r22 = fl(det * invdet), the other four entries +0 (Eigen's
+ *       may be -0, which changes no keypoint but a -0 input).  fwd and bwd are written row-major.  A keypoint (kx, ky) maps to
+ *       (fl(fl(r00 * kx) + r02), fl(fl(r11 * ky) + r12)), uncontracted.  This is what the reference computes on any x86 build: every
+ *       term an FMA could fuse with is an exact zero (0 * x, or a cofactor made of zero products), and fl(r00 * kx) + r02 is the sum
+ *       of two different products of which Eigen's row sum forms the first before adding the second.
+ *
+ *   color_dev[f]     : device uchar4 [H * W] (4-byte aligned), the masked colour map (btba_apply_masks leaves it so)
+ *   roi_host         : host float [n_frames][4]
+ *   bgr_out_dev      : NULL, or device uint8 [n_frames][S][S][3] (4-byte aligned): exactly the bytes the reference sends the server
+ *   gray_out_dev     : NULL, or device float [n_frames][S][S] (16-byte aligned): g / 255.0f
+ *   kpts_in_dev[f]   : device float2 [n_kpts[f]] in detector pixels (0 <= n_kpts[f] <= 8192; NULL allowed where n_kpts[f] = 0)
+ *   kpts_out_dev[f]  : device float2 [n_kpts[f]] in full-resolution pixels, btba_match_pairs' kpts_dev format; may equal
+ *                      kpts_in_dev[f] (in place)
+ * Both device calls are asynchronous on the workspace stream and read no host memory after they return (frames go in chunks
+ * whose pointers and coefficients travel as kernel arguments).  BTBA_EINVAL: NULL ws, params or tables, or a NULL entry in one of
+ * them (a NULL kpts entry with n_kpts[f] > 0); a non-integral ROI, Wc < 1 or Hc < 1, or a crop outside the H x W image; out_size
+ * not a multiple of 4 in 4 .. 4096; n_frames < 1, H < 1 or W < 1; a misaligned color_dev entry, output or keypoint buffer (float2:
+ * 8 bytes); n_kpts[f] outside
+ * 0 .. 8192.  btba_detector_transform needs no GPU and no workspace. */
+typedef struct btba_detector_params {
+    int32_t out_size;                /* S: the detector's square input side (default 400, Lfnet::detectFeature's H_input = W_input) */
+} btba_detector_params;
+BTBA_API void btba_detector_params_default(btba_detector_params *p);
+BTBA_API int btba_detector_transform(const btba_detector_params *params, const float *roi, float *fwd, float *bwd);
+BTBA_API int btba_detector_inputs(btba_workspace *ws, const btba_detector_params *params, int n_frames, int H, int W,
+                                  const uint8_t *const *color_dev, const float *roi_host, uint8_t *bgr_out_dev, float *gray_out_dev);
+BTBA_API int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_params *params, int n_frames, const float *roi_host,
+                                              const float *const *kpts_in_dev, const int32_t *n_kpts, float *const *kpts_out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_mask_params_default", "btba_apply_masks",
     "btba_detector_params_default", "btba_detector_transform", "btba_detector_inputs", "btba_detector_keypoints_to_image",
+    "btba_pose_errors",
 ]
 
 # btba_match (include/btba.h): one descriptor match, 40 bytes
@@ -244,6 +245,8 @@ def lib() -> C.CDLL:
                                            C.c_void_p, C.c_void_p]
         L.btba_detector_keypoints_to_image.argtypes = [C.c_void_p, C.POINTER(DetectorParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+        L.btba_pose_errors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

@@ -136,6 +136,45 @@ void solveRigidTransformBetweenPoints(const std::vector<float> &points1, const s
     pose = out;
 }
 
+void poseErrors(btba_workspace *ws, const std::vector<const float *> &models_dev, const std::vector<int32_t> &n_pts,
+                const std::vector<int32_t> &model_index, const std::vector<Matrix4f> &poses_pred, const std::vector<Matrix4f> &poses_gt,
+                std::vector<float> &add, std::vector<float> &adds)
+{
+    const size_t n = model_index.size();
+    if (models_dev.size() != n_pts.size() || poses_pred.size() != n || poses_gt.size() != n) throw Error(BTBA_EINVAL, "poseErrors: sizes differ");
+    std::vector<float> pp(16 * n), pg(16 * n);                    // row-major, as the C ABI takes them
+    for (size_t e = 0; e < n; e++)
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) {
+                pp[16 * e + 4 * r + c] = poses_pred[e](r, c);
+                pg[16 * e + 4 * r + c] = poses_gt[e](r, c);
+            }
+    add.assign(n, 0.0f);
+    adds.assign(n, 0.0f);
+    const int rc = btba_pose_errors(ws, /*device_resident=*/0, (int)models_dev.size(), models_dev.data(), n_pts.data(), (int)n, model_index.data(),
+                                    pp.data(), pg.data(), add.data(), adds.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_pose_errors");
+}
+
+double vocapAuc(const std::vector<double> &errors, double max_threshold)
+{
+    const size_t n = errors.size();
+    std::vector<double> b;                                        // the errors strictly below the threshold (NaN never is), sorted
+    for (double x : errors)
+        if (x < max_threshold) b.push_back(x);
+    const size_t m = b.size();
+    if (m == 0) return 0.0;
+    std::sort(b.begin(), b.end());
+    double area = 0.0, prev = 0.0;
+    for (size_t k = 1; k <= m; k++)
+        if (b[k - 1] != prev) {
+            area += (b[k - 1] - prev) * (double)k / (double)n;
+            prev = b[k - 1];
+        }
+    area += (max_threshold - prev) * (double)m / (double)n;
+    return area / max_threshold;
+}
+
 std::string formatPoseTxt(const Matrix4f &M)
 {
     char cell[16][32];

@@ -134,6 +134,16 @@ void segmentationByMaskMultiFrame(btba_workspace *ws, const std::vector<std::sha
 void prepareDetectorInputs(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, uint8_t *bgr_out, float *gray_out, int out_size = 400);
 void keypointsToImage(btba_workspace *ws, const std::shared_ptr<Frame> &frame, const float2 *kpts_in, int n, float2 *kpts_out, int out_size = 400);
 
+// scripts/eval_ycbineoat.py's per-frame errors (Utils.py add / adi) on btba_pose_errors: evaluation e scores poses_pred[e] against
+// poses_gt[e] (object-in-camera, Bundler::saveNewframeResult's ob_in_cam) on the device point set models_dev[model_index[e]]
+// (float [n_pts[m]][3], metres).  add and adds are resized to the number of evaluations.  Needs the GPU; synchronous.
+void poseErrors(btba_workspace *ws, const std::vector<const float *> &models_dev, const std::vector<int32_t> &n_pts,
+                const std::vector<int32_t> &model_index, const std::vector<Matrix4f> &poses_pred, const std::vector<Matrix4f> &poses_gt,
+                std::vector<float> &add, std::vector<float> &adds);
+// VOCap (eval_ycbineoat.py:54-81) in closed form, the same arithmetic as bundletrack_amd/evaluation.py::vocap_auc: the area under
+// the accuracy-vs-threshold curve on [0, max_threshold] over max_threshold (0 without errors below the threshold).
+double vocapAuc(const std::vector<double> &errors, double max_threshold = 0.1);
+
 // Utils::solveRigidTransformBetweenPoints (Utils.cpp:180-214): the rigid transform points1 -> points2 (n x 3 each, xyz
 // triples), identity when fewer than 3 points, a non-orthonormal V U^T or a non-finite result.
 void solveRigidTransformBetweenPoints(const std::vector<float> &points1, const std::vector<float> &points2, Matrix4f &pose);

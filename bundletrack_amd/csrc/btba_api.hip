@@ -27,6 +27,7 @@
 #include "btba_match.hpp"
 #include "btba_mask.hpp"
 #include "btba_detect.hpp"
+#include "btba_eval.hpp"
 
 using namespace btba;
 
@@ -169,6 +170,7 @@ struct btba_workspace {
     std::vector<float> ransac_u_host;
     DevBuf match;                                           // btba_match_pairs: tables, norms, candidate lists, selections, counts, host-form staging
     DevBuf mask;                                            // btba_apply_masks: labels, counts, argmax keys, row extents, spans, hull stacks, ROI slots
+    DevBuf eval;                                            // btba_pose_errors: chunk tables, host-form poses and outputs, per-point minima
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;
@@ -308,7 +310,7 @@ void btba_workspace_destroy(btba_workspace *ws)
     for (auto e : ws->event_pool) (void)hipEventDestroy(e);
     DevBuf *bufs[] = { &ws->x, &ws->T, &ws->Tinv, &ws->sparse_part, &ws->dense_part, &ws->pairsum, &ws->dense_pairs, &ws->ptrs, &ws->big_A, &ws->solve_tab,
                        &ws->corr, &ws->offsets, &ws->poses, &ws->campos, &ws->normals, &ws->nvalid, &ws->valid_lists, &ws->valid_counts, &ws->block_ranges,
-                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->mask, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens };
+                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->mask, &ws->eval, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens };
     for (auto b : bufs) b->release();
     if (ws->corr_stage) (void)hipHostFree(ws->corr_stage);
     if (ws->chain_error) (void)hipHostFree(ws->chain_error);
@@ -2388,6 +2390,86 @@ int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_par
         k_detect_keypoints<<<dim3((n_max + 255) / 256, nf), 256, 0, ws->stream>>>(F);
         HIP_TRY(hipGetLastError());
     }
+    return BTBA_OK;
+}
+
+int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, const float *const *model_pts_dev, const int32_t *n_pts,
+                     int n_evals, const int32_t *model_index, const float *poses_pred, const float *poses_gt,
+                     float *add_out, float *adds_out)
+{
+    // every argument is checked before the first HIP call
+    if (!ws || n_models < 1 || !model_pts_dev || !n_pts || n_evals < 0) return BTBA_EINVAL;
+    for (int m = 0; m < n_models; m++)
+        if (!model_pts_dev[m] || (reinterpret_cast<uintptr_t>(model_pts_dev[m]) & 3) || n_pts[m] < 1 || n_pts[m] > BTBA_EVAL_MAX_POINTS)
+            return BTBA_EINVAL;
+    if (n_evals == 0) return BTBA_OK;
+    if (!model_index || !poses_pred || !poses_gt || !add_out || !adds_out) return BTBA_EINVAL;
+    for (int e = 0; e < n_evals; e++)
+        if (model_index[e] < 0 || model_index[e] >= n_models) return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+
+    // chunks: at most kEvalChunkEvals evaluations and kEvalScratchPoints per-point minima each
+    std::vector<EvalRec> rec(n_evals);
+    std::vector<int> chunk_start{ 0 };
+    int64_t pts_in_chunk = 0, max_chunk_pts = 0;
+    for (int e = 0; e < n_evals; e++) {
+        const int n = n_pts[model_index[e]];
+        if (e > chunk_start.back() && (pts_in_chunk + n > kEvalScratchPoints || e - chunk_start.back() >= kEvalChunkEvals)) {
+            chunk_start.push_back(e);
+            pts_in_chunk = 0;
+        }
+        rec[e] = EvalRec{ model_pts_dev[model_index[e]], n, (int)pts_in_chunk };
+        pts_in_chunk += n;
+        max_chunk_pts = std::max(max_chunk_pts, pts_in_chunk);
+    }
+    chunk_start.push_back(n_evals);
+    const int max_chunk = std::min(n_evals, kEvalChunkEvals);
+    const bool dev = device_resident != 0;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t o = 0;
+    const size_t o_rec = o; o += al(sizeof(EvalRec) * max_chunk);
+    const size_t o_pp = o; o += dev ? 0 : al(sizeof(float) * 16 * max_chunk);
+    const size_t o_pg = o; o += dev ? 0 : al(sizeof(float) * 16 * max_chunk);
+    const size_t o_out = o; o += dev ? 0 : al(sizeof(float) * 2 * max_chunk);
+    const size_t o_min = o; o += al(sizeof(unsigned) * (size_t)max_chunk_pts);
+    int rc = ws->eval.ensure(o);
+    if (rc) return rc;
+    unsigned char *base = ws->eval.as<unsigned char>();
+    EvalRec *d_rec = reinterpret_cast<EvalRec *>(base + o_rec);
+    unsigned *d_min = reinterpret_cast<unsigned *>(base + o_min);
+    for (size_t c = 0; c + 1 < chunk_start.size(); c++) {
+        const int e0 = chunk_start[c], ne = chunk_start[c + 1] - e0;
+        int max_n = 0;
+        for (int e = e0; e < e0 + ne; e++) max_n = std::max(max_n, rec[e].n);
+        const float *pp = poses_pred + 16 * (size_t)e0, *pg = poses_gt + 16 * (size_t)e0;
+        float *oa = add_out + e0, *os = adds_out + e0;
+        HIP_TRY(hipMemcpyAsync(d_rec, rec.data() + e0, sizeof(EvalRec) * ne, hipMemcpyHostToDevice, ws->stream));
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(base + o_pp, pp, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
+            HIP_TRY(hipMemcpyAsync(base + o_pg, pg, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
+            pp = reinterpret_cast<const float *>(base + o_pp);
+            pg = reinterpret_cast<const float *>(base + o_pg);
+            oa = reinterpret_cast<float *>(base + o_out);
+            os = oa + max_chunk;
+        }
+        // split the candidates when evaluations x query tiles cannot fill the chip (the result does not depend on it)
+        const int tiles = (max_n + kEvalQTile - 1) / kEvalQTile;
+        const int64_t wgs = (int64_t)ne * tiles;
+        int splits = 1;
+        if (wgs < 2048) splits = (int)std::min<int64_t>((2048 + wgs - 1) / wgs, (max_n + kEvalCTile - 1) / kEvalCTile);
+        int per = (max_n + splits - 1) / splits;
+        per = (per + kEvalCTile - 1) / kEvalCTile * kEvalCTile;
+        splits = (max_n + per - 1) / per;
+        if (splits > 1) HIP_TRY(hipMemsetAsync(d_min, 0xff, sizeof(unsigned) * (size_t)(rec[e0 + ne - 1].off + rec[e0 + ne - 1].n), ws->stream));
+        k_eval_nn<<<dim3(ne, tiles, splits), kEvalThreads, 0, ws->stream>>>(d_rec, pp, pg, per, splits > 1 ? 1 : 0, d_min);
+        k_eval_reduce<<<ne, kEvalRedThreads, 0, ws->stream>>>(d_rec, pp, pg, d_min, oa, os);
+        HIP_TRY(hipGetLastError());
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(add_out + e0, oa, sizeof(float) * ne, hipMemcpyDeviceToHost, ws->stream));
+            HIP_TRY(hipMemcpyAsync(adds_out + e0, os, sizeof(float) * ne, hipMemcpyDeviceToHost, ws->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host tables above may go
     return BTBA_OK;
 }
 

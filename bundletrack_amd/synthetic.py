@@ -497,3 +497,10 @@ def make_color(T_cam2model: np.ndarray, K: np.ndarray, H: int = 480, W: int = 64
     out = np.zeros((H, W, 4), np.uint8)
     out[..., :3] = np.where((depth > 0)[..., None], obj, np.rint(bg)).astype(np.uint8)
     return out
+
+
+def model_points(n: int, seed: int = 0) -> np.ndarray:
+    """float32 [n, 3] points on the ellipsoid's surface (object frame, metres): a model to score poses against
+    (evaluation.pose_errors).  Its own generator: no other function's draws change."""
+    p, _ = _sample_surface(np.random.default_rng(seed), n)
+    return p.astype(np.float32)

@@ -641,6 +641,40 @@ BTBA_API int btba_detector_inputs(btba_workspace *ws, const btba_detector_params
 BTBA_API int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_params *params, int n_frames, const float *roi_host,
                                               const float *const *kpts_in_dev, const int32_t *n_kpts, float *const *kpts_out_dev);
 
+/* ---- pose accuracy: ADD and ADD-S (the YCBInEOAT evaluation) -------------------------------------------------------
+ * The per-frame errors the reference's evaluation averages into its AUC figures (scripts/eval_ycbineoat.py:54-163 with
+ * scripts/Utils.py:69-95, add / adi), for many evaluations in one call.  One evaluation is a model point set x_0 .. x_{N-1}
+ * (object frame, metres), a predicted pose P and a ground-truth pose G, both row-major 4 x 4 OBJECT-IN-CAMERA (the
+ * reference's poses/*.txt, Bundler.cpp:372-376; the tracker's own camera -> model poses are their inverses).
+ *   q_i = G x_i (queries), c_j = P x_j (candidates), each row one fmaf chain:
+ *       p_r = fmaf(T_r2, z, fmaf(T_r1, y, fmaf(T_r0, x, T_r3)))
+ *   d2(a, b) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) with d = a - b (dx * dx a plain multiply; nothing else contracted)
+ *   add_i  = sqrtf(d2(q_i, c_i))
+ *   adds_i = sqrtf(min_j d2(q_i, c_j))                 (the reference's adi: a tree on the predicted points, queried with
+ *                                                         the ground-truth points)
+ *   sqrtf is the IEEE, correctly rounded square root.
+ *   ADD = mean_i add_i, ADD-S = mean_i adds_i, each summed in fp64 in a fixed order: slot l of 256 sums (double) d_i for
+ *   i = l (mod 256) in ascending i from +0; then s = 128, 64, .., 1: acc[l] += acc[l + s] for l < s; output
+ *   (float)(acc[0] / N).
+ * Consequences: adds_i <= add_i bit for bit (j = i is a candidate, same arithmetic), so ADD-S <= ADD; P == G gives 0 and 0.
+ * An evaluation with a non-finite entry among its 32 pose entries gives a quiet NaN in both outputs; the others are
+ * unaffected.  Model points must be finite (precondition, not checked).
+ *
+ *   model_pts_dev[m] : device float [n_pts[m]][3] (4-byte aligned), 1 <= n_pts[m] <= 2^22 (host int32 array)
+ *   model_index      : host int32 [n_evals], each in 0 .. n_models - 1
+ *   poses_pred, poses_gt : float [n_evals][16] row-major object-in-camera
+ *   add_out, adds_out    : float [n_evals]
+ * device_resident = 1: poses and outputs are device pointers; 0: host pointers.  n_evals == 0 is a no-op.  Synchronous on the
+ * workspace stream; scratch (per-point minima, at most 64 MB: evaluations go in chunks) is grow-only in the workspace.
+ * BTBA_EINVAL before any GPU work: ws, a table or an output NULL, a NULL model pointer, n_models < 1, n_evals < 0, a count
+ * outside 1 .. 2^22, a model_index entry out of range. */
+#define BTBA_EVAL_MAX_POINTS (1 << 22)
+BTBA_API int btba_pose_errors(btba_workspace *ws, int device_resident,
+                              int n_models, const float *const *model_pts_dev, const int32_t *n_pts,
+                              int n_evals, const int32_t *model_index,
+                              const float *poses_pred, const float *poses_gt,
+                              float *add_out, float *adds_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,17 +115,20 @@ class BtbaError(RuntimeError):
         super().__init__(f"{where}: {msg}{extra}")
 
 
+# The hipcc flags of libbtba.so, shared with the test-only device probe (tests/hip/btba_probe.hip) so that both compile the product's
+# device functions identically.  -fno-slp-vectorize: the SLP pass packs neighbouring fp32 operations into v_pk_{mul,add,fma}_f32, which
+# issue at half rate on gfx950 and need register-pair shuffling (v_mov) around them; measured -14 % on the dense sweep, -7 % on the
+# sparse sweep without it.
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-pass-failed", "-fPIC", "-shared", "-fvisibility=hidden"]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(SRC_DIR, f) for f in os.listdir(SRC_DIR)] + [HEADER]
     newest = max(os.path.getmtime(s) for s in srcs)
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
         return LIB_PATH
-    # -fno-slp-vectorize: the SLP pass packs neighbouring fp32 operations into v_pk_{mul,add,fma}_f32, which issue at half
-    # rate on gfx950 and need register-pair shuffling (v_mov) around them; measured -14 % on the dense sweep, -7 % on
-    # the sparse sweep without it (DESIGN.md 4.2).
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-pass-failed", "-fPIC", "-shared", "-fvisibility=hidden",
-           "-o", LIB_PATH, os.path.join(SRC_DIR, "btba_api.hip")]
+    cmd = ["hipcc"] + HIPCC_FLAGS + ["-o", LIB_PATH, os.path.join(SRC_DIR, "btba_api.hip")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

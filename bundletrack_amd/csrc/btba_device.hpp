@@ -68,7 +68,7 @@ __device__ __forceinline__ Mat4 mat_inverse(const Mat4 &a)
 
 // Division and square root of the SE(3) helpers.  FAST = false: IEEE (v_div_scale / v_div_fmas / v_div_fixup sequences, refined square root) -- what the seam
 // kernels (k_prepare, k_poses_to_matrices) and k_system_solve use.  FAST = true (round 6, the update phase of k_solve_small / k_solve_mid): x * v_rcp_f32(y) and
-// v_sqrt_f32, 1 ulp each -- the class of arithmetic the reference's own build has (-use_fast_math: --prec-div=false --prec-sqrt=false, CMakeLists.txt:7) and the
+// v_sqrt_f32, within 1 ulp each (tests/test_gpu_device_math.py) -- the class of arithmetic the reference's own build has (-use_fast_math: --prec-div=false --prec-sqrt=false, CMakeLists.txt:7) and the
 // PCG's alpha / beta already use; ten divisions and nine square roots are ~170 of the ~650 dependent instructions of the one-lane-per-frame update chain.
 template <bool FAST> __device__ __forceinline__ float se3_div(float a, float b) { return FAST ? a * __builtin_amdgcn_rcpf(b) : a / b; }
 template <bool FAST> __device__ __forceinline__ float se3_sqrt(float x) { return FAST ? __builtin_amdgcn_sqrtf(x) : sqrtf(x); }
@@ -106,7 +106,7 @@ __device__ __forceinline__ void exp_rotation(const float w[3], float r[9])
     } else {
         const float inv_theta = se3_div<FAST>(1.0f, theta);
         float sn, cs;
-        sincosf(theta, &sn, &cs);                     // one argument reduction for both (the values of sinf / cosf, bit for bit)
+        sincosf(theta, &sn, &cs);                     // one argument reduction for both (the values of sinf / cosf, bit for bit: tests/test_gpu_device_math.py)
         A = sn * inv_theta;
         B = (1.0f - cs) * (inv_theta * inv_theta);
     }
@@ -120,7 +120,7 @@ __device__ __forceinline__ void ln_rotation(const float R[9], float out[3])
     float r0 = (R[7] - R[5]) * 0.5f, r1 = (R[2] - R[6]) * 0.5f, r2 = (R[3] - R[1]) * 0.5f;
     const float sin_angle_abs = se3_sqrt<FAST>(r0 * r0 + r1 * r1 + r2 * r2);
     if (cos_angle > 0.70710678118654752440f) {
-        if (sin_angle_abs > 0) {
+        if (!(sin_angle_abs <= 0.0f)) {               // = sin_angle_abs > 0 for every number; a NaN input scales (and so poisons) all three components
             const float s = se3_div<FAST>(asinf(sin_angle_abs), sin_angle_abs);
             r0 *= s; r1 *= s; r2 *= s;
         }
@@ -148,8 +148,9 @@ __device__ __forceinline__ void ln_rotation(const float R[9], float out[3])
 // SE(3) log: 4x4 -> (rot, trans)   (matrixToPose)
 // The reference evaluates sinf(theta / 2) for the translation's scale and, inside exp_rotation(-rot / 2), sinf and cosf of |rot / 2| again:
 // |-rot / 2| = sqrtf(sum (rot_i / 2)^2) = theta / 2 BIT FOR BIT (scaling by a power of two commutes with every rounding of the sum and of the
-// correctly rounded square root), so one sincosf serves both -- ~40 instructions off k_solve_small's one-lane update chain, same bits
-// (tests/test_gpu_parity.py::test_se3_helpers_bit_exact against the reference's own LieDerivUtil.h).
+// square root: se3_sqrt(x / 4) = se3_sqrt(x) / 2 in both flavours, v_sqrt_f32 included, on every float in [1, 4) and on random normal floats --
+// tests/test_gpu_device_math.py::test_sqrt_commutes_with_scaling_by_four), so one sincosf serves both -- ~40 instructions off k_solve_small's
+// one-lane update chain, same bits.
 template <bool FAST = false>
 __device__ __forceinline__ void matrix_to_pose(const Mat4 &M, float rot[3], float trans[3])
 {

@@ -10,7 +10,7 @@
 // (no contraction), the reciprocal square root is correctly rounded like CUDA's __frsqrt_rn.
 //
 // Plain C++ (host and device): tests/cpp compiles it with g++ and holds it bit for bit against the reference's own
-// function (oracle/_ref/libbtba_ref_ransac.so).
+// function (oracle/_ref/libbtba_ref_ransac.so); tests/test_gpu_device_math.py holds the device build equal to that host build.
 #pragma once
 #include <math.h>
 #include <stdint.h>

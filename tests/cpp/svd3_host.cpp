@@ -27,3 +27,21 @@ extern "C" __attribute__((visibility("default"))) void rsqrt_rn_host(const float
 {
     for (int k = 0; k < n; k++) out[k] = btba::svd3::rsqrt_rn(x[k]);
 }
+
+// rsqrt_refined over an array (tests/test_gpu_device_math.py: device build against this host build)
+extern "C" __attribute__((visibility("default"))) void rsqrt_refined_host(const float *x, int n, float *out)
+{
+    for (int k = 0; k < n; k++) out[k] = btba::svd3::rsqrt_refined(x[k]);
+}
+
+// svd over n row-major 3x3 matrices
+extern "C" __attribute__((visibility("default"))) void svd3_batch_host(const float *A, int n, float *U, float *s, float *V)
+{
+    for (int i = 0; i < n; i++) svd3_host(A + 9 * i, U + 9 * i, s + 3 * i, V + 9 * i);
+}
+
+// procrustes_reference on n point sets: set i is points [off[i], off[i + 1]) of src / dst (xyzw floats)
+extern "C" __attribute__((visibility("default"))) void procrustes_batch_host(const float *src, const float *dst, const int *off, int n, float *pose16, int *ok)
+{
+    for (int i = 0; i < n; i++) ok[i] = procrustes_reference_host(src + 4 * off[i], dst + 4 * off[i], off[i + 1] - off[i], pose16 + 16 * i);
+}

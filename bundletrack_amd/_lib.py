@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "btba_mask_params_default", "btba_apply_masks",
     "btba_detector_params_default", "btba_detector_transform", "btba_detector_inputs", "btba_detector_keypoints_to_image",
     "btba_pose_errors",
+    "btba_mappoints_create", "btba_mappoints_destroy", "btba_mappoints_register_frame", "btba_mappoints_forget_frame", "btba_mappoints_export",
+    "btba_corres_params_default", "btba_corres_chain_capacity", "btba_corres_chain",
 ]
 
 # btba_match (include/btba.h): one descriptor match, 40 bytes
@@ -105,6 +107,11 @@ class ZnAux(C.Structure):
 class TraceLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in
                 ("record_floats", "off_x", "off_T", "off_rhs", "off_precond", "off_pcg", "off_delta", "off_dense_pair", "off_A", "off_clk")]
+
+
+class CorresParams(C.Structure):
+    """btba_corres_params (include/btba.h): the RANSAC settings of btba_corres_chain."""
+    _fields_ = [("n_trials", C.c_int32), ("dist_thres", C.c_float), ("hypothesis", C.c_int32), ("pad", C.c_int32), ("seed", C.c_uint64)]
 
 
 class BtbaError(RuntimeError):
@@ -250,6 +257,18 @@ def lib() -> C.CDLL:
                                                        C.c_void_p]
         L.btba_pose_errors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
+        L.btba_mappoints_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.btba_mappoints_destroy.argtypes = [C.c_void_p]
+        L.btba_mappoints_destroy.restype = None
+        L.btba_mappoints_register_frame.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
+        L.btba_mappoints_forget_frame.argtypes = [C.c_void_p, C.c_int32]
+        L.btba_mappoints_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_corres_params_default.argtypes = [C.POINTER(CorresParams)]
+        L.btba_corres_params_default.restype = None
+        L.btba_corres_chain_capacity.argtypes = L.btba_match_capacity.argtypes
+        L.btba_corres_chain.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MatchParams), C.POINTER(CorresParams), C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -273,6 +292,17 @@ def match_params(**kw) -> MatchParams:
     """btba_match_params_default with fields overridden by keyword."""
     p = MatchParams()
     lib().btba_match_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def corres_params(**kw) -> CorresParams:
+    """btba_corres_params_default with fields overridden by keyword."""
+    p = CorresParams()
+    lib().btba_corres_params_default(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)

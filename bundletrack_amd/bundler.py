@@ -186,6 +186,21 @@ def solve_rigid_transform_between_points(points1: np.ndarray, points2: np.ndarra
     return pose
 
 
+def procrustes_by_correspondence(matches: dict, frameA, frameB) -> np.ndarray:
+    """FeatureManager::procrustesByCorrespondence of the C++ host layer (src/FeatureManager.cpp:523-556): Kabsch of
+    matches[(A.id, B.id)] moved into the model frame with the frames' current poses (fp32, T_r0 x + T_r1 y + T_r2 z + T_r3 in that
+    order), identity below 5 matches."""
+    ptA, ptB = matches.get((frameA.id, frameB.id), (np.zeros((0, 3), np.float32),) * 2)
+    ptA, ptB = np.asarray(ptA, np.float32).reshape(-1, 3), np.asarray(ptB, np.float32).reshape(-1, 3)
+    if len(ptA) < 5:
+        return np.eye(4, dtype=np.float32)
+
+    def move(p, T):
+        T = np.asarray(T, np.float32)
+        return np.stack([((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3] for r in range(3)], 1)
+    return solve_rigid_transform_between_points(move(ptA, frameA.pose_in_model), move(ptB, frameB.pose_in_model))
+
+
 def format_pose_txt(ob_in_cam: np.ndarray) -> str:
     """`ff << std::setprecision(10) << ob_in_cam << std::endl` (Bundler.cpp:372-377) with Eigen's default
     IOFormat: coefficients in %.10g, every column padded to the widest coefficient, single-space separator."""
@@ -220,6 +235,8 @@ class Bundler:
         matches                            -> dict as above
         procrustes_by_correspondence(frameA, frameB) -> 4x4 model-frame offset (FeatureManager.cpp:523-556)
         forget_frame(frame)                -> None
+    and may offer find_corres_chain([(frameA, frameB), ...]) (correspondence.GpuFeatureManager): optimize_gpu then hands it the
+    window's pairs in find_corres order in one call.
     """
 
     def __init__(self, optimizer, feature_manager, K, H, W, *, window_size=2, max_BA_frames=15, min_rot_deg=10.0,
@@ -339,9 +356,13 @@ class Bundler:
     def optimize_gpu(self) -> None:
         """Bundler::optimizeGPU (:279-359): match every pair of the window, marshal, gate, optimise, write back."""
         frames = sorted(self.local_frames, key=lambda f: f.id)
-        for i in range(len(frames)):
-            for j in range(i + 1, len(frames)):
-                self.fm.find_corres(frames[j], frames[i])
+        chain = getattr(self.fm, "find_corres_chain", None)         # a feature manager that runs the window's pairs as one device chain
+        if chain is not None:
+            chain([(frames[j], frames[i]) for i in range(len(frames)) for j in range(i + 1, len(frames))])
+        else:
+            for i in range(len(frames)):
+                for j in range(i + 1, len(frames)):
+                    self.fm.find_corres(frames[j], frames[i])
         win = marshal_window(frames, self.fm.matches, self.newframe, self.min_fm_edges_newframe)
         self.last_window = win
         if not win.run_ba:

@@ -7,6 +7,7 @@
 #include <fstream>
 #include <cmath>
 #include <limits>
+#include <set>
 
 namespace btba {
 
@@ -486,6 +487,115 @@ void keypointsToImage(btba_workspace *ws, const std::shared_ptr<Frame> &frame, c
     frame->_n_keypts = n;
 }
 
+// ---- GpuFeatureManager: findCorres with map points on btba_corres_chain --------------------------------------------
+GpuFeatureManager::GpuFeatureManager(btba_workspace *ws, std::shared_ptr<Config> yml1) : ws_(ws)
+{
+    yml = yml1 ? std::move(yml1) : std::make_shared<Config>();
+    const int rc = btba_mappoints_create(ws, &mp_);
+    if (rc != BTBA_OK) throw Error(rc, "btba_mappoints_create");
+}
+
+GpuFeatureManager::~GpuFeatureManager() { btba_mappoints_destroy(mp_); }
+
+void GpuFeatureManager::findCorres(const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB) { findCorresChain({ { frameA, frameB } }); }
+
+void GpuFeatureManager::forgetFrame(const std::shared_ptr<Frame> &frame)
+{
+    FeatureManager::forgetFrame(frame);
+    for (auto it = _records.begin(); it != _records.end();)
+        it = (it->first.first == frame->_id || it->first.second == frame->_id) ? _records.erase(it) : std::next(it);
+    const auto s = slots_.find(frame->_id);
+    if (s == slots_.end()) return;
+    const int rc = btba_mappoints_forget_frame(mp_, s->second);
+    slots_.erase(s);
+    if (rc != BTBA_OK) throw Error(rc, "btba_mappoints_forget_frame");
+}
+
+bool GpuFeatureManager::findCorresChain(const std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> &all)
+{
+    std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> pairs;     // pairs already matched are skipped (:176)
+    std::set<std::pair<int, int>> seen;
+    for (const auto &p : all) {
+        const std::pair<int, int> key{ p.first->_id, p.second->_id };
+        if (_matches.count(key) || !seen.insert(key).second) continue;
+        pairs.push_back(p);
+    }
+    if (pairs.empty()) return true;
+    const Config &cfg = *yml;
+    btba_match_params prm;
+    btba_match_params_default(&prm);
+    prm.mutual = cfg.feature_corres_mutual ? 1 : 0;
+    prm.max_dist_neighbor = cfg.feature_corres_max_dist_neighbor;
+    prm.cos_max_normal_neighbor = (float)std::cos(cfg.feature_corres_max_normal_neighbor / 180.0 * M_PI);     // :252-255
+    prm.max_dist_no_neighbor = cfg.feature_corres_max_dist_no_neighbor;
+    prm.cos_max_normal_no_neighbor = (float)std::cos(cfg.feature_corres_max_normal_no_neighbor / 180.0 * M_PI);
+    btba_corres_params rp;
+    btba_corres_params_default(&rp);
+    rp.n_trials = cfg.ransac_max_iter;
+    rp.dist_thres = cfg.ransac_inlier_dist;
+    std::vector<Frame *> frames;                                                  // every frame once, in order of first appearance
+    std::map<const Frame *, int> index;
+    std::vector<int32_t> pr;
+    for (const auto &p : pairs)
+        for (const Frame *f : { p.first.get(), p.second.get() }) {
+            auto it = index.find(f);
+            if (it == index.end()) { it = index.emplace(f, (int)frames.size()).first; frames.push_back(const_cast<Frame *>(f)); }
+            pr.push_back(it->second);
+        }
+    const int n = (int)frames.size();
+    const Frame &f0 = *frames[0];
+    int D = 4;
+    std::vector<const float *> desc(n), kpts(n), depth(n), normal(n);
+    std::vector<int32_t> n_kpts(n), ids(n), slots(n), status(n);
+    std::vector<float> poses(16 * (size_t)n);
+    for (int k = 0; k < n; k++) {
+        Frame &f = *frames[k];
+        if (f._H != f0._H || f._W != f0._W) throw Error(BTBA_EINVAL, "findCorresChain: frames of different sizes");
+        if (f._n_keypts > 0) D = f._feat_dim;
+        desc[k] = f._feat_des_gpu; kpts[k] = reinterpret_cast<const float *>(f._kpts_gpu);
+        depth[k] = f._depth_gpu; normal[k] = reinterpret_cast<const float *>(f._normal_gpu);
+        n_kpts[k] = f._n_keypts; ids[k] = f._id;
+        status[k] = f._status == Frame::FAIL ? 1 : 0;
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) poses[16 * (size_t)k + 4 * r + c] = f._pose_in_model(r, c);
+        auto s = slots_.find(f._id);
+        if (s == slots_.end()) {
+            int32_t slot = -1;
+            const int rc = btba_mappoints_register_frame(mp_, f._n_keypts, reinterpret_cast<const float *>(f._kpts_gpu), &slot);
+            if (rc != BTBA_OK) throw Error(rc, "btba_mappoints_register_frame");
+            s = slots_.emplace(f._id, slot).first;
+        }
+        slots[k] = s->second;
+    }
+    float K[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) K[3 * r + c] = f0._K(r, c);
+    int64_t cap = 0;
+    int rc = btba_corres_chain_capacity(&prm, n, f0._H, f0._W, D, n_kpts.data(), (int)pairs.size(), pr.data(), &cap);
+    if (rc != BTBA_OK) throw Error(rc, "btba_corres_chain_capacity");
+    std::vector<btba_match> out(std::max<int64_t>(cap, 1));
+    std::vector<int32_t> n_out(pairs.size());
+    rc = btba_corres_chain(ws_, mp_, &prm, &rp, /*device_resident=*/0, n, f0._H, f0._W, K, desc.data(), D, kpts.data(), n_kpts.data(), depth.data(),
+                           normal.data(), poses.data(), ids.data(), slots.data(), status.data(), (int)pairs.size(), pr.data(), out.data(), n_out.data(), nullptr);
+    if (rc != BTBA_OK) throw Error(rc, "btba_corres_chain");
+    for (int k = 0; k < n; k++)
+        if (status[k]) frames[k]->_status = Frame::FAIL;
+    size_t o = 0;
+    for (size_t p = 0; p < pairs.size(); p++) {
+        const std::pair<int, int> key{ pairs[p].first->_id, pairs[p].second->_id };
+        Correspondences &m = _matches[key];
+        std::vector<btba_match> &rec = _records[key];
+        m = Correspondences{};
+        rec.assign(out.begin() + o, out.begin() + o + n_out[p]);
+        for (const btba_match &r : rec) {
+            m.ptA_cam.insert(m.ptA_cam.end(), r.ptA_cam, r.ptA_cam + 3);
+            m.ptB_cam.insert(m.ptB_cam.end(), r.ptB_cam, r.ptB_cam + 3);
+        }
+        o += (size_t)n_out[p];
+    }
+    return true;
+}
+
 void DetectorFeatureManager::detectFeature(const std::shared_ptr<Frame> &frame)              // FeatureManager.cpp:811-908
 {
     prepareDetectorInputs(ws_, { frame }, bgr_, gray_, out_size_);
@@ -579,8 +689,11 @@ void Bundler::processNewFrame(std::shared_ptr<Frame> frame)
 void Bundler::optimizeGPU()
 {
     std::sort(_local_frames.begin(), _local_frames.end(), [](const std::shared_ptr<Frame> &a, const std::shared_ptr<Frame> &b) { return a->_id < b->_id; });   // :286
+    std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> pairs;
     for (size_t i = 0; i < _local_frames.size(); i++)
-        for (size_t j = i + 1; j < _local_frames.size(); j++) _fm->findCorres(_local_frames[j], _local_frames[i]);                                       // :303
+        for (size_t j = i + 1; j < _local_frames.size(); j++) pairs.emplace_back(_local_frames[j], _local_frames[i]);                                    // :303
+    if (!_fm->findCorresChain(pairs))                                           // a feature manager without a chain: pair by pair
+        for (const auto &p : pairs) _fm->findCorres(p.first, p.second);
     last_window = marshalWindow(_local_frames, _fm->_matches, _newframe, yml->min_fm_edges_newframe);          // :296-347 (sets NO_BA)
     if (!last_window.run_ba) return;
     const auto &fr = last_window.frames;

@@ -188,6 +188,9 @@ public:
     // fills _matches[{frameA->_id, frameB->_id}] unless present (:176); may mark frameA FAIL
     virtual void findCorres(const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB) = 0;
     virtual void forgetFrame(const std::shared_ptr<Frame> &frame);                                                   // :142-170
+    // Bundler::optimizeGPU's opt-in: a feature manager that runs a window's pairs (findCorres order) in one call does so and returns
+    // true (GpuFeatureManager); the default does nothing and returns false, and the Bundler then calls findCorres pair by pair.
+    virtual bool findCorresChain(const std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> & /*pairs*/) { return false; }
     int countInlierCorres(const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB) const;          // :746-758
     // :523-556: Kabsch of the matches moved into the model frame with the frames' current poses; identity below 5 matches
     virtual Matrix4f procrustesByCorrespondence(const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB);
@@ -228,6 +231,27 @@ private:
     uint8_t *bgr_;
     float *gray_;
     int out_size_;
+};
+
+// SiftManager::findCorres (FeatureManager.cpp:173-240) with its map points on btba_corres_chain: NN, propagation along the map
+// points, RANSAC (ransac.max_iter / inlier_dist of yml), the map-point update and the FAIL gates for an ordered list of pairs in one
+// call, the frames' map points in a btba_mappoints on `ws` (a frame is registered at its first pair, by _id; forgetFrame frees its
+// slot).  Frames need _kpts_gpu, _feat_des_gpu, _feat_dim, _depth_gpu, _normal_gpu, _H, _W, _K.  _records keeps the btba_match
+// records of every pair (propagated ones: dir = 2).  Needs the GPU; every call is synchronous.
+class GpuFeatureManager : public FeatureManager {
+public:
+    std::map<std::pair<int, int>, std::vector<btba_match>> _records;
+    explicit GpuFeatureManager(btba_workspace *ws, std::shared_ptr<Config> yml1 = nullptr);
+    ~GpuFeatureManager() override;
+    GpuFeatureManager(const GpuFeatureManager &) = delete;
+    GpuFeatureManager &operator=(const GpuFeatureManager &) = delete;
+    void findCorres(const std::shared_ptr<Frame> &frameA, const std::shared_ptr<Frame> &frameB) override;
+    bool findCorresChain(const std::vector<std::pair<std::shared_ptr<Frame>, std::shared_ptr<Frame>>> &pairs) override;
+    void forgetFrame(const std::shared_ptr<Frame> &frame) override;
+private:
+    btba_workspace *ws_;
+    btba_mappoints *mp_ = nullptr;
+    std::map<int, int32_t> slots_;                                  // frame id -> slot
 };
 
 // Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its depth and normals on the device: the

@@ -28,6 +28,7 @@
 #include "btba_mask.hpp"
 #include "btba_detect.hpp"
 #include "btba_eval.hpp"
+#include "btba_mappoints.hpp"
 
 using namespace btba;
 
@@ -171,6 +172,7 @@ struct btba_workspace {
     DevBuf match;                                           // btba_match_pairs: tables, norms, candidate lists, selections, counts, host-form staging
     DevBuf mask;                                            // btba_apply_masks: labels, counts, argmax keys, row extents, spans, hull stacks, ROI slots
     DevBuf eval;                                            // btba_pose_errors: chunk tables, host-form poses and outputs, per-point minima
+    DevBuf corres;                                          // btba_corres_chain: frame / pair tables, NN output, working lists, per-pair words
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;
@@ -1955,6 +1957,32 @@ int btba_solve_batch_zn_aux(btba_workspace *ws, const btba_params *params, int n
 
 
 // ---- correspondence RANSAC ---------------------------------------------------------
+// the reference's per-trial cuRAND streams = one table of uniforms for all pairs; rebuilt only when the seed changes or
+// more trials are asked for than the table holds (a longer table for the same seed starts with the shorter one)
+static int ransac_uniform_table(btba_workspace *ws, uint64_t seed, int n_trials)
+{
+    if (ws->ransac_u_host.size() >= 3 * (size_t)n_trials && ws->ransac_u_seed == seed) return BTBA_OK;
+    HIP_TRY(hipStreamSynchronize(ws->stream));      // an earlier call's kernels / upload may still be using the old table
+    ws->ransac_u_host.assign(3 * (size_t)n_trials, 0.0f);
+    xorwow::ransac_uniform_table(seed, n_trials, ws->ransac_u_host.data());
+    ws->ransac_u_seed = seed;
+    int rc;
+    if ((rc = ws->ransac_u.ensure(12 * (size_t)n_trials))) return rc;
+    HIP_TRY(hipMemcpyAsync(ws->ransac_u.p, ws->ransac_u_host.data(), 12 * (size_t)n_trials, hipMemcpyHostToDevice, ws->stream));
+    return BTBA_OK;
+}
+
+// vote + extraction for D.n_pairs pairs whose point counts are on the DEVICE (offsets[p] .. offsets[p + 1]); `best` zeroed by the caller.
+// Asynchronous on the workspace stream: btba_ransac_pairs_ex and btba_corres_chain (one pair per call, its count written by an earlier kernel).
+static int ransac_enqueue(btba_workspace *ws, const RansacDims &D, const float4 *dA, const float4 *dB, const int *d_offsets, const int *dS, float *d_pose,
+                          int *d_cnt, unsigned long long *d_best, int *d_ids, int *d_nin, int *d_bt, float *d_bp)
+{
+    k_ransac_vote<<<dim3((D.n_trials + 255) / 256, D.n_pairs), 256, 0, ws->stream>>>(D, dA, dB, d_offsets, dS, ws->ransac_u.as<float>(), d_pose, d_cnt, d_best);
+    k_ransac_extract<<<D.n_pairs, 256, 0, ws->stream>>>(D, dA, dB, d_offsets, d_pose, d_best, d_ids, d_nin, d_bt, d_bp);
+    HIP_TRY(hipGetLastError());
+    return BTBA_OK;
+}
+
 int btba_ransac_pairs_ex(btba_workspace *ws, int hypothesis, int device_resident, int n_pairs, const float *ptsA, const float *ptsB, const int32_t *n_pts,
                          int n_trials, float dist_thres, const int32_t *samples, uint64_t seed,
                          int32_t *inlier_ids_out, int32_t *n_inliers_out, int32_t *best_trial_out, float *best_pose_out,
@@ -1997,18 +2025,7 @@ int btba_ransac_pairs_ex(btba_workspace *ws, int hypothesis, int device_resident
     HIP_TRY(hipStreamSynchronize(ws->stream));          // `offsets` is a local (16 B per pair: the only host wait of the device-resident form)
     if (samples && !dev) HIP_TRY(hipMemcpyAsync(base + o_smp, samples, 12 * NT, hipMemcpyHostToDevice, ws->stream));
     HIP_TRY(hipMemsetAsync(base + o_best, 0, 8 * (size_t)n_pairs, ws->stream));
-    if (!samples && !draw_hash) {
-        // the reference's per-trial cuRAND streams = one table of uniforms for all pairs; rebuilt only when the seed changes or
-        // more trials are asked for than the table holds (a longer table for the same seed starts with the shorter one)
-        if (ws->ransac_u_host.size() < 3 * (size_t)n_trials || ws->ransac_u_seed != seed) {
-            HIP_TRY(hipStreamSynchronize(ws->stream));      // an earlier call's kernels / upload may still be using the old table
-            ws->ransac_u_host.assign(3 * (size_t)n_trials, 0.0f);
-            xorwow::ransac_uniform_table(seed, n_trials, ws->ransac_u_host.data());
-            ws->ransac_u_seed = seed;
-            if ((rc = ws->ransac_u.ensure(12 * (size_t)n_trials))) return rc;
-            HIP_TRY(hipMemcpyAsync(ws->ransac_u.p, ws->ransac_u_host.data(), 12 * (size_t)n_trials, hipMemcpyHostToDevice, ws->stream));
-        }
-    }
+    if (!samples && !draw_hash && (rc = ransac_uniform_table(ws, seed, n_trials))) return rc;
     RansacDims D{};
     D.n_pairs = n_pairs; D.n_trials = n_trials; D.dist_thres = dist_thres; D.seed = seed; D.hypothesis = hypothesis;
     D.draw = samples ? 1 : (draw_hash ? 0 : 2);
@@ -2022,11 +2039,9 @@ int btba_ransac_pairs_ex(btba_workspace *ws, int hypothesis, int device_resident
     float *d_bp = (dev && best_pose_out) ? best_pose_out : reinterpret_cast<float *>(base + o_bp);
     int *d_cnt = (dev && trial_counts_out) ? trial_counts_out : reinterpret_cast<int *>(base + o_cnt);
     float *d_pose = (dev && trial_poses_out) ? trial_poses_out : reinterpret_cast<float *>(base + o_pose);
-    k_ransac_vote<<<dim3((n_trials + 255) / 256, n_pairs), 256, 0, ws->stream>>>(
-        D, dA, dB, reinterpret_cast<const int *>(base + o_off), dS, ws->ransac_u.as<float>(), d_pose, d_cnt, reinterpret_cast<unsigned long long *>(base + o_best));
-    k_ransac_extract<<<n_pairs, 256, 0, ws->stream>>>(
-        D, dA, dB, reinterpret_cast<const int *>(base + o_off), d_pose, reinterpret_cast<const unsigned long long *>(base + o_best), d_ids, d_nin, d_bt, d_bp);
-    HIP_TRY(hipGetLastError());
+    if ((rc = ransac_enqueue(ws, D, dA, dB, reinterpret_cast<const int *>(base + o_off), dS, d_pose, d_cnt, reinterpret_cast<unsigned long long *>(base + o_best),
+                             d_ids, d_nin, d_bt, d_bp)))
+        return rc;
     if (dev) return BTBA_OK;                          // asynchronous on the workspace stream
     // the inlier lists are written only up to each pair's count: fetch counts first, ids after
     HIP_TRY(hipMemcpyAsync(n_inliers_out, d_nin, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost, ws->stream));
@@ -2087,18 +2102,14 @@ int btba_match_capacity(const btba_match_params *prm, int n_frames, int H, int W
     return BTBA_OK;
 }
 
-int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int device_resident, int n_frames, int H, int W,
-                     const float *K, const float *const *desc_dev, int D, const float *const *kpts_dev,
-                     const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev, const float *poses,
-                     const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
-                     btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, int32_t *n_out)
+// every pointer argument btba_match_pairs / btba_corres_chain read before their first HIP call
+static int match_check_frames(const btba_match_params *prm, int n_frames, int H, int W, int D, const int32_t *n_kpts, int n_pairs, const int32_t *pairs,
+                              const float *K, const float *const *desc_dev, const float *const *kpts_dev, const float *const *depth_dev,
+                              const float *const *normal_dev, const float *poses, const int32_t *frame_ids, int64_t *cap)
 {
-    // every argument is checked before the first HIP call
-    int64_t cap = 0;
-    int rc = btba_match_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, &cap);
+    int rc = btba_match_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, cap);
     if (rc) return rc;
-    if (!ws || !K || !desc_dev || !kpts_dev || !depth_dev || !normal_dev || !poses || !frame_ids || (n_pairs && !n_out) || (cap && !matches_out))
-        return BTBA_EINVAL;
+    if (!K || !desc_dev || !kpts_dev || !depth_dev || !normal_dev || !poses || !frame_ids) return BTBA_EINVAL;
     std::vector<char> used(n_frames, 0);
     for (int p = 0; p < n_pairs; p++) used[pairs[2 * p]] = used[pairs[2 * p + 1]] = 1;
     auto misaligned = [](const void *q, size_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
@@ -2106,11 +2117,29 @@ int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int devic
         if (used[f] && n_kpts[f] > 0 &&
             (!desc_dev[f] || !kpts_dev[f] || !depth_dev[f] || !normal_dev[f] || misaligned(desc_dev[f], 16) || misaligned(kpts_dev[f], 8) || misaligned(normal_dev[f], 16)))
             return BTBA_EINVAL;
-    if (n_pairs == 0) return BTBA_OK;
-    DeviceGuard device_guard(ws);
+    return BTBA_OK;
+}
 
+// The matcher's launches for validated arguments, asynchronous on the workspace stream.  The host tables stay in E until the
+// caller has synchronised; E.d_cnt / E.d_off are the per-pair counts and offsets (device, in ws->match).
+struct MatchEnqueue {
+    std::vector<MatchFrame> fr;
+    std::vector<MatchPair> pt;
+    int *d_cnt = nullptr, *d_off = nullptr;
+    btba_match *d_out = nullptr;
+    float4 *d_pa = nullptr, *d_pb = nullptr;
+};
+
+static int match_enqueue(btba_workspace *ws, const btba_match_params *prm, bool dev, int n_frames, int H, int W, const float *K,
+                         const float *const *desc_dev, int D, const float *const *kpts_dev, const int32_t *n_kpts, const float *const *depth_dev,
+                         const float *const *normal_dev, const float *poses, const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
+                         btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, MatchEnqueue &E)
+{
+    std::vector<char> used(n_frames, 0);
+    for (int p = 0; p < n_pairs; p++) used[pairs[2 * p]] = used[pairs[2 * p + 1]] = 1;
     // host tables: frames, pairs (thresholds chosen by frame ids, FeatureManager.cpp:259)
-    std::vector<MatchFrame> fr(n_frames);
+    std::vector<MatchFrame> &fr = E.fr;
+    fr.assign(n_frames, MatchFrame{});
     int n_norms = 0, max_n = 0;
     for (int f = 0; f < n_frames; f++) {
         MatchFrame &m = fr[f];
@@ -2123,7 +2152,8 @@ int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int devic
         max_n = std::max(max_n, m.n);
         for (int k = 0; k < 12; k++) m.pose[k] = poses[16 * f + k];
     }
-    std::vector<MatchPair> pt(n_pairs);
+    std::vector<MatchPair> &pt = E.pt;
+    pt.assign(n_pairs, MatchPair{});
     int qbase = 0, max_q = 0;
     for (int p = 0; p < n_pairs; p++) {
         const int a = pairs[2 * p], b = pairs[2 * p + 1];
@@ -2135,7 +2165,6 @@ int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int devic
         max_q = std::max(max_q, nq);
     }
     const size_t Q = (size_t)qbase;
-    const bool dev = device_resident != 0;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     size_t o = 0;
     const size_t o_fr = o; o += al(sizeof(MatchFrame) * n_frames);
@@ -2149,6 +2178,7 @@ int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int devic
     const size_t o_out = o; o += dev ? 0 : al(sizeof(btba_match) * (Q ? Q : 1));
     const size_t o_pa = o; o += (dev || !ptsA_model_out) ? 0 : al(16 * (Q ? Q : 1));
     const size_t o_pb = o; o += (dev || !ptsB_model_out) ? 0 : al(16 * (Q ? Q : 1));
+    int rc;
     if ((rc = ws->match.ensure(o))) return rc;
     unsigned char *base = ws->match.as<unsigned char>();
     HIP_TRY(hipMemcpyAsync(base + o_fr, fr.data(), sizeof(MatchFrame) * n_frames, hipMemcpyHostToDevice, ws->stream));
@@ -2176,15 +2206,37 @@ int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int devic
     if (max_q > 0)
         k_match_pack<<<dim3(n_pairs, (max_q + 255) / 256), 256, 0, ws->stream>>>(M, dF, dP, d_cand, d_sel, d_pos, d_off, d_out, d_pa, d_pb);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(n_out, d_cnt, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, ws->stream));
-    HIP_TRY(hipStreamSynchronize(ws->stream));                       // n_out valid; the host tables above may go
+    E.d_cnt = d_cnt; E.d_off = d_off; E.d_out = d_out; E.d_pa = d_pa; E.d_pb = d_pb;
+    return BTBA_OK;
+}
+
+int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int device_resident, int n_frames, int H, int W,
+                     const float *K, const float *const *desc_dev, int D, const float *const *kpts_dev,
+                     const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev, const float *poses,
+                     const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
+                     btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, int32_t *n_out)
+{
+    // every argument is checked before the first HIP call
+    int64_t cap = 0;
+    int rc = match_check_frames(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, K, desc_dev, kpts_dev, depth_dev, normal_dev, poses, frame_ids, &cap);
+    if (rc) return rc;
+    if (!ws || (n_pairs && !n_out) || (cap && !matches_out)) return BTBA_EINVAL;
+    if (n_pairs == 0) return BTBA_OK;
+    DeviceGuard device_guard(ws);
+    const bool dev = device_resident != 0;
+    MatchEnqueue E;
+    if ((rc = match_enqueue(ws, prm, dev, n_frames, H, W, K, desc_dev, D, kpts_dev, n_kpts, depth_dev, normal_dev, poses, frame_ids, n_pairs, pairs,
+                            matches_out, ptsA_model_out, ptsB_model_out, E)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(n_out, E.d_cnt, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, ws->stream));
+    HIP_TRY(hipStreamSynchronize(ws->stream));                       // n_out valid; the host tables in E may go
     if (!dev) {
         size_t total = 0;
         for (int p = 0; p < n_pairs; p++) total += (size_t)n_out[p];
         if (total) {
-            HIP_TRY(hipMemcpyAsync(matches_out, d_out, sizeof(btba_match) * total, hipMemcpyDeviceToHost, ws->stream));
-            if (d_pa) HIP_TRY(hipMemcpyAsync(ptsA_model_out, d_pa, 16 * total, hipMemcpyDeviceToHost, ws->stream));
-            if (d_pb) HIP_TRY(hipMemcpyAsync(ptsB_model_out, d_pb, 16 * total, hipMemcpyDeviceToHost, ws->stream));
+            HIP_TRY(hipMemcpyAsync(matches_out, E.d_out, sizeof(btba_match) * total, hipMemcpyDeviceToHost, ws->stream));
+            if (E.d_pa) HIP_TRY(hipMemcpyAsync(ptsA_model_out, E.d_pa, 16 * total, hipMemcpyDeviceToHost, ws->stream));
+            if (E.d_pb) HIP_TRY(hipMemcpyAsync(ptsB_model_out, E.d_pb, 16 * total, hipMemcpyDeviceToHost, ws->stream));
             HIP_TRY(hipStreamSynchronize(ws->stream));
         }
     }
@@ -2474,3 +2526,357 @@ int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, cons
 }
 
 }  // extern "C"
+
+// ---- map-point memory and the tracker's findCorres (btba_mappoints.hpp) ------------------------------------------------------
+struct btba_mappoints {
+    btba_workspace *ws = nullptr;
+    int device = 0;                        // the workspace's device: destroy does not touch the workspace (it may be gone already)
+    struct Slot { bool live = false; int n = 0; DevBuf data; };     // data: kpts float2[n] | canon int[n] | order int[n] | map int[n]
+    std::vector<Slot> slots;
+    int slot_cap = 0, mp_cap = 0;
+    DevBuf table;                          // MpSlot[slot_cap]
+    DevBuf img;                            // int [mp_cap][slot_cap]
+    DevBuf stamp, stack;                   // int [mp_cap] each
+    DevBuf hdr;                            // kMpNext, kMpTop, kMpErr
+    int64_t live_known = 0;                // live map points at the last host synchronisation of forget
+    int64_t bound = 0;                     // upper bound of live map points: live_known + keypoints of every slot that may still create some
+    bool broken = false;                   // the device allocator's guard fired (unreachable while capacity >= bound): the memory is unusable
+};
+
+namespace {
+constexpr int kMpMaxSlots = 1024;
+constexpr int64_t kMpMaxImgInts = (int64_t)1 << 28;     // 1 GiB of img rows
+
+size_t mp_slot_bytes(int n) { return (size_t)n * 8 + 3 * (size_t)n * 4 + 64; }
+MpSlot mp_slot_view(btba_mappoints::Slot &s)
+{
+    MpSlot v{};
+    unsigned char *b = s.data.as<unsigned char>();
+    v.kpts = reinterpret_cast<const float2 *>(b);
+    v.canon = reinterpret_cast<const int *>(b + (size_t)s.n * 8);
+    v.order = reinterpret_cast<const int *>(b + (size_t)s.n * 12);
+    v.map = reinterpret_cast<int *>(b + (size_t)s.n * 16);
+    v.n = s.n;
+    return v;
+}
+
+// grow img / stamp / stack / the slot table to (slots, points); contents kept, new entries -1.  Synchronous.
+int mp_grow(btba_mappoints *M, int slots, int points)
+{
+    if (slots <= M->slot_cap && points <= M->mp_cap) return BTBA_OK;
+    hipStream_t st = M->ws->stream;
+    const int ns = std::max(slots, M->slot_cap), np = std::max(points, M->mp_cap);
+    if ((int64_t)ns * np > kMpMaxImgInts || ns > kMpMaxSlots) return BTBA_ENOMEM;
+    DevBuf img, stamp, stack, table;
+    int rc;
+    if ((rc = img.ensure((size_t)ns * np * 4)) || (rc = stamp.ensure((size_t)np * 4)) || (rc = stack.ensure((size_t)np * 4)) ||
+        (rc = table.ensure(sizeof(MpSlot) * ns))) {
+        img.release(); stamp.release(); stack.release(); table.release();
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(img.p, 0xFF, (size_t)ns * np * 4, st));
+    HIP_TRY(hipMemsetAsync(stamp.p, 0xFF, (size_t)np * 4, st));
+    HIP_TRY(hipMemsetAsync(table.p, 0, sizeof(MpSlot) * ns, st));
+    if (M->mp_cap && M->slot_cap) {
+        HIP_TRY(hipMemcpy2DAsync(img.p, (size_t)ns * 4, M->img.p, (size_t)M->slot_cap * 4, (size_t)M->slot_cap * 4, M->mp_cap, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(stack.p, M->stack.p, (size_t)M->mp_cap * 4, hipMemcpyDeviceToDevice, st));
+    }
+    if (M->slot_cap) HIP_TRY(hipMemcpyAsync(table.p, M->table.p, sizeof(MpSlot) * M->slot_cap, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    M->img.release(); M->stamp.release(); M->stack.release(); M->table.release();
+    M->img = img; M->stamp = stamp; M->stack = stack; M->table = table;
+    M->slot_cap = ns; M->mp_cap = np;
+    return BTBA_OK;
+}
+}  // namespace
+
+int btba_mappoints_create(btba_workspace *ws, btba_mappoints **out)
+{
+    if (!ws || !out) return BTBA_EINVAL;
+    *out = nullptr;
+    DeviceGuard device_guard(ws);
+    btba_mappoints *M = new (std::nothrow) btba_mappoints;
+    if (!M) return BTBA_ENOMEM;
+    M->ws = ws;
+    M->device = ws->device;
+    int rc;
+    if ((rc = M->hdr.ensure(16))) { delete M; return rc; }
+    hipError_t e = hipMemsetAsync(M->hdr.p, 0, 16, ws->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
+    if (e != hipSuccess) { g_last_hip_error = (int)e; M->hdr.release(); delete M; return BTBA_EHIP; }
+    *out = M;
+    return BTBA_OK;
+}
+
+void btba_mappoints_destroy(btba_mappoints *M)
+{
+    if (!M) return;
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
+    (void)hipDeviceSynchronize();                                     // hipFree below; no workspace access
+    for (auto &s : M->slots) s.data.release();
+    M->img.release(); M->stamp.release(); M->stack.release(); M->table.release(); M->hdr.release();
+    delete M;
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+int btba_mappoints_register_frame(btba_mappoints *M, int n_kpts, const float *kpts_dev, int32_t *slot_out)
+{
+    if (!M || !slot_out || n_kpts < 0 || n_kpts > kMatchMaxKpts || (n_kpts && !kpts_dev) || (reinterpret_cast<uintptr_t>(kpts_dev) & 7)) return BTBA_EINVAL;
+    if (M->broken) return BTBA_ENOMEM;
+    DeviceGuard device_guard(M->ws);
+    hipStream_t st = M->ws->stream;
+    int slot = 0;
+    while (slot < (int)M->slots.size() && M->slots[slot].live) slot++;
+    int rc;
+    // capacity first: a failure here leaves the memory as it was
+    if ((rc = mp_grow(M, slot + 1 > M->slot_cap ? std::max(2 * M->slot_cap, std::max(slot + 1, 16)) : M->slot_cap,
+                      M->bound + n_kpts > M->mp_cap ? (int)std::min<int64_t>(std::max<int64_t>(2 * (int64_t)M->mp_cap, M->bound + n_kpts + 1024), INT_MAX) : M->mp_cap)))
+        return rc;
+    btba_mappoints::Slot fresh;
+    if ((rc = fresh.data.ensure(mp_slot_bytes(n_kpts)))) return rc;
+    fresh.n = n_kpts;
+    MpSlot v = mp_slot_view(fresh);
+    int *bad = reinterpret_cast<int *>(fresh.data.as<unsigned char>() + (size_t)n_kpts * 20);
+    HIP_TRY(hipMemsetAsync(bad, 0, 4, st));
+    if (n_kpts) {
+        HIP_TRY(hipMemcpyAsync(const_cast<float2 *>(v.kpts), kpts_dev, (size_t)n_kpts * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(const_cast<int *>(v.order), 0xFF, (size_t)n_kpts * 4, st));
+        const int g = (n_kpts + 255) / 256;
+        k_mp_canon<<<g, 256, 0, st>>>(v.kpts, n_kpts, const_cast<int *>(v.canon), bad);
+        k_mp_order<<<g, 256, 0, st>>>(v.kpts, n_kpts, v.canon, const_cast<int *>(v.order), v.map);
+        HIP_TRY(hipGetLastError());
+    }
+    int bad_h = 0;
+    HIP_TRY(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad_h) { fresh.data.release(); return BTBA_EINVAL; }                 // a non-finite keypoint
+    HIP_TRY(hipMemcpy(M->table.as<MpSlot>() + slot, &v, sizeof(MpSlot), hipMemcpyHostToDevice));
+    if (slot == (int)M->slots.size()) M->slots.emplace_back();
+    M->slots[slot].data.release();
+    M->slots[slot].data = fresh.data;
+    M->slots[slot].n = n_kpts;
+    M->slots[slot].live = true;
+    M->bound += n_kpts;
+    *slot_out = slot;
+    return BTBA_OK;
+}
+
+int btba_mappoints_forget_frame(btba_mappoints *M, int32_t slot)
+{
+    if (!M || slot < 0 || slot >= (int)M->slots.size() || !M->slots[slot].live) return BTBA_EINVAL;
+    if (M->broken) return BTBA_ENOMEM;
+    DeviceGuard device_guard(M->ws);
+    hipStream_t st = M->ws->stream;
+    if (M->mp_cap) {
+        k_mp_forget<<<1, 256, 0, st>>>(slot, M->slot_cap, M->img.as<int>(), M->hdr.as<int>(), M->stack.as<int>());
+        HIP_TRY(hipGetLastError());
+    }
+    int h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, M->hdr.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    M->slots[slot].live = false;
+    M->slots[slot].data.release();
+    M->slots[slot].n = 0;
+    MpSlot dead{};
+    HIP_TRY(hipMemcpy(M->table.as<MpSlot>() + slot, &dead, sizeof(MpSlot), hipMemcpyHostToDevice));
+    M->live_known = h[kMpNext] - h[kMpTop];
+    M->bound = M->live_known;
+    for (auto &s : M->slots)
+        if (s.live) M->bound += s.n;
+    return BTBA_OK;
+}
+
+int btba_mappoints_export(btba_mappoints *M, int32_t *dims_out, int32_t *slot_n_out, int32_t *canon_out, int32_t *map_out, int32_t *img_out)
+{
+    if (!M || !dims_out) return BTBA_EINVAL;
+    DeviceGuard device_guard(M->ws);
+    hipStream_t st = M->ws->stream;
+    int h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, M->hdr.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int S = (int)M->slots.size();
+    int64_t total = 0;
+    for (auto &s : M->slots) total += s.live ? s.n : 0;
+    dims_out[0] = S; dims_out[1] = h[kMpNext]; dims_out[2] = (int32_t)total; dims_out[3] = h[kMpErr];
+    if (slot_n_out)
+        for (int k = 0; k < S; k++) slot_n_out[k] = M->slots[k].live ? M->slots[k].n : -1;
+    int64_t off = 0;
+    for (int k = 0; k < S; k++) {
+        btba_mappoints::Slot &s = M->slots[k];
+        if (!s.live || !s.n) continue;
+        MpSlot v = mp_slot_view(s);
+        if (canon_out) HIP_TRY(hipMemcpyAsync(canon_out + off, v.canon, (size_t)s.n * 4, hipMemcpyDeviceToHost, st));
+        if (map_out) HIP_TRY(hipMemcpyAsync(map_out + off, v.map, (size_t)s.n * 4, hipMemcpyDeviceToHost, st));
+        off += s.n;
+    }
+    if (img_out && h[kMpNext] && S)
+        HIP_TRY(hipMemcpy2DAsync(img_out, (size_t)S * 4, M->img.p, (size_t)M->slot_cap * 4, (size_t)S * 4, h[kMpNext], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BTBA_OK;
+}
+
+void btba_corres_params_default(btba_corres_params *p)
+{
+    if (!p) return;
+    p->n_trials = 2000;                                               // ransac.max_iter (btba::Config::ransac_max_iter)
+    p->dist_thres = 0.01f;                                            // ransac.inlier_dist
+    p->hypothesis = BTBA_RANSAC_REFERENCE_SVD;
+    p->pad = 0;
+    p->seed = 0;                                                      // the reference's literal curand_init seed
+}
+
+int btba_corres_chain_capacity(const btba_match_params *prm, int n_frames, int H, int W, int D, const int32_t *n_kpts,
+                               int n_pairs, const int32_t *pairs, int64_t *capacity_out)
+{
+    int64_t nn = 0;
+    int rc = btba_match_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, &nn);
+    if (rc) return rc;
+    std::vector<std::pair<int, int>> seen;
+    seen.reserve(n_pairs);
+    int64_t cap = nn;
+    for (int p = 0; p < n_pairs; p++) {
+        const int a = pairs[2 * p], b = pairs[2 * p + 1];
+        seen.emplace_back(std::min(a, b), std::max(a, b));
+        cap += n_kpts[a];                                             // propagated matches: at most one per key of A
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return BTBA_EINVAL;     // a frame pair twice
+    if (cap > INT_MAX) return BTBA_EINVAL;
+    *capacity_out = cap;
+    return BTBA_OK;
+}
+
+int btba_corres_chain(btba_workspace *ws, btba_mappoints *M, const btba_match_params *prm, const btba_corres_params *rprm, int device_resident,
+                      int n_frames, int H, int W, const float *K, const float *const *desc_dev, int D, const float *const *kpts_dev,
+                      const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev, const float *poses,
+                      const int32_t *frame_ids, const int32_t *slots, int32_t *status, int n_pairs, const int32_t *pairs,
+                      btba_match *matches_out, int32_t *n_out, int32_t *stage_counts_out)
+{
+    // every argument is checked before the first HIP call
+    int64_t cap = 0, cap_nn = 0;
+    int rc = btba_corres_chain_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, &cap);
+    if (rc) return rc;
+    if ((rc = match_check_frames(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, K, desc_dev, kpts_dev, depth_dev, normal_dev, poses, frame_ids, &cap_nn)))
+        return rc;
+    if (!ws || !M || M->ws != ws || !rprm || !slots || !status || (n_pairs && !n_out) || (cap && !matches_out)) return BTBA_EINVAL;
+    if (M->broken || M->bound > M->mp_cap) return BTBA_ENOMEM;         // before any launch: nothing changes
+    const int hyp = rprm->hypothesis & ~BTBA_RANSAC_DRAW_HASH;
+    if (rprm->n_trials < 1 || !(rprm->dist_thres >= 0.0f) || (hyp != BTBA_RANSAC_REFERENCE_SVD && hyp != BTBA_RANSAC_HORN)) return BTBA_EINVAL;
+    std::vector<int> slot_user(M->slots.size(), -1);
+    for (int p = 0; p < n_pairs; p++)
+        for (int s = 0; s < 2; s++) {
+            const int f = pairs[2 * p + s], sl = slots[f];
+            if (sl < 0 || sl >= (int)M->slots.size() || !M->slots[sl].live || M->slots[sl].n != n_kpts[f]) return BTBA_EINVAL;
+            if (slot_user[sl] >= 0 && slot_user[sl] != f) return BTBA_EINVAL;    // two frames of the call on one slot
+            slot_user[sl] = f;
+        }
+    for (int p = 0; p < n_pairs; p++)
+        if (frame_ids[pairs[2 * p]] <= frame_ids[pairs[2 * p + 1]]) return BTBA_EINVAL;   // A is the newer frame
+    if (n_pairs == 0) return BTBA_OK;
+    DeviceGuard device_guard(ws);
+    hipStream_t st = ws->stream;
+
+    // host tables (alive until the final synchronisation)
+    std::vector<CorresFrame> cf(n_frames);
+    for (int f = 0; f < n_frames; f++) {
+        cf[f] = CorresFrame{};
+        cf[f].depth = depth_dev[f];
+        for (int k = 0; k < 12; k++) cf[f].pose[k] = poses[16 * f + k];
+        cf[f].slot = slots[f];
+    }
+    std::vector<CorresPair> cp(n_pairs);
+    int64_t base = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        const int a = pairs[2 * p], b = pairs[2 * p + 1];
+        cp[p] = CorresPair{ a, b, std::abs((long long)frame_ids[a] - (long long)frame_ids[b]) == 1 ? 1 : 0, (int)base };
+        base += n_kpts[a] + (prm->mutual ? n_kpts[b] : 0) + n_kpts[a];
+    }
+    const size_t L = (size_t)std::max<int64_t>(base, 1), Nn = (size_t)std::max<int64_t>(cap_nn, 1), NT = (size_t)rprm->n_trials;
+    const bool dev = device_resident != 0;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t o = 0;
+    const size_t o_cf = o; o += al(sizeof(CorresFrame) * n_frames);
+    const size_t o_cp = o; o += al(sizeof(CorresPair) * n_pairs);
+    const size_t o_nn = o; o += al(sizeof(btba_match) * Nn);
+    const size_t o_npa = o; o += al(16 * Nn);
+    const size_t o_npb = o; o += al(16 * Nn);
+    const size_t o_list = o; o += al(sizeof(btba_match) * L);
+    const size_t o_la = o; o += al(16 * L);
+    const size_t o_lb = o; o += al(16 * L);
+    const size_t o_ids = o; o += al(4 * L);
+    const size_t o_ump = o; o += al(4 * L);
+    const size_t o_ua = o; o += al(4 * L);
+    const size_t o_out = o; o += dev ? 0 : al(sizeof(btba_match) * (size_t)std::max<int64_t>(cap, 1));
+    const size_t o_meta = o; o += al(8 * (size_t)n_pairs);
+    const size_t o_roff = o; o += al(8 * (size_t)n_pairs);
+    const size_t o_best = o; o += al(8 * (size_t)n_pairs);
+    const size_t o_nin = o; o += al(4 * (size_t)n_pairs);
+    const size_t o_bt = o; o += al(4 * (size_t)n_pairs);
+    const size_t o_bp = o; o += al(64 * (size_t)n_pairs);
+    const size_t o_tp = o; o += al(48 * NT);
+    const size_t o_tc = o; o += al(4 * NT);
+    const size_t o_res = o; o += al(4 * ((size_t)n_frames + 1 + 2 * (size_t)n_pairs + 4 * (size_t)n_pairs) + 16);   // status | out_off | n_out | stage | hdr copy
+    if ((rc = ws->corres.ensure(o))) return rc;
+    if (!(rprm->hypothesis & BTBA_RANSAC_DRAW_HASH) && (rc = ransac_uniform_table(ws, rprm->seed, rprm->n_trials))) return rc;
+    unsigned char *b0 = ws->corres.as<unsigned char>();
+    int *d_status = reinterpret_cast<int *>(b0 + o_res), *d_outoff = d_status + n_frames, *d_nout = d_outoff + n_pairs + 1, *d_stage = d_nout + n_pairs;
+    HIP_TRY(hipMemcpyAsync(b0 + o_cf, cf.data(), sizeof(CorresFrame) * n_frames, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b0 + o_cp, cp.data(), sizeof(CorresPair) * n_pairs, hipMemcpyHostToDevice, st));
+    std::vector<int32_t> st_in(status, status + n_frames);
+    HIP_TRY(hipMemcpyAsync(d_status, st_in.data(), 4 * (size_t)n_frames, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_outoff, 0, 4, st));
+
+    // NN for every pair at once (it reads no map state)
+    MatchEnqueue E;
+    if ((rc = match_enqueue(ws, prm, true, n_frames, H, W, K, desc_dev, D, kpts_dev, n_kpts, depth_dev, normal_dev, poses, frame_ids, n_pairs, pairs,
+                            reinterpret_cast<btba_match *>(b0 + o_nn), reinterpret_cast<float *>(b0 + o_npa), reinterpret_cast<float *>(b0 + o_npb), E)))
+        return rc;
+
+    CorresDims Cd{};
+    Cd.W = W; Cd.H = H; Cd.slot_cap = M->slot_cap; Cd.mp_cap = M->mp_cap;
+    float intr[4];
+    scaled_intrinsics(H, W, H, W, K, intr, &Cd.Kinv);
+    RansacDims Rd{};
+    Rd.n_pairs = 1; Rd.n_trials = rprm->n_trials; Rd.dist_thres = rprm->dist_thres; Rd.seed = rprm->seed; Rd.hypothesis = hyp;
+    Rd.draw = (rprm->hypothesis & BTBA_RANSAC_DRAW_HASH) ? 0 : 2;
+    const CorresFrame *dF = reinterpret_cast<const CorresFrame *>(b0 + o_cf);
+    const CorresPair *dP = reinterpret_cast<const CorresPair *>(b0 + o_cp);
+    btba_match *d_list = reinterpret_cast<btba_match *>(b0 + o_list);
+    float4 *d_la = reinterpret_cast<float4 *>(b0 + o_la), *d_lb = reinterpret_cast<float4 *>(b0 + o_lb);
+    int *d_ids = reinterpret_cast<int *>(b0 + o_ids), *d_meta = reinterpret_cast<int *>(b0 + o_meta), *d_roff = reinterpret_cast<int *>(b0 + o_roff);
+    unsigned long long *d_best = reinterpret_cast<unsigned long long *>(b0 + o_best);
+    int *d_nin = reinterpret_cast<int *>(b0 + o_nin), *d_bt = reinterpret_cast<int *>(b0 + o_bt);
+    float *d_bp = reinterpret_cast<float *>(b0 + o_bp), *d_tp = reinterpret_cast<float *>(b0 + o_tp);
+    int *d_tc = reinterpret_cast<int *>(b0 + o_tc);
+    btba_match *d_out = dev ? matches_out : reinterpret_cast<btba_match *>(b0 + o_out);
+    const MpSlot *dS = M->table.as<MpSlot>();
+    // per pair, in order: propagation, RANSAC (vote + inlier list), update + gates.  No host synchronisation in between.
+    for (int p = 0; p < n_pairs; p++) {
+        const int bs = cp[p].base;
+        k_corres_prop<<<1, 256, 0, st>>>(Cd, p, dF, dP, dS, M->img.as<int>(), reinterpret_cast<const btba_match *>(b0 + o_nn),
+                                         reinterpret_cast<const float4 *>(b0 + o_npa), reinterpret_cast<const float4 *>(b0 + o_npb), E.d_cnt, E.d_off,
+                                         d_status, d_list, d_la, d_lb, d_meta, d_roff, d_best, d_stage);
+        if ((rc = ransac_enqueue(ws, Rd, d_la + bs, d_lb + bs, d_roff + 2 * p, nullptr, d_tp, d_tc, d_best + p, d_ids + bs, d_nin + p, d_bt + p, d_bp + 16 * p)))
+            return rc;
+        k_corres_update<<<1, 256, 0, st>>>(Cd, p, dF, dP, dS, M->img.as<int>(), M->stamp.as<int>(), M->hdr.as<int>(), M->stack.as<int>(), d_status,
+                                           d_list, d_meta, d_ids, d_nin, reinterpret_cast<int *>(b0 + o_ump), reinterpret_cast<int *>(b0 + o_ua),
+                                           d_out, d_outoff, d_nout, d_stage);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> res((size_t)n_frames + 1 + 2 * (size_t)n_pairs + 4 * (size_t)n_pairs);
+    int hdr[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(res.data(), d_status, 4 * res.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hdr, M->hdr.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                              // the chain's one host synchronisation
+    if (hdr[kMpErr]) { M->broken = true; return BTBA_ENOMEM; }     // unreachable (capacity >= bound, checked above); should it fire, the memory is unusable
+    std::memcpy(status, res.data(), 4 * (size_t)n_frames);
+    const int32_t *r_off = res.data() + n_frames, *r_nout = r_off + n_pairs + 1, *r_stage = r_nout + n_pairs;
+    std::memcpy(n_out, r_nout, 4 * (size_t)n_pairs);
+    if (stage_counts_out) std::memcpy(stage_counts_out, r_stage, 16 * (size_t)n_pairs);
+    if (!dev && r_off[n_pairs]) {
+        HIP_TRY(hipMemcpyAsync(matches_out, d_out, sizeof(btba_match) * (size_t)r_off[n_pairs], hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return BTBA_OK;
+}

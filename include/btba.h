@@ -675,6 +675,86 @@ BTBA_API int btba_pose_errors(btba_workspace *ws, int device_resident,
                               const float *poses_pred, const float *poses_gt,
                               float *add_out, float *adds_out);
 
+/* ---- map points and the tracker's findCorres (the step between the matcher and BA) --------------------------------------
+ * The memory behind SiftManager::findCorres (src/FeatureManager.cpp:173-240): map points (feature tracks) link the RANSAC inliers
+ * of every processed pair (updateFramePairMapPoints, :448-487) and add PROPAGATED correspondences to non-neighbouring pairs
+ * (findCorresByMapPoints, :489-521).  The rules below are integer bookkeeping; the GPU reproduces them exactly.
+ * State.  Every live frame F has map_F: (u, v) -> map point, keyed by the keypoint's float (u, v) in std::map order (u, then v;
+ * Frame::_map_points, Frame.h:71).  A map point has img: frame -> (u, v).  forgetFrame(F) (:142-170) erases img[F] from every
+ * map point and touches no other frame's map.  Keys are (u, v) values, not indices: two keypoints of a frame with equal (u, v)
+ * (fp32 ==, so -0 == +0) are ONE key, represented by the lowest such index (the canonical index); a non-finite keypoint is
+ * BTBA_EINVAL at registration.
+ * findCorres(A, B), A newer, the pair not processed before, neighbor = |idA - idB| == 1:
+ *   1. NN: when both frames have keypoints, the btba_match_pairs records (A -> B, then B -> A, duplicates kept); neighbor and
+ *      fewer than 5 matches marks A FAIL.  With 0 keypoints on either side nothing is appended and nothing is marked.
+ *   2. A FAIL (now, or set by an earlier pair): the pair keeps its matches as they are; stop.
+ *   3. Propagation (non-neighbours): walk map_A in key order, skip map points without img[B]; candidate (uvA, uvB = img[B]) with
+ *      the camera-space points at roundf of each keypoint (the matcher's xyz convention, no gate); drop it if a match already in
+ *      the list (candidates appended earlier in this walk included) has the same A key or the same B key; else append it.
+ *   4. RANSAC (:561-657, 659-741; the propogated_samples / rand() code there is dead): <= 5 matches are cleared; otherwise
+ *      btba_ransac_pairs_ex on the model-frame points of all matches (this pair alone, n_pairs = 1) and the list becomes its
+ *      inliers in ascending order, cleared when fewer than 5 (:728-731).
+ *   5. (A FAIL: stop -- cannot happen after step 2.)
+ *   6. Update, match by match in order: both keys mapped (uvA in map_A, uvB in map_B): skip.  uvB not in map_B: a new map point
+ *      with img = {B: uvB}, map_B[uvB] = it; else mp = map_B[uvB].  Then mp.img[A] = uvA and map_A[uvA] = mp (overwriting; for a
+ *      map point shared by several matches the last one wins).  Later matches see earlier matches' effects.
+ *   7. Fewer than 5 matches: cleared, and A marked FAIL when neighbor.
+ *
+ * btba_mappoints lives on one workspace's device and stream.  A frame occupies a SLOT from registration to forget:
+ *   per slot: its keypoints (copied), canonical indices, walk order, and map_F as one int32 map-point id per keypoint;
+ *   per map point: one row of canonical keypoint indices, one per slot (-1 = none); ids of map points whose row becomes empty
+ *   on forget are recycled (such a point is unreachable: map_F[uv] = mp implies img[F] is present until F is forgotten).
+ * Slot count and map-point capacity are grow-only; capacity is reserved at registration for every map point the live slots can
+ * still create, so a chain never allocates.  Beyond the hard limits (1024 slots, 2^28 img entries) registration returns
+ * BTBA_ENOMEM and changes nothing.  A chain checks before its first launch that the capacity covers the bound (BTBA_ENOMEM, nothing
+ * changed, otherwise); the device allocator also guards every id it hands out.  That guard cannot fire while the bound holds; should it
+ * ever fire, the chain returns BTBA_ENOMEM with the memory partly updated and marks it unusable: every later register / forget / chain
+ * on it returns BTBA_ENOMEM (destroy and create a new one).  register / forget / export synchronise the workspace stream; _destroy does
+ * not touch the workspace (it may be destroyed before or after it).
+ *   _register_frame : n_kpts 0 .. 8192 device float2 keypoints (8-byte aligned) -> *slot_out (the lowest free slot)
+ *   _forget_frame   : forgetFrame; the slot is free for the next registration
+ *   _export         : host copy for tests.  dims_out[4] = {slots S, map-point ids M (high-water mark), sum of live slots' n, overflow
+ *                     flag}; any other pointer may be NULL (call once with them NULL to size them): slot_n_out[S] (n, or -1 for a free
+ *                     slot), canon_out / map_out (the live slots' arrays back to back in slot order), img_out [M][S] (-1 = none; rows of
+ *                     recycled ids are all -1).
+ *
+ * btba_corres_chain runs findCorres for an ORDERED list of pairs: btba_match_pairs' frame arguments (each frame's keypoints must
+ * be the ones its slot was registered with), slots[n_frames] (the frames of one pair list must occupy distinct slots), status
+ * [n_frames] host in / out (nonzero = FAIL; the chain writes 1), btba_corres_params (defaults = btba::Config: 2000 trials, 0.01 m,
+ * BTBA_RANSAC_REFERENCE_SVD, seed 0).  pairs: [n_pairs][2] frame indices, A first with frame_ids[A] > frame_ids[B], no frame pair
+ * twice.  NN runs once for all pairs (five launches); then per pair in order four single-workgroup-or-small launches: propagation,
+ * RANSAC vote, RANSAC inlier list, update + gates.  Nothing in between synchronises the host, allocates or copies to the host; the
+ * call synchronises once at the end (the host output form copies the records after that).
+ *   matches_out      : btba_match records of all pairs back to back, pair p at sum_{q<p} n_out[q]; capacity from
+ *                      btba_corres_chain_capacity (sum over pairs of nA + nB (mutual) + nA).  NN records as btba_match_pairs writes
+ *                      them; propagated records have dir = 2, dist = -1 and CANONICAL keypoint indices.
+ *   n_out            : host int32 [n_pairs]
+ *   stage_counts_out : NULL or host int32 [n_pairs][4]: after NN, after propagation, after RANSAC, final (a stage that did not run
+ *                      repeats the count before it).
+ * device_resident = 1: matches_out is a device pointer; 0: a host pointer. */
+typedef struct btba_mappoints btba_mappoints;
+typedef struct btba_corres_params {
+    int32_t n_trials;                       /* RANSAC trials (ransac.max_iter, 2000) */
+    float dist_thres;                       /* inlier distance (ransac.inlier_dist, 0.01 m) */
+    int32_t hypothesis;                     /* BTBA_RANSAC_REFERENCE_SVD or BTBA_RANSAC_HORN, optionally | BTBA_RANSAC_DRAW_HASH */
+    int32_t pad;
+    uint64_t seed;                          /* 0 */
+} btba_corres_params;
+BTBA_API int btba_mappoints_create(btba_workspace *ws, btba_mappoints **out);
+BTBA_API void btba_mappoints_destroy(btba_mappoints *mp);
+BTBA_API int btba_mappoints_register_frame(btba_mappoints *mp, int n_kpts, const float *kpts_dev, int32_t *slot_out);
+BTBA_API int btba_mappoints_forget_frame(btba_mappoints *mp, int32_t slot);
+BTBA_API int btba_mappoints_export(btba_mappoints *mp, int32_t *dims_out, int32_t *slot_n_out, int32_t *canon_out, int32_t *map_out, int32_t *img_out);
+BTBA_API void btba_corres_params_default(btba_corres_params *p);
+/* btba_match_capacity's validation plus: no frame pair twice.  Host-only: no GPU, no workspace, no map-point memory. */
+BTBA_API int btba_corres_chain_capacity(const btba_match_params *params, int n_frames, int H, int W, int D, const int32_t *n_kpts,
+                                        int n_pairs, const int32_t *pairs, int64_t *capacity_out);
+BTBA_API int btba_corres_chain(btba_workspace *ws, btba_mappoints *mp, const btba_match_params *params, const btba_corres_params *ransac,
+                               int device_resident, int n_frames, int H, int W, const float *K_rowmajor, const float *const *desc_dev, int D,
+                               const float *const *kpts_dev, const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev,
+                               const float *poses, const int32_t *frame_ids, const int32_t *slots, int32_t *status, int n_pairs,
+                               const int32_t *pairs, btba_match *matches_out, int32_t *n_out, int32_t *stage_counts_out);
+
 #ifdef __cplusplus
 }
 #endif

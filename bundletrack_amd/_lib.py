@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "btba_pose_errors",
     "btba_mappoints_create", "btba_mappoints_destroy", "btba_mappoints_register_frame", "btba_mappoints_forget_frame", "btba_mappoints_export",
     "btba_corres_params_default", "btba_corres_chain_capacity", "btba_corres_chain",
+    "btba_window_layout", "btba_marshal_windows", "btba_procrustes_pairs",
 ]
 
 # btba_match (include/btba.h): one descriptor match, 40 bytes
@@ -269,6 +270,12 @@ def lib() -> C.CDLL:
         L.btba_corres_chain.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MatchParams), C.POINTER(CorresParams), C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_window_layout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint32),
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_marshal_windows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_procrustes_pairs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

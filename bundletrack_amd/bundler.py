@@ -153,6 +153,24 @@ def marshal_window(local_frames, matches, newframe, min_fm_edges_newframe: int =
     return Window(frames=frames, corr=corr, n_match_per_pair=np.asarray(counts, np.int32), n_edges_newframe=n_edges, run_ba=run)
 
 
+class DeviceWindow:
+    """A Window assembled on the device (window.marshal_windows): the same fields, with `corr` downloaded on first use."""
+
+    def __init__(self, frames, n_match_per_pair, n_edges_newframe, run_ba, layout, corr_dev=None, pair_offsets_dev=None):
+        self.frames, self.n_match_per_pair = frames, n_match_per_pair
+        self.n_edges_newframe, self.run_ba, self.layout = n_edges_newframe, run_ba, layout
+        self.corr_dev, self.pair_offsets_dev = corr_dev, pair_offsets_dev          # uint8 [1, stride, 32], int32 [1, P + 1] CUDA
+        self._corr = None
+
+    @property
+    def corr(self) -> np.ndarray:
+        if self._corr is None:
+            n = int(self.n_match_per_pair.sum())
+            self._corr = (self.corr_dev[0, :n].cpu().numpy().view(ENTRYJ_DTYPE).reshape(-1).copy() if n and self.corr_dev is not None
+                          else np.zeros(0, ENTRYJ_DTYPE))
+        return self._corr
+
+
 # ---------------------------------------------------------------------------------------------------------
 # The rest of Bundler's BA-facing slice: Kabsch initialisation, the per-frame driver, the pose-file format.
 # Feature detection / matching / RANSAC (LF-Net, SiftGPU, cuda_ransac) stay behind `feature_manager`.
@@ -237,12 +255,23 @@ class Bundler:
         forget_frame(frame)                -> None
     and may offer find_corres_chain([(frameA, frameB), ...]) (correspondence.GpuFeatureManager): optimize_gpu then hands it the
     window's pairs in find_corres order in one call.
+
+    device_window (off by default): with a feature manager that keeps its records on the device (device_segments / device_records /
+    procrustes_by_correspondence_device, as GpuFeatureManager does) the initial pose comes from btba_procrustes_pairs and the window
+    is assembled by btba_marshal_windows and solved from device memory (BatchSolver.solve_zn on per-frame compact caches kept by
+    frame id); the gate, last_window, n_ba_calls and the status handling are the host path's.  A feature manager without device
+    records takes the host path silently.
     """
 
     def __init__(self, optimizer, feature_manager, K, H, W, *, window_size=2, max_BA_frames=15, min_rot_deg=10.0,
                  min_feat_num=0, min_fm_edges_newframe=5, pose_dir=None, persistent_frame_cache=False,
-                 mask_largest_component_hull=False, mask_dilate=5, mask_workspace=None, detector=None, detector_out_size=400):
+                 mask_largest_component_hull=False, mask_dilate=5, mask_workspace=None, detector=None, detector_out_size=400,
+                 device_window=False):
         self.opt, self.fm = optimizer, feature_manager
+        self.device_window = bool(device_window)
+        self.last_procrustes_err = None                                          # device_window: err of the last initial pose (FeatureManager.cpp:550)
+        self._zn_cache: dict = {}                                                # device_window: frame id -> (depth ptr, normal ptr, zn [Hd, Wd, 4])
+        self._batch_solver = None
         self.detector = detector                                                 # None: frames arrive with kpts_gpu / desc_gpu set
         self.detector_out_size = int(detector_out_size)                          # Lfnet::detectFeature's H_input = W_input = 400
         self.mask_largest_component_hull = bool(mask_largest_component_hull)     # the reference's `data_dir contains "NOCS"` (Frame.cpp:255,280)
@@ -297,7 +326,10 @@ class Bundler:
                 self.need_reinit = True
                 self.fm.forget_frame(frame)
                 return
-            offset = self.fm.procrustes_by_correspondence(frame, last)                 # :134-136
+            if self._device_records():
+                offset, self.last_procrustes_err = self.fm.procrustes_by_correspondence_device(frame, last)
+            else:
+                offset = self.fm.procrustes_by_correspondence(frame, last)             # :134-136
             frame.pose_in_model = (np.asarray(offset, np.float32) @ frame.pose_in_model).astype(np.float32)
         if len(self.frames) >= self.window_size + 3:                                   # :150-158
             if self.frames[0] not in self.keyframes:
@@ -363,6 +395,9 @@ class Bundler:
             for i in range(len(frames)):
                 for j in range(i + 1, len(frames)):
                     self.fm.find_corres(frames[j], frames[i])
+        if self._device_records():
+            self._optimize_from_device(frames)
+            return
         win = marshal_window(frames, self.fm.matches, self.newframe, self.min_fm_edges_newframe)
         self.last_window = win
         if not win.run_ba:
@@ -374,6 +409,67 @@ class Bundler:
                                 [f.normal_gpu for f in win.frames], poses, self.K, **extra)
         self.n_ba_calls += 1
         for f, T in zip(win.frames, poses):
+            f.pose_in_model = np.array(T, np.float32)
+
+    def _device_records(self) -> bool:
+        return (self.device_window and getattr(self.opt, "workspace", None) is not None and hasattr(self.fm, "device_segments")
+                and hasattr(self.fm, "procrustes_by_correspondence_device") and self.fm.device_records() is not None)
+
+    def assemble_window_on_device(self, frames) -> DeviceWindow:
+        """marshal_window's result from the feature manager's device records (window.window_layout + window.marshal_windows):
+        frames sorted by id.  Marks the new frame NO_BA when the gate fails, like marshal_window."""
+        from .window import marshal_windows, window_layout
+        n = len(frames)
+        segs = [self.fm.device_segments.get((frames[j].id, frames[i].id), (0, 0)) for i in range(n) for j in range(i + 1, n)]
+        counts = np.array([c for _, c in segs], np.int32)
+        new_index = next(k for k, f in enumerate(frames) if f.id == self.newframe.id)
+        lay = window_layout(counts[None], n, new_index, self.min_fm_edges_newframe)
+        run = bool(lay.run_ba[0])
+        win = DeviceWindow(frames, counts, int(lay.n_edges_newframe[0]), run, lay)
+        if not run:
+            self.newframe.status = "NO_BA"
+        if run or counts.sum():
+            win.corr_dev, win.pair_offsets_dev, _ = marshal_windows(self.opt.workspace, self.fm.device_records(), np.asarray(segs, np.int64)[None], n, lay)
+        return win
+
+    def _window_caches(self, frames):
+        """Compact (z, n) caches of the window's frames [1, N, Hd, Wd, 4], each built once per frame id and pair of maps."""
+        import torch
+        from .optimizer import build_cache_zn
+        ws = self.opt.workspace
+        keep = {f.id for f in frames} | {f.id for f in self.frames} | {f.id for f in self.keyframes}
+        for fid in [k for k in self._zn_cache if k not in keep]:
+            del self._zn_cache[fid]
+        for f in frames:
+            tag = (f.depth_gpu.data_ptr(), f.normal_gpu.data_ptr())
+            if f.id not in self._zn_cache or self._zn_cache[f.id][0] != tag:
+                zn, _, _ = build_cache_zn(ws, [f.depth_gpu], [f.normal_gpu], self.H, self.W, self.K, float(self.opt.params.image_downscale))
+                self._zn_cache[f.id] = (tag, zn[0])
+        return torch.stack([self._zn_cache[f.id][1] for f in frames])[None]
+
+    def _optimize_from_device(self, frames) -> None:
+        """optimize_gpu from the marshalling on, on device memory."""
+        import ctypes
+        import torch
+        from ._lib import BTBA_ENUMERIC, BtbaError, Params
+        from .optimizer import BatchSolver
+        win = self.assemble_window_on_device(frames)
+        self.last_window = win
+        if not win.run_ba:
+            return
+        if self._batch_solver is None:
+            self._batch_solver = BatchSolver(workspace=self.opt.workspace)
+        prm = Params()
+        ctypes.memmove(ctypes.byref(prm), ctypes.byref(self.opt.params), ctypes.sizeof(Params))
+        self._batch_solver.params = prm
+        zn = self._window_caches(frames)
+        poses_dev = torch.from_numpy(np.stack([np.asarray(f.pose_in_model, np.float32) for f in frames])[None].copy()).to(zn.device)
+        self._batch_solver.solve_zn(zn, self.H, self.W, self.K, win.corr_dev, win.pair_offsets_dev, win.layout.max_corr_per_pair, poses_dev)
+        poses = poses_dev[0].cpu().numpy()
+        if not np.isfinite(poses).all():
+            raise BtbaError(BTBA_ENUMERIC, "btba_solve_batch_zn")
+        self.n_ba_calls += 1
+        for f, T in zip(frames, poses):
             f.pose_in_model = np.array(T, np.float32)
 
     def save_newframe_result(self) -> None:

@@ -143,7 +143,9 @@ def find_corres_chain(ws, memory: MapPointMemory, frames, pairs, slots, status, 
 class GpuFeatureManager:
     """A concrete feature manager (the slice of SiftManager the Bundler uses) on btba_corres_chain: frames bring kpts_gpu / desc_gpu
     (float32 CUDA), depth_gpu and normal_gpu; matches[(A.id, B.id)] = (ptA_cam [n,3], ptB_cam [n,3]); records[...] keeps the
-    btba_match records.  cfg: config_ycbineoat.yml-shaped dict (feature_corres.*, ransac.max_iter / inlier_dist) or None."""
+    btba_match records.  cfg: config_ycbineoat.yml-shaped dict (feature_corres.*, ransac.max_iter / inlier_dist) or None.
+    Every processed pair's records also stay on the device: device_segments[(A.id, B.id)] = (first record, count) in
+    device_records(), one int32 CUDA tensor [n, 10] -- what window.marshal_windows and window.procrustes_pairs read."""
 
     def __init__(self, ws, K, H: int, W: int, cfg: dict | None = None, *, seed: int = 0, hypothesis: int = 0):
         self.ws, self.K, self.H, self.W = ws, np.asarray(K, np.float32), int(H), int(W)
@@ -156,6 +158,9 @@ class GpuFeatureManager:
         self.records: dict = {}
         self.stage_counts: dict = {}
         self._slots: dict = {}                 # frame id -> slot
+        self.device_segments: dict = {}        # (A.id, B.id) -> (first record, count) in the record pool
+        self._pool = None                      # int32 CUDA [capacity, 10]: the live pairs' btba_match records
+        self._pool_used = 0
 
     def _slot(self, frame) -> int:
         if frame.id not in self._slots:
@@ -193,6 +198,35 @@ class GpuFeatureManager:
             self.records[key] = m
             self.stage_counts[key] = sc.copy()
             self.matches[key] = (np.ascontiguousarray(m["ptA_cam"]), np.ascontiguousarray(m["ptB_cam"]))
+        self._keep_on_device(todo, res)
+
+    def _keep_on_device(self, todo, res) -> None:
+        """Append the chain's records (already pair after pair in res.matches_dev) to the pool; a full pool is rebuilt from its live
+        segments at twice the size it needs."""
+        import torch
+        total = int(res.n_out.sum())
+        if res.matches_dev is None:
+            return
+        if self._pool is None or self._pool_used + total > self._pool.shape[0]:
+            live = sorted(self.device_segments.items(), key=lambda kv: kv[1][0])
+            need = sum(c for _, (_, c) in live) + total
+            fresh = torch.zeros((max(2 * need, 4096), _MATCH_WORDS), dtype=torch.int32, device=res.matches_dev.device)
+            at = 0
+            for key, (first, count) in live:
+                fresh[at:at + count] = self._pool[first:first + count]
+                self.device_segments[key] = (at, count)
+                at += count
+            self._pool, self._pool_used = fresh, at
+        self._pool[self._pool_used:self._pool_used + total] = res.matches_dev[:total]
+        at = self._pool_used
+        for (fa, fb), n in zip(todo, res.n_out):
+            self.device_segments[(fa.id, fb.id)] = (at, int(n))
+            at += int(n)
+        self._pool_used = at
+
+    def device_records(self):
+        """The record pool (int32 CUDA [capacity, 10]) device_segments index, or None before the first chain."""
+        return self._pool
 
     def forget_frame(self, frame) -> None:
         """SiftManager::forgetFrame: the frame's pairs and its img entries go; its slot is free again."""
@@ -200,6 +234,7 @@ class GpuFeatureManager:
             del self.matches[key]
             self.records.pop(key, None)
             self.stage_counts.pop(key, None)
+            self.device_segments.pop(key, None)
         slot = self._slots.pop(frame.id, None)
         if slot is not None:
             self.memory.forget_frame(slot)
@@ -208,6 +243,17 @@ class GpuFeatureManager:
         """FeatureManager::procrustesByCorrespondence (:523-556), as the C++ host layer: bundler.procrustes_by_correspondence."""
         from .bundler import procrustes_by_correspondence
         return procrustes_by_correspondence(self.matches, frameA, frameB)
+
+    def procrustes_by_correspondence_device(self, frameA, frameB):
+        """The same from the pair's device records (window.procrustes_pairs: fp64 moments and rotation, rounded once): returns
+        (4x4 float32, err).  Identity for a pair without records, as on the host."""
+        from .window import procrustes_pairs
+        first, count = self.device_segments.get((frameA.id, frameB.id), (0, 0))
+        if self._pool is None or count == 0:
+            return np.eye(4, dtype=np.float32), 0.0
+        pose, err, _ = procrustes_pairs(self.ws, self._pool, [(first, count)], np.asarray(frameA.pose_in_model, np.float32)[None],
+                                        np.asarray(frameB.pose_in_model, np.float32)[None])
+        return pose[0].copy(), float(err[0])
 
     def close(self) -> None:
         self.memory.close()

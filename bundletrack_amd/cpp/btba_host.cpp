@@ -157,6 +157,55 @@ void poseErrors(btba_workspace *ws, const std::vector<const float *> &models_dev
     if (rc != BTBA_OK) throw Error(rc, "btba_pose_errors");
 }
 
+WindowLayout windowLayout(int n_frames, const std::vector<int32_t> &seg_counts, const std::vector<int32_t> &newframe_index, int min_fm_edges_newframe)
+{
+    const int P = n_frames >= 2 ? n_frames * (n_frames - 1) / 2 : 0;
+    const size_t nw = newframe_index.size();
+    if (nw == 0 || P == 0 || seg_counts.size() != nw * (size_t)P) throw Error(BTBA_EINVAL, "windowLayout: sizes differ");
+    WindowLayout L;
+    L.pair_offsets.assign(nw * (size_t)(P + 1), 0u);
+    L.n_edges_newframe.assign(nw, 0);
+    L.run_ba.assign(nw, 0);
+    const int rc = btba_window_layout((int)nw, n_frames, seg_counts.data(), newframe_index.data(), min_fm_edges_newframe, &L.corr_stride,
+                                      &L.max_corr_per_pair, L.pair_offsets.data(), L.n_edges_newframe.data(), L.run_ba.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_window_layout");
+    return L;
+}
+
+void marshalWindows(btba_workspace *ws, int n_windows, int n_frames, const btba_match *matches_dev, int64_t n_records, const uint32_t *segments_dev,
+                    const WindowLayout &layout, btba_entryj *corr_dev, uint32_t *pair_offsets_dev, float *corr24_dev)
+{
+    const int rc = btba_marshal_windows(ws, n_windows, n_frames, matches_dev, n_records, segments_dev, layout.max_corr_per_pair,
+                                        std::max<int64_t>(layout.corr_stride, 1), corr_dev, pair_offsets_dev, corr24_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_marshal_windows");
+}
+
+void procrustesPairs(btba_workspace *ws, const btba_match *matches_dev, int64_t n_records, const std::vector<std::pair<int32_t, int32_t>> &segments,
+                     const std::vector<Matrix4f> &posesA, const std::vector<Matrix4f> &posesB, std::vector<Matrix4f> &poses, std::vector<float> &err)
+{
+    const size_t n = segments.size();
+    if (posesA.size() != n || posesB.size() != n) throw Error(BTBA_EINVAL, "procrustesPairs: sizes differ");
+    std::vector<int32_t> seg(2 * n);
+    std::vector<float> pa(16 * n), pb(16 * n), out(16 * n);       // row-major, as the C ABI takes them
+    for (size_t e = 0; e < n; e++) {
+        seg[2 * e] = segments[e].first;
+        seg[2 * e + 1] = segments[e].second;
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) {
+                pa[16 * e + 4 * r + c] = posesA[e](r, c);
+                pb[16 * e + 4 * r + c] = posesB[e](r, c);
+            }
+    }
+    err.assign(n, 0.0f);
+    const int rc = btba_procrustes_pairs(ws, /*device_resident=*/0, (int)n, matches_dev, n_records, seg.data(), pa.data(), pb.data(), out.data(),
+                                         err.data(), nullptr);
+    if (rc != BTBA_OK) throw Error(rc, "btba_procrustes_pairs");
+    poses.resize(n);
+    for (size_t e = 0; e < n; e++)
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) poses[e](r, c) = out[16 * e + 4 * r + c];
+}
+
 double vocapAuc(const std::vector<double> &errors, double max_threshold)
 {
     const size_t n = errors.size();

@@ -140,6 +140,25 @@ void keypointsToImage(btba_workspace *ws, const std::shared_ptr<Frame> &frame, c
 void poseErrors(btba_workspace *ws, const std::vector<const float *> &models_dev, const std::vector<int32_t> &n_pts,
                 const std::vector<int32_t> &model_index, const std::vector<Matrix4f> &poses_pred, const std::vector<Matrix4f> &poses_gt,
                 std::vector<float> &add, std::vector<float> &adds);
+// Window assembly on the device (include/btba.h, "window assembly"): thin wrappers over the C ABI.
+// windowLayout (host-only): seg_counts[w * P + p] matches of canonical pair p of window w, newframe_index[w] -> the layout.
+// marshalWindows: the chain's device records + a device segment table uint32 [n_windows][P][2] = (first record, count) -> corr_dev,
+// pair_offsets_dev and (optional, may be null) corr24_dev, all caller-owned device buffers; asynchronous on the workspace stream.
+// procrustesPairs: the Kabsch fit of pair e = segments[e] = (first record, count) with the camera -> model poses of the newer (A) and
+// the older (B) frame; poses and err are resized to the number of pairs.  Needs the GPU; synchronous.
+struct WindowLayout {
+    int64_t corr_stride = 0;
+    uint32_t max_corr_per_pair = 0;
+    std::vector<uint32_t> pair_offsets;                                          // [n_windows][P + 1]
+    std::vector<int64_t> n_edges_newframe;                                       // [n_windows]
+    std::vector<int32_t> run_ba;                                                 // [n_windows]: 1 = n_edges_newframe > min_fm_edges_newframe
+};
+WindowLayout windowLayout(int n_frames, const std::vector<int32_t> &seg_counts, const std::vector<int32_t> &newframe_index, int min_fm_edges_newframe = 5);
+void marshalWindows(btba_workspace *ws, int n_windows, int n_frames, const btba_match *matches_dev, int64_t n_records, const uint32_t *segments_dev,
+                    const WindowLayout &layout, btba_entryj *corr_dev, uint32_t *pair_offsets_dev, float *corr24_dev = nullptr);
+void procrustesPairs(btba_workspace *ws, const btba_match *matches_dev, int64_t n_records, const std::vector<std::pair<int32_t, int32_t>> &segments,
+                     const std::vector<Matrix4f> &posesA, const std::vector<Matrix4f> &posesB, std::vector<Matrix4f> &poses, std::vector<float> &err);
+
 // VOCap (eval_ycbineoat.py:54-81) in closed form, the same arithmetic as bundletrack_amd/evaluation.py::vocap_auc: the area under
 // the accuracy-vs-threshold curve on [0, max_threshold] over max_threshold (0 without errors below the threshold).
 double vocapAuc(const std::vector<double> &errors, double max_threshold = 0.1);

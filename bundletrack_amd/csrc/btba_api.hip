@@ -29,6 +29,7 @@
 #include "btba_detect.hpp"
 #include "btba_eval.hpp"
 #include "btba_mappoints.hpp"
+#include "btba_window.hpp"
 
 using namespace btba;
 
@@ -173,6 +174,7 @@ struct btba_workspace {
     DevBuf mask;                                            // btba_apply_masks: labels, counts, argmax keys, row extents, spans, hull stacks, ROI slots
     DevBuf eval;                                            // btba_pose_errors: chunk tables, host-form poses and outputs, per-point minima
     DevBuf corres;                                          // btba_corres_chain: frame / pair tables, NN output, working lists, per-pair words
+    DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;
@@ -312,7 +314,7 @@ void btba_workspace_destroy(btba_workspace *ws)
     for (auto e : ws->event_pool) (void)hipEventDestroy(e);
     DevBuf *bufs[] = { &ws->x, &ws->T, &ws->Tinv, &ws->sparse_part, &ws->dense_part, &ws->pairsum, &ws->dense_pairs, &ws->ptrs, &ws->big_A, &ws->solve_tab,
                        &ws->corr, &ws->offsets, &ws->poses, &ws->campos, &ws->normals, &ws->nvalid, &ws->valid_lists, &ws->valid_counts, &ws->block_ranges,
-                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->mask, &ws->eval, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens };
+                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->mask, &ws->eval, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens, &ws->window };
     for (auto b : bufs) b->release();
     if (ws->corr_stage) (void)hipHostFree(ws->corr_stage);
     if (ws->chain_error) (void)hipHostFree(ws->chain_error);
@@ -2522,6 +2524,121 @@ int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, cons
         }
     }
     HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host tables above may go
+    return BTBA_OK;
+}
+
+int btba_window_layout(int n_windows, int n_frames, const int32_t *seg_counts, const int32_t *newframe_index, int32_t min_fm_edges_newframe,
+                       int64_t *corr_stride_out, uint32_t *max_corr_per_pair_out, uint32_t *pair_offsets_out,
+                       int64_t *n_edges_newframe_out, int32_t *run_ba_out)
+{
+    if (n_windows < 1 || n_frames < 2 || n_frames > BTBA_MAX_FRAMES || !seg_counts || !newframe_index) return BTBA_EINVAL;
+    const int P = n_frames * (n_frames - 1) / 2;
+    int64_t stride = 0;
+    int32_t longest = 0;
+    for (int w = 0; w < n_windows; w++) {                             // validate everything before the first output is written
+        if (newframe_index[w] < 0 || newframe_index[w] >= n_frames) return BTBA_EINVAL;
+        int64_t total = 0;
+        for (int p = 0; p < P; p++) {
+            const int32_t c = seg_counts[(size_t)w * P + p];
+            if (c < 0) return BTBA_EINVAL;
+            total += c;
+            longest = std::max(longest, c);
+        }
+        if (total > (int64_t)UINT32_MAX) return BTBA_EINVAL;
+        stride = std::max(stride, total);
+    }
+    for (int w = 0; w < n_windows; w++) {
+        const int32_t *cnt = seg_counts + (size_t)w * P;
+        const int nf = newframe_index[w];
+        int64_t edges = 0;
+        uint32_t at = 0;
+        int p = 0;
+        for (int i = 0; i < n_frames; i++)
+            for (int j = i + 1; j < n_frames; j++, p++) {
+                if (pair_offsets_out) pair_offsets_out[(size_t)w * (P + 1) + p] = at;
+                at += (uint32_t)cnt[p];
+                if (i == nf || j == nf) edges += cnt[p];
+            }
+        if (pair_offsets_out) pair_offsets_out[(size_t)w * (P + 1) + P] = at;
+        if (n_edges_newframe_out) n_edges_newframe_out[w] = edges;
+        if (run_ba_out) run_ba_out[w] = edges > (int64_t)min_fm_edges_newframe ? 1 : 0;
+    }
+    if (corr_stride_out) *corr_stride_out = stride;
+    if (max_corr_per_pair_out) *max_corr_per_pair_out = (uint32_t)longest;
+    return BTBA_OK;
+}
+
+int btba_marshal_windows(btba_workspace *ws, int n_windows, int n_frames, const btba_match *matches_dev, int64_t n_records,
+                         const uint32_t *segments_dev, uint32_t max_corr_per_pair, int64_t corr_stride,
+                         btba_entryj *corr_dev, uint32_t *pair_offsets_dev, float *corr24_dev)
+{
+    if (!ws || n_windows < 1 || n_windows > 65535 || n_frames < 2 || n_frames > BTBA_MAX_FRAMES || n_records < 0 || n_records > (int64_t)UINT32_MAX ||
+        (!matches_dev && n_records) || !segments_dev || !corr_dev || !pair_offsets_dev || corr_stride < 1)
+        return BTBA_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(matches_dev) & 15) || (reinterpret_cast<uintptr_t>(segments_dev) & 7) || (reinterpret_cast<uintptr_t>(corr_dev) & 15) ||
+        (reinterpret_cast<uintptr_t>(pair_offsets_dev) & 3) || (reinterpret_cast<uintptr_t>(corr24_dev) & 7))
+        return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+    const int P = n_frames * (n_frames - 1) / 2;
+    const unsigned tiles = std::max(1u, (max_corr_per_pair + (unsigned)kWinThreads - 1u) / (unsigned)kWinThreads);      // tile 0 also writes the offsets
+    k_window_marshal<<<dim3(tiles, (unsigned)P, (unsigned)n_windows), kWinThreads, 0, ws->stream>>>(
+        n_frames, P, segments_dev, reinterpret_cast<const unsigned char *>(matches_dev), (unsigned long long)n_records, (unsigned long long)corr_stride,
+        reinterpret_cast<uint4 *>(corr_dev), pair_offsets_dev, reinterpret_cast<float2 *>(corr24_dev));
+    HIP_TRY(hipGetLastError());
+    return BTBA_OK;
+}
+
+int btba_procrustes_pairs(btba_workspace *ws, int device_resident, int n_pairs, const btba_match *matches_dev, int64_t n_records,
+                          const int32_t *segments, const float *posesA, const float *posesB, float *pose_out, float *err_out, double *moments_out)
+{
+    // every argument is checked before the first HIP call
+    if (!ws || n_pairs < 0 || n_records < 0 || n_records > (int64_t)UINT32_MAX) return BTBA_EINVAL;
+    if (n_pairs == 0) return BTBA_OK;
+    if (!segments || !posesA || !posesB || !pose_out || !err_out || (!matches_dev && n_records) || (reinterpret_cast<uintptr_t>(matches_dev) & 7))
+        return BTBA_EINVAL;
+    std::vector<KabschRec> rec(n_pairs);
+    for (int e = 0; e < n_pairs; e++) {
+        const int64_t off = segments[2 * e], n = segments[2 * e + 1];
+        if (off < 0 || n < 0 || off + n > n_records) return BTBA_EINVAL;
+        rec[e] = KabschRec{ (uint32_t)off, (int32_t)n };
+    }
+    DeviceGuard device_guard(ws);
+    const bool dev = device_resident != 0;
+    const size_t np = (size_t)n_pairs;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t o = 0;
+    const size_t o_rec = o; o += al(sizeof(KabschRec) * np);
+    const size_t o_mom = o; o += moments_out && dev ? 0 : al(sizeof(double) * 16 * np);
+    const size_t o_pa = o; o += dev ? 0 : al(sizeof(float) * 16 * np);
+    const size_t o_pb = o; o += dev ? 0 : al(sizeof(float) * 16 * np);
+    const size_t o_out = o; o += dev ? 0 : al(sizeof(float) * 16 * np);
+    const size_t o_err = o; o += dev ? 0 : al(sizeof(float) * np);
+    int rc = ws->window.ensure(o);
+    if (rc) return rc;
+    unsigned char *base = ws->window.as<unsigned char>();
+    KabschRec *d_rec = reinterpret_cast<KabschRec *>(base + o_rec);
+    double *d_mom = moments_out && dev ? moments_out : reinterpret_cast<double *>(base + o_mom);
+    const float *pa = posesA, *pb = posesB;
+    float *po = pose_out, *pe = err_out;
+    HIP_TRY(hipMemcpyAsync(d_rec, rec.data(), sizeof(KabschRec) * np, hipMemcpyHostToDevice, ws->stream));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(base + o_pa, posesA, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
+        HIP_TRY(hipMemcpyAsync(base + o_pb, posesB, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
+        pa = reinterpret_cast<const float *>(base + o_pa);
+        pb = reinterpret_cast<const float *>(base + o_pb);
+        po = reinterpret_cast<float *>(base + o_out);
+        pe = reinterpret_cast<float *>(base + o_err);
+    }
+    const unsigned char *recs = reinterpret_cast<const unsigned char *>(matches_dev);
+    k_kabsch_moments<<<n_pairs, kKabschThreads, 0, ws->stream>>>(d_rec, recs, pa, pb, d_mom);
+    k_kabsch_solve<<<n_pairs, kKabschThreads, 0, ws->stream>>>(d_rec, recs, pa, pb, d_mom, po, pe);
+    HIP_TRY(hipGetLastError());
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(pose_out, po, sizeof(float) * 16 * np, hipMemcpyDeviceToHost, ws->stream));
+        HIP_TRY(hipMemcpyAsync(err_out, pe, sizeof(float) * np, hipMemcpyDeviceToHost, ws->stream));
+        if (moments_out) HIP_TRY(hipMemcpyAsync(moments_out, d_mom, sizeof(double) * 16 * np, hipMemcpyDeviceToHost, ws->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host table above may go
     return BTBA_OK;
 }
 

@@ -755,6 +755,85 @@ BTBA_API int btba_corres_chain(btba_workspace *ws, btba_mappoints *mp, const btb
                                const float *poses, const int32_t *frame_ids, const int32_t *slots, int32_t *status, int n_pairs,
                                const int32_t *pairs, btba_match *matches_out, int32_t *n_out, int32_t *stage_counts_out);
 
+/* ---- window assembly (the step between findCorres and the solver) ------------------------------------------------------
+ * The two host steps between btba_corres_chain and btba_solve_batch_zn(_aux), on the chain's device-resident btba_match records:
+ * Bundler::optimizeGPU's marshalling (src/Bundler.cpp:286-347) and SiftManager::procrustesByCorrespondence
+ * (src/FeatureManager.cpp:523-557 with Utils::solveRigidTransformBetweenPoints, src/Utils.cpp:180-214).
+ *
+ * Marshalling.  A window is n_frames frames sorted by id (index 0 the oldest); its P = n_frames (n_frames - 1) / 2 canonical pairs
+ * (i, j), i < j, come in the order (0,1) (0,2) .. (N-2,N-1).  Pair (i, j) owns a SEGMENT (first record, count) of one btba_match
+ * array: the records of findCorres(A = frame j, B = frame i), count 0 for a pair without matches.  Record k of the segment becomes
+ *   EntryJ{imgIdx_i = i, imgIdx_j = j, pos_i = ptB_cam, pos_j = ptA_cam}                                (Bundler.cpp:311-316)
+ * at entry pair_offsets[p] + k of the window: pair-major, records in their order.  pair_offsets[0] = 0, pair_offsets[p + 1] =
+ * pair_offsets[p] + count[p].  n_edges_newframe = the sum of the counts of the pairs that contain the new frame's index; BA runs
+ * iff n_edges_newframe > min_fm_edges_newframe (Bundler.cpp:343-347; otherwise the caller marks the frame NO_BA).  Windows of one
+ * call share n_frames and corr_stride = the largest window total, as in btba_solve_batch.
+ *
+ * btba_window_layout: host-only (no GPU, no workspace).
+ *   seg_counts      : host int32 [n_windows][P]
+ *   newframe_index  : host int32 [n_windows], each in 0 .. n_frames - 1
+ *   corr_stride_out : the largest window total (0 when no window has a match: allocate at least one entry, btba_solve_batch_zn
+ *                     wants corr_stride >= 1);  max_corr_per_pair_out : the largest count
+ *   pair_offsets_out: host uint32 [n_windows][P + 1];  n_edges_newframe_out : host int64 [n_windows];  run_ba_out : host int32
+ *                     [n_windows], 1 = the gate passed.  Any output may be NULL.
+ *   BTBA_EINVAL: n_windows < 1, n_frames outside 2 .. BTBA_MAX_FRAMES, a NULL table, a negative count, a new-frame index out of
+ *   range, a window total beyond uint32.  Nothing is written then.
+ *
+ * btba_marshal_windows: one launch for all windows, asynchronous on the workspace stream, no atomics, no host synchronisation.
+ * Every data pointer is a DEVICE pointer.
+ *   matches_dev      : btba_match [n_records] (16-byte aligned; the chain's matches_out with device_resident = 1)
+ *   segments_dev     : uint32 [n_windows][P][2] = (first record, count) -- the table btba_window_layout was given, with the records'
+ *                      places.  A segment that leaves [0, n_records) is not read and its entries are not written (its count still
+ *                      enters the offsets).
+ *   max_corr_per_pair, corr_stride : as btba_window_layout returns them (corr_stride may be larger, >= 1)
+ *   corr_dev         : btba_entryj [n_windows][corr_stride] (16-byte aligned).  Entries at or beyond pair_offsets[P] of a window
+ *                      are NOT written (as are entries at or beyond corr_stride, should the table not match the layout).
+ *   pair_offsets_dev : uint32 [n_windows][P + 1]
+ *   corr24_dev       : NULL, or the array of btba_pack_correspondences24 for this corr_dev / corr_stride, written in the same pass:
+ *                      bit for bit what that call makes of corr_dev.
+ *   BTBA_EINVAL: NULL ws / matches_dev (with n_records > 0) / segments_dev / corr_dev / pair_offsets_dev, n_windows < 1, n_frames
+ *   outside 2 .. BTBA_MAX_FRAMES, n_records < 0 or beyond uint32, corr_stride < 1, a misaligned array.
+ *
+ * btba_procrustes_pairs: the Kabsch fit of many pairs in two launches.  Pair e is a segment (first record, count n) of
+ * matches_dev and two row-major camera -> model poses TA, TB (frame A = the newer one, as in the records).
+ * ARITHMETIC CONTRACT:
+ *   a_k = TA ptA_cam, b_k = TB ptB_cam in the matcher's uncontracted fp32: P_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3.
+ *   n < 5 (countInlierCorres < 5, FeatureManager.cpp:527): pose = identity, err = 0, moments = (n, 0, .., 0).
+ *   All sums are fp64 in the fixed order of btba_pose_errors: slot l of 256 sums the terms of k = l (mod 256) in ascending k from
+ *   +0; then s = 128, 64, .., 1: acc[l] += acc[l + s] for l < s.  Products are plain fp64 multiplies, nothing is contracted.
+ *   m1 = (sum (double) a_k) / n, m2 = (sum (double) b_k) / n;  S_rc = sum ((double) a_k,r - m1_r) * ((double) b_k,c - m2_c): the
+ *   reference's P^T Q.  This part is reproducible bit for bit on a CPU (tests/window_ref.py); moments_out = n, m1, m2, S row-major.
+ *   R = the proper rotation that maximises tr(R S) -- the reference's V U^T with V's last column flipped when det < 0 -- by Horn's
+ *   quaternion method: the eigenvector of the largest eigenvalue of the symmetric 4 x 4 N(S), by cyclic Jacobi in fp64
+ *   (bundletrack_amd/csrc/btba_window.hpp writes the algorithm out).  No reflection case exists.  A rank-deficient S gives a finite
+ *   proper rotation: one of the maximisers when they are not unique (collinear points), the identity for S = 0.
+ *   t_r = m2_r - ((R_r0 m1_0 + R_r1 m1_1) + R_r2 m1_2) in fp64.  R and t are rounded ONCE to fp32 into a row-major 4 x 4 (last row
+ *   0 0 0 1).
+ *   err = (float) (sqrt(sum_k |d_k|^2) / n), d_k,r = (((R_r0 a_0 + R_r1 a_1) + R_r2 a_2) + t_r) - b_r with the fp64 R, t and the
+ *   points converted to fp64, |d|^2 = (d_0^2 + d_1^2) + d_2^2, summed over k in the fixed order: ||R a + t - b||_F / n, the quantity
+ *   of FeatureManager.cpp:550.  The library never aborts on it; a caller applies the reference's err > 1e-3 gate if it wants to.
+ *   A non-finite moment or a non-finite rounded result gives identity and err = 0 (the reference's isMatrixFinite / isApprox
+ *   fallbacks).  A pair never affects another pair.
+ *
+ *   matches_dev      : device btba_match [n_records] (8-byte aligned)
+ *   segments         : HOST int32 [n_pairs][2] = (first record, count)
+ *   posesA, posesB   : float [n_pairs][16];  pose_out : float [n_pairs][16];  err_out : float [n_pairs]
+ *   moments_out      : NULL, or double [n_pairs][16]
+ * device_resident = 1: poses and the three outputs are device pointers; 0: host pointers.  n_pairs == 0 is a no-op.  Synchronous
+ * on the workspace stream; scratch (the table, the moments, host-form staging) is grow-only in the workspace.
+ * BTBA_EINVAL before any GPU work: NULL ws, n_pairs < 0, n_records < 0 or beyond uint32; with n_pairs > 0 a NULL table, pose array,
+ * pose_out or err_out, matches_dev NULL with n_records > 0, a misaligned matches_dev, a negative first record or count, a segment
+ * that leaves [0, n_records). */
+BTBA_API int btba_window_layout(int n_windows, int n_frames, const int32_t *seg_counts, const int32_t *newframe_index,
+                                int32_t min_fm_edges_newframe, int64_t *corr_stride_out, uint32_t *max_corr_per_pair_out,
+                                uint32_t *pair_offsets_out, int64_t *n_edges_newframe_out, int32_t *run_ba_out);
+BTBA_API int btba_marshal_windows(btba_workspace *ws, int n_windows, int n_frames, const btba_match *matches_dev, int64_t n_records,
+                                  const uint32_t *segments_dev, uint32_t max_corr_per_pair, int64_t corr_stride,
+                                  btba_entryj *corr_dev, uint32_t *pair_offsets_dev, float *corr24_dev);
+BTBA_API int btba_procrustes_pairs(btba_workspace *ws, int device_resident, int n_pairs, const btba_match *matches_dev, int64_t n_records,
+                                   const int32_t *segments, const float *posesA, const float *posesB,
+                                   float *pose_out, float *err_out, double *moments_out);
+
 #ifdef __cplusplus
 }
 #endif

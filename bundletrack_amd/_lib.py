@@ -285,58 +285,39 @@ def check(status: int, where: str) -> None:
         raise BtbaError(status, where)
 
 
-def default_params(**kw) -> Params:
-    p = Params()
-    lib().btba_params_default(C.byref(p))
+def _params(cls, default_fn: str, kw: dict):
+    """A `cls` filled by the library's `default_fn`, then fields overridden from kw (AttributeError on an unknown field)."""
+    p = cls()
+    getattr(lib(), default_fn)(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_params(**kw) -> Params:
+    return _params(Params, "btba_params_default", kw)
 
 
 def match_params(**kw) -> MatchParams:
     """btba_match_params_default with fields overridden by keyword."""
-    p = MatchParams()
-    lib().btba_match_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(MatchParams, "btba_match_params_default", kw)
 
 
 def corres_params(**kw) -> CorresParams:
     """btba_corres_params_default with fields overridden by keyword."""
-    p = CorresParams()
-    lib().btba_corres_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(CorresParams, "btba_corres_params_default", kw)
 
 
 def mask_params(**kw) -> MaskParams:
     """btba_mask_params_default with fields overridden by keyword."""
-    p = MaskParams()
-    lib().btba_mask_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(MaskParams, "btba_mask_params_default", kw)
 
 
 def detector_params(**kw) -> DetectorParams:
     """btba_detector_params_default with fields overridden by keyword."""
-    p = DetectorParams()
-    lib().btba_detector_params_default(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(DetectorParams, "btba_detector_params_default", kw)
 
 
 def declared_symbols() -> list[str]:

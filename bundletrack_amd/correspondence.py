@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import MATCH_DTYPE, CorresParams, check, corres_params, lib, match_params
-from .matching import _MATCH_WORDS, _dims, params_from_config
+from .matching import _MATCH_WORDS, _dims, _frame_tables, params_from_config
 
 
 class MapPointMemory:
@@ -94,28 +94,14 @@ def find_corres_chain(ws, memory: MapPointMemory, frames, pairs, slots, status, 
     """btba_corres_chain.  frames: FrameRef-like objects as matching.match_pairs takes them; pairs: [(ia, ib)] indices into frames,
     A newer, in processing order; slots: each frame's MapPointMemory slot; status: int32 [n_frames] (nonzero = FAIL) going in."""
     import torch
-    from .optimizer import _dev_ptr
     prm = params if params is not None else match_params()
     rp = ransac if ransac is not None else corres_params()
     n = len(frames)
     D = _dims(frames)
     cap = chain_capacity(frames, pairs, prm, H=H, W=W)
-    n_kpts = np.array([0 if f.kpts_gpu is None else int(f.kpts_gpu.shape[0]) for f in frames], np.int32)
-    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
-
-    def ptrs(attr):
-        arr = (C.c_void_p * max(n, 1))()
-        for k, f in enumerate(frames):
-            t = getattr(f, attr)
-            arr[k] = _dev_ptr(t, f"frame {k} {attr}") if (t is not None and t.numel() > 0) else None
-        return arr
-
-    desc, kpts, depth, normal = ptrs("desc_gpu"), ptrs("kpts_gpu"), ptrs("depth_gpu"), ptrs("normal_gpu")
-    poses = np.ascontiguousarray(np.stack([np.asarray(f.pose_in_model, np.float32).reshape(16) for f in frames]), np.float32)
-    ids = np.array([int(f.id) for f in frames], np.int32)
+    n_kpts, pr, (desc, kpts, depth, normal), poses, ids, Kf = _frame_tables(frames, pairs, K)
     sl = np.ascontiguousarray(np.asarray(slots, np.int32).reshape(n))
     st = np.ascontiguousarray(np.asarray(status, np.int32).reshape(n)).copy()
-    Kf = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
     P = pr.shape[0]
     n_out = np.zeros(max(P, 1), np.int32)
     stages = np.zeros((max(P, 1), 4), np.int32)

@@ -15,6 +15,7 @@
 #include <string>
 #include <map>
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "../../include/btba.h"
@@ -46,9 +47,20 @@ static thread_local int g_last_hip_error = 0;
 
 namespace {
 
+// Growable device memory that frees itself.  Move-only: a copy would be a second owner of p.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int ensure(size_t bytes)
     {
         if (bytes <= cap) return BTBA_OK;
@@ -62,6 +74,46 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+
+// Growable pinned host memory that frees itself.  `want` is the capacity allocated when the block has to grow.
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int ensure(size_t bytes, size_t want = 0)
+    {
+        if (bytes <= cap) return BTBA_OK;
+        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+        if (!want) want = bytes + bytes / 2 + 4096;
+        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e != hipSuccess) { g_last_hip_error = (int)e; p = nullptr; return e == hipErrorOutOfMemory ? BTBA_ENOMEM : BTBA_EHIP; }
+        cap = want;
+        return BTBA_OK;
+    }
+};
+
+// The layout of one call's scratch in a DevBuf.  Regions are added in order; a present region takes its bytes rounded up to
+// 256, an absent one takes none and reads as nullptr.  After bind() a region converts to its typed device pointer.
+struct Scratch {
+    size_t bytes = 0;
+    unsigned char *base = nullptr;
+    template <class T> struct Region {
+        const Scratch *s; size_t off; bool present;
+        operator T *() const { return present ? reinterpret_cast<T *>(s->base + off) : nullptr; }
+    };
+    template <class T> Region<T> add(size_t count, bool present = true)
+    {
+        Region<T> r{ this, bytes, present };
+        if (present) bytes += (sizeof(T) * count + 255) & ~(size_t)255;
+        return r;
+    }
+    int bind(DevBuf &buf, size_t floor = 0) { int rc = buf.ensure(bytes > floor ? bytes : floor); base = buf.as<unsigned char>(); return rc; }
+};
+
+inline bool misaligned(const void *q, size_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
 
 struct EventPair { hipEvent_t a, b; int kind; };   // kind 0 dense, 1 sparse, 2 system, 3 solve region, 4 cache
 
@@ -130,28 +182,8 @@ struct btba_workspace {
     // the solve need (pointer tables, slot maps, valid counts) go through ONE pinned staging block, so that no call has to synchronise just to keep a local alive
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_copy = nullptr, ev_cache = nullptr;
-    void *pin = nullptr; size_t pin_cap = 0;
-    void *pin_io = nullptr; size_t pin_io_cap = 0;          // pinned: [poses out | poses in | pair offsets] of one optimize_frames call (small pageable copies cost ~10 us of host time each)
-    int pin_io_ensure(size_t bytes)
-    {
-        if (bytes <= pin_io_cap) return BTBA_OK;
-        if (pin_io) { (void)hipHostFree(pin_io); pin_io = nullptr; pin_io_cap = 0; }
-        const size_t want = bytes + bytes / 2 + 4096;
-        hipError_t e = hipHostMalloc(&pin_io, want, hipHostMallocDefault);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; pin_io = nullptr; return e == hipErrorOutOfMemory ? BTBA_ENOMEM : BTBA_EHIP; }
-        pin_io_cap = want;
-        return BTBA_OK;
-    }
-    int pin_ensure(size_t bytes)
-    {
-        if (bytes <= pin_cap) return BTBA_OK;
-        if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_cap = 0; }
-        const size_t want = bytes + bytes / 2 + 4096;
-        hipError_t e = hipHostMalloc(&pin, want, hipHostMallocDefault);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; pin = nullptr; return e == hipErrorOutOfMemory ? BTBA_ENOMEM : BTBA_EHIP; }
-        pin_cap = want;
-        return BTBA_OK;
-    }
+    PinBuf pin;
+    PinBuf pin_io;                                          // pinned: [poses out | poses in | pair offsets] of one optimize_frames call (small pageable copies cost ~10 us of host time each)
     struct PendingSlot { int slot; uint64_t key; const float *depth, *normal; };
     std::vector<PendingSlot> pool_pending;                  // frames cached by the call in flight: committed (live, n_valid) once their counts have come back
 
@@ -166,7 +198,7 @@ struct btba_workspace {
     DevBuf corr_pool, corr_desc, corr_stage_dev, corr_lens;   // pool of 24-byte correspondences; staging of a call's fresh EntryJ segments; the window's segment lengths
     std::map<std::pair<uint64_t, uint64_t>, CorrSeg> corr_index;
     size_t corr_pool_used = 0;                              // in entries
-    void *corr_stage = nullptr; size_t corr_stage_cap = 0;  // pinned host staging of the segments uploaded by one call
+    PinBuf corr_stage;                                      // pinned host staging of the segments uploaded by one call
     DevBuf ransac;                                          // btba_ransac_pairs staging (points, samples, per-trial poses and counts, results)
     DevBuf ransac_u;                                        // the reference's sample stream: n_trials x 3 uniforms (btba_xorwow.hpp), kept per (seed, n_trials)
     std::vector<float> ransac_u_host;
@@ -312,23 +344,16 @@ void btba_workspace_destroy(btba_workspace *ws)
     (void)hipStreamSynchronize(ws->stream);
     for (auto &ep : ws->events) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (auto e : ws->event_pool) (void)hipEventDestroy(e);
-    DevBuf *bufs[] = { &ws->x, &ws->T, &ws->Tinv, &ws->sparse_part, &ws->dense_part, &ws->pairsum, &ws->dense_pairs, &ws->ptrs, &ws->big_A, &ws->solve_tab,
-                       &ws->corr, &ws->offsets, &ws->poses, &ws->campos, &ws->normals, &ws->nvalid, &ws->valid_lists, &ws->valid_counts, &ws->block_ranges,
-                       &ws->chain_sync, &ws->chain_trace, &ws->live_blocks, &ws->corr24_tmp, &ws->pool_zn, &ws->pool_lists, &ws->pool_counts, &ws->pool_nvalid, &ws->pool_map, &ws->pool_ranges, &ws->ransac, &ws->ransac_u, &ws->match, &ws->mask, &ws->eval, &ws->corr_pool, &ws->corr_desc, &ws->corr_stage_dev, &ws->corr_lens, &ws->window };
-    for (auto b : bufs) b->release();
-    if (ws->corr_stage) (void)hipHostFree(ws->corr_stage);
     if (ws->chain_error) (void)hipHostFree(ws->chain_error);
     for (auto st : ws->aux_streams) if (st) (void)hipStreamDestroy(st);
     if (ws->copy_stream) (void)hipStreamDestroy(ws->copy_stream);
     if (ws->ev_copy) (void)hipEventDestroy(ws->ev_copy);
     if (ws->ev_cache) (void)hipEventDestroy(ws->ev_cache);
-    if (ws->pin) (void)hipHostFree(ws->pin);
-    if (ws->pin_io) (void)hipHostFree(ws->pin_io);
     if (ws->ev_fork) (void)hipEventDestroy(ws->ev_fork);
     for (auto e : ws->ev_join) if (e) (void)hipEventDestroy(e);
     if (ws->ev_order) (void)hipEventDestroy(ws->ev_order);
     if (ws->owns_stream) (void)hipStreamDestroy(ws->stream);
-    delete ws;
+    delete ws;                                              // its DevBuf / PinBuf members free themselves, on the workspace's device
 }
 
 int btba_workspace_set_option(btba_workspace *ws, int option, int64_t value)
@@ -1377,8 +1402,8 @@ static int optimize_frames_impl(btba_workspace *ws_in, const btba_params *params
     hipError_t e;
     // poses in (+ one word for the device's "not pair-major" flag, 0), poses out and the pair offsets go through a pinned block of the workspace (round 6)
     const size_t io_floats = 16 * (size_t)N + 1;
-    if ((rc = ws->pin_io_ensure(sizeof(float) * 2 * io_floats + sizeof(uint32_t) * (size_t)(P + 1) + sizeof(uint32_t) * 5 * (size_t)P + 64))) return finish(rc);
-    float *out = static_cast<float *>(ws->pin_io), *stage = out + io_floats;
+    if ((rc = ws->pin_io.ensure(sizeof(float) * 2 * io_floats + sizeof(uint32_t) * (size_t)(P + 1) + sizeof(uint32_t) * 5 * (size_t)P + 64))) return finish(rc);
+    float *out = static_cast<float *>(ws->pin_io.p), *stage = out + io_floats;
     uint32_t *offsets_pin = reinterpret_cast<uint32_t *>(stage + io_floats), *lens_pin = offsets_pin + (P + 1), *desc_pin = lens_pin + P;      // (keyed correspondences: segment lengths [P], descriptors [<= 4 P])
     // Keyed correspondence cache: with frame keys, the trusted pair-major layout and BTBA_FLAG_KEYED_CORR, a pair's segment is looked
     // up under (key_i, key_j, count); only the segments not seen before cross PCIe (into the pool), then one small kernel gathers
@@ -1426,13 +1451,7 @@ static int optimize_frames_impl(btba_workspace *ws_in, const btba_params *params
             corr_pairs_uploaded = 0;
             // the new segments are packed into ONE pinned staging buffer and cross PCIe in one copy (a pageable hipMemcpyAsync per
             // segment costs ~10 us each: 14 of them were as slow as uploading everything)
-            if (need * sizeof(btba_entryj) > ws->corr_stage_cap) {
-                if (ws->corr_stage) (void)hipHostFree(ws->corr_stage);
-                ws->corr_stage = nullptr; ws->corr_stage_cap = 0;
-                const size_t want = std::max<size_t>(2 * need * sizeof(btba_entryj), 1u << 20);
-                if ((r = hipHostMalloc(&ws->corr_stage, want, hipHostMallocDefault)) != hipSuccess) return r;
-                ws->corr_stage_cap = want;
-            }
+            if (ws->corr_stage.ensure(need * sizeof(btba_entryj), std::max<size_t>(2 * need * sizeof(btba_entryj), 1u << 20)) != BTBA_OK) return (hipError_t)g_last_hip_error;
             if (ws->corr_stage_dev.ensure(sizeof(btba_entryj) * (need ? need : 1)) != BTBA_OK) return hipErrorOutOfMemory;
             const size_t pool_base = ws->corr_pool_used;
             size_t staged = 0;
@@ -1449,7 +1468,7 @@ static int optimize_frames_impl(btba_workspace *ws_in, const btba_params *params
                         auto it = ws->corr_index.find(key);
                         if (it == ws->corr_index.end() || it->second.count != cnt) {
                             at = (uint32_t)(pool_base + staged);
-                            std::memcpy(static_cast<btba_entryj *>(ws->corr_stage) + staged, corres_host + offsets[q], sizeof(btba_entryj) * cnt);
+                            std::memcpy(static_cast<btba_entryj *>(ws->corr_stage.p) + staged, corres_host + offsets[q], sizeof(btba_entryj) * cnt);
                             desc.insert(desc.end(), { (uint32_t)staged, at, cnt, ((uint32_t)i << 16) | (uint32_t)j });      // staging offset -> pool offset
                             staged += cnt;
                             fresh_index.push_back({ key, btba_workspace::CorrSeg{ at, cnt } });
@@ -1463,7 +1482,7 @@ static int optimize_frames_impl(btba_workspace *ws_in, const btba_params *params
             offs_up[P] = 0;
             fresh_entries = staged;
             if (staged) {
-                if ((r = hipMemcpyAsync(ws->corr_stage_dev.p, ws->corr_stage, sizeof(btba_entryj) * staged, hipMemcpyHostToDevice, up_st)) != hipSuccess) return r;
+                if ((r = hipMemcpyAsync(ws->corr_stage_dev.p, ws->corr_stage.p, sizeof(btba_entryj) * staged, hipMemcpyHostToDevice, up_st)) != hipSuccess) return r;
                 if (ws->corr_desc.ensure(sizeof(uint32_t) * desc.size()) != BTBA_OK) return hipErrorOutOfMemory;
                 std::memcpy(desc_pin, desc.data(), sizeof(uint32_t) * desc.size());
                 if ((r = hipMemcpyAsync(ws->corr_desc.p, desc_pin, sizeof(uint32_t) * desc.size(), hipMemcpyHostToDevice, up_st)) != hipSuccess) return r;
@@ -1505,22 +1524,22 @@ static int optimize_frames_impl(btba_workspace *ws_in, const btba_params *params
         Mat4 Kinv_unused;
         scaled_intrinsics(H, W, Hd, Wd, K, intr, &Kinv_unused);
         const size_t off_nv = (sizeof(void *) * 2 * (size_t)N + 15) & ~(size_t)15;
-        if ((rc = ws->pin_ensure(off_nv + sizeof(int32_t) * (size_t)N))) return finish(rc);
+        if ((rc = ws->pin.ensure(off_nv + sizeof(int32_t) * (size_t)N))) return finish(rc);
         if ((rc = ws->ptrs.ensure(off_nv))) return finish(rc);
         if ((rc = ws->valid_lists.ensure(sizeof(uint32_t) * (size_t)N * npix))) return finish(rc);
         if ((rc = ws->valid_counts.ensure(sizeof(int) * (size_t)N))) return finish(rc);
         if ((rc = ws->block_ranges.ensure(sizeof(float2) * (size_t)N * ((Wd / 8) * (Hd / 8) + 1)))) return finish(rc);
-        auto **pp = reinterpret_cast<const float **>(ws->pin);
+        auto **pp = reinterpret_cast<const float **>(ws->pin.p);
         for (int k = 0; k < N; k++) {
             if (!depth_dev[k] || !normal_dev[k]) return finish(BTBA_EINVAL);
             pp[k] = depth_dev[k]; pp[N + k] = normal_dev[k];
         }
-        if ((e = hipMemcpyAsync(ws->ptrs.p, ws->pin, sizeof(void *) * 2 * (size_t)N, hipMemcpyHostToDevice, ws->stream)) != hipSuccess) return hip_fail(e);
+        if ((e = hipMemcpyAsync(ws->ptrs.p, ws->pin.p, sizeof(void *) * 2 * (size_t)N, hipMemcpyHostToDevice, ws->stream)) != hipSuccess) return hip_fail(e);
         rc = enqueue_frame_cache(ws, N, H, W, Hd, Wd, ws->ptrs.as<const float *>(), nullptr, nullptr, ws->campos.as<float4>(), ws->nvalid.as<int32_t>(),
                                  ws->valid_lists.as<uint32_t>(), ws->valid_counts.as<int>(), ws->block_ranges.as<float2>());
         if (!rc) {
-            nv_pinned = reinterpret_cast<const int32_t *>(static_cast<unsigned char *>(ws->pin) + off_nv);
-            if ((e = hipMemcpyAsync(static_cast<unsigned char *>(ws->pin) + off_nv, ws->nvalid.p, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, ws->stream)) != hipSuccess) return hip_fail(e);
+            nv_pinned = reinterpret_cast<const int32_t *>(static_cast<unsigned char *>(ws->pin.p) + off_nv);
+            if ((e = hipMemcpyAsync(static_cast<unsigned char *>(ws->pin.p) + off_nv, ws->nvalid.p, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, ws->stream)) != hipSuccess) return hip_fail(e);
             have_aux = true;
         }
     } else rc = btba_build_cache(ws, N, H, W, K, prm.image_downscale, depth_dev, normal_dev, ws->campos.as<float>(), ws->normals.as<float>(), ws->nvalid.as<int32_t>(), intr);
@@ -1768,8 +1787,8 @@ static int pool_resolve(btba_workspace *ws, int N, int H, int W, int Hd, int Wd,
     *n_built = (int)miss.size();
     const int M = (int)miss.size();
     const size_t off_slots = sizeof(void *) * 2 * (size_t)M, off_map = off_slots + sizeof(int32_t) * (size_t)M, off_nv = (off_map + sizeof(int32_t) * (size_t)N + 15) & ~(size_t)15;
-    if ((rc = ws->pin_ensure(off_nv + sizeof(int32_t) * cap))) return rc;
-    unsigned char *pin = static_cast<unsigned char *>(ws->pin);
+    if ((rc = ws->pin.ensure(off_nv + sizeof(int32_t) * cap))) return rc;
+    unsigned char *pin = static_cast<unsigned char *>(ws->pin.p);
     int32_t *pin_map = reinterpret_cast<int32_t *>(pin + off_map);
     for (int k = 0; k < N; k++) pin_map[k] = slot_of[k];
     *nv_pinned = reinterpret_cast<const int32_t *>(pin + off_nv);
@@ -2003,47 +2022,41 @@ int btba_ransac_pairs_ex(btba_workspace *ws, int hypothesis, int device_resident
     const size_t T = (size_t)offsets[n_pairs], NT = (size_t)n_pairs * n_trials;
     if (T && (!ptsA || !ptsB)) return BTBA_EINVAL;
     const bool dev = device_resident != 0;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t o = 0;
-    const size_t o_a = o; o += dev ? 0 : al(16 * (T ? T : 1));
-    const size_t o_b = o; o += dev ? 0 : al(16 * (T ? T : 1));
-    const size_t o_off = o; o += al(4 * (size_t)(n_pairs + 1));
-    const size_t o_smp = o; o += (samples && !dev) ? al(12 * NT) : al(4);
-    const size_t o_pose = o; o += al(48 * NT);
-    const size_t o_cnt = o; o += al(4 * NT);
-    const size_t o_best = o; o += al(8 * (size_t)n_pairs);
-    const size_t o_ids = o; o += dev ? 0 : al(4 * (T ? T : 1));
-    const size_t o_nin = o; o += al(4 * (size_t)n_pairs);
-    const size_t o_bt = o; o += al(4 * (size_t)n_pairs);
-    const size_t o_bp = o; o += al(64 * (size_t)n_pairs);
+    Scratch S;
+    const auto s_a = S.add<float4>(T ? T : 1, !dev), s_b = S.add<float4>(T ? T : 1, !dev);
+    const auto s_off = S.add<int>((size_t)n_pairs + 1);
+    const auto s_smp = S.add<int>((samples && !dev) ? 3 * NT : 1);      // (absent: one word)
+    const auto s_pose = S.add<float>(12 * NT);
+    const auto s_cnt = S.add<int>(NT);
+    const auto s_best = S.add<unsigned long long>((size_t)n_pairs);
+    const auto s_ids = S.add<int>(T ? T : 1, !dev);
+    const auto s_nin = S.add<int>((size_t)n_pairs), s_bt = S.add<int>((size_t)n_pairs);
+    const auto s_bp = S.add<float>(16 * (size_t)n_pairs);
     int rc;
-    if ((rc = ws->ransac.ensure(o ? o : 256))) return rc;
-    unsigned char *base = ws->ransac.as<unsigned char>();
+    if ((rc = S.bind(ws->ransac, 256))) return rc;
     if (T && !dev) {
-        HIP_TRY(hipMemcpyAsync(base + o_a, ptsA, 16 * T, hipMemcpyHostToDevice, ws->stream));
-        HIP_TRY(hipMemcpyAsync(base + o_b, ptsB, 16 * T, hipMemcpyHostToDevice, ws->stream));
+        HIP_TRY(hipMemcpyAsync(s_a, ptsA, 16 * T, hipMemcpyHostToDevice, ws->stream));
+        HIP_TRY(hipMemcpyAsync(s_b, ptsB, 16 * T, hipMemcpyHostToDevice, ws->stream));
     }
-    HIP_TRY(hipMemcpyAsync(base + o_off, offsets.data(), 4 * (size_t)(n_pairs + 1), hipMemcpyHostToDevice, ws->stream));
+    HIP_TRY(hipMemcpyAsync(s_off, offsets.data(), 4 * (size_t)(n_pairs + 1), hipMemcpyHostToDevice, ws->stream));
     HIP_TRY(hipStreamSynchronize(ws->stream));          // `offsets` is a local (16 B per pair: the only host wait of the device-resident form)
-    if (samples && !dev) HIP_TRY(hipMemcpyAsync(base + o_smp, samples, 12 * NT, hipMemcpyHostToDevice, ws->stream));
-    HIP_TRY(hipMemsetAsync(base + o_best, 0, 8 * (size_t)n_pairs, ws->stream));
+    if (samples && !dev) HIP_TRY(hipMemcpyAsync(s_smp, samples, 12 * NT, hipMemcpyHostToDevice, ws->stream));
+    HIP_TRY(hipMemsetAsync(s_best, 0, 8 * (size_t)n_pairs, ws->stream));
     if (!samples && !draw_hash && (rc = ransac_uniform_table(ws, seed, n_trials))) return rc;
     RansacDims D{};
     D.n_pairs = n_pairs; D.n_trials = n_trials; D.dist_thres = dist_thres; D.seed = seed; D.hypothesis = hypothesis;
     D.draw = samples ? 1 : (draw_hash ? 0 : 2);
-    const float4 *dA = dev ? reinterpret_cast<const float4 *>(ptsA) : reinterpret_cast<const float4 *>(base + o_a);
-    const float4 *dB = dev ? reinterpret_cast<const float4 *>(ptsB) : reinterpret_cast<const float4 *>(base + o_b);
-    const int *dS = (samples && dev) ? samples : reinterpret_cast<const int *>(base + o_smp);
+    const float4 *dA = dev ? reinterpret_cast<const float4 *>(ptsA) : s_a;
+    const float4 *dB = dev ? reinterpret_cast<const float4 *>(ptsB) : s_b;
+    const int *dS = (samples && dev) ? samples : s_smp;
     // device-resident: results go straight to the caller's device buffers (the optional per-trial tables too)
-    int *d_ids = dev ? inlier_ids_out : reinterpret_cast<int *>(base + o_ids);
-    int *d_nin = dev ? n_inliers_out : reinterpret_cast<int *>(base + o_nin);
-    int *d_bt = (dev && best_trial_out) ? best_trial_out : reinterpret_cast<int *>(base + o_bt);
-    float *d_bp = (dev && best_pose_out) ? best_pose_out : reinterpret_cast<float *>(base + o_bp);
-    int *d_cnt = (dev && trial_counts_out) ? trial_counts_out : reinterpret_cast<int *>(base + o_cnt);
-    float *d_pose = (dev && trial_poses_out) ? trial_poses_out : reinterpret_cast<float *>(base + o_pose);
-    if ((rc = ransac_enqueue(ws, D, dA, dB, reinterpret_cast<const int *>(base + o_off), dS, d_pose, d_cnt, reinterpret_cast<unsigned long long *>(base + o_best),
-                             d_ids, d_nin, d_bt, d_bp)))
-        return rc;
+    int *d_ids = dev ? inlier_ids_out : s_ids;
+    int *d_nin = dev ? n_inliers_out : s_nin;
+    int *d_bt = (dev && best_trial_out) ? best_trial_out : s_bt;
+    float *d_bp = (dev && best_pose_out) ? best_pose_out : s_bp;
+    int *d_cnt = (dev && trial_counts_out) ? trial_counts_out : s_cnt;
+    float *d_pose = (dev && trial_poses_out) ? trial_poses_out : s_pose;
+    if ((rc = ransac_enqueue(ws, D, dA, dB, s_off, dS, d_pose, d_cnt, s_best, d_ids, d_nin, d_bt, d_bp))) return rc;
     if (dev) return BTBA_OK;                          // asynchronous on the workspace stream
     // the inlier lists are written only up to each pair's count: fetch counts first, ids after
     HIP_TRY(hipMemcpyAsync(n_inliers_out, d_nin, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost, ws->stream));
@@ -2114,7 +2127,6 @@ static int match_check_frames(const btba_match_params *prm, int n_frames, int H,
     if (!K || !desc_dev || !kpts_dev || !depth_dev || !normal_dev || !poses || !frame_ids) return BTBA_EINVAL;
     std::vector<char> used(n_frames, 0);
     for (int p = 0; p < n_pairs; p++) used[pairs[2 * p]] = used[pairs[2 * p + 1]] = 1;
-    auto misaligned = [](const void *q, size_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
     for (int f = 0; f < n_frames; f++)
         if (used[f] && n_kpts[f] > 0 &&
             (!desc_dev[f] || !kpts_dev[f] || !depth_dev[f] || !normal_dev[f] || misaligned(desc_dev[f], 16) || misaligned(kpts_dev[f], 8) || misaligned(normal_dev[f], 16)))
@@ -2167,38 +2179,29 @@ static int match_enqueue(btba_workspace *ws, const btba_match_params *prm, bool 
         max_q = std::max(max_q, nq);
     }
     const size_t Q = (size_t)qbase;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t o = 0;
-    const size_t o_fr = o; o += al(sizeof(MatchFrame) * n_frames);
-    const size_t o_pr = o; o += al(sizeof(MatchPair) * n_pairs);
-    const size_t o_nrm = o; o += al(sizeof(float) * (n_norms ? n_norms : 1));
-    const size_t o_cand = o; o += al(sizeof(MatchCand) * prm->k * (Q ? Q : 1));
-    const size_t o_sel = o; o += al(sizeof(int) * (Q ? Q : 1));
-    const size_t o_pos = o; o += al(sizeof(int) * (Q ? Q : 1));
-    const size_t o_cnt = o; o += al(sizeof(int) * n_pairs);
-    const size_t o_off = o; o += al(sizeof(int) * n_pairs);
-    const size_t o_out = o; o += dev ? 0 : al(sizeof(btba_match) * (Q ? Q : 1));
-    const size_t o_pa = o; o += (dev || !ptsA_model_out) ? 0 : al(16 * (Q ? Q : 1));
-    const size_t o_pb = o; o += (dev || !ptsB_model_out) ? 0 : al(16 * (Q ? Q : 1));
+    const size_t Q1 = Q ? Q : 1;
+    Scratch S;
+    const auto dF = S.add<MatchFrame>(n_frames);
+    const auto dP = S.add<MatchPair>(n_pairs);
+    const auto d_nrm = S.add<float>(n_norms ? n_norms : 1);
+    const auto d_cand = S.add<MatchCand>(prm->k * Q1);
+    const auto d_sel = S.add<int>(Q1), d_pos = S.add<int>(Q1);
+    const auto s_cnt = S.add<int>(n_pairs), s_off = S.add<int>(n_pairs);
+    const auto s_out = S.add<btba_match>(Q1, !dev);
+    const auto s_pa = S.add<float4>(Q1, !dev && ptsA_model_out), s_pb = S.add<float4>(Q1, !dev && ptsB_model_out);
     int rc;
-    if ((rc = ws->match.ensure(o))) return rc;
-    unsigned char *base = ws->match.as<unsigned char>();
-    HIP_TRY(hipMemcpyAsync(base + o_fr, fr.data(), sizeof(MatchFrame) * n_frames, hipMemcpyHostToDevice, ws->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_pr, pt.data(), sizeof(MatchPair) * n_pairs, hipMemcpyHostToDevice, ws->stream));
+    if ((rc = S.bind(ws->match))) return rc;
+    HIP_TRY(hipMemcpyAsync(dF, fr.data(), sizeof(MatchFrame) * n_frames, hipMemcpyHostToDevice, ws->stream));
+    HIP_TRY(hipMemcpyAsync(dP, pt.data(), sizeof(MatchPair) * n_pairs, hipMemcpyHostToDevice, ws->stream));
 
     MatchDims M{};
     M.W = W; M.H = H; M.D = D; M.k = prm->k; M.mutual = prm->mutual ? 1 : 0; M.min_z = prm->min_z;
     float intr[4];
     scaled_intrinsics(H, W, H, W, K, intr, &M.Kinv);                 // btba_depth_to_normals' inverse: the same camera-space points
-    const MatchFrame *dF = reinterpret_cast<const MatchFrame *>(base + o_fr);
-    const MatchPair *dP = reinterpret_cast<const MatchPair *>(base + o_pr);
-    float *d_nrm = reinterpret_cast<float *>(base + o_nrm);
-    MatchCand *d_cand = reinterpret_cast<MatchCand *>(base + o_cand);
-    int *d_sel = reinterpret_cast<int *>(base + o_sel), *d_pos = reinterpret_cast<int *>(base + o_pos);
-    int *d_cnt = reinterpret_cast<int *>(base + o_cnt), *d_off = reinterpret_cast<int *>(base + o_off);
-    btba_match *d_out = dev ? matches_out : reinterpret_cast<btba_match *>(base + o_out);
-    float4 *d_pa = dev ? reinterpret_cast<float4 *>(ptsA_model_out) : (ptsA_model_out ? reinterpret_cast<float4 *>(base + o_pa) : nullptr);
-    float4 *d_pb = dev ? reinterpret_cast<float4 *>(ptsB_model_out) : (ptsB_model_out ? reinterpret_cast<float4 *>(base + o_pb) : nullptr);
+    int *d_cnt = s_cnt, *d_off = s_off;
+    btba_match *d_out = dev ? matches_out : s_out;
+    float4 *d_pa = dev ? reinterpret_cast<float4 *>(ptsA_model_out) : s_pa;      // (nullptr when the caller wants no points)
+    float4 *d_pb = dev ? reinterpret_cast<float4 *>(ptsB_model_out) : s_pb;
     if (max_n > 0) {
         k_match_norms<<<dim3((max_n + 255) / 256, n_frames), 256, 0, ws->stream>>>(dF, D, d_nrm);
         k_match_topk<<<dim3(n_pairs, (max_n + kMatchRows - 1) / kMatchRows, 1 + M.mutual), 256, 0, ws->stream>>>(M, dF, dP, d_nrm, d_cand);
@@ -2261,30 +2264,25 @@ int btba_apply_masks(btba_workspace *ws, const btba_mask_params *prm, int n_fram
         (int64_t)H * W >= ((int64_t)1 << 31) || !mask_dev || !depth_dev || !normal_dev)
         return BTBA_EINVAL;
     for (int f = 0; f < n_frames; f++)
-        if (!mask_dev[f] || !depth_dev[f] || !normal_dev[f] || (reinterpret_cast<uintptr_t>(normal_dev[f]) & 15) ||
-            (color_dev && color_dev[f] && (reinterpret_cast<uintptr_t>(color_dev[f]) & 3)) ||
+        if (!mask_dev[f] || !depth_dev[f] || !normal_dev[f] || misaligned(normal_dev[f], 16) ||
+            (color_dev && color_dev[f] && misaligned(color_dev[f], 4)) ||
             (mask_out_dev && mask_out_dev[f] && static_cast<const void *>(mask_out_dev[f]) == static_cast<const void *>(mask_dev[f])))
             return BTBA_EINVAL;
     DeviceGuard device_guard(ws);
     const bool hull = prm->largest_component_hull != 0;
     const int r = prm->dilate / 2, chunk = std::min(n_frames, kMaskChunk);
     const size_t HW = (size_t)H * W;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t o = 0;
-    const size_t o_roi = o; o += roi_out ? al(sizeof(int) * 4 * n_frames) : 0;
-    const size_t o_lab = o; o += hull ? al(sizeof(int) * chunk * HW) : 0;
-    const size_t o_cnt = o; o += hull ? al(sizeof(int) * chunk * HW) : 0;
-    const size_t o_best = o; o += hull ? al(sizeof(unsigned long long) * chunk) : 0;
-    const size_t o_rows = o; o += hull ? al(sizeof(int2) * chunk * (size_t)H) : 0;
-    const size_t o_span = o; o += hull ? al(sizeof(int2) * chunk * (size_t)H) : 0;
-    const size_t o_stk = o; o += (hull && H > kHullLdsMaxH) ? al(sizeof(int2) * chunk * (4 * (size_t)H + 2)) : 0;
+    Scratch S;
+    const auto s_roi = S.add<int>(4 * (size_t)n_frames, roi_out != nullptr);
+    const auto s_lab = S.add<int>(chunk * HW, hull), s_cnt = S.add<int>(chunk * HW, hull);
+    const auto s_best = S.add<unsigned long long>(chunk, hull);
+    const auto s_rows = S.add<int2>(chunk * (size_t)H, hull), s_span = S.add<int2>(chunk * (size_t)H, hull);
+    const auto s_stk = S.add<int2>(chunk * (4 * (size_t)H + 2), hull && H > kHullLdsMaxH);
     int rc;
-    if ((rc = ws->mask.ensure(o ? o : 256))) return rc;
-    unsigned char *base = ws->mask.as<unsigned char>();
-    int *d_roi = roi_out ? reinterpret_cast<int *>(base + o_roi) : nullptr;
-    int *d_lab = reinterpret_cast<int *>(base + o_lab), *d_cnt = reinterpret_cast<int *>(base + o_cnt);
-    unsigned long long *d_best = reinterpret_cast<unsigned long long *>(base + o_best);
-    int2 *d_rows = reinterpret_cast<int2 *>(base + o_rows), *d_span = reinterpret_cast<int2 *>(base + o_span), *d_stk = reinterpret_cast<int2 *>(base + o_stk);
+    if ((rc = S.bind(ws->mask, 256))) return rc;
+    int *d_roi = s_roi, *d_lab = s_lab, *d_cnt = s_cnt;
+    unsigned long long *d_best = s_best;
+    int2 *d_rows = s_rows, *d_span = s_span, *d_stk = s_stk;
     if (d_roi) HIP_TRY(hipMemsetAsync(d_roi, 0, sizeof(int) * 4 * n_frames, ws->stream));      // the zero start of k_mask_apply's ROI encoding
     const dim3 lgrid((W + kLabelTile - 1) / kLabelTile, (H + kLabelTile - 1) / kLabelTile, 1), lblock(kLabelTile, kLabelTile);
     const dim3 agrid((W + kMaskTileW - 1) / kMaskTileW, (H + kMaskTileH - 1) / kMaskTileH, 1), ablock(kMaskTileW, 4);
@@ -2389,11 +2387,11 @@ int btba_detector_inputs(btba_workspace *ws, const btba_detector_params *prm, in
 {
     // every argument is checked before the first HIP call
     if (!ws || !det_params_ok(prm) || n_frames < 1 || H < 1 || W < 1 || !color_dev || !roi_host ||
-        (reinterpret_cast<uintptr_t>(bgr_out_dev) & 3) || (reinterpret_cast<uintptr_t>(gray_out_dev) & 15))
+        misaligned(bgr_out_dev, 4) || misaligned(gray_out_dev, 16))
         return BTBA_EINVAL;
     std::vector<DetRoi> rois(n_frames);
     for (int f = 0; f < n_frames; f++)
-        if (!color_dev[f] || (reinterpret_cast<uintptr_t>(color_dev[f]) & 3) || !det_roi(roi_host + 4 * f, H, W, rois[f])) return BTBA_EINVAL;
+        if (!color_dev[f] || misaligned(color_dev[f], 4) || !det_roi(roi_host + 4 * f, H, W, rois[f])) return BTBA_EINVAL;
     if (!bgr_out_dev && !gray_out_dev) return BTBA_OK;
     DeviceGuard device_guard(ws);
     const int S = prm->out_size;
@@ -2423,7 +2421,7 @@ int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_par
     for (int f = 0; f < n_frames; f++) {
         DetRoi r;
         if (n_kpts[f] < 0 || n_kpts[f] > kDetMaxKpts || (n_kpts[f] > 0 && (!kpts_in_dev[f] || !kpts_out_dev[f])) ||
-            (reinterpret_cast<uintptr_t>(kpts_in_dev[f]) & 7) || (reinterpret_cast<uintptr_t>(kpts_out_dev[f]) & 7) || !det_roi(roi_host + 4 * f, 0, 0, r))
+            misaligned(kpts_in_dev[f], 8) || misaligned(kpts_out_dev[f], 8) || !det_roi(roi_host + 4 * f, 0, 0, r))
             return BTBA_EINVAL;
         det_transform(prm->out_size, roi_host + 4 * f, r, nullptr, bwd.data() + 9 * f);
     }
@@ -2454,7 +2452,7 @@ int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, cons
     // every argument is checked before the first HIP call
     if (!ws || n_models < 1 || !model_pts_dev || !n_pts || n_evals < 0) return BTBA_EINVAL;
     for (int m = 0; m < n_models; m++)
-        if (!model_pts_dev[m] || (reinterpret_cast<uintptr_t>(model_pts_dev[m]) & 3) || n_pts[m] < 1 || n_pts[m] > BTBA_EVAL_MAX_POINTS)
+        if (!model_pts_dev[m] || misaligned(model_pts_dev[m], 4) || n_pts[m] < 1 || n_pts[m] > BTBA_EVAL_MAX_POINTS)
             return BTBA_EINVAL;
     if (n_evals == 0) return BTBA_OK;
     if (!model_index || !poses_pred || !poses_gt || !add_out || !adds_out) return BTBA_EINVAL;
@@ -2479,18 +2477,15 @@ int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, cons
     chunk_start.push_back(n_evals);
     const int max_chunk = std::min(n_evals, kEvalChunkEvals);
     const bool dev = device_resident != 0;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t o = 0;
-    const size_t o_rec = o; o += al(sizeof(EvalRec) * max_chunk);
-    const size_t o_pp = o; o += dev ? 0 : al(sizeof(float) * 16 * max_chunk);
-    const size_t o_pg = o; o += dev ? 0 : al(sizeof(float) * 16 * max_chunk);
-    const size_t o_out = o; o += dev ? 0 : al(sizeof(float) * 2 * max_chunk);
-    const size_t o_min = o; o += al(sizeof(unsigned) * (size_t)max_chunk_pts);
-    int rc = ws->eval.ensure(o);
+    Scratch S;
+    const auto s_rec = S.add<EvalRec>(max_chunk);
+    const auto s_pp = S.add<float>(16 * (size_t)max_chunk, !dev), s_pg = S.add<float>(16 * (size_t)max_chunk, !dev);
+    const auto s_out = S.add<float>(2 * (size_t)max_chunk, !dev);
+    const auto s_min = S.add<unsigned>((size_t)max_chunk_pts);
+    int rc = S.bind(ws->eval);
     if (rc) return rc;
-    unsigned char *base = ws->eval.as<unsigned char>();
-    EvalRec *d_rec = reinterpret_cast<EvalRec *>(base + o_rec);
-    unsigned *d_min = reinterpret_cast<unsigned *>(base + o_min);
+    EvalRec *d_rec = s_rec;
+    unsigned *d_min = s_min;
     for (size_t c = 0; c + 1 < chunk_start.size(); c++) {
         const int e0 = chunk_start[c], ne = chunk_start[c + 1] - e0;
         int max_n = 0;
@@ -2499,11 +2494,11 @@ int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, cons
         float *oa = add_out + e0, *os = adds_out + e0;
         HIP_TRY(hipMemcpyAsync(d_rec, rec.data() + e0, sizeof(EvalRec) * ne, hipMemcpyHostToDevice, ws->stream));
         if (!dev) {
-            HIP_TRY(hipMemcpyAsync(base + o_pp, pp, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
-            HIP_TRY(hipMemcpyAsync(base + o_pg, pg, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
-            pp = reinterpret_cast<const float *>(base + o_pp);
-            pg = reinterpret_cast<const float *>(base + o_pg);
-            oa = reinterpret_cast<float *>(base + o_out);
+            HIP_TRY(hipMemcpyAsync(s_pp, pp, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
+            HIP_TRY(hipMemcpyAsync(s_pg, pg, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
+            pp = s_pp;
+            pg = s_pg;
+            oa = s_out;
             os = oa + max_chunk;
         }
         // split the candidates when evaluations x query tiles cannot fill the chip (the result does not depend on it)
@@ -2575,8 +2570,8 @@ int btba_marshal_windows(btba_workspace *ws, int n_windows, int n_frames, const 
     if (!ws || n_windows < 1 || n_windows > 65535 || n_frames < 2 || n_frames > BTBA_MAX_FRAMES || n_records < 0 || n_records > (int64_t)UINT32_MAX ||
         (!matches_dev && n_records) || !segments_dev || !corr_dev || !pair_offsets_dev || corr_stride < 1)
         return BTBA_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(matches_dev) & 15) || (reinterpret_cast<uintptr_t>(segments_dev) & 7) || (reinterpret_cast<uintptr_t>(corr_dev) & 15) ||
-        (reinterpret_cast<uintptr_t>(pair_offsets_dev) & 3) || (reinterpret_cast<uintptr_t>(corr24_dev) & 7))
+    if (misaligned(matches_dev, 16) || misaligned(segments_dev, 8) || misaligned(corr_dev, 16) ||
+        misaligned(pair_offsets_dev, 4) || misaligned(corr24_dev, 8))
         return BTBA_EINVAL;
     DeviceGuard device_guard(ws);
     const int P = n_frames * (n_frames - 1) / 2;
@@ -2594,7 +2589,7 @@ int btba_procrustes_pairs(btba_workspace *ws, int device_resident, int n_pairs, 
     // every argument is checked before the first HIP call
     if (!ws || n_pairs < 0 || n_records < 0 || n_records > (int64_t)UINT32_MAX) return BTBA_EINVAL;
     if (n_pairs == 0) return BTBA_OK;
-    if (!segments || !posesA || !posesB || !pose_out || !err_out || (!matches_dev && n_records) || (reinterpret_cast<uintptr_t>(matches_dev) & 7))
+    if (!segments || !posesA || !posesB || !pose_out || !err_out || (!matches_dev && n_records) || misaligned(matches_dev, 8))
         return BTBA_EINVAL;
     std::vector<KabschRec> rec(n_pairs);
     for (int e = 0; e < n_pairs; e++) {
@@ -2605,29 +2600,25 @@ int btba_procrustes_pairs(btba_workspace *ws, int device_resident, int n_pairs, 
     DeviceGuard device_guard(ws);
     const bool dev = device_resident != 0;
     const size_t np = (size_t)n_pairs;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t o = 0;
-    const size_t o_rec = o; o += al(sizeof(KabschRec) * np);
-    const size_t o_mom = o; o += moments_out && dev ? 0 : al(sizeof(double) * 16 * np);
-    const size_t o_pa = o; o += dev ? 0 : al(sizeof(float) * 16 * np);
-    const size_t o_pb = o; o += dev ? 0 : al(sizeof(float) * 16 * np);
-    const size_t o_out = o; o += dev ? 0 : al(sizeof(float) * 16 * np);
-    const size_t o_err = o; o += dev ? 0 : al(sizeof(float) * np);
-    int rc = ws->window.ensure(o);
+    Scratch S;
+    const auto s_rec = S.add<KabschRec>(np);
+    const auto s_mom = S.add<double>(16 * np, !(moments_out && dev));
+    const auto s_pa = S.add<float>(16 * np, !dev), s_pb = S.add<float>(16 * np, !dev), s_out = S.add<float>(16 * np, !dev);
+    const auto s_err = S.add<float>(np, !dev);
+    int rc = S.bind(ws->window);
     if (rc) return rc;
-    unsigned char *base = ws->window.as<unsigned char>();
-    KabschRec *d_rec = reinterpret_cast<KabschRec *>(base + o_rec);
-    double *d_mom = moments_out && dev ? moments_out : reinterpret_cast<double *>(base + o_mom);
+    KabschRec *d_rec = s_rec;
+    double *d_mom = moments_out && dev ? moments_out : s_mom;
     const float *pa = posesA, *pb = posesB;
     float *po = pose_out, *pe = err_out;
     HIP_TRY(hipMemcpyAsync(d_rec, rec.data(), sizeof(KabschRec) * np, hipMemcpyHostToDevice, ws->stream));
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(base + o_pa, posesA, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
-        HIP_TRY(hipMemcpyAsync(base + o_pb, posesB, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
-        pa = reinterpret_cast<const float *>(base + o_pa);
-        pb = reinterpret_cast<const float *>(base + o_pb);
-        po = reinterpret_cast<float *>(base + o_out);
-        pe = reinterpret_cast<float *>(base + o_err);
+        HIP_TRY(hipMemcpyAsync(s_pa, posesA, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
+        HIP_TRY(hipMemcpyAsync(s_pb, posesB, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
+        pa = s_pa;
+        pb = s_pb;
+        po = s_out;
+        pe = s_err;
     }
     const unsigned char *recs = reinterpret_cast<const unsigned char *>(matches_dev);
     k_kabsch_moments<<<n_pairs, kKabschThreads, 0, ws->stream>>>(d_rec, recs, pa, pb, d_mom);
@@ -2687,10 +2678,8 @@ int mp_grow(btba_mappoints *M, int slots, int points)
     DevBuf img, stamp, stack, table;
     int rc;
     if ((rc = img.ensure((size_t)ns * np * 4)) || (rc = stamp.ensure((size_t)np * 4)) || (rc = stack.ensure((size_t)np * 4)) ||
-        (rc = table.ensure(sizeof(MpSlot) * ns))) {
-        img.release(); stamp.release(); stack.release(); table.release();
+        (rc = table.ensure(sizeof(MpSlot) * ns)))
         return rc;
-    }
     HIP_TRY(hipMemsetAsync(img.p, 0xFF, (size_t)ns * np * 4, st));
     HIP_TRY(hipMemsetAsync(stamp.p, 0xFF, (size_t)np * 4, st));
     HIP_TRY(hipMemsetAsync(table.p, 0, sizeof(MpSlot) * ns, st));
@@ -2700,8 +2689,7 @@ int mp_grow(btba_mappoints *M, int slots, int points)
     }
     if (M->slot_cap) HIP_TRY(hipMemcpyAsync(table.p, M->table.p, sizeof(MpSlot) * M->slot_cap, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
-    M->img.release(); M->stamp.release(); M->stack.release(); M->table.release();
-    M->img = img; M->stamp = stamp; M->stack = stack; M->table = table;
+    M->img = std::move(img); M->stamp = std::move(stamp); M->stack = std::move(stack); M->table = std::move(table);
     M->slot_cap = ns; M->mp_cap = np;
     return BTBA_OK;
 }
@@ -2720,7 +2708,7 @@ int btba_mappoints_create(btba_workspace *ws, btba_mappoints **out)
     if ((rc = M->hdr.ensure(16))) { delete M; return rc; }
     hipError_t e = hipMemsetAsync(M->hdr.p, 0, 16, ws->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; M->hdr.release(); delete M; return BTBA_EHIP; }
+    if (e != hipSuccess) { g_last_hip_error = (int)e; delete M; return BTBA_EHIP; }
     *out = M;
     return BTBA_OK;
 }
@@ -2730,16 +2718,14 @@ void btba_mappoints_destroy(btba_mappoints *M)
     if (!M) return;
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
-    (void)hipDeviceSynchronize();                                     // hipFree below; no workspace access
-    for (auto &s : M->slots) s.data.release();
-    M->img.release(); M->stamp.release(); M->stack.release(); M->table.release(); M->hdr.release();
+    (void)hipDeviceSynchronize();                                     // delete frees the buffers; no workspace access
     delete M;
     if (prev >= 0) (void)hipSetDevice(prev);
 }
 
 int btba_mappoints_register_frame(btba_mappoints *M, int n_kpts, const float *kpts_dev, int32_t *slot_out)
 {
-    if (!M || !slot_out || n_kpts < 0 || n_kpts > kMatchMaxKpts || (n_kpts && !kpts_dev) || (reinterpret_cast<uintptr_t>(kpts_dev) & 7)) return BTBA_EINVAL;
+    if (!M || !slot_out || n_kpts < 0 || n_kpts > kMatchMaxKpts || (n_kpts && !kpts_dev) || misaligned(kpts_dev, 8)) return BTBA_EINVAL;
     if (M->broken) return BTBA_ENOMEM;
     DeviceGuard device_guard(M->ws);
     hipStream_t st = M->ws->stream;
@@ -2767,13 +2753,11 @@ int btba_mappoints_register_frame(btba_mappoints *M, int n_kpts, const float *kp
     int bad_h = 0;
     HIP_TRY(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (bad_h) { fresh.data.release(); return BTBA_EINVAL; }                 // a non-finite keypoint
+    if (bad_h) return BTBA_EINVAL;                                   // a non-finite keypoint
     HIP_TRY(hipMemcpy(M->table.as<MpSlot>() + slot, &v, sizeof(MpSlot), hipMemcpyHostToDevice));
     if (slot == (int)M->slots.size()) M->slots.emplace_back();
-    M->slots[slot].data.release();
-    M->slots[slot].data = fresh.data;
-    M->slots[slot].n = n_kpts;
-    M->slots[slot].live = true;
+    fresh.live = true;
+    M->slots[slot] = std::move(fresh);
     M->bound += n_kpts;
     *slot_out = slot;
     return BTBA_OK;
@@ -2792,9 +2776,7 @@ int btba_mappoints_forget_frame(btba_mappoints *M, int32_t slot)
     int h[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, M->hdr.p, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    M->slots[slot].live = false;
-    M->slots[slot].data.release();
-    M->slots[slot].n = 0;
+    M->slots[slot] = btba_mappoints::Slot{};
     MpSlot dead{};
     HIP_TRY(hipMemcpy(M->table.as<MpSlot>() + slot, &dead, sizeof(MpSlot), hipMemcpyHostToDevice));
     M->live_known = h[kMpNext] - h[kMpTop];
@@ -2911,43 +2893,36 @@ int btba_corres_chain(btba_workspace *ws, btba_mappoints *M, const btba_match_pa
     }
     const size_t L = (size_t)std::max<int64_t>(base, 1), Nn = (size_t)std::max<int64_t>(cap_nn, 1), NT = (size_t)rprm->n_trials;
     const bool dev = device_resident != 0;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t o = 0;
-    const size_t o_cf = o; o += al(sizeof(CorresFrame) * n_frames);
-    const size_t o_cp = o; o += al(sizeof(CorresPair) * n_pairs);
-    const size_t o_nn = o; o += al(sizeof(btba_match) * Nn);
-    const size_t o_npa = o; o += al(16 * Nn);
-    const size_t o_npb = o; o += al(16 * Nn);
-    const size_t o_list = o; o += al(sizeof(btba_match) * L);
-    const size_t o_la = o; o += al(16 * L);
-    const size_t o_lb = o; o += al(16 * L);
-    const size_t o_ids = o; o += al(4 * L);
-    const size_t o_ump = o; o += al(4 * L);
-    const size_t o_ua = o; o += al(4 * L);
-    const size_t o_out = o; o += dev ? 0 : al(sizeof(btba_match) * (size_t)std::max<int64_t>(cap, 1));
-    const size_t o_meta = o; o += al(8 * (size_t)n_pairs);
-    const size_t o_roff = o; o += al(8 * (size_t)n_pairs);
-    const size_t o_best = o; o += al(8 * (size_t)n_pairs);
-    const size_t o_nin = o; o += al(4 * (size_t)n_pairs);
-    const size_t o_bt = o; o += al(4 * (size_t)n_pairs);
-    const size_t o_bp = o; o += al(64 * (size_t)n_pairs);
-    const size_t o_tp = o; o += al(48 * NT);
-    const size_t o_tc = o; o += al(4 * NT);
-    const size_t o_res = o; o += al(4 * ((size_t)n_frames + 1 + 2 * (size_t)n_pairs + 4 * (size_t)n_pairs) + 16);   // status | out_off | n_out | stage | hdr copy
-    if ((rc = ws->corres.ensure(o))) return rc;
+    const size_t np = (size_t)n_pairs, n_res = (size_t)n_frames + 1 + 2 * np + 4 * np;      // status | out_off | n_out | stage
+    Scratch S;
+    const auto dF = S.add<CorresFrame>(n_frames);
+    const auto dP = S.add<CorresPair>(np);
+    const auto d_nn = S.add<btba_match>(Nn);
+    const auto s_npa = S.add<float4>(Nn), s_npb = S.add<float4>(Nn);
+    const auto s_list = S.add<btba_match>(L);
+    const auto s_la = S.add<float4>(L), s_lb = S.add<float4>(L);
+    const auto s_ids = S.add<int>(L), d_ump = S.add<int>(L), d_ua = S.add<int>(L);
+    const auto s_out = S.add<btba_match>((size_t)std::max<int64_t>(cap, 1), !dev);
+    const auto s_meta = S.add<int>(2 * np), s_roff = S.add<int>(2 * np);
+    const auto s_best = S.add<unsigned long long>(np);
+    const auto s_nin = S.add<int>(np), s_bt = S.add<int>(np);
+    const auto s_bp = S.add<float>(16 * np), s_tp = S.add<float>(12 * NT);
+    const auto s_tc = S.add<int>(NT);
+    const auto s_res = S.add<int>(n_res + 4);                          // ... | hdr copy
+    if ((rc = S.bind(ws->corres))) return rc;
     if (!(rprm->hypothesis & BTBA_RANSAC_DRAW_HASH) && (rc = ransac_uniform_table(ws, rprm->seed, rprm->n_trials))) return rc;
-    unsigned char *b0 = ws->corres.as<unsigned char>();
-    int *d_status = reinterpret_cast<int *>(b0 + o_res), *d_outoff = d_status + n_frames, *d_nout = d_outoff + n_pairs + 1, *d_stage = d_nout + n_pairs;
-    HIP_TRY(hipMemcpyAsync(b0 + o_cf, cf.data(), sizeof(CorresFrame) * n_frames, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b0 + o_cp, cp.data(), sizeof(CorresPair) * n_pairs, hipMemcpyHostToDevice, st));
+    int *d_status = s_res, *d_outoff = d_status + n_frames, *d_nout = d_outoff + n_pairs + 1, *d_stage = d_nout + n_pairs;
+    HIP_TRY(hipMemcpyAsync(dF, cf.data(), sizeof(CorresFrame) * n_frames, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dP, cp.data(), sizeof(CorresPair) * n_pairs, hipMemcpyHostToDevice, st));
     std::vector<int32_t> st_in(status, status + n_frames);
     HIP_TRY(hipMemcpyAsync(d_status, st_in.data(), 4 * (size_t)n_frames, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_outoff, 0, 4, st));
 
     // NN for every pair at once (it reads no map state)
+    float4 *d_npa = s_npa, *d_npb = s_npb;
     MatchEnqueue E;
     if ((rc = match_enqueue(ws, prm, true, n_frames, H, W, K, desc_dev, D, kpts_dev, n_kpts, depth_dev, normal_dev, poses, frame_ids, n_pairs, pairs,
-                            reinterpret_cast<btba_match *>(b0 + o_nn), reinterpret_cast<float *>(b0 + o_npa), reinterpret_cast<float *>(b0 + o_npb), E)))
+                            d_nn, reinterpret_cast<float *>(d_npa), reinterpret_cast<float *>(d_npb), E)))
         return rc;
 
     CorresDims Cd{};
@@ -2957,31 +2932,24 @@ int btba_corres_chain(btba_workspace *ws, btba_mappoints *M, const btba_match_pa
     RansacDims Rd{};
     Rd.n_pairs = 1; Rd.n_trials = rprm->n_trials; Rd.dist_thres = rprm->dist_thres; Rd.seed = rprm->seed; Rd.hypothesis = hyp;
     Rd.draw = (rprm->hypothesis & BTBA_RANSAC_DRAW_HASH) ? 0 : 2;
-    const CorresFrame *dF = reinterpret_cast<const CorresFrame *>(b0 + o_cf);
-    const CorresPair *dP = reinterpret_cast<const CorresPair *>(b0 + o_cp);
-    btba_match *d_list = reinterpret_cast<btba_match *>(b0 + o_list);
-    float4 *d_la = reinterpret_cast<float4 *>(b0 + o_la), *d_lb = reinterpret_cast<float4 *>(b0 + o_lb);
-    int *d_ids = reinterpret_cast<int *>(b0 + o_ids), *d_meta = reinterpret_cast<int *>(b0 + o_meta), *d_roff = reinterpret_cast<int *>(b0 + o_roff);
-    unsigned long long *d_best = reinterpret_cast<unsigned long long *>(b0 + o_best);
-    int *d_nin = reinterpret_cast<int *>(b0 + o_nin), *d_bt = reinterpret_cast<int *>(b0 + o_bt);
-    float *d_bp = reinterpret_cast<float *>(b0 + o_bp), *d_tp = reinterpret_cast<float *>(b0 + o_tp);
-    int *d_tc = reinterpret_cast<int *>(b0 + o_tc);
-    btba_match *d_out = dev ? matches_out : reinterpret_cast<btba_match *>(b0 + o_out);
+    btba_match *d_list = s_list, *d_out = dev ? matches_out : s_out;
+    float4 *d_la = s_la, *d_lb = s_lb;
+    int *d_ids = s_ids, *d_meta = s_meta, *d_roff = s_roff, *d_nin = s_nin, *d_bt = s_bt, *d_tc = s_tc;
+    unsigned long long *d_best = s_best;
+    float *d_bp = s_bp, *d_tp = s_tp;
     const MpSlot *dS = M->table.as<MpSlot>();
     // per pair, in order: propagation, RANSAC (vote + inlier list), update + gates.  No host synchronisation in between.
     for (int p = 0; p < n_pairs; p++) {
         const int bs = cp[p].base;
-        k_corres_prop<<<1, 256, 0, st>>>(Cd, p, dF, dP, dS, M->img.as<int>(), reinterpret_cast<const btba_match *>(b0 + o_nn),
-                                         reinterpret_cast<const float4 *>(b0 + o_npa), reinterpret_cast<const float4 *>(b0 + o_npb), E.d_cnt, E.d_off,
+        k_corres_prop<<<1, 256, 0, st>>>(Cd, p, dF, dP, dS, M->img.as<int>(), d_nn, d_npa, d_npb, E.d_cnt, E.d_off,
                                          d_status, d_list, d_la, d_lb, d_meta, d_roff, d_best, d_stage);
         if ((rc = ransac_enqueue(ws, Rd, d_la + bs, d_lb + bs, d_roff + 2 * p, nullptr, d_tp, d_tc, d_best + p, d_ids + bs, d_nin + p, d_bt + p, d_bp + 16 * p)))
             return rc;
         k_corres_update<<<1, 256, 0, st>>>(Cd, p, dF, dP, dS, M->img.as<int>(), M->stamp.as<int>(), M->hdr.as<int>(), M->stack.as<int>(), d_status,
-                                           d_list, d_meta, d_ids, d_nin, reinterpret_cast<int *>(b0 + o_ump), reinterpret_cast<int *>(b0 + o_ua),
-                                           d_out, d_outoff, d_nout, d_stage);
+                                           d_list, d_meta, d_ids, d_nin, d_ump, d_ua, d_out, d_outoff, d_nout, d_stage);
     }
     HIP_TRY(hipGetLastError());
-    std::vector<int32_t> res((size_t)n_frames + 1 + 2 * (size_t)n_pairs + 4 * (size_t)n_pairs);
+    std::vector<int32_t> res(n_res);
     int hdr[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(res.data(), d_status, 4 * res.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(hdr, M->hdr.p, 16, hipMemcpyDeviceToHost, st));

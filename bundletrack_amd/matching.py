@@ -56,6 +56,26 @@ def _dims(frames):
     return D if D is not None else 4
 
 
+def _frame_tables(frames, pairs, K):
+    """The per-frame host tables btba_match_pairs and btba_corres_chain take: (n_kpts int32 [n], pairs int32 [P, 2], the desc /
+    kpts / depth / normal pointer arrays (an empty or missing tensor = NULL), poses float32 [n, 16], ids int32 [n], K float32 [9])."""
+    from .optimizer import _dev_ptr
+    n_kpts = np.array([0 if f.kpts_gpu is None else int(f.kpts_gpu.shape[0]) for f in frames], np.int32)
+    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+
+    def ptrs(attr):
+        arr = (C.c_void_p * max(len(frames), 1))()
+        for k, f in enumerate(frames):
+            t = getattr(f, attr)
+            arr[k] = _dev_ptr(t, f"frame {k} {attr}") if (t is not None and t.numel() > 0) else None
+        return arr
+
+    poses = np.ascontiguousarray(np.stack([np.asarray(f.pose_in_model, np.float32).reshape(16) for f in frames]), np.float32)
+    ids = np.array([int(f.id) for f in frames], np.int32)
+    Kf = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+    return n_kpts, pr, tuple(ptrs(a) for a in ("desc_gpu", "kpts_gpu", "depth_gpu", "normal_gpu")), poses, ids, Kf
+
+
 def match_pairs(ws, frames, pairs, params=None, *, K, H: int, W: int, device_resident: bool = True, want_points: bool = True) -> MatchResult:
     """btba_match_pairs.  frames: FrameRef-like objects with id, pose_in_model [4,4], kpts_gpu [n,2], desc_gpu [n,D] (float32 CUDA;
     None or empty = no keypoints), depth_gpu [H,W] and normal_gpu [H,W,4] (btba_depth_to_normals' format).  pairs: [(ia, ib)]
@@ -66,24 +86,11 @@ def match_pairs(ws, frames, pairs, params=None, *, K, H: int, W: int, device_res
     prm = params if params is not None else match_params()
     n = len(frames)
     D = _dims(frames)
-    n_kpts = np.array([0 if f.kpts_gpu is None else int(f.kpts_gpu.shape[0]) for f in frames], np.int32)
-    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    n_kpts, pr, (desc, kpts, depth, normal), poses, ids, Kf = _frame_tables(frames, pairs, K)
     cap = C.c_int64(0)
     check(lib().btba_match_capacity(C.byref(prm), n, int(H), int(W), D, n_kpts.ctypes.data, pr.shape[0], pr.ctypes.data, C.byref(cap)),
           "btba_match_capacity")
     cap = int(cap.value)
-
-    def ptrs(attr):
-        arr = (C.c_void_p * max(n, 1))()
-        for k, f in enumerate(frames):
-            t = getattr(f, attr)
-            arr[k] = _dev_ptr(t, f"frame {k} {attr}") if (t is not None and t.numel() > 0) else None
-        return arr
-
-    desc, kpts, depth, normal = ptrs("desc_gpu"), ptrs("kpts_gpu"), ptrs("depth_gpu"), ptrs("normal_gpu")
-    poses = np.ascontiguousarray(np.stack([np.asarray(f.pose_in_model, np.float32).reshape(16) for f in frames]), np.float32)
-    ids = np.array([int(f.id) for f in frames], np.int32)
-    Kf = np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
     n_out = np.zeros(max(pr.shape[0], 1), np.int32)
     res = MatchResult(per_pair=[], n_out=n_out[: pr.shape[0]], offsets=np.zeros(pr.shape[0] + 1, np.int64))
     if device_resident:

@@ -304,6 +304,35 @@ def test_propagated_matches_link_planted_landmarks(ws, scene):
     assert good / total >= 0.9, (good, total)
 
 
+def test_workspace_destroy_returns_the_chain_scratch(scene):
+    """A workspace hands its chain scratch back to the device when it is destroyed.  One chain of 2^22 hash-drawn trials makes the
+    per-trial regions (48 + 4 bytes a trial) about 218 MB, about 272 MB after the buffer's growth rule; once the memory and the
+    workspace are closed, free device memory is back within the 64 MiB that test_scratch_does_not_grow_over_repeated_calls allows
+    for allocator noise.  Own workspace: the module's one stays alive."""
+    import torch
+    from bundletrack_amd.correspondence import MapPointMemory, find_corres_chain
+    from bundletrack_amd.optimizer import Workspace
+    pb, kp, frames = scene
+    L = _spread_landmarks(kp, [0, 1], 36, min_dist=0.02)
+    dev = _dev([_small_frame(kp, frames, 0, L), _small_frame(kp, frames, 1, L)])
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    w = Workspace()
+    mem = MapPointMemory(w)
+    slots = [mem.register_frame(f.kpts_gpu) for f in dev]
+    rp = _lib.corres_params(hypothesis=_lib.RANSAC_REFERENCE_SVD | _lib.RANSAC_DRAW_HASH, n_trials=1 << 22)
+    res = find_corres_chain(w, mem, dev, [(1, 0)], slots, np.zeros(2, np.int32), _lib.match_params(), rp, K=pb.K, H=pb.H, W=pb.W)
+    held = free0 - torch.cuda.mem_get_info()[0]
+    assert res.stage_counts[0][0] > 0                      # the chain ran: there were matches to vote on
+    mem.close()
+    w.close()
+    del res
+    torch.cuda.synchronize()
+    kept = free0 - torch.cuda.mem_get_info()[0]
+    print(f"device memory held during the chain {held / 2**20:.1f} MiB, kept after destroy {kept / 2**20:.1f} MiB")
+    assert kept < 64 << 20, kept
+
+
 def _session_driver():
     import ctypes as C
     import os

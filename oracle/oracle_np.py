@@ -128,7 +128,7 @@ def solve(campos, normals, intr, corr, poses, pairs=None, **kw):
     ci, cj = corr["imgIdx_i"].astype(np.int64), corr["imgIdx_j"].astype(np.int64)
     valid = corr["imgIdx_i"] != 0xFFFFFFFF
     pi, pj = corr["pos_i"].astype(np.float64), corr["pos_j"].astype(np.float64)
-    out = dict(T_after=[], x_after=[], dense_count=[], pcg_scalars=[], A=[], b=[])
+    out = dict(T_after=[], x_after=[], dense_count=[], pcg_scalars=[], A=[], b=[], Mdiag=[])
     dim = 6 * N
     for it in range(prm["n_gn_iters"]):
         T = np.stack([se3_exp(*x[k]) for k in range(N)])
@@ -198,6 +198,6 @@ def solve(campos, normals, intr, corr, poses, pairs=None, **kw):
             x[k] = se3_log(se3_exp(dk[3:], dk[:3]) @ se3_exp(*x[k]))
         out["T_after"].append(np.stack([se3_exp(*x[k]) for k in range(N)]))
         out["x_after"].append(np.stack([np.concatenate(x[k]) for k in range(N)]))
-        out["dense_count"].append(cnts); out["pcg_scalars"].append(sc); out["A"].append(A); out["b"].append(b)
+        out["dense_count"].append(cnts); out["pcg_scalars"].append(sc); out["A"].append(A); out["b"].append(b); out["Mdiag"].append(Mdiag)
     out["poses"] = out["T_after"][-1]
     return out

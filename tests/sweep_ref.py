@@ -1,0 +1,482 @@
+"""Threshold-aware fp64 references for the dense and the sparse sweep (numpy only; test infrastructure).
+
+The sweeps sum per-pixel / per-correspondence terms behind HARD accept tests, so a tight comparison of sums has to
+say what happens to a term that sits on a threshold.  Here every term is classified in fp64:
+
+  accept      every gate passes by more than a margin           -> goes into the reference sums
+  reject      some gate fails by more than a margin             -> contributes nothing
+  borderline  everything else                                   -> counted, and BUDGETED: an implementation may take
+                                                                   it or leave it, so it widens the bound by |term|
+
+The margin is EPS = 1e-4.  Derivation: the gate quantities are u, v (pixels), depths and distances (metres) and a
+cosine.  In fp32 (unit round-off 6e-8) a projected coordinate u = fx qx / qz + cx with |u| <= 275 px carries a few
+ulps of 275, i.e. <= 1e-6 px after the 1-ulp reciprocal, the 4 x 4 product and the pose round-off; depths (~1 m) and
+the cosine (<= 1) carry <= 5e-7 absolute; the distance 0.02 m is a difference of ~1 m points, error <= 5e-7 m, i.e.
+2.5e-5 RELATIVE to the threshold.  1e-4 (relative for the distance, absolute for the others) is ~100 x the
+evaluation error of u, v, depth and cosine and 4 x that of the relative distance -- a pixel outside the margin is
+decided the same way by any correct fp32 evaluation on caches up to 275 px wide.
+
+Bound for an implementation's sum X of a reference sum R:   |X - R| <= Bud + gamma * Sc
+  Bud  per-entry budget of the borderline terms, sum |term|
+  Sc   per-entry round-off scale: the same sum with every factor replaced by its absolute value (dense: taken in the
+       target camera frame and pushed through |M|, because the kernel sums camera-frame rows a' = [-n ; n x q] and then
+       applies the congruence S = M S' M^T of dense_epilogue; |M a'| <= |M| |a'| entrywise makes the same scale valid
+       for an evaluation that sums model-frame rows directly)
+  gamma  a small multiple of the fp32 unit round-off, MEASURED on the project's fp32 CPU oracle (see the tests)."""
+from __future__ import annotations
+
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from oracle import oracle_np as ONP  # noqa: E402
+
+EPS = 1e-4
+DEFAULT_PRM = dict(robust_delta=0.005, dense_dist_thresh=0.02, dense_normal_thresh=float(np.float32(np.cos(np.pi / 4))),
+                   depth_min=0.1, depth_max=9999.0, weight_sparse=1.0, weight_dense_depth=1.0)
+ENTRYJ = np.dtype([("imgIdx_i", "<u4"), ("imgIdx_j", "<u4"), ("pos_i", "<f4", (3,)), ("pos_j", "<f4", (3,))])
+TRI = [(r, c) for r in range(6) for c in range(r, 6)]          # the 21 upper-triangle entries, row-major (tri21 of the kernels)
+
+
+def congruence(Ti):
+    """M = [[R, 0], [[t]x R, R]] of the target pose: model-frame row a = M a' (dense_epilogue)."""
+    R, t = Ti[:3, :3], Ti[:3, 3]
+    M = np.zeros((6, 6))
+    M[:3, :3] = R
+    M[3:, :3] = ONP.skew(t) @ R
+    M[3:, 3:] = R
+    return M
+
+
+def dense_pair_ref(campos, normals, intr, Ti, Tj, Tinv_i=None, prm=None, eps=EPS):
+    """campos / normals [2, Hd, Wd, 4] = (target, source) caches; Ti, Tj camera -> model matrices AS THE IMPLEMENTATION
+    HOLDS THEM (fp32 values, taken as exact); Tinv_i its inverse of Ti (None: the fp64 inverse).  The gates are those of
+    oracle_np.dense_pair_sums, in its order.  Returns a dict:
+      S [6,6], g [6], count          sums over the accepts, [trans, rot] model-frame layout
+      borderline                     number of borderline pixels
+      bud_S [6,6], bud_g [6]         sum over borderline pixels of w |a_r| |a_c| and w |a_r| |res|
+      sc_S [6,6], sc_g [6]           |M| (sum_accept w |a'| |a'|^T) |M|^T and |M| sum_accept w |a'| sum_k (|ci_k| + |q_k|) |ni_k|
+      taps                           per accepted pixel: number of taps with non-zero weight that hold a valid depth
+      taps_in_image                  per accepted pixel: number of taps inside the image"""
+    p = dict(DEFAULT_PRM)
+    p.update(prm or {})
+    Ti, Tj = np.asarray(Ti, np.float64), np.asarray(Tj, np.float64)
+    Tinv_i = np.linalg.inv(Ti) if Tinv_i is None else np.asarray(Tinv_i, np.float64)
+    fx, fy, cx, cy = [float(v) for v in intr]
+    cs4 = campos[1].reshape(-1, 4).astype(np.float64)
+    ns4 = normals[1].reshape(-1, 4).astype(np.float64)
+    H, W = campos[0].shape[:2]
+    dmin, dmax = p["depth_min"], p["depth_max"]
+
+    def gate_gt(x, thr):        # x > thr:  (+1 passes by the margin, -1 fails by the margin, 0 inside the margin)
+        return np.where(x > thr + eps, 1, np.where(x < thr - eps, -1, 0))
+
+    def gate_lt(x, thr):
+        return -gate_gt(x, thr)
+
+    gates = [gate_gt(cs4[:, 2], dmin), gate_lt(cs4[:, 2], dmax)]
+    Tij = Tinv_i @ Tj
+    cs = cs4[:, :3]
+    q = cs @ Tij[:3, :3].T + Tij[:3, 3]
+    nq = ns4[:, :3] @ Tij[:3, :3].T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = q[:, 0] * fx / q[:, 2] + cx
+        v = q[:, 1] * fy / q[:, 2] + cy
+    fin = np.isfinite(u) & np.isfinite(v)
+    u, v = np.where(fin, u, -1e9), np.where(fin, v, -1e9)
+    # rounded coordinate inside the image  <=>  -0.5 < u < W - 0.5  (round half away from zero; the kernel's form of the test)
+    gates += [gate_gt(u, -0.5), gate_lt(u, W - 0.5), gate_gt(v, -0.5), gate_lt(v, H - 0.5)]
+    alive = np.all(np.stack(gates) >= 0, 0)                       # not decisively rejected so far: the taps are defined
+    u, v = np.where(alive, u, 0.0), np.where(alive, v, 0.0)
+    near_int = (np.abs(u - np.rint(u)) < eps) | (np.abs(v - np.rint(v)) < eps)
+    vc, ci = ONP.bilinear4(campos[0], u, v)
+    vn, ni = ONP.bilinear4(normals[0], u, v)
+    tap_ok = vc & vn
+    ci, ni = np.where(tap_ok[:, None], ci, 0.0), np.where(tap_ok[:, None], ni, 0.0)
+    gates += [np.where(tap_ok, 1, -1), gate_gt(ci[:, 2], dmin), gate_lt(ci[:, 2], dmax)]
+    dist = np.linalg.norm(q - ci[:, :3], axis=1)
+    dn = (nq * ni[:, :3]).sum(1)
+    dthr = p["dense_dist_thresh"]
+    gates += [np.where(dist <= dthr * (1 - eps), 1, np.where(dist > dthr * (1 + eps), -1, 0)),
+              np.where(dn >= p["dense_normal_thresh"] + eps, 1, np.where(dn < p["dense_normal_thresh"] - eps, -1, 0))]
+    G = np.stack(gates)
+    rejected = np.any(G < 0, 0)
+    accept = np.all(G > 0, 0) & ~near_int
+    border = ~rejected & ~accept
+
+    res = ((ci[:, :3] - q) * ni[:, :3]).sum(1)
+    wgt = p["weight_dense_depth"] * ONP.huber_w(res * res, p["robust_delta"])
+    w_world = cs @ Tj[:3, :3].T + Tj[:3, 3]
+    n_w = ni[:, :3] @ Ti[:3, :3].T
+    a_all = np.concatenate([-n_w, np.cross(n_w, w_world)], 1)
+    a, wa, ra = a_all[accept], wgt[accept], res[accept]
+    S = (a * wa[:, None]).T @ a
+    g = (a * (wa * ra)[:, None]).sum(0)
+    ab, wb, rb = np.abs(a_all[border]), wgt[border], np.abs(res[border])
+    bud_S = (ab * wb[:, None]).T @ ab
+    bud_g = (ab * (wb * rb)[:, None]).sum(0)
+    ac = np.abs(np.concatenate([-ni[:, :3], np.cross(ni[:, :3], q)], 1)[accept])          # |a'|, camera frame
+    Mabs = np.abs(congruence(Ti))
+    sc_S = Mabs @ ((ac * wa[:, None]).T @ ac) @ Mabs.T
+    # the residual (ci - q) . ni is a difference of ~1 m points: its fp32 error is a round-off of |ci| + |q|, not of |res|
+    rs = ((np.abs(ci[:, :3]) + np.abs(q)) * np.abs(ni[:, :3])).sum(1)[accept]
+    sc_g = Mabs @ (ac * (wa * rs)[:, None]).sum(0)
+
+    # tap census of the accepted pixels
+    x0, y0 = np.floor(u).astype(np.int64), np.floor(v).astype(np.int64)
+    al, be = u - x0, v - y0
+    zt = campos[0][..., 2].astype(np.float64)
+    taps = np.zeros(u.shape[0], np.int64)
+    taps_in = np.zeros(u.shape[0], np.int64)
+    for dx, dy, wt in ((0, 0, (1 - al) * (1 - be)), (1, 0, al * (1 - be)), (0, 1, (1 - al) * be), (1, 1, al * be)):
+        x, y = x0 + dx, y0 + dy
+        inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+        z = zt[np.clip(y, 0, H - 1), np.clip(x, 0, W - 1)]
+        taps_in += inside
+        taps += inside & (wt > 0) & (z > dmin)
+    return dict(S=S, g=g, count=int(accept.sum()), borderline=int(border.sum()), bud_S=bud_S, bud_g=bud_g, sc_S=sc_S, sc_g=sc_g,
+                taps=taps[accept], taps_in_image=taps_in[accept], accept_mask=accept)
+
+
+def record27(S, g):
+    """(S, g) -> the 27 sums of a traced dense-pair record: 21 upper-triangle entries of S, then g."""
+    return np.concatenate([np.array([S[r, c] for r, c in TRI]), np.asarray(g)])
+
+
+def dense_normalised_error(rec, ref):
+    """(eS, eg): max over the 21 sums of S, and over the 6 of g, of (|rec - ref| - Bud) / Sc for one record against dense_pair_ref's
+    dict; an entry whose scale is zero must match the reference within the budget exactly (inf otherwise)."""
+    d = np.abs(np.asarray(rec[:27], np.float64) - record27(ref["S"], ref["g"])) - record27(ref["bud_S"], ref["bud_g"])
+    sc = record27(ref["sc_S"], ref["sc_g"])
+    out = np.where(d <= 0, 0.0, np.where(sc > 0, d / np.where(sc > 0, sc, 1.0), np.inf))
+    return float(out[:21].max()), float(out[21:].max())
+
+
+# ---- sparse ------------------------------------------------------------------------------------------------------------
+def _cross_abs(a, b):
+    """entrywise bound of |a x b| from |a|, |b|"""
+    return np.stack([a[:, 1] * b[:, 2] + a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] + a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] + a[:, 1] * b[:, 0]], 1)
+
+
+def _jblk(w, absolute=False):
+    n = w.shape[0]
+    s = 1.0 if absolute else -1.0
+    J = np.zeros((n, 3, 6))
+    J[:, :, :3] = np.eye(3)
+    J[:, 0, 4], J[:, 0, 5] = w[:, 2], s * w[:, 1]
+    J[:, 1, 3], J[:, 1, 5] = s * w[:, 2], w[:, 0]
+    J[:, 2, 3], J[:, 2, 4] = w[:, 1], s * w[:, 0]
+    return J
+
+
+def sparse_system(corr, T, prm=None):
+    """fp64 A [6N,6N], b [6N], Mdiag [6N] of the feature term at the matrices T [N,4,4] (taken as exact), in oracle_np.solve's
+    [trans, rot] layout and with its formulas, plus their round-off scales sc_A, sc_b, sc_M: the same sums with every factor
+    replaced by its absolute value, a world point w = R p + t by |R| |p| + |t| and a residual r = w_i - w_j by the sum of both."""
+    p = dict(DEFAULT_PRM)
+    p.update(prm or {})
+    T = np.asarray(T, np.float64)
+    N = T.shape[0]
+    dim = 6 * N
+    ws = p["weight_sparse"]
+    valid = corr["imgIdx_i"] != 0xFFFFFFFF
+    ci, cj = corr["imgIdx_i"][valid].astype(np.int64), corr["imgIdx_j"][valid].astype(np.int64)
+    pi, pj = corr["pos_i"][valid].astype(np.float64), corr["pos_j"][valid].astype(np.float64)
+    A = np.zeros((dim, dim)); b = np.zeros(dim); Md = np.zeros(dim)
+    sA = np.zeros((dim, dim)); sb = np.zeros(dim); sM = np.zeros(dim)
+    if ws > 0 and ci.size:
+        wi = np.einsum("nab,nb->na", T[ci, :3, :3], pi) + T[ci, :3, 3]
+        wj = np.einsum("nab,nb->na", T[cj, :3, :3], pj) + T[cj, :3, 3]
+        Wi = np.einsum("nab,nb->na", np.abs(T[ci, :3, :3]), np.abs(pi)) + np.abs(T[ci, :3, 3])
+        Wj = np.einsum("nab,nb->na", np.abs(T[cj, :3, :3]), np.abs(pj)) + np.abs(T[cj, :3, 3])
+        r, Rs = wi - wj, Wi + Wj
+        rho = ONP.huber_w((r * r).sum(1), p["robust_delta"])
+        sq = lambda w: np.stack([w[:, 1]**2 + w[:, 2]**2, w[:, 0]**2 + w[:, 2]**2, w[:, 0]**2 + w[:, 1]**2], 1)
+        for k in range(1, N):
+            for (sel, w, Wa, sign) in ((ci == k, wi, Wi, 1.0), (cj == k, wj, Wj, -1.0)):
+                if not sel.any():
+                    continue
+                rh = rho[sel]
+                b[6 * k:6 * k + 3] += -ws * sign * (rh[:, None] * r[sel]).sum(0)
+                b[6 * k + 3:6 * k + 6] += -ws * sign * (rh[:, None] * np.cross(w[sel], r[sel])).sum(0)
+                sb[6 * k:6 * k + 3] += ws * (rh[:, None] * Rs[sel]).sum(0)
+                sb[6 * k + 3:6 * k + 6] += ws * (rh[:, None] * _cross_abs(Wa[sel], Rs[sel])).sum(0)
+                Md[6 * k:6 * k + 3] += rh.sum()
+                Md[6 * k + 3:6 * k + 6] += (rh[:, None] * sq(w[sel])).sum(0)
+                sM[6 * k:6 * k + 3] += rh.sum()
+                sM[6 * k + 3:6 * k + 6] += (rh[:, None] * sq(Wa[sel])).sum(0)
+        Ji, Jj, Ai, Aj = _jblk(wi), _jblk(wj), _jblk(Wi, True), _jblk(Wj, True)
+        for (a_, b_) in sorted(set(zip(ci.tolist(), cj.tolist()))):
+            sel = (ci == a_) & (cj == b_)
+            for (M_, Ja, Jb, sg) in ((A, Ji, Jj, 1.0), (sA, Ai, Aj, -1.0)):
+                if a_ > 0:
+                    M_[6 * a_:6 * a_ + 6, 6 * a_:6 * a_ + 6] += ws * np.einsum("nka,nkb->ab", Ja[sel], Ja[sel])
+                if b_ > 0:
+                    M_[6 * b_:6 * b_ + 6, 6 * b_:6 * b_ + 6] += ws * np.einsum("nka,nkb->ab", Jb[sel], Jb[sel])
+                if a_ > 0 and b_ > 0:
+                    X = ws * np.einsum("nka,nkb->ab", Ja[sel], Jb[sel])
+                    M_[6 * a_:6 * a_ + 6, 6 * b_:6 * b_ + 6] -= sg * X; M_[6 * b_:6 * b_ + 6, 6 * a_:6 * a_ + 6] -= sg * X.T
+    return dict(A=A, b=b, Mdiag=Md, sc_A=sA, sc_b=sb, sc_M=sM)
+
+
+def precond_ref(Mdiag, sc_M):
+    """The Jacobi preconditioner with its `> 1e-6` guard and its round-off scale |d(1/M)| = sc_M / M^2 (0 where the guard holds)."""
+    on = Mdiag > ONP.EPS
+    safe = np.where(on, Mdiag, 1.0)
+    return np.where(on, 1.0 / safe, 1.0), np.where(on, sc_M / safe**2, 0.0)
+
+
+def to_rot_trans(v6N):
+    """[trans, rot] per frame (oracle_np) -> [N, 6] in the traced (rot, trans) order of rhs / precond."""
+    v = np.asarray(v6N).reshape(-1, 6)
+    return np.concatenate([v[:, 3:], v[:, :3]], 1)
+
+
+def normalised(diff_abs, scale):
+    """max |diff| / scale; an entry with zero scale must be exact."""
+    diff_abs, scale = np.asarray(diff_abs, np.float64), np.asarray(scale, np.float64)
+    out = np.where(diff_abs == 0, 0.0, np.where(scale > 0, diff_abs / np.where(scale > 0, scale, 1.0), np.inf))
+    return float(out.max()) if out.size else 0.0
+
+
+# ---- the inputs of tests/test_gpu_sweep_sums.py (checked on the CPU by tests/test_sweep_ref.py) -------------------------------
+# Rendered scenes: synthetic.make_problem(3, 40, seed) at a frame size whose cache (frame / 4) has the wanted shape, intrinsics scaled
+# with the frame.  The seeds are those at which NO pixel of any ordered pair is borderline (except the full-size scene), so the count
+# bracket of the GPU test is an equality there.
+#   name: (H, W, background, seed, K[0,1] of the full-resolution K)
+RENDERED = {
+    "bg32x24": (96, 128, True, 36, 0.0),            # three full workgroups; 4 x 3 blocks of 8 x 8 (block walk)
+    "skew32x24": (96, 128, True, 23, 3.7),          # general back-projection of the compact cache
+    "bg50x30": (120, 200, True, 21, 0.0),           # 1500 pixels, not a multiple of 256; step_x = 6, step_y = 5
+    "bg275x8": (32, 1100, True, 25, 0.0),           # wider than a workgroup, step_y = 0
+    "mask80x60": (240, 320, False, 21, 0.0),        # object only: valid-pixel lists (the 128 x 96 masked frame has 9 - 16 accepts: too few)
+    "bg160x120": (480, 640, True, 21, 0.0),         # the product's shape
+}
+# Hand-made scenes: one smooth surface seen from three nearly identical poses (all frames share one depth image, so a source pixel
+# lands within a fraction of a pixel of the target pixel of the same index).
+MADE = ("smooth13x9", "hole32x24", "edge32x24")
+SCENES = tuple(RENDERED) + MADE
+PAIRS_FWD = ((0, 1), (0, 2), (1, 2))
+PAIRS_REV = ((1, 0), (2, 0), (2, 1))
+_scene_cache = {}
+
+
+def _made_scene(name, S):
+    H, W = (37, 53) if name == "smooth13x9" else (96, 128)
+    Hd, Wd = H // 4, W // 4
+    K = S.NOCS_K.astype(np.float64).copy()
+    K[0] *= W / 640.0; K[1] *= H / 480.0
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    xn, yn = xs / W - 0.5, ys / H - 0.5
+    z0 = 0.3 if name == "smooth13x9" else 0.8        # (13 x 9: the cache's nearest-neighbour sampling misregisters by a fraction of a 5 cm pixel at 0.8 m)
+    z = z0 + 0.06 * xn - 0.04 * yn + 0.10 * (xn * xn + yn * yn)
+    # unit normals of the surface z(x, y) in camera coordinates, facing the camera
+    X, Y = (xs - K[0, 2]) / K[0, 0] * z, (ys - K[1, 2]) / K[1, 1] * z
+    P = np.stack([X, Y, z], -1)
+    du, dv = np.gradient(P, axis=1), np.gradient(P, axis=0)
+    n = np.cross(dv, du)
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    n *= -np.sign(n[..., 2:3])
+    depth = np.repeat(z[None], 3, 0).astype(np.float32)
+    normals = np.zeros((3, H, W, 4), np.float32)
+    normals[..., :3] = n
+    xi, yi = S.cache_source_pixels(H, W, Hd, Wd)
+
+    def cache_mask(frame, mask_d):      # zero the full-resolution pixels that the cache pixels in mask_d [Hd, Wd] sample
+        full = np.zeros((H, W), bool)
+        full[np.ix_(yi, xi)] = mask_d
+        depth[frame][full] = 0.0
+        normals[frame][full] = 0.0
+
+    fxc = K[0, 0] * Wd / W                # cache focal length in pixels
+    if name == "hole32x24":
+        hole = np.zeros((Hd, Wd), bool)
+        # small holes of three kinds on a lattice: single pixels (a neighbour blends 3 valid taps), 2 x 2 blocks (2) and L-shaped triples (1).
+        # The cache samples the frame at rounded positions, so a source pixel lands up to 1/8 pixel off the target pixel of the same index
+        # and the weight of a zero tap varies from hole to hole; the pixels where it stays under ~2 % pass the 2 cm gate.
+        for cy_ in range(4):
+            for cx_ in range(6):
+                y_, x_, kind = 2 + 5 * cy_, 2 + 5 * cx_, (cy_ + cx_) % 3
+                hole[y_, x_] = True
+                if kind >= 1:
+                    hole[y_ + 1, x_] = hole[y_, x_ + 1] = True
+                if kind == 1:
+                    hole[y_ + 1, x_ + 1] = True
+        cache_mask(0, hole)
+        shifts = [(0, 0, 0), (0.008, 0.008, 0.0004), (-0.008, 0.008, -0.0003)]      # (pixels, pixels, metres)
+    elif name == "edge32x24":
+        one = np.ones((Hd, Wd), bool)
+        one[11, 17] = False
+        cache_mask(1, one)                 # frame 1: exactly one valid pixel
+        cache_mask(2, np.ones((Hd, Wd), bool))      # frame 2: none
+        shifts = [(0, 0, 0), (0.3, 0.2, 0.001), (0.1, -0.2, 0.002)]
+    else:
+        shifts = [(0, 0, 0), (0.05, 0.03, 0.003), (-0.045, 0.065, -0.004)]           # residuals on both sides of the 5 mm Huber knee
+    T0 = S.orbit_pose(0.3)
+    poses = np.zeros((3, 4, 4), np.float32)
+    for k, (sx, sy, tz) in enumerate(shifts):
+        D = S.se3_exp(np.array([0.0002, -0.0003, 0.0004]) * k if name == "smooth13x9" else np.zeros(3), np.array([sx * z0 / fxc, sy * z0 / fxc, tz]))
+        poses[k] = (T0 @ D).astype(np.float32)
+    rng = np.random.default_rng(5)
+    corr = np.zeros(3 * 40, ENTRYJ)
+    for q, (i, j) in enumerate(PAIRS_FWD):
+        pm = rng.uniform(-0.1, 0.1, (40, 3))
+        inv_i, inv_j = np.linalg.inv(poses[i].astype(np.float64)), np.linalg.inv(poses[j].astype(np.float64))
+        blk = corr[40 * q:40 * q + 40]
+        blk["imgIdx_i"], blk["imgIdx_j"] = i, j
+        blk["pos_i"] = pm @ inv_i[:3, :3].T + inv_i[:3, 3] + rng.normal(scale=0.001, size=(40, 3))
+        blk["pos_j"] = pm @ inv_j[:3, :3].T + inv_j[:3, 3] + rng.normal(scale=0.001, size=(40, 3))
+    return K.astype(np.float32), H, W, depth, normals, poses, corr
+
+
+
+def scene(name):
+    """dict(K, H, W, campos [3,Hd,Wd,4], normals, intr, poses [3,4,4] f32, corr) -- the float4 cache is the oracle's (bit-identical
+    to the device's cache builder, test_gpu_parity.test_frame_cache_bit_exact)."""
+    if name in _scene_cache:
+        return _scene_cache[name]
+    from bundletrack_amd import synthetic as S
+    from oracle import oracle as O
+    if name in RENDERED:
+        H, W, bg, seed, skew = RENDERED[name]
+        K = S.NOCS_K.copy()
+        K[0] *= W / 640.0; K[1] *= H / 480.0
+        K[0, 1] = skew * W / 640.0
+        pb = S.make_problem(3, 40, seed, background=bg, H=H, W=W, K=K)
+        K, depth, normals, poses, corr = pb.K, pb.depth, pb.normals, pb.poses_init, pb.corr
+    else:
+        K, H, W, depth, normals, poses, corr = _made_scene(name, S)
+    caches = [O.build_cache(depth[k], normals[k], K, 4.0) for k in range(3)]
+    sc = dict(name=name, K=np.asarray(K, np.float32), H=H, W=W, campos=np.stack([c["campos"] for c in caches]), normals=np.stack([c["normals"] for c in caches]),
+              intr=caches[0]["intr"], poses=np.ascontiguousarray(poses, np.float32), corr=np.ascontiguousarray(corr, ENTRYJ),
+              n_valid=[c["n_valid"] for c in caches])
+    _scene_cache[name] = sc
+    return sc
+
+
+def oracle_matrices(poses):
+    """T = Exp(Log(pose)) and its inverse as the fp32 CPU oracle forms them."""
+    from oracle import oracle as O
+    T = np.stack([O.pose_to_matrix(*O.matrix_to_pose(p)) for p in poses])
+    return T, np.stack([O.mat4_inverse(t) for t in T])
+
+
+def scene_refs(sc, T, Tinv, pairs):
+    """dense_pair_ref of every (target, source) in `pairs` at the matrices T, Tinv [3,4,4]."""
+    return [dense_pair_ref(sc["campos"][[i, j]], sc["normals"][[i, j]], sc["intr"], T[i], T[j], Tinv[i]) for (i, j) in pairs]
+
+
+def oracle_dense_records(sc, pairs, accum_mode):
+    """The fp32 CPU oracle's 28-float record of every pair: S and g from dense_JtJ / dense_Jtr of the two-frame window (target, source)
+    with the target fixed, first linearisation (dense_Jtr of the source block is +g: test_sweep_ref.test_oracle_record_layout)."""
+    from oracle import oracle as O
+    out = []
+    for (i, j) in pairs:
+        tr = O.solve(sc["campos"][[i, j]], sc["normals"][[i, j]], sc["intr"], sc["corr"][:0], sc["poses"][[i, j]],
+                     params=O.default_params(n_gn_iters=1, accum_mode=accum_mode))
+        Sx, gx = tr.dense_JtJ[0][6:, 6:].astype(np.float64), tr.dense_Jtr[0][6:].astype(np.float64)
+        out.append(np.concatenate([record27(Sx, gx), [float(tr.dense_count[0][0])]]))
+    return out
+
+
+
+
+def oracle_dense_floor(names=SCENES):
+    """(floor_S, floor_g, per scene): max over scenes, ordered pairs and both accumulation modes of the oracle's normalised error
+    (S entries, g entries) against the fp64 reference evaluated at the oracle's own matrices."""
+    per = {}
+    for name in names:
+        sc = scene(name)
+        T, Tinv = oracle_matrices(sc["poses"])
+        pairs = PAIRS_FWD + PAIRS_REV
+        refs = scene_refs(sc, T, Tinv, pairs)
+        worst = np.zeros(2)
+        for mode in (0, 1):
+            for rec, ref in zip(oracle_dense_records(sc, pairs, mode), refs):
+                assert ref["count"] <= rec[27] <= ref["count"] + ref["borderline"], (name, mode, rec[27], ref["count"], ref["borderline"])
+                worst = np.maximum(worst, dense_normalised_error(rec, ref))
+        per[name] = worst
+    return max(v[0] for v in per.values()), max(v[1] for v in per.values()), per
+
+
+# ---- sparse inputs ---------------------------------------------------------------------------------------------------------
+SEGMENTS = {2: (1000,), 3: (65, 1000, 256), 5: (0, 1, 63, 64, 65, 255, 256, 257, 1000, 513)}      # entries per pair, pair-major
+SPARSE_CHUNKS = (1, 2, 4, 7)
+
+
+def sparse_case(N):
+    """(corr, poses): one window of N frames whose pair segments have the lengths SEGMENTS[N] (pair-major, every slot counted),
+    with invalid entries (imgIdx_i = 0xFFFFFFFF) at segment starts and ends and on one side (alternating) of every chunk boundary of
+    SPARSE_CHUNKS, noise of 1 mm and 5 % of the residuals planted at 2 - 5 cm (beyond the 5 mm Huber knee)."""
+    from bundletrack_amd import synthetic as S
+    pb = S.make_problem(N, 8, seed=70 + N, background=False, full_res=False)
+    rng = np.random.default_rng(700 + N)
+    inv = np.linalg.inv(pb.poses_gt)
+    blocks = []
+    pairs = [(i, j) for i in range(N) for j in range(i + 1, N)]
+    for (i, j), m in zip(pairs, SEGMENTS[N]):
+        blk = np.zeros(m, ENTRYJ)
+        pts, _ = S._sample_surface(rng, m)
+        pi = pts @ inv[i, :3, :3].T + inv[i, :3, 3] + rng.normal(scale=0.001, size=(m, 3))
+        pj = pts @ inv[j, :3, :3].T + inv[j, :3, 3] + rng.normal(scale=0.001, size=(m, 3))
+        out = rng.random(m) < 0.05
+        d = rng.normal(size=(m, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        pj[out] += (d * rng.uniform(0.02, 0.05, (m, 1)))[out]
+        blk["imgIdx_i"], blk["imgIdx_j"], blk["pos_i"], blk["pos_j"] = i, j, pi, pj
+        if m >= 63:
+            bad = {0, m - 1}
+            # one side of every chunk boundary is invalid and the other valid, alternating: an entry lost on either side of a boundary
+            # is a VALID one for some (segment, chunk count)
+            for c in SPARSE_CHUNKS:
+                per = -(-m // c)
+                for q in range(1, c):
+                    bad.add(min(m - 1, per * q - (q + c) % 2))
+            bad -= {m // 3}                      # (never a whole short segment)
+            blk["imgIdx_i"][sorted(bad)] = 0xFFFFFFFF
+            blk["pos_i"][sorted(bad)[::2]] = np.nan          # an invalid slot's payload may be anything
+        blocks.append(blk)
+    return np.concatenate(blocks), pb.poses_init
+
+
+def sparse_offsets(N):
+    return np.concatenate([[0], np.cumsum(SEGMENTS[N])]).astype(np.uint32)
+
+
+def sparse_normalised(rhs, precond, A, sp):
+    """(e_rhs, e_precond, e_A): an implementation's traced rhs / precond [N, 6] in (rot, trans) order (frames 1 .. N - 1) and, where
+    given, its A [6N, 6N] in [trans, rot] order against sparse_system's dict, in units of the absolute-value scales."""
+    M, scM = precond_ref(sp["Mdiag"], sp["sc_M"])
+    e_r = normalised(np.abs(np.asarray(rhs, np.float64) - to_rot_trans(sp["b"]))[1:], to_rot_trans(sp["sc_b"])[1:])
+    e_p = normalised(np.abs(np.asarray(precond, np.float64) - to_rot_trans(M))[1:], to_rot_trans(scM)[1:])
+    e_A = normalised(np.abs(np.asarray(A, np.float64) - sp["A"]), sp["sc_A"]) if A is not None else 0.0
+    return e_r, e_p, e_A
+
+
+def oracle_sparse_floor(corr, poses):
+    """(rhs, precond, A) normalised errors of the fp32 CPU oracle's first linearisation (feature term only) against the fp64 system at the
+    oracle's own matrices.  The oracle applies J^T J matrix-free, so its A is read off column by column with unit vectors (sparse_apply)."""
+    from oracle import oracle as O
+    N = poses.shape[0]
+    T, _ = oracle_matrices(poses)
+    sp = sparse_system(corr, T)
+    clean = corr.copy()
+    clean["pos_i"][corr["imgIdx_i"] == 0xFFFFFFFF] = 0
+    worst = np.zeros(3)
+    for mode in (0, 1):
+        prm = O.default_params(n_gn_iters=1, weight_dense_depth=0.0, accum_mode=mode)
+        tr = O.solve(np.zeros((N, 2, 2, 4), np.float32), np.zeros((N, 2, 2, 4), np.float32), np.array([1, 1, 0, 0], np.float32), clean, poses, params=prm)
+        A = np.zeros((6 * N, 6 * N))
+        for k in range(6, 6 * N):                      # column k in [trans, rot] order; sparse_apply speaks (rot, trans)
+            e = np.zeros(6 * N, np.float32)
+            e[k] = 1
+            col = O.sparse_apply(clean, T, to_rot_trans(e), params=prm).astype(np.float64)
+            A[:, k] = np.concatenate([col[:, 3:], col[:, :3]], 1).reshape(-1)
+        A[:6] = 0
+        worst = np.maximum(worst, sparse_normalised(tr.rhs[0], tr.precond[0], A, sp))
+    return tuple(float(w) for w in worst)

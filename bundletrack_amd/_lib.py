@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = [
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_mask_params_default", "btba_apply_masks",
     "btba_detector_params_default", "btba_detector_transform", "btba_detector_inputs", "btba_detector_keypoints_to_image",
-    "btba_pose_errors",
+    "btba_pose_errors", "btba_nocs_params_default", "btba_nocs_errors",
     "btba_mappoints_create", "btba_mappoints_destroy", "btba_mappoints_register_frame", "btba_mappoints_forget_frame", "btba_mappoints_export",
     "btba_corres_params_default", "btba_corres_chain_capacity", "btba_corres_chain",
     "btba_window_layout", "btba_marshal_windows", "btba_procrustes_pairs",
@@ -81,6 +81,12 @@ class MaskParams(C.Structure):
 class DetectorParams(C.Structure):
     """btba_detector_params (include/btba.h)."""
     _fields_ = [("out_size", C.c_int32)]
+
+
+class NocsParams(C.Structure):
+    """btba_nocs_params (include/btba.h)."""
+    _fields_ = [("rot_thresh_deg", C.c_double), ("shift_thresh", C.c_double), ("iou_thresh", C.c_double), ("n_sym_steps", C.c_int32),
+                ("flip_z180_pred", C.c_int32), ("normalize_columns", C.c_int32), ("clamp_acos", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -258,6 +264,10 @@ def lib() -> C.CDLL:
                                                        C.c_void_p]
         L.btba_pose_errors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
+        L.btba_nocs_params_default.argtypes = [C.POINTER(NocsParams)]
+        L.btba_nocs_params_default.restype = None
+        L.btba_nocs_errors.argtypes = [C.c_void_p, C.POINTER(NocsParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_mappoints_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.btba_mappoints_destroy.argtypes = [C.c_void_p]
         L.btba_mappoints_destroy.restype = None
@@ -318,6 +328,11 @@ def mask_params(**kw) -> MaskParams:
 def detector_params(**kw) -> DetectorParams:
     """btba_detector_params_default with fields overridden by keyword."""
     return _params(DetectorParams, "btba_detector_params_default", kw)
+
+
+def nocs_params(**kw) -> NocsParams:
+    """btba_nocs_params_default with fields overridden by keyword."""
+    return _params(NocsParams, "btba_nocs_params_default", kw)
 
 
 def declared_symbols() -> list[str]:

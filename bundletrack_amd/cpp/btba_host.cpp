@@ -157,6 +157,80 @@ void poseErrors(btba_workspace *ws, const std::vector<const float *> &models_dev
     if (rc != BTBA_OK) throw Error(rc, "btba_pose_errors");
 }
 
+btba_nocs_params nocsParams()
+{
+    btba_nocs_params p;
+    btba_nocs_params_default(&p);
+    return p;
+}
+
+void nocsErrors(btba_workspace *ws, const btba_nocs_params &params, const std::vector<NocsBox> &boxes, const std::vector<int32_t> &class_id,
+                const std::vector<int32_t> &handle_visible, const std::vector<int32_t> &box_index, const std::vector<Matrix4d> &poses_pred,
+                const std::vector<Matrix4d> &poses_gt, std::vector<double> &theta_deg, std::vector<double> &shift, std::vector<double> &iou)
+{
+    const size_t n = class_id.size();
+    if (box_index.size() != n || poses_pred.size() != n || poses_gt.size() != n || (!handle_visible.empty() && handle_visible.size() != n))
+        throw Error(BTBA_EINVAL, "nocsErrors: sizes differ");
+    std::vector<double> pp(16 * n), pg(16 * n);                   // row-major, as the C ABI takes them
+    for (size_t e = 0; e < n; e++)
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) {
+                pp[16 * e + 4 * r + c] = poses_pred[e](r, c);
+                pg[16 * e + 4 * r + c] = poses_gt[e](r, c);
+            }
+    theta_deg.assign(n, 0.0);
+    shift.assign(n, 0.0);
+    iou.assign(n, 0.0);
+    const int rc = btba_nocs_errors(ws, &params, /*device_resident=*/0, (int)boxes.size(), boxes.empty() ? nullptr : boxes[0].data(), (int)n,
+                                    class_id.data(), handle_visible.empty() ? nullptr : handle_visible.data(), box_index.data(), pp.data(),
+                                    pg.data(), theta_deg.data(), shift.data(), iou.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_nocs_errors");
+}
+
+NocsReport nocsReport(const std::vector<double> &theta_deg, const std::vector<double> &shift, const std::vector<double> &iou,
+                      const std::vector<int32_t> &class_id, const std::vector<int64_t> &n_listed, const btba_nocs_params &params)
+{
+    const size_t n = class_id.size();
+    if (theta_deg.size() != n || shift.size() != n || iou.size() != n || (!n_listed.empty() && n_listed.size() != 6))
+        throw Error(BTBA_EINVAL, "nocsReport: sizes differ");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    NocsReport rep;
+    double acc55 = 0.0, acc25 = 0.0, acc_rot = 0.0, acc_trans = 0.0;
+    for (int c = 1; c <= 6; c++) {
+        int64_t items = 0, in55 = 0, over = 0, n_rot = 0;
+        double sum_rot = 0.0, sum_trans = 0.0;
+        for (size_t e = 0; e < n; e++) {
+            if (class_id[e] != c) continue;
+            items++;
+            if (theta_deg[e] < params.rot_thresh_deg && shift[e] < params.shift_thresh) in55++;
+            if (iou[e] > params.iou_thresh) {
+                over++;
+                sum_trans += shift[e];
+                if (theta_deg[e] < 360.0) { sum_rot += theta_deg[e]; n_rot++; }
+            }
+        }
+        NocsRow &row = rep.cls[c - 1];
+        row.n = n_listed.empty() ? items : n_listed[c - 1];
+        rep.overall.n += row.n;
+        const double s55 = row.n ? (double)in55 / (double)row.n : nan, s25 = row.n ? (double)over / (double)row.n : nan;
+        row.rot_err_deg = n_rot ? sum_rot / (double)n_rot : nan;
+        row.trans_err = over ? sum_trans / (double)over : nan;
+        acc55 = acc55 + s55 / 6;
+        acc25 = acc25 + s25 / 6;
+        acc_rot = acc_rot + row.rot_err_deg / 6;
+        acc_trans = acc_trans + row.trans_err / 6;
+        row.acc_5deg5cm = s55 * 100;
+        row.acc_iou25 = s25 * 100;
+        row.trans_err_cm = row.trans_err / 10;
+    }
+    rep.overall.acc_5deg5cm = acc55 * 100;
+    rep.overall.acc_iou25 = acc25 * 100;
+    rep.overall.rot_err_deg = acc_rot;
+    rep.overall.trans_err = acc_trans;
+    rep.overall.trans_err_cm = acc_trans / 10;
+    return rep;
+}
+
 WindowLayout windowLayout(int n_frames, const std::vector<int32_t> &seg_counts, const std::vector<int32_t> &newframe_index, int min_fm_edges_newframe)
 {
     const int P = n_frames >= 2 ? n_frames * (n_frames - 1) / 2 : 0;

@@ -17,6 +17,7 @@
 // changes.  Only libbtba.so's C ABI (include/btba.h) is called: plain host C++ (g++), no
 // device code, no torch; HIP contributes the float4 / uchar4 pixel types only.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <deque>
 #include <functional>
@@ -38,6 +39,12 @@ struct Matrix4f {                      // Eigen::Matrix4f: column-major
     float &operator()(int r, int c) { return d[c * 4 + r]; }
     float operator()(int r, int c) const { return d[c * 4 + r]; }
     static Matrix4f Identity() { Matrix4f M{}; for (int k = 0; k < 4; k++) M(k, k) = 1.0f; return M; }
+};
+struct Matrix4d {                      // Eigen::Matrix4d: column-major
+    double d[16];
+    double &operator()(int r, int c) { return d[c * 4 + r]; }
+    double operator()(int r, int c) const { return d[c * 4 + r]; }
+    static Matrix4d Identity() { Matrix4d M{}; for (int k = 0; k < 4; k++) M(k, k) = 1.0; return M; }
 };
 struct Matrix3f {                      // Eigen::Matrix3f: column-major
     float d[9];
@@ -140,6 +147,23 @@ void keypointsToImage(btba_workspace *ws, const std::shared_ptr<Frame> &frame, c
 void poseErrors(btba_workspace *ws, const std::vector<const float *> &models_dev, const std::vector<int32_t> &n_pts,
                 const std::vector<int32_t> &model_index, const std::vector<Matrix4f> &poses_pred, const std::vector<Matrix4f> &poses_gt,
                 std::vector<float> &add, std::vector<float> &adds);
+
+// scripts/benchmark.py's per-frame figures (compute_RT_degree_cm_symmetry, compute_3d_iou_new as called at :262-272) on
+// btba_nocs_errors: item e scores poses_pred[e] against poses_gt[e] (object-in-camera, translation in the unit of
+// params.shift_thresh) as class class_id[e] (1 .. 6) with the box boxes[box_index[e]] (8 corner rows of 3, row-major).
+// handle_visible may be empty (all visible).  theta_deg, shift and iou are resized to the number of items.  Needs the GPU; synchronous.
+using NocsBox = std::array<double, 24>;
+btba_nocs_params nocsParams();                                                   // btba_nocs_params_default
+void nocsErrors(btba_workspace *ws, const btba_nocs_params &params, const std::vector<NocsBox> &boxes, const std::vector<int32_t> &class_id,
+                const std::vector<int32_t> &handle_visible, const std::vector<int32_t> &box_index, const std::vector<Matrix4d> &poses_pred,
+                const std::vector<Matrix4d> &poses_gt, std::vector<double> &theta_deg, std::vector<double> &shift, std::vector<double> &iou);
+// benchmark.py:276-319 for one experiment, the same arithmetic in the same order as bundletrack_amd/nocs_eval.py::nocs_report (the two
+// agree bit for bit): cls[c - 1] is the row of class c, overall the sum over the classes of (row value / 6).  n_listed: empty (each
+// class's number of items) or 6 counts, class 1 first (the reference's cls_num).  Host only.
+struct NocsRow { int64_t n = 0; double acc_5deg5cm = 0, acc_iou25 = 0, rot_err_deg = 0, trans_err = 0, trans_err_cm = 0; };
+struct NocsReport { NocsRow cls[6]; NocsRow overall; };
+NocsReport nocsReport(const std::vector<double> &theta_deg, const std::vector<double> &shift, const std::vector<double> &iou,
+                      const std::vector<int32_t> &class_id, const std::vector<int64_t> &n_listed, const btba_nocs_params &params);
 // Window assembly on the device (include/btba.h, "window assembly"): thin wrappers over the C ABI.
 // windowLayout (host-only): seg_counts[w * P + p] matches of canonical pair p of window w, newframe_index[w] -> the layout.
 // marshalWindows: the chain's device records + a device segment table uint32 [n_windows][P][2] = (first record, count) -> corr_dev,

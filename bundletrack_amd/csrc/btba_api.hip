@@ -29,6 +29,7 @@
 #include "btba_mask.hpp"
 #include "btba_detect.hpp"
 #include "btba_eval.hpp"
+#include "btba_nocs.hpp"
 #include "btba_mappoints.hpp"
 #include "btba_window.hpp"
 
@@ -205,6 +206,7 @@ struct btba_workspace {
     DevBuf match;                                           // btba_match_pairs: tables, norms, candidate lists, selections, counts, host-form staging
     DevBuf mask;                                            // btba_apply_masks: labels, counts, argmax keys, row extents, spans, hull stacks, ROI slots
     DevBuf eval;                                            // btba_pose_errors: chunk tables, host-form poses and outputs, per-point minima
+    DevBuf nocs;                                            // btba_nocs_errors: item words, boxes, step table, host-form poses and outputs
     DevBuf corres;                                          // btba_corres_chain: frame / pair tables, NN output, working lists, per-pair words
     DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
     uint64_t ransac_u_seed = 0;
@@ -2516,6 +2518,84 @@ int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, cons
         if (!dev) {
             HIP_TRY(hipMemcpyAsync(add_out + e0, oa, sizeof(float) * ne, hipMemcpyDeviceToHost, ws->stream));
             HIP_TRY(hipMemcpyAsync(adds_out + e0, os, sizeof(float) * ne, hipMemcpyDeviceToHost, ws->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host tables above may go
+    return BTBA_OK;
+}
+
+void btba_nocs_params_default(btba_nocs_params *p)
+{
+    if (!p) return;
+    p->rot_thresh_deg = 5.0;
+    p->shift_thresh = 50.0;
+    p->iou_thresh = 0.25;
+    p->n_sym_steps = 20;
+    p->flip_z180_pred = 1;
+    p->normalize_columns = 1;
+    p->clamp_acos = 0;
+}
+
+int btba_nocs_errors(btba_workspace *ws, const btba_nocs_params *params_in, int device_resident, int n_boxes, const double *boxes,
+                     int n_evals, const int32_t *class_id, const int32_t *handle_visible, const int32_t *box_index,
+                     const double *poses_pred, const double *poses_gt, double *theta_deg_out, double *shift_out, double *iou_out)
+{
+    // every argument is checked before the first HIP call
+    btba_nocs_params prm;
+    if (params_in) prm = *params_in; else btba_nocs_params_default(&prm);
+    if (!ws || !boxes || n_boxes < 1 || n_boxes > (1 << 30) || n_evals < 0 || prm.n_sym_steps < 1 || prm.n_sym_steps > kNocsMaxSteps) return BTBA_EINVAL;
+    if (n_evals == 0) return BTBA_OK;
+    if (!class_id || !box_index || !poses_pred || !poses_gt || !theta_deg_out || !shift_out || !iou_out) return BTBA_EINVAL;
+    const bool dev = device_resident != 0;
+    if (dev && (misaligned(poses_pred, 8) || misaligned(poses_gt, 8) || misaligned(theta_deg_out, 8) || misaligned(shift_out, 8) || misaligned(iou_out, 8)))
+        return BTBA_EINVAL;
+    std::vector<int32_t> meta(n_evals);                     // box_index << 1 | rotation-symmetric
+    for (int e = 0; e < n_evals; e++) {
+        const int32_t c = class_id[e];
+        if (c < 1 || c > 6 || box_index[e] < 0 || box_index[e] >= n_boxes) return BTBA_EINVAL;
+        const bool sym = c == 1 || c == 2 || c == 4 || (c == 6 && handle_visible && handle_visible[e] == 0);
+        meta[e] = box_index[e] << 1 | (sym ? 1 : 0);
+    }
+    double table[2 * kNocsMaxSteps] = {};                   // (cos, sin) of ((2 pi) i) / n_sym_steps: the bits every item rotates by
+    for (int i = 0; i < prm.n_sym_steps; i++) {
+        const double a = 2.0 * M_PI * (double)i / (double)prm.n_sym_steps;
+        table[2 * i] = std::cos(a);
+        table[2 * i + 1] = std::sin(a);
+    }
+    const int flags = (prm.flip_z180_pred ? kNocsFlip : 0) | (prm.normalize_columns ? kNocsNormalize : 0) | (prm.clamp_acos ? kNocsClamp : 0);
+    DeviceGuard device_guard(ws);
+
+    const int max_chunk = std::min(n_evals, kNocsChunkItems);
+    Scratch S;
+    const auto s_meta = S.add<int32_t>(max_chunk);
+    const auto s_box = S.add<double>(24 * (size_t)n_boxes);
+    const auto s_tab = S.add<double>(2 * kNocsMaxSteps);
+    const auto s_pp = S.add<double>(16 * (size_t)max_chunk, !dev), s_pg = S.add<double>(16 * (size_t)max_chunk, !dev);
+    const auto s_out = S.add<double>(3 * (size_t)max_chunk, !dev);
+    int rc = S.bind(ws->nocs);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(s_box, boxes, sizeof(double) * 24 * (size_t)n_boxes, hipMemcpyHostToDevice, ws->stream));
+    HIP_TRY(hipMemcpyAsync(s_tab, table, sizeof(table), hipMemcpyHostToDevice, ws->stream));
+    for (int e0 = 0; e0 < n_evals; e0 += kNocsChunkItems) {
+        const int ne = std::min(kNocsChunkItems, n_evals - e0);
+        const double *pp = poses_pred + 16 * (size_t)e0, *pg = poses_gt + 16 * (size_t)e0;
+        double *ot = theta_deg_out + e0, *os = shift_out + e0, *oi = iou_out + e0;
+        HIP_TRY(hipMemcpyAsync(s_meta, meta.data() + e0, sizeof(int32_t) * ne, hipMemcpyHostToDevice, ws->stream));
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(s_pp, pp, sizeof(double) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
+            HIP_TRY(hipMemcpyAsync(s_pg, pg, sizeof(double) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
+            pp = s_pp;
+            pg = s_pg;
+            ot = s_out;
+            os = ot + max_chunk;
+            oi = os + max_chunk;
+        }
+        k_nocs_errors<<<(ne + kNocsItems - 1) / kNocsItems, kNocsThreads, 0, ws->stream>>>(ne, s_meta, s_box, pp, pg, s_tab, prm.n_sym_steps, flags, ot, os, oi);
+        HIP_TRY(hipGetLastError());
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(theta_deg_out + e0, ot, sizeof(double) * ne, hipMemcpyDeviceToHost, ws->stream));
+            HIP_TRY(hipMemcpyAsync(shift_out + e0, os, sizeof(double) * ne, hipMemcpyDeviceToHost, ws->stream));
+            HIP_TRY(hipMemcpyAsync(iou_out + e0, oi, sizeof(double) * ne, hipMemcpyDeviceToHost, ws->stream));
         }
     }
     HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host tables above may go

@@ -675,6 +675,69 @@ BTBA_API int btba_pose_errors(btba_workspace *ws, int device_resident,
                               const float *poses_pred, const float *poses_gt,
                               float *add_out, float *adds_out);
 
+/* ---- pose accuracy: 5 deg 5 cm, IoU25, rotation and translation error (the NOCS evaluation, 6-PACK protocol) -----------
+ * The per-frame figures the reference's NOCS scorer turns into its per-class report (scripts/benchmark.py:65-159 called as at
+ * :262-272), for many items in one call.  One item is a predicted pose, a ground-truth pose (both row-major 4 x 4 OBJECT-IN-
+ * CAMERA, translation in the unit of shift_thresh: the protocol's is mm), a class and a box.  Class ids are the reference's
+ * synset_names: 1 bottle, 2 bowl, 3 camera, 4 can, 5 laptop, 6 mug.  An item is ROTATION-SYMMETRIC when its class is 1, 2 or 4,
+ * or 6 with handle_visible == 0.  (The reference's third branch names phone / eggbox / glue, classes this list does not have: it
+ * is left out.)  All arithmetic is fp64; every product, sum and quotient below is rounded on its own (no fma), sums run left to
+ * right as written.
+ *   1. Pre-processing (:262-269).  flip_z180_pred: rows 0 and 1 of the predicted pose are negated, translation included.
+ *      normalize_columns: each of the first three columns of each pose is divided by sqrt(m_0c^2 + m_1c^2 + m_2c^2 + m_3c^2).
+ *      P and G below are the pre-processed prediction and ground truth.
+ *   2. Errors (:120-159).  If the bottom row of P or of G is not exactly (0, 0, 0, 1): theta = shift = 10000, iou = NaN.
+ *      Otherwise R = M[:3, :3] / cbrt(det M[:3, :3]) for each pose, det by cofactors along row 0:
+ *          det = m00 (m11 m22 - m12 m21) - m01 (m10 m22 - m12 m20) + m02 (m10 m21 - m11 m20)
+ *      rotation-symmetric: a = (y1 . y2) / (|y1| |y2|), y the second column of R, |y| = sqrt(y . y)
+ *      otherwise:          a = (t0 + t1 + t2 - 1) / 2, t_r = the dot product of row r of R1 with row r of R2  (tr(R1 R2^T))
+ *      theta = acos(a) * (180 / pi) degrees; shift = sqrt(dx^2 + dy^2 + dz^2), d = T_P - T_G.
+ *   3. acos outside [-1, 1].  clamp_acos = 0: NaN, as numpy gives -- round-off puts a at 1 + 1 ulp for a good share of IDENTICAL
+ *      pose pairs, whose theta is then NaN and who fail every theta < threshold test; the reference scores them so and the default
+ *      keeps scores comparable.  clamp_acos = 1: a > 1 becomes 1 and a < -1 becomes -1 first (a NaN stays).
+ *   4. IoU (:65-111; the call at :272 hands the GROUND TRUTH over as the pose that is rotated).  Under a pose M, corner k =
+ *      (x, y, z) becomes p_r = (m_r0 x + m_r1 y + m_r2 z + m_r3) / (m_30 x + m_31 y + m_32 z + m_33), r = 0 .. 2.  The reference
+ *      reduces its 3 x 8 corner array along axis 0 (:75-78), and so does this: lo_k = min(p_0, p_1, p_2) and hi_k = max(p_0, p_1,
+ *      p_2) of corner k -- EIGHT values per pose, one per corner, not three per-axis extents.  It is the published protocol's
+ *      figure, not a geometric box overlap.  e_k = min(hi1_k, hi2_k) - max(lo1_k, lo2_k); inter = 0 if any e_k < 0, else
+ *      e_0 e_1 .. e_7; iou = inter / (v1 + v2 - inter), v = (hi_0 - lo_0)(hi_1 - lo_1) .. (hi_7 - lo_7), products from the left.
+ *      rotation-symmetric: m = 0; for i = 0 .. n_sym_steps - 1: x = iou(G Ry_i, P), m = x if x > m; iou = m -- a NaN x is never
+ *      taken.  Ry_i is the rotation about y by 2 pi i / n_sym_steps: columns 0 and 2 of G Ry_i are g_0 c + g_2 (-s) and
+ *      g_0 s + g_2 c (all four rows), with (c, s) = (cos, sin) of ((2 pi) i) / n_sym_steps from the host's C library in double:
+ *      one table per call, the same bits for every item.
+ *      otherwise: iou = iou(G, P) as it comes (NaN when v1 + v2 - inter is 0 / 0).
+ *   5. An item with a non-finite entry among its 32 pose entries (as given) has NaN in all three outputs; the others are
+ *      unaffected.  Box corners must be finite (precondition, not checked).
+ * rot_thresh_deg, shift_thresh and iou_thresh are not read by btba_nocs_errors: they travel with the parameters to the report
+ * (btba::nocsReport, bundletrack_amd.nocs_eval.nocs_report), which counts theta < rot_thresh_deg && shift < shift_thresh and
+ * iou > iou_thresh.
+ *
+ *   boxes            : host double [n_boxes][8][3], the eight corner rows of a model_scales/<model>.txt
+ *   class_id         : host int32 [n_evals], each in 1 .. 6
+ *   handle_visible   : host int32 [n_evals], or NULL (all 1, as the reference's scorer passes)
+ *   box_index        : host int32 [n_evals], each in 0 .. n_boxes - 1
+ *   poses_pred, poses_gt : double [n_evals][16] row-major
+ *   theta_deg_out, shift_out, iou_out : double [n_evals]
+ * device_resident = 1: poses and outputs are device pointers (8-byte aligned); 0: host pointers.  params NULL: the defaults.
+ * n_evals == 0 is a no-op.  Synchronous on the workspace stream; items go in chunks of 2^18, staging is grow-only in the workspace.
+ * BTBA_EINVAL before any GPU work: ws, boxes, a table or an output NULL, n_boxes < 1 or > 2^30, n_evals < 0, n_sym_steps outside
+ * 1 .. 32, a class_id outside 1 .. 6, a box_index out of range, a misaligned device pointer. */
+typedef struct btba_nocs_params {
+    double rot_thresh_deg;           /* 5 */
+    double shift_thresh;             /* 50, in the poses' unit (the protocol's mm: 5 cm) */
+    double iou_thresh;               /* 0.25 */
+    int32_t n_sym_steps;             /* 20 (1 .. 32) */
+    int32_t flip_z180_pred;          /* 1 */
+    int32_t normalize_columns;       /* 1 */
+    int32_t clamp_acos;              /* 0 */
+} btba_nocs_params;
+BTBA_API void btba_nocs_params_default(btba_nocs_params *p);
+BTBA_API int btba_nocs_errors(btba_workspace *ws, const btba_nocs_params *params, int device_resident,
+                              int n_boxes, const double *boxes,
+                              int n_evals, const int32_t *class_id, const int32_t *handle_visible, const int32_t *box_index,
+                              const double *poses_pred, const double *poses_gt,
+                              double *theta_deg_out, double *shift_out, double *iou_out);
+
 /* ---- map points and the tracker's findCorres (the step between the matcher and BA) --------------------------------------
  * The memory behind SiftManager::findCorres (src/FeatureManager.cpp:173-240): map points (feature tracks) link the RANSAC inliers
  * of every processed pair (updateFramePairMapPoints, :448-487) and add PROPAGATED correspondences to non-neighbouring pairs

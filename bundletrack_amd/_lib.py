@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = [
     "btba_optimize_frames", "btba_optimize_frames_keyed", "btba_frame_cache_clear", "btba_frame_cache_evict", "btba_ransac_pairs", "btba_ransac_pairs_ex", "btba_ransac_reference_uniforms", "btba_build_cache", "btba_solve_batch", "btba_solve_cached", "btba_collect_stats",
     "btba_trace_layout_get", "btba_bucket_correspondences",
     "btba_matrices_to_poses", "btba_poses_to_matrices",
-    "btba_process_depth", "btba_depth_to_normals",
+    "btba_process_depth", "btba_depth_to_normals", "btba_ingest_params_default", "btba_ingest_frames",
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_mask_params_default", "btba_apply_masks",
@@ -76,6 +76,12 @@ class MatchParams(C.Structure):
 class MaskParams(C.Structure):
     """btba_mask_params (include/btba.h)."""
     _fields_ = [("largest_component_hull", C.c_int32), ("dilate", C.c_int32)]
+
+
+class IngestParams(C.Structure):
+    """btba_ingest_params (include/btba.h)."""
+    _fields_ = [("depth_format", C.c_int32), ("erode_radius", C.c_int32), ("erode_diff", C.c_float), ("erode_ratio", C.c_float),
+                ("bf_radius", C.c_int32), ("sigma_d", C.c_float), ("sigma_r", C.c_float)]
 
 
 class DetectorParams(C.Structure):
@@ -245,6 +251,10 @@ def lib() -> C.CDLL:
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.btba_process_depth.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float]
         L.btba_depth_to_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_ingest_params_default.argtypes = [C.POINTER(IngestParams)]
+        L.btba_ingest_params_default.restype = None
+        L.btba_ingest_frames.argtypes = [C.c_void_p, C.POINTER(IngestParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_match_params_default.argtypes = [C.POINTER(MatchParams)]
         L.btba_match_params_default.restype = None
         L.btba_match_capacity.argtypes = [C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
@@ -323,6 +333,11 @@ def corres_params(**kw) -> CorresParams:
 def mask_params(**kw) -> MaskParams:
     """btba_mask_params_default with fields overridden by keyword."""
     return _params(MaskParams, "btba_mask_params_default", kw)
+
+
+def ingest_params(**kw) -> IngestParams:
+    """btba_ingest_params_default with fields overridden by keyword."""
+    return _params(IngestParams, "btba_ingest_params_default", kw)
 
 
 def detector_params(**kw) -> DetectorParams:

@@ -53,6 +53,8 @@ class FrameRef:
     desc_gpu: object = None              # [n, D] float32 CUDA tensor: their descriptors (Frame::_feat_des_gpu)
     mask_gpu: object = None              # [H, W] uint8 CUDA tensor: the raw object mask, nonzero = foreground (the mask PNG)
     fg_mask_gpu: object = None           # [H, W] uint8 CUDA tensor: the final 0 / 1 mask segmentation made of it (Frame::_fg_mask)
+    depth_code_gpu: object = None        # [H, W] uint16 / int16 CUDA tensor: the depth PNG's millimetre codes; ingest makes depth_gpu, normal_gpu of it
+    bgr_gpu: object = None               # [H, W, 3] uint8 CUDA tensor: the colour image as imread gives it; ingest makes color_gpu of it
 
     def __hash__(self):
         return hash(self.id)
@@ -241,8 +243,9 @@ def load_pose_txt(path: str) -> np.ndarray:
 
 
 class Bundler:
-    """Bundler::processNewFrame (src/Bundler.cpp:52-183) from the point where a frame has depth, normals and features:
-    the segmentation by its mask when `mask_gpu` is set (segmentation.apply_masks on `mask_workspace` or the optimiser's
+    """Bundler::processNewFrame (src/Bundler.cpp:52-183) from the point where a frame has depth, normals and features --
+    or, for a frame that carries only `depth_code_gpu` (and `bgr_gpu`), from its images: Bundler.ingest then makes depth_gpu,
+    normal_gpu and color_gpu first (ingest.ingest_frames, what Frame's constructor does).  Then the segmentation by its mask when `mask_gpu` is set (segmentation.apply_masks on `mask_workspace` or the optimiser's
     workspace; the ROI gate then sees the real ROI), feature detection when a `detector` is given (Bundler.detect: the
     detector's input and the keypoints' way back on the GPU, the detector itself a callable; an exception from it marks the
     frame FAIL), pose initialisation from the previous frame, sliding window, keyframe subset, bundle adjustment through an
@@ -303,6 +306,8 @@ class Bundler:
         if last is not None:
             frame.id = last.id + 1
             frame.pose_in_model = np.array(last.pose_in_model, np.float32)             # :78-79
+        if frame.depth_gpu is None and frame.depth_code_gpu is not None:               # Frame's constructor (Frame.cpp:45-89), minus the imreads
+            self.ingest(frame)
         if frame.mask_gpu is not None:                                                 # :80/:84 segmentationByMaskFile (minus the PNG read)
             self.segment(frame)
         if frame.roi[1] - frame.roi[0] < 10 or frame.roi[3] - frame.roi[2] < 10:        # :88-93: empty cloud -> FAIL and a plain return
@@ -350,6 +355,12 @@ class Bundler:
         self.memory.check_and_add_keyframe(frame)
         if self.pose_dir is not None:
             self.save_newframe_result()
+
+    def ingest(self, frame: FrameRef) -> None:
+        """Frame's constructor on the GPU (btba_ingest_frames): frame.depth_gpu, normal_gpu and (with bgr_gpu) color_gpu made of
+        frame.depth_code_gpu and frame.bgr_gpu, on the workspace `segment` uses."""
+        from .ingest import ingest_frames
+        ingest_frames(self._workspace("ingest"), [frame], K=self.K)
 
     def segment(self, frame: FrameRef) -> None:
         """Frame::segmentationByMaskFile on the GPU (btba_apply_masks): frame.depth_gpu, normal_gpu, color_gpu zeroed outside

@@ -545,6 +545,41 @@ void FeatureManager::findCorresbyNN(btba_workspace *ws, const std::shared_ptr<Fr
     if (is_neighbor && countInlierCorres(frameA, frameB) < 5) frameA->_status = Frame::FAIL;      // :280-285
 }
 
+btba_ingest_params ingestParams()
+{
+    btba_ingest_params p;
+    btba_ingest_params_default(&p);
+    return p;
+}
+
+void ingestFrames(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, const btba_ingest_params &params)
+{
+    if (frames.empty()) return;
+    if (params.depth_format != 0) throw Error(BTBA_EINVAL, "ingestFrames: Frame::_depth_code_gpu holds uint16 codes (depth_format 0)");
+    const int n = (int)frames.size(), H = frames[0]->_H, W = frames[0]->_W;
+    std::vector<const void *> depth_in(n);
+    std::vector<const uint8_t *> bgr(n);
+    std::vector<float *> depth(n), normal(n), raw(n), xyz(n);
+    std::vector<uint8_t *> color(n);
+    for (int k = 0; k < n; k++) {
+        const Frame &f = *frames[k];
+        if (f._H != H || f._W != W) throw Error(BTBA_EINVAL, "ingestFrames: frames of different sizes");
+        depth_in[k] = f._depth_code_gpu;
+        bgr[k] = f._color_gpu ? f._bgr_gpu : nullptr;
+        depth[k] = f._depth_gpu;
+        normal[k] = reinterpret_cast<float *>(f._normal_gpu);
+        color[k] = f._bgr_gpu ? reinterpret_cast<uint8_t *>(f._color_gpu) : nullptr;
+        raw[k] = f._depth_raw_gpu;
+        xyz[k] = reinterpret_cast<float *>(f._xyz_gpu);
+    }
+    float K[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) K[3 * r + c] = frames[0]->_K(r, c);
+    const int rc = btba_ingest_frames(ws, &params, n, H, W, K, depth_in.data(), bgr.data(), depth.data(), normal.data(), color.data(), raw.data(), xyz.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_ingest_frames");
+    for (auto &f : frames) f->_ingested = true;
+}
+
 void segmentationByMaskMultiFrame(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, bool largest_component_hull, int dilate)
 {
     if (frames.empty()) return;
@@ -744,14 +779,19 @@ void Bundler::processNewFrame(std::shared_ptr<Frame> frame)
         frame->_id = last_frame->_id + 1;
         frame->_pose_in_model = last_frame->_pose_in_model;
     }
-    if (frame->_mask_gpu) {                                                      // :80/:84 segmentationByMaskFile
+    const bool ingest = frame->_depth_code_gpu && !frame->_ingested;             // Frame's constructor (Frame.cpp:45-89), minus the imreads
+    if (ingest || frame->_mask_gpu) {
         if (frame->_H == 0 && frame->_W == 0) { frame->_H = H; frame->_W = W; }
         btba_workspace *ws = mask_ws;
         if (!ws) {
             if (!own_opt_) own_opt_ = std::make_unique<OptimizerGpu>(yml);
             ws = own_opt_->workspace();
         }
-        segmentationByMask(ws, frame, yml->mask_largest_component_hull, yml->mask_dilate);
+        if (ingest) {
+            if (frame->_K(2, 2) == 0.0f) frame->_K = K;                          // unset (a real K has 1 there): the Bundler's own
+            ingestFrames(ws, { frame }, ingestParams());
+        }
+        if (frame->_mask_gpu) segmentationByMask(ws, frame, yml->mask_largest_component_hull, yml->mask_dilate);      // :80/:84 segmentationByMaskFile
     }
     if (frame->_roi[1] - frame->_roi[0] < 10 || frame->_roi[3] - frame->_roi[2] < 10) {      // :88-93: "cloud is empty, marked FAIL" -- a plain return:
         frame->_status = Frame::FAIL;                                            // no forgetFrame, no re-initialisation request

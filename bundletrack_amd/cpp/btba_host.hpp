@@ -124,7 +124,20 @@ struct Frame {                                   // the fields of Frame (src/Fra
     int _feat_dim = 0;
     uint8_t *_mask_gpu = nullptr;                // [_H * _W] the raw object mask on the device, nonzero = foreground (the mask PNG); null = none
     uint8_t *_fg_mask_gpu = nullptr;             // [_H * _W] caller-owned: receives the final 0 / 1 mask (Frame::_fg_mask); null = not kept
+    const uint16_t *_depth_code_gpu = nullptr;   // [_H * _W] the depth PNG's millimetre codes on the device (cv::imread(path, CV_16UC1)); null = the frame arrives with its maps made
+    const uint8_t *_bgr_gpu = nullptr;           // [_H * _W * 3] the colour image on the device, imread's layout; null = no colour map is made
+    float *_depth_raw_gpu = nullptr;             // [_H * _W] caller-owned: receives the decoded, unfiltered depth (Frame::_depth_raw); null = not kept
+    float4 *_xyz_gpu = nullptr;                  // [_H * _W] caller-owned: receives the camera-space points (the xyz of Frame::_cloud); null = not kept
+    bool _ingested = false;                      // ingestFrames has filled _depth_gpu / _normal_gpu / _color_gpu from the two images
 };
+
+// The body of Frame's constructor after the two imreads (Frame.cpp:45-89, Utils::readDepthImage) on btba_ingest_frames, for many frames
+// in one call: _depth_code_gpu decoded to metres, processDepth and depthToCloudAndNormals into the caller-owned _depth_gpu and
+// _normal_gpu (the reference's constructor allocates them, :68-70), _bgr_gpu packed into _color_gpu where both are set, _depth_raw_gpu
+// and _xyz_gpu filled where set; _ingested = true.  Frames need _depth_code_gpu, _depth_gpu, _normal_gpu, _H, _W, _K (one size and one
+// K per call: the first frame's).  params.depth_format must be 0.  Asynchronous on the workspace stream.
+btba_ingest_params ingestParams();                                               // btba_ingest_params_default
+void ingestFrames(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, const btba_ingest_params &params);
 
 // Frame::segmentationByMaskFile (Frame.cpp:236-373) minus the PNG read, on btba_apply_masks: optionally the largest 8-connected
 // component's filled convex hull, a dilate x dilate dilation, colour / depth / normals zeroed outside the mask in place, _roi set and
@@ -297,7 +310,9 @@ private:
     std::map<int, int32_t> slots_;                                  // frame id -> slot
 };
 
-// Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its depth and normals on the device: the
+// Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its depth and normals on the device -- or, for a
+// frame with _depth_code_gpu set and _ingested false, from its images: ingestFrames (default parameters) on the segmentation's
+// workspace makes the maps first.  Then the
 // segmentation by its mask when _mask_gpu is set (segmentationByMask on mask_ws, or on the workspace of the Bundler's own
 // OptimizerGpu when mask_ws is null), pose initialisation from the previous frame, the sliding window, the keyframe subset, bundle adjustment, keyframe insertion,
 // the pose file.  `optimize` defaults to one persistent OptimizerGpu (the reference constructs a new one per call, :349);

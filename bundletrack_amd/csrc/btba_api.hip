@@ -23,6 +23,7 @@
 #include "btba_solve_small.hpp"
 #include "btba_solve_mid.hpp"
 #include "btba_image.hpp"
+#include "btba_ingest.hpp"
 #include "btba_ransac.hpp"
 #include "btba_xorwow.hpp"
 #include "btba_match.hpp"
@@ -1867,6 +1868,74 @@ int btba_depth_to_normals(btba_workspace *ws, int H, int W, const float *K, cons
     scaled_intrinsics(H, W, H, W, K, intr, &Kinv);       // only the generic cofactor inverse of the 4x4 embedding is used
     k_depth_to_normals<<<dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, ws->stream>>>(W, H, Kinv, depth_dev, reinterpret_cast<float4 *>(normals_dev), reinterpret_cast<float4 *>(xyz_dev));
     HIP_TRY(hipGetLastError());
+    return BTBA_OK;
+}
+
+void btba_ingest_params_default(btba_ingest_params *p)
+{
+    if (!p) return;
+    p->depth_format = 0;
+    p->erode_radius = 1; p->erode_diff = 0.001f; p->erode_ratio = 0.8f;          // config_ycbineoat.yml:9-16
+    p->bf_radius = 2; p->sigma_d = 2.0f; p->sigma_r = 100000.0f;
+}
+
+int btba_ingest_frames(btba_workspace *ws, const btba_ingest_params *prm, int n_frames, int H, int W, const float *K,
+                       const void *const *depth_in_dev, const uint8_t *const *bgr_in_dev, float *const *depth_out_dev,
+                       float *const *normal_out_dev, uint8_t *const *color_out_dev, float *const *depth_raw_out_dev,
+                       float *const *xyz_out_dev)
+{
+    // every argument is checked before the first HIP call
+    if (!ws || !prm || n_frames < 1 || H < 1 || W < 1 || !K || !depth_in_dev || !depth_out_dev || !normal_out_dev) return BTBA_EINVAL;
+    if (prm->depth_format < 0 || prm->depth_format > 1) return BTBA_EINVAL;
+    if (prm->erode_radius < 0 || prm->bf_radius < 0 || prm->erode_radius + 2 * prm->bf_radius > 16 || !(prm->sigma_d > 0.0f) || !(prm->sigma_r > 0.0f))
+        return BTBA_EINVAL;
+    const size_t n_px = (size_t)H * W, in_bytes = n_px * (prm->depth_format == 0 ? sizeof(uint16_t) : sizeof(float));
+    for (int f = 0; f < n_frames; f++) {
+        const void *in = depth_in_dev[f];
+        const uint8_t *bgr = bgr_in_dev ? bgr_in_dev[f] : nullptr;
+        uint8_t *color = color_out_dev ? color_out_dev[f] : nullptr;
+        float *raw = depth_raw_out_dev ? depth_raw_out_dev[f] : nullptr, *xyz = xyz_out_dev ? xyz_out_dev[f] : nullptr;
+        if (!in || !depth_out_dev[f] || !normal_out_dev[f] || (color && !bgr)) return BTBA_EINVAL;
+        if (misaligned(in, prm->depth_format == 0 ? 2 : 4) || misaligned(depth_out_dev[f], 4) || misaligned(normal_out_dev[f], 16) ||
+            misaligned(color, 4) || misaligned(raw, 4) || misaligned(xyz, 16))
+            return BTBA_EINVAL;
+        auto overlaps_input = [&](const void *q, size_t bytes) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(q);
+            return q && a < b + bytes && b < a + in_bytes;
+        };
+        if (overlaps_input(depth_out_dev[f], 4 * n_px) || overlaps_input(normal_out_dev[f], 16 * n_px) || overlaps_input(color, 4 * n_px) ||
+            overlaps_input(raw, 4 * n_px) || overlaps_input(xyz, 16 * n_px))
+            return BTBA_EINVAL;
+    }
+    DeviceGuard device_guard(ws);
+    DepthFilterParams P{ W, H, prm->erode_radius, prm->erode_diff, prm->erode_ratio, prm->bf_radius, prm->sigma_d, prm->sigma_r };
+    const int h = P.erode_radius + 2 * P.bf_radius;
+    const size_t lds = 2 * sizeof(float) * (size_t)(kTileW + 2 * h) * (kTileH + 2 * h);
+    float intr[4];
+    Mat4 Kinv;
+    scaled_intrinsics(H, W, H, W, K, intr, &Kinv);       // btba_depth_to_normals' inverse
+    for (int b0 = 0; b0 < n_frames; b0 += kIngestChunk) {
+        const int nf = std::min(kIngestChunk, n_frames - b0);
+        IngestDepthFrames D{};
+        IngestMapFrames M{};
+        for (int z = 0; z < nf; z++) {
+            const int f = b0 + z;
+            D.in[z] = depth_in_dev[f];
+            D.out[z] = depth_out_dev[f];
+            D.raw[z] = depth_raw_out_dev ? depth_raw_out_dev[f] : nullptr;
+            M.depth[z] = depth_out_dev[f];
+            M.normals[z] = reinterpret_cast<float4 *>(normal_out_dev[f]);
+            M.xyz[z] = xyz_out_dev ? reinterpret_cast<float4 *>(xyz_out_dev[f]) : nullptr;
+            M.color[z] = color_out_dev ? reinterpret_cast<uint32_t *>(color_out_dev[f]) : nullptr;
+            M.bgr[z] = M.color[z] ? bgr_in_dev[f] : nullptr;
+        }
+        const dim3 grid_d((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH, nf);
+        if (prm->depth_format == 0) launch_ingest_depth<uint16_t>(P, D, grid_d, lds, ws->stream);
+        else launch_ingest_depth<float>(P, D, grid_d, lds, ws->stream);
+        HIP_TRY(hipGetLastError());
+        k_ingest_maps<<<dim3((W + 63) / 64, (H + 3) / 4, nf), dim3(64, 4), 0, ws->stream>>>(W, H, Kinv, M);
+        HIP_TRY(hipGetLastError());
+    }
     return BTBA_OK;
 }
 

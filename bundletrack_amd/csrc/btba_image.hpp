@@ -10,6 +10,7 @@
 // materialising a float4 xyz map.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include "btba_device.hpp"
 
 namespace btba {
@@ -22,6 +23,18 @@ struct DepthFilterParams {
     int bf_radius; float sigma_d, sigma_r;
 };
 
+// one raw depth sample in metres, as the tile's stage 0 loads it.  float: as it is.  uint16 code u (a 16-bit depth PNG in millimetres,
+// Utils::readDepthImage, src/Utils.cpp:50-69): d = (float)((double)(float)u * 0.001), 0 when (double)d < 0.1 -- exactly u < 100 -> 0, and
+// code 100 -> 0.1f is kept.  The product is taken in double as the reference takes it: u * 0.001f differs in the last bit for most codes.
+__device__ __forceinline__ float depth_metres(float d) { return d; }
+__device__ __forceinline__ float depth_metres(uint16_t u)
+{
+#pragma clang fp contract(off)
+    const float f = (float)u;
+    const float d = (float)((double)f * 0.001);
+    return ((double)d < 0.1) ? 0.0f : d;
+}
+
 // dynamic LDS: two float planes of (kTileW + 2h) x (kTileH + 2h), h = erode_radius + 2 bf_radius.
 // RE / RF: the radii at compile time (the tracker's 1 and 2: 3 x 3 and 5 x 5 windows fully unrolled, LDS reads at immediate offsets), or -1 for
 // radii read from P.  A workgroup whose whole LDS tile lies inside the image (INTERIOR: all but the frame's rim) drops the four coordinate
@@ -30,8 +43,11 @@ struct DepthFilterParams {
 //     the double 0.01 and its successor above, so the two tests accept the same floats;
 //   * the weight is exp(s(dx, dy) - (centre - c)^2 / (2 sigma_r^2)) with the spatial term s = -(dx^2 + dy^2) / (2 sigma_d^2) divided once per
 //     thread (it takes six values for a 5 x 5 window) instead of once per tap, and the range term multiplied by 1 / (2 sigma_r^2).
-template <int RE, int RF, bool INTERIOR>
-__device__ __forceinline__ void process_depth_tile(const DepthFilterParams &P, const float *__restrict__ in, float *__restrict__ out, float *tile)
+// TIn: float metres or uint16 codes, decoded while the tile is filled (depth_metres).  raw: NULL, or a map that receives the decoded,
+// unfiltered depth: every workgroup writes its own kTileW x kTileH interior from the tile.
+template <int RE, int RF, bool INTERIOR, typename TIn = float>
+__device__ __forceinline__ void process_depth_tile(const DepthFilterParams &P, const TIn *__restrict__ in, float *__restrict__ out, float *tile,
+                                                   float *__restrict__ raw = nullptr)
 {
     const int re = RE >= 0 ? RE : P.erode_radius, rf = RF >= 0 ? RF : P.bf_radius, h = re + 2 * rf;
     const int LW = kTileW + 2 * h, LH = kTileH + 2 * h;
@@ -42,9 +58,13 @@ __device__ __forceinline__ void process_depth_tile(const DepthFilterParams &P, c
     // stage 0: raw depth (anything for out-of-image cells: consumers test coordinates, not values)
     for (int e = tid; e < LW * LH; e += 256) {
         const int lx = e % LW, ly = e / LW, gx = x0 + lx, gy = y0 + ly;
-        b0[e] = inside(gx, gy) ? in[(size_t)gy * P.W + gx] : 0.0f;
+        b0[e] = inside(gx, gy) ? depth_metres(in[(size_t)gy * P.W + gx]) : 0.0f;
     }
     __syncthreads();
+    if (raw) {                                                   // (uniform) b0 stays as loaded until the barrier after stage 1
+        const int lx = h + tid % kTileW, ly = h + tid / kTileW, gx = x0 + lx, gy = y0 + ly;
+        if (INTERIOR || (gx < P.W && gy < P.H)) raw[(size_t)gy * P.W + gx] = b0[ly * LW + lx];
+    }
     // stage 1: erode on the region that the two filter passes will read (margin re)
     {
         const int m = re, RW = LW - 2 * m, RH = LH - 2 * m;
@@ -140,12 +160,11 @@ __device__ __forceinline__ float3 backproject(const float *Ki, int x, int y, flo
     return make_float3(Ki[0] * vx + Ki[1] * vy + Ki[2] * d + Ki[3] * d, Ki[4] * vx + Ki[5] * vy + Ki[6] * d + Ki[7] * d, Ki[12] * vx + Ki[13] * vy + Ki[14] * d + Ki[15] * d);
 }
 
-// grid (ceil(W/64), ceil(H/4)) x (64, 4).  normals (and optionally the xyz map) for one frame.
-__global__ void __launch_bounds__(256) k_depth_to_normals(int W, int H, Mat4 Kinv, const float *__restrict__ depth, float4 *__restrict__ normals, float4 *__restrict__ xyz_out)
+// the normal (and optionally the camera-space point) of pixel (x, y), x < W, y < H
+__device__ __forceinline__ void depth_to_normals_pixel(int W, int H, const Mat4 &Kinv, const float *__restrict__ depth, float4 *__restrict__ normals,
+                                                       float4 *__restrict__ xyz_out, int x, int y)
 {
 #pragma clang fp contract(off)
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= W || y >= H) return;
     const size_t o = (size_t)y * W + x;
     const float dC = depth[o];
     const float3 CC = backproject(Kinv.m, x, y, dC);
@@ -174,6 +193,14 @@ __global__ void __launch_bounds__(256) k_depth_to_normals(int W, int H, Mat4 Kin
         }
     }
     normals[o] = res;
+}
+
+// grid (ceil(W/64), ceil(H/4)) x (64, 4).  normals (and optionally the xyz map) for one frame.
+__global__ void __launch_bounds__(256) k_depth_to_normals(int W, int H, Mat4 Kinv, const float *__restrict__ depth, float4 *__restrict__ normals, float4 *__restrict__ xyz_out)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= W || y >= H) return;
+    depth_to_normals_pixel(W, H, Kinv, depth, normals, xyz_out, x, y);
 }
 
 }  // namespace btba

@@ -538,6 +538,50 @@ BTBA_API int btba_match_pairs(btba_workspace *ws, const btba_match_params *param
                               const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
                               btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, int32_t *n_out);
 
+/* ---- frame ingest (what makes a frame's device maps from its two images) ------------------------------------------
+ * Replaces the body of Frame's constructor after the two imreads (src/Frame.cpp:45-89 with Utils::readDepthImage,
+ * src/Utils.cpp:50-69) for many frames in one call: the depth decode, Frame::updateColorGPU, Frame::processDepth and
+ * Frame::depthToCloudAndNormals.  _gray is not produced (the reference never reads it).  Every rule is exact, so a CPU
+ * restatement reproduces the decode and the colour bit for bit, and the depth chain and the normals equal the per-frame calls':
+ *   Decode, depth_format 0: for the code u, d = (float)((double)(float)u * 0.001): the product in double, rounded to float once.
+ *       The result is 0 when (double)d < 0.1.  That is exactly u < 100 -> 0: code 100 gives 0.1f, the smallest float above
+ *       0.1, and is kept.  (u * 0.001f, the product in float, differs from it in the last bit for 38 850 of the 65 536 codes.)
+ *   Decode, depth_format 1: the floats pass through unchanged; the call is then a batched btba_process_depth +
+ *       btba_depth_to_normals.
+ *   Colour: pixel p of the BGR image (bytes 3p, 3p + 1, 3p + 2) -> (B, G, R, 0), Frame::updateColorGPU.
+ *   Depth chain and normals: depth_out is btba_process_depth of the decoded depth with the six parameters below; normal_out and
+ *       xyz_out are btba_depth_to_normals(..., xyz) of depth_out with the same K (the same device functions, the same Kinv):
+ *       bit for bit what those two calls give frame by frame.
+ *
+ *   depth_in_dev[f]      : device uint16 [H*W] (2-byte aligned; format 0) or device float [H*W] (format 1)
+ *   bgr_in_dev           : NULL, or [f] device uint8 [H*W*3] (entries may be NULL), cv::imread's layout; any alignment (a
+ *                          4-byte-aligned image is read a dword at a time)
+ *   depth_out_dev[f]     : device float [H*W]: the processed depth (Frame::_depth_gpu)
+ *   normal_out_dev[f]    : device float4 [H*W], 16-byte aligned (Frame::_normal_gpu; btba_depth_to_normals' format)
+ *   color_out_dev        : NULL, or [f] device uchar4 [H*W], 4-byte aligned (entries NULL where bgr_in is NULL) (Frame::_color_gpu)
+ *   depth_raw_out_dev    : NULL, or [f] device float [H*W] (entries may be NULL): the decoded, unfiltered depth (Frame::_depth_raw)
+ *   xyz_out_dev          : NULL, or [f] device float4 [H*W], 16-byte aligned (entries may be NULL): camera-space points, w = 1
+ *                          (zeros where depth_out < 0.1): the contents of Frame::_cloud together with the normals
+ * Asynchronous on the workspace stream: no host synchronisation, no scratch, and no host memory is read after the call returns
+ * (frames go in chunks of BTBA_INGEST_CHUNK whose pointers travel as kernel arguments; two launches per chunk).
+ * BTBA_EINVAL, decided before the first launch: NULL ws, params, K_rowmajor, depth_in_dev, depth_out_dev or normal_out_dev, or a
+ * NULL entry in one of those three tables; n_frames < 1, H < 1 or W < 1; depth_format outside 0 .. 1; btba_process_depth's limits
+ * (a negative radius, erode_radius + 2 bf_radius > 16, sigma_d or sigma_r not > 0); a misaligned depth code map, normal, xyz or
+ * colour output; a colour output entry without its BGR input; any output of a frame that overlaps that frame's depth input. */
+#define BTBA_INGEST_CHUNK 32     /* frames per launch */
+typedef struct btba_ingest_params {
+    int32_t depth_format;            /* 0 (default): uint16 codes, as cv::imread(path, CV_16UC1) gives them; 1: float32 metres, taken as they are */
+    int32_t erode_radius;            /* btba_process_depth's six, same defaults: 1, 0.001, 0.8 */
+    float erode_diff, erode_ratio;
+    int32_t bf_radius;               /* 2, 2, 100000 */
+    float sigma_d, sigma_r;
+} btba_ingest_params;
+BTBA_API void btba_ingest_params_default(btba_ingest_params *p);
+BTBA_API int btba_ingest_frames(btba_workspace *ws, const btba_ingest_params *params, int n_frames, int H, int W,
+                                const float *K_rowmajor, const void *const *depth_in_dev, const uint8_t *const *bgr_in_dev,
+                                float *const *depth_out_dev, float *const *normal_out_dev, uint8_t *const *color_out_dev,
+                                float *const *depth_raw_out_dev, float *const *xyz_out_dev);
+
 /* ---- foreground-mask segmentation (the first step of every frame) ------------------------------------------------
  * Replaces Frame::segmentationByMaskFile minus the PNG read (src/Frame.cpp:236-373, called first by Bundler::processNewFrame,
  * src/Bundler.cpp:80,84) for many frames in one call.  Every rule is exact integer logic, so a CPU restatement reproduces the

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "btba_trace_layout_get", "btba_bucket_correspondences",
     "btba_matrices_to_poses", "btba_poses_to_matrices",
     "btba_process_depth", "btba_depth_to_normals", "btba_ingest_params_default", "btba_ingest_frames",
+     "btba_vos_params_default", "btba_vos_sample_frames", "btba_vos_first_labels", "btba_vos_propagate", "btba_vos_masks", "btba_vos_inputs",
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_mask_params_default", "btba_apply_masks",
@@ -82,6 +83,12 @@ class IngestParams(C.Structure):
     """btba_ingest_params (include/btba.h)."""
     _fields_ = [("depth_format", C.c_int32), ("erode_radius", C.c_int32), ("erode_diff", C.c_float), ("erode_ratio", C.c_float),
                 ("bf_radius", C.c_int32), ("sigma_d", C.c_float), ("sigma_r", C.c_float)]
+
+
+class VosParams(C.Structure):
+    """btba_vos_params (include/btba.h)."""
+    _fields_ = [("ref_num", C.c_int32), ("range", C.c_int32), ("sigma_dense", C.c_float), ("sigma_sparse", C.c_float), ("temperature", C.c_float),
+                ("continuous_frames", C.c_int32), ("sparse_after", C.c_int32)]
 
 
 class DetectorParams(C.Structure):
@@ -255,6 +262,14 @@ def lib() -> C.CDLL:
         L.btba_ingest_params_default.restype = None
         L.btba_ingest_frames.argtypes = [C.c_void_p, C.POINTER(IngestParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_vos_params_default.argtypes = [C.POINTER(VosParams)]
+        L.btba_vos_params_default.restype = None
+        L.btba_vos_sample_frames.argtypes = [C.POINTER(VosParams), C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.btba_vos_first_labels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.btba_vos_propagate.argtypes = [C.c_void_p, C.POINTER(VosParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_vos_masks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.btba_vos_inputs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.btba_match_params_default.argtypes = [C.POINTER(MatchParams)]
         L.btba_match_params_default.restype = None
         L.btba_match_capacity.argtypes = [C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
@@ -338,6 +353,11 @@ def mask_params(**kw) -> MaskParams:
 def ingest_params(**kw) -> IngestParams:
     """btba_ingest_params_default with fields overridden by keyword."""
     return _params(IngestParams, "btba_ingest_params_default", kw)
+
+
+def vos_params(**kw) -> VosParams:
+    """btba_vos_params_default with fields overridden by keyword."""
+    return _params(VosParams, "btba_vos_params_default", kw)
 
 
 def detector_params(**kw) -> DetectorParams:

@@ -245,7 +245,9 @@ def load_pose_txt(path: str) -> np.ndarray:
 class Bundler:
     """Bundler::processNewFrame (src/Bundler.cpp:52-183) from the point where a frame has depth, normals and features --
     or, for a frame that carries only `depth_code_gpu` (and `bgr_gpu`), from its images: Bundler.ingest then makes depth_gpu,
-    normal_gpu and color_gpu first (ingest.ingest_frames, what Frame's constructor does).  Then the segmentation by its mask when `mask_gpu` is set (segmentation.apply_masks on `mask_workspace` or the optimiser's
+    normal_gpu and color_gpu first (ingest.ingest_frames, what Frame's constructor does).  With a `segmenter` (the video
+    segmentation's backbone, a callable) and a `mask_propagator` (vos.MaskPropagator) a frame with `bgr_gpu` and no `mask_gpu` gets
+    its mask from the propagation (Bundler.propagate_mask); off by default.  Then the segmentation by its mask when `mask_gpu` is set (segmentation.apply_masks on `mask_workspace` or the optimiser's
     workspace; the ROI gate then sees the real ROI), feature detection when a `detector` is given (Bundler.detect: the
     detector's input and the keypoints' way back on the GPU, the detector itself a callable; an exception from it marks the
     frame FAIL), pose initialisation from the previous frame, sliding window, keyframe subset, bundle adjustment through an
@@ -269,8 +271,12 @@ class Bundler:
     def __init__(self, optimizer, feature_manager, K, H, W, *, window_size=2, max_BA_frames=15, min_rot_deg=10.0,
                  min_feat_num=0, min_fm_edges_newframe=5, pose_dir=None, persistent_frame_cache=False,
                  mask_largest_component_hull=False, mask_dilate=5, mask_workspace=None, detector=None, detector_out_size=400,
-                 device_window=False):
+                 device_window=False, segmenter=None, mask_propagator=None):
         self.opt, self.fm = optimizer, feature_manager
+        if (segmenter is None) != (mask_propagator is None):
+            raise ValueError("Bundler: segmenter and mask_propagator go together")
+        self.segmenter = segmenter                                               # None (default): frames arrive with mask_gpu set, as before
+        self.mask_propagator = mask_propagator                                   # vos.MaskPropagator: the video's propagation state
         self.device_window = bool(device_window)
         self.last_procrustes_err = None                                          # device_window: err of the last initial pose (FeatureManager.cpp:550)
         self._zn_cache: dict = {}                                                # device_window: frame id -> (depth ptr, normal ptr, zn [Hd, Wd, 4])
@@ -308,6 +314,8 @@ class Bundler:
             frame.pose_in_model = np.array(last.pose_in_model, np.float32)             # :78-79
         if frame.depth_gpu is None and frame.depth_code_gpu is not None:               # Frame's constructor (Frame.cpp:45-89), minus the imreads
             self.ingest(frame)
+        if self.segmenter is not None and frame.bgr_gpu is not None and (frame.mask_gpu is None or self.mask_propagator.n_frames == 0):
+            self.propagate_mask(frame)                                                 # run_video.py: the mask file's content, made here
         if frame.mask_gpu is not None:                                                 # :80/:84 segmentationByMaskFile (minus the PNG read)
             self.segment(frame)
         if frame.roi[1] - frame.roi[0] < 10 or frame.roi[3] - frame.roi[2] < 10:        # :88-93: empty cloud -> FAIL and a plain return
@@ -361,6 +369,19 @@ class Bundler:
         frame.depth_code_gpu and frame.bgr_gpu, on the workspace `segment` uses."""
         from .ingest import ingest_frames
         ingest_frames(self._workspace("ingest"), [frame], K=self.K)
+
+    def propagate_mask(self, frame: FrameRef) -> None:
+        """run_video.py's loop body around the injected backbone: segmenter(float32 [1, 3, H, W] normalised RGB) -> features
+        [C, Hd, Wd] (or [1, C, Hd, Wd]).  A frame that brings its mask while the propagator is empty is the annotated first frame
+        (MaskPropagator.start); a frame without one gets frame.mask_gpu from MaskPropagator.step."""
+        from .vos import normalize_inputs
+        feats = self.segmenter(normalize_inputs(self._workspace("propagate_mask"), [frame.bgr_gpu]))
+        if feats.dim() == 4:
+            feats = feats[0]
+        if frame.mask_gpu is not None:
+            self.mask_propagator.start(frame.mask_gpu, feats)
+        else:
+            frame.mask_gpu = self.mask_propagator.step(feats)
 
     def segment(self, frame: FrameRef) -> None:
         """Frame::segmentationByMaskFile on the GPU (btba_apply_masks): frame.depth_gpu, normal_gpu, color_gpu zeroed outside

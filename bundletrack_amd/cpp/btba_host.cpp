@@ -580,6 +580,92 @@ void ingestFrames(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> 
     for (auto &f : frames) f->_ingested = true;
 }
 
+btba_vos_params vosParams()
+{
+    btba_vos_params p;
+    btba_vos_params_default(&p);
+    return p;
+}
+
+void vosSampleFrames(const btba_vos_params &params, int frame_idx, std::vector<int> &idx, int &n_dense)
+{
+    std::vector<int32_t> buf((size_t)std::max(params.ref_num, 1));
+    int32_t n = 0, nd = 0;
+    const int rc = btba_vos_sample_frames(&params, frame_idx, buf.data(), &n, &nd);
+    if (rc != BTBA_OK) throw Error(rc, "btba_vos_sample_frames");
+    idx.assign(buf.begin(), buf.begin() + n);
+    n_dense = nd;
+}
+
+void vosFirstLabels(btba_workspace *ws, int H, int W, int d, const uint8_t *label_dev, float *labels_out_dev)
+{
+    const int rc = btba_vos_first_labels(ws, H, W, d, label_dev, labels_out_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_vos_first_labels");
+}
+
+void vosPropagate(btba_workspace *ws, const btba_vos_params &params, int C, int d, int Hd, int Wd,
+                  const std::vector<std::vector<const float *>> &refs, const std::vector<std::vector<const float *>> &labels,
+                  const std::vector<const float *> &targets, const std::vector<int> &n_dense, const std::vector<float *> &pred,
+                  const std::vector<float *> &onehot)
+{
+    const size_t n = targets.size();
+    if (n == 0) return;
+    if (refs.size() != n || labels.size() != n || n_dense.size() != n || pred.size() != n || (!onehot.empty() && onehot.size() != n))
+        throw Error(BTBA_EINVAL, "vosPropagate: one entry per video in every table");
+    std::vector<int32_t> n_ref(n), nd(n_dense.begin(), n_dense.end());
+    std::vector<const float *> rf, lb;
+    for (size_t b = 0; b < n; b++) {
+        if (refs[b].size() != labels[b].size()) throw Error(BTBA_EINVAL, "vosPropagate: as many labels as references");
+        n_ref[b] = (int32_t)refs[b].size();
+        rf.insert(rf.end(), refs[b].begin(), refs[b].end());
+        lb.insert(lb.end(), labels[b].begin(), labels[b].end());
+    }
+    const int rc = btba_vos_propagate(ws, &params, (int)n, C, d, Hd, Wd, n_ref.data(), nd.data(), rf.data(), lb.data(), targets.data(), pred.data(),
+                                      onehot.empty() ? nullptr : onehot.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_vos_propagate");
+}
+
+void vosMasks(btba_workspace *ws, int d, int Hd, int Wd, int H, int W, const float *pred_dev, uint8_t *mask_out_dev)
+{
+    const int rc = btba_vos_masks(ws, d, Hd, Wd, H, W, pred_dev, mask_out_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_vos_masks");
+}
+
+void vosInputs(btba_workspace *ws, const std::vector<const uint8_t *> &bgr_dev, int H, int W, float *rgb_out_dev)
+{
+    const int rc = btba_vos_inputs(ws, (int)bgr_dev.size(), H, W, bgr_dev.data(), rgb_out_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_vos_inputs");
+}
+
+MaskPropagator::MaskPropagator(btba_workspace *ws1, int d1, int H1, int W1, int C1, const btba_vos_params &params1, float *feats_dev,
+                               float *labels_dev, float *pred_dev, uint8_t *mask_dev)
+    : ws(ws1), d(d1), H(H1), W(W1), C(C1), Hd((H1 + 7) / 8), Wd((W1 + 7) / 8), params(params1), feats(feats_dev), labels(labels_dev),
+      pred(pred_dev), mask(mask_dev)
+{
+    if (!feats || !labels || !pred || !mask || params.range < 0) throw Error(BTBA_EINVAL, "MaskPropagator: null buffer");
+}
+
+void MaskPropagator::start(const uint8_t *label_dev)
+{
+    vosFirstLabels(ws, H, W, d, label_dev, labelsOf(0));             // the features of frame 0 are in featuresOf(0) = nextFeatures()
+    n_frames = 1;
+}
+
+const uint8_t *MaskPropagator::step()
+{
+    if (n_frames < 1) throw Error(BTBA_EINVAL, "MaskPropagator::step before start");
+    const int f = n_frames;
+    std::vector<int> idx;
+    int n_dense = 0;
+    vosSampleFrames(params, f, idx, n_dense);
+    std::vector<const float *> rf, lb;
+    for (int i : idx) { rf.push_back(featuresOf(i)); lb.push_back(labelsOf(i)); }
+    vosPropagate(ws, params, C, d, Hd, Wd, { rf }, { lb }, { featuresOf(f) }, { n_dense }, { pred }, { labelsOf(f) });
+    vosMasks(ws, d, Hd, Wd, H, W, pred, mask);
+    n_frames = f + 1;
+    return mask;
+}
+
 void segmentationByMaskMultiFrame(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, bool largest_component_hull, int dilate)
 {
     if (frames.empty()) return;
@@ -780,7 +866,8 @@ void Bundler::processNewFrame(std::shared_ptr<Frame> frame)
         frame->_pose_in_model = last_frame->_pose_in_model;
     }
     const bool ingest = frame->_depth_code_gpu && !frame->_ingested;             // Frame's constructor (Frame.cpp:45-89), minus the imreads
-    if (ingest || frame->_mask_gpu) {
+    const bool propagate = segmenter && mask_propagator && frame->_bgr_gpu && (!frame->_mask_gpu || mask_propagator->n_frames == 0);
+    if (ingest || propagate || frame->_mask_gpu) {
         if (frame->_H == 0 && frame->_W == 0) { frame->_H = H; frame->_W = W; }
         btba_workspace *ws = mask_ws;
         if (!ws) {
@@ -790,6 +877,13 @@ void Bundler::processNewFrame(std::shared_ptr<Frame> frame)
         if (ingest) {
             if (frame->_K(2, 2) == 0.0f) frame->_K = K;                          // unset (a real K has 1 there): the Bundler's own
             ingestFrames(ws, { frame }, ingestParams());
+        }
+        if (propagate) {                                                         // run_video.py's loop body around the backbone
+            if (!rgb_dev) throw Error(BTBA_EINVAL, "Bundler: segmenter set without rgb_dev");
+            vosInputs(ws, { frame->_bgr_gpu }, frame->_H, frame->_W, rgb_dev);
+            segmenter(rgb_dev, mask_propagator->nextFeatures());
+            if (frame->_mask_gpu) mask_propagator->start(frame->_mask_gpu);
+            else frame->_mask_gpu = const_cast<uint8_t *>(mask_propagator->step());
         }
         if (frame->_mask_gpu) segmentationByMask(ws, frame, yml->mask_largest_component_hull, yml->mask_dilate);      // :80/:84 segmentationByMaskFile
     }

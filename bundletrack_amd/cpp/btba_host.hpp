@@ -139,6 +139,45 @@ struct Frame {                                   // the fields of Frame (src/Fra
 btba_ingest_params ingestParams();                                               // btba_ingest_params_default
 void ingestFrames(btba_workspace *ws, const std::vector<std::shared_ptr<Frame>> &frames, const btba_ingest_params &params);
 
+// The video segmentation around its backbone (transductive-vos.pytorch/run_video.py, lib/predict.py) on btba_vos_*; the rules are in
+// include/btba.h.  vosSampleFrames needs no GPU; the others are asynchronous on the workspace stream and throw Error on a refusal.
+// vosPropagate: refs[b] / labels[b] are video b's reference features [C][Hd*Wd] and labels [d][Hd*Wd], oldest first, the last
+// n_dense[b] of them with sigma_dense; onehot may be empty (not wanted) or hold null entries.
+btba_vos_params vosParams();                                                     // btba_vos_params_default
+void vosSampleFrames(const btba_vos_params &params, int frame_idx, std::vector<int> &idx, int &n_dense);
+void vosFirstLabels(btba_workspace *ws, int H, int W, int d, const uint8_t *label_dev, float *labels_out_dev);
+void vosPropagate(btba_workspace *ws, const btba_vos_params &params, int C, int d, int Hd, int Wd,
+                  const std::vector<std::vector<const float *>> &refs, const std::vector<std::vector<const float *>> &labels,
+                  const std::vector<const float *> &targets, const std::vector<int> &n_dense, const std::vector<float *> &pred,
+                  const std::vector<float *> &onehot);
+void vosMasks(btba_workspace *ws, int d, int Hd, int Wd, int H, int W, const float *pred_dev, uint8_t *mask_out_dev);
+void vosInputs(btba_workspace *ws, const std::vector<const uint8_t *> &bgr_dev, int H, int W, float *rgb_out_dev);
+
+// One video's propagation state: run_video.py's feats_history / label_history as a device ring of range + 5 slots (no frame older
+// than frame_idx - range - 4 is ever sampled; the reference keeps every frame).  The memory is the caller's, as a Frame's maps are:
+//   feats [slots()][C][Hd*Wd] float, labels [slots()][d][Hd*Wd] float, pred [d][Hd*Wd] float, mask [H*W] uint8.
+// The backbone writes a frame's features straight into nextFeatures() -- the slot the frame will occupy -- and then start(label_dev)
+// (the annotated frame 0; a uint8 [H*W] label image with classes 0 .. d-1) or step() (every later frame: predict against the
+// sampled history, the one-hot labels into the ring, the class map into `mask`) takes the frame into the history.
+class MaskPropagator {
+public:
+    btba_workspace *ws;
+    int d, H, W, C, Hd, Wd;
+    btba_vos_params params;
+    float *feats, *labels, *pred;
+    uint8_t *mask;
+    int n_frames = 0;                                               // frames in the history = the next frame_idx
+
+    MaskPropagator(btba_workspace *ws1, int d1, int H1, int W1, int C1, const btba_vos_params &params1, float *feats_dev, float *labels_dev,
+                   float *pred_dev, uint8_t *mask_dev);
+    int slots() const { return params.range + 5; }
+    float *featuresOf(int frame) const { return feats + (size_t)(frame % slots()) * C * Hd * Wd; }
+    float *labelsOf(int frame) const { return labels + (size_t)(frame % slots()) * d * Hd * Wd; }
+    float *nextFeatures() const { return featuresOf(n_frames); }
+    void start(const uint8_t *label_dev);
+    const uint8_t *step();                                          // returns `mask`
+};
+
 // Frame::segmentationByMaskFile (Frame.cpp:236-373) minus the PNG read, on btba_apply_masks: optionally the largest 8-connected
 // component's filled convex hull, a dilate x dilate dilation, colour / depth / normals zeroed outside the mask in place, _roi set and
 // the final mask written to _fg_mask_gpu when that is set.  Frames need _mask_gpu, _depth_gpu, _normal_gpu, _H, _W (one size per
@@ -312,7 +351,8 @@ private:
 
 // Bundler (src/Bundler.h, Bundler.cpp:56-377) from the point where a frame has its depth and normals on the device -- or, for a
 // frame with _depth_code_gpu set and _ingested false, from its images: ingestFrames (default parameters) on the segmentation's
-// workspace makes the maps first.  Then the
+// workspace makes the maps first.  With `segmenter` and `mask_propagator` set, a frame with _bgr_gpu and no _mask_gpu then gets its mask
+// from the video segmentation (run_video.py's loop body).  Then the
 // segmentation by its mask when _mask_gpu is set (segmentationByMask on mask_ws, or on the workspace of the Bundler's own
 // OptimizerGpu when mask_ws is null), pose initialisation from the previous frame, the sliding window, the keyframe subset, bundle adjustment, keyframe insertion,
 // the pose file.  `optimize` defaults to one persistent OptimizerGpu (the reference constructs a new one per call, :349);
@@ -333,6 +373,14 @@ public:
     int n_ba_calls = 0;
     Window last_window;                                             // what the last optimizeGPU marshalled
     btba_workspace *mask_ws = nullptr;                              // the caller's workspace for the segmentation (not owned)
+    // The video segmentation's backbone: normalised RGB float [3][H][W] on the device -> features float [C][Hd][Wd] written to
+    // features_out_dev.  With it and a mask_propagator set (both off by default) a frame with _bgr_gpu and no _mask_gpu gets its mask
+    // from the propagation; a frame that brings its mask while the propagator is empty is the annotated first frame.  rgb_dev is the
+    // caller's float [3][H][W] buffer the normalised image goes to.
+    using SegmentFn = std::function<void(const float *rgb_dev, float *features_out_dev)>;
+    SegmentFn segmenter;
+    std::shared_ptr<MaskPropagator> mask_propagator;
+    float *rgb_dev = nullptr;
 
     Bundler(std::shared_ptr<Config> yml1, std::shared_ptr<FeatureManager> fm, const Matrix3f &K1, int H1, int W1, OptimizeFn optimize = {});
     void processNewFrame(std::shared_ptr<Frame> frame);             // :56-183

@@ -582,6 +582,79 @@ BTBA_API int btba_ingest_frames(btba_workspace *ws, const btba_ingest_params *pa
                                 float *const *depth_out_dev, float *const *normal_out_dev, uint8_t *const *color_out_dev,
                                 float *const *depth_raw_out_dev, float *const *xyz_out_dev);
 
+/* ---- mask propagation (where a frame's object mask comes from) ---------------------------------------------------
+ * Replaces transductive-vos.pytorch/run_video.py around its backbone: rgb_normalize (:81,113-114), prepare_first_frame (:68-82),
+ * lib/predict.py::predict with sample_frames and get_spatial_weight (:11-59, :62-78, :118-134), the one-hot history entry (:145)
+ * and the upsampled arg-max mask (:151-155).  The backbone (a torch model) stays with the caller: it maps btba_vos_inputs' output to
+ * features float [C][Hd][Wd], Hd = ceil(H / 8), Wd = ceil(W / 8).  The mask btba_vos_masks writes is what btba_apply_masks takes.
+ *
+ * btba_vos_sample_frames (host only; no GPU, no workspace): the history indices predict reads for target frame frame_idx >= 1
+ * (frame 0 is the annotated one) and how many of them, counted from the end, take sigma_dense:
+ *   frame_idx <= ref_num :  0 .. frame_idx - 1
+ *   otherwise            :  trunc(np.linspace(ref_start, ref_end, ref_num - (continuous_frames - 1))), then the continuous_frames - 1
+ *                           frames before the target, with ref_end = frame_idx - continuous_frames, ref_start = max(ref_end - range, 0).
+ *                           linspace is numpy's: in double, element i = (double)i * step + ref_start with step = (ref_end - ref_start) /
+ *                           (n - 1), product and sum rounded separately, the last element ref_end itself; one element = ref_start.
+ *   n_dense = n for frame_idx <= sparse_after, else min(continuous_frames, n): the last FOUR selected frames take the dense sigma
+ *   although only three of them are the contiguous ones (predict:48-55; kept, the scores depend on it).
+ *   idx_out needs room for ref_num entries.  EINVAL: NULL arguments, frame_idx < 1, or parameters outside: continuous_frames >= 1,
+ *   max(1, continuous_frames - 1) <= ref_num <= BTBA_VOS_MAX_REF, range >= 0, sparse_after >= 0, both sigmas > 0, temperature finite.
+ *
+ * btba_vos_propagate: n_items independent videos in one call.  Item b has n_ref[b] reference frames (their pointers are consecutive
+ * in the two flat tables, item after item), of which the last n_dense[b] take sigma_dense and the others sigma_sparse.  With
+ * k = (r, p) a reference and a position in it, q a target position, (py, px) = (p / Wd, p % Wd):
+ *   s[k,q]    = temperature * sum_c ref_r[c,p] * tgt[c,q]                     fp32 products and sums (fp32-input MFMA: an fma chain over c)
+ *   P[k,q]    = exp(s[k,q] - m[q]) / sum_k' exp(s[k',q] - m[q]),  m[q] = max_k' s[k',q]      ONE softmax over all references' positions
+ *   w[k,q]    = exp(-((py-qy)^2 + (px-qx)^2) / sigma(r)^2)                    applied after the softmax, not renormalised
+ *   pred[c,q] = sum_k label_r[c,p] * P[k,q] * w[k,q]
+ * and, where onehot_out_dev is given, onehot[c,q] = 1 for the lowest c that attains max_c pred[c,q], else 0 (run_video.py:145).
+ * The similarity matrix and the weight tables are never formed: an online softmax over key tiles, the keys split over workgroups
+ * and the splits merged in a fixed order without atomics, so a call returns the same bits every time and an item's bits do not
+ * depend on the batch around it.  Against the fp64 evaluation of the formulas the error is that of the fp32 logits; the bars the
+ * tests hold it to are measured from the reference's own fp32 run.
+ *   ref_feat_dev[k]   : device float [C][Hd*Wd] (the backbone's output as it is)
+ *   ref_label_dev[k]  : device float [d][Hd*Wd] (btba_vos_first_labels' output for frame 0, one-hot afterwards)
+ *   target_dev[b]     : device float [C][Hd*Wd]
+ *   pred_out_dev[b]   : device float [d][Hd*Wd]
+ *   onehot_out_dev    : NULL, or [b] device float [d][Hd*Wd] (entries may be NULL)
+ * Asynchronous on the workspace stream; no host memory is read after the call returns (items go in chunks whose pointers travel as
+ * kernel arguments; two launches per chunk).  Scratch: 16 (2 + d) Hd Wd floats per item in the workspace.
+ * BTBA_EINVAL, decided before any GPU work: NULL ws, params or table, a NULL or misaligned (4 bytes) entry; n_items < 1; C not a
+ * multiple of 8 in 8 .. BTBA_VOS_MAX_CHANNELS; d outside 2 .. BTBA_VOS_MAX_CLASSES; Hd or Wd < 1 or Hd*Wd > BTBA_VOS_MAX_POSITIONS;
+ * n_ref[b] outside 1 .. BTBA_VOS_MAX_REF; n_dense[b] outside 0 .. n_ref[b]; parameters outside btba_vos_sample_frames' limits.
+ *
+ * btba_vos_first_labels: the one-hot of a uint8 [H][W] label image (classes 0 .. d-1; another value belongs to no class) taken
+ * bilinearly to [d][Hd][Wd], Hd = ceil(H / 8), Wd = ceil(W / 8).  btba_vos_masks: pred [d][Hd][Wd] taken bilinearly to H x W and the
+ * arg-max class (lowest on ties) written as uint8 [H][W]; the d x H x W image is never stored.  Both interpolate as torch's
+ * interpolate(mode='bilinear', align_corners=False) does, all in fp32: src = (float)in / (float)out * (dst + 0.5f) - 0.5f, below 0 -> 0;
+ * i0 = (int)src, i1 = i0 + (i0 < in - 1), w1 = src - i0, w0 = 1 - w1; value = wy0 (wx0 v00 + wx1 v01) + wy1 (wx0 v10 + wx1 v11).
+ * EINVAL: NULL pointers, sizes < 1, d outside 2 .. BTBA_VOS_MAX_CLASSES, Hd*Wd > BTBA_VOS_MAX_POSITIONS.
+ *
+ * btba_vos_inputs: bgr_dev[f] device uint8 [H*W*3] (cv::imread's layout) -> rgb_out_dev float [n_frames][3][H][W], planes R, G, B:
+ * ((float)v / 255.0f - mean) / std in fp32 with mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225).  EINVAL: NULL ws, table,
+ * entry or output, n_frames, H or W < 1. */
+#define BTBA_VOS_MAX_REF 32
+#define BTBA_VOS_MAX_CLASSES 16
+#define BTBA_VOS_MAX_CHANNELS 512
+#define BTBA_VOS_MAX_POSITIONS 65536
+typedef struct btba_vos_params {
+    int32_t ref_num;                 /* 9: reference frames sampled per target */
+    int32_t range;                   /* 40: how far back the sparse references reach */
+    float sigma_dense, sigma_sparse; /* 8, 21: the Gaussian's sigma in grid cells */
+    float temperature;               /* 1 */
+    int32_t continuous_frames;       /* 4: references that take sigma_dense once frame_idx > sparse_after */
+    int32_t sparse_after;            /* 15 */
+} btba_vos_params;
+BTBA_API void btba_vos_params_default(btba_vos_params *p);
+BTBA_API int btba_vos_sample_frames(const btba_vos_params *params, int frame_idx, int32_t *idx_out, int32_t *n_out, int32_t *n_dense_out);
+BTBA_API int btba_vos_first_labels(btba_workspace *ws, int H, int W, int d, const uint8_t *label_dev, float *labels_out_dev);
+BTBA_API int btba_vos_propagate(btba_workspace *ws, const btba_vos_params *params, int n_items, int C, int d, int Hd, int Wd,
+                                const int32_t *n_ref, const int32_t *n_dense, const float *const *ref_feat_dev,
+                                const float *const *ref_label_dev, const float *const *target_dev, float *const *pred_out_dev,
+                                float *const *onehot_out_dev);
+BTBA_API int btba_vos_masks(btba_workspace *ws, int d, int Hd, int Wd, int H, int W, const float *pred_dev, uint8_t *mask_out_dev);
+BTBA_API int btba_vos_inputs(btba_workspace *ws, int n_frames, int H, int W, const uint8_t *const *bgr_dev, float *rgb_out_dev);
+
 /* ---- foreground-mask segmentation (the first step of every frame) ------------------------------------------------
  * Replaces Frame::segmentationByMaskFile minus the PNG read (src/Frame.cpp:236-373, called first by Bundler::processNewFrame,
  * src/Bundler.cpp:80,84) for many frames in one call.  Every rule is exact integer logic, so a CPU restatement reproduces the

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
      "btba_vos_params_default", "btba_vos_sample_frames", "btba_vos_first_labels", "btba_vos_propagate", "btba_vos_masks", "btba_vos_inputs",
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
+    "btba_lfnet_params_default", "btba_lfnet_heatmaps", "btba_lfnet_select", "btba_lfnet_crops", "btba_lfnet_keypoints",
     "btba_mask_params_default", "btba_apply_masks",
     "btba_detector_params_default", "btba_detector_transform", "btba_detector_inputs", "btba_detector_keypoints_to_image",
     "btba_pose_errors", "btba_nocs_params_default", "btba_nocs_errors",
@@ -89,6 +90,14 @@ class VosParams(C.Structure):
     """btba_vos_params (include/btba.h)."""
     _fields_ = [("ref_num", C.c_int32), ("range", C.c_int32), ("sigma_dense", C.c_float), ("sigma_sparse", C.c_float), ("temperature", C.c_float),
                 ("continuous_frames", C.c_int32), ("sparse_after", C.c_int32)]
+
+
+class LfnetParams(C.Structure):
+    """btba_lfnet_params (include/btba.h)."""
+    _fields_ = [("sm_ksize", C.c_int32), ("com_strength", C.c_float), ("score_com_strength", C.c_float), ("scale_com_strength", C.c_float),
+                ("nms_thresh", C.c_float), ("nms_ksize", C.c_int32), ("top_k", C.c_int32), ("pad_size", C.c_int32), ("crop_radius", C.c_int32),
+                ("soft_kpts", C.c_int32), ("kp_loc_size", C.c_int32), ("do_softmax_kp_refine", C.c_int32), ("kp_com_strength", C.c_float),
+                ("patch_size", C.c_int32)]
 
 
 class DetectorParams(C.Structure):
@@ -270,6 +279,12 @@ def lib() -> C.CDLL:
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_vos_masks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.btba_vos_inputs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.btba_lfnet_params_default.argtypes = [C.POINTER(LfnetParams)]
+        L.btba_lfnet_params_default.restype = None
+        L.btba_lfnet_heatmaps.argtypes = [C.c_void_p, C.POINTER(LfnetParams), C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.btba_lfnet_select.argtypes = [C.c_void_p, C.POINTER(LfnetParams), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
+        L.btba_lfnet_crops.argtypes = [C.c_void_p, C.POINTER(LfnetParams), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
+        L.btba_lfnet_keypoints.argtypes = [C.c_void_p, C.POINTER(LfnetParams), C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 15
         L.btba_match_params_default.argtypes = [C.POINTER(MatchParams)]
         L.btba_match_params_default.restype = None
         L.btba_match_capacity.argtypes = [C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
@@ -358,6 +373,11 @@ def ingest_params(**kw) -> IngestParams:
 def vos_params(**kw) -> VosParams:
     """btba_vos_params_default with fields overridden by keyword."""
     return _params(VosParams, "btba_vos_params_default", kw)
+
+
+def lfnet_params(**kw) -> LfnetParams:
+    """btba_lfnet_params_default with fields overridden by keyword."""
+    return _params(LfnetParams, "btba_lfnet_params_default", kw)
 
 
 def detector_params(**kw) -> DetectorParams:

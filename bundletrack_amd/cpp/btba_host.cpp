@@ -840,6 +840,39 @@ bool GpuFeatureManager::findCorresChain(const std::vector<std::pair<std::shared_
     return true;
 }
 
+btba_lfnet_params lfnetParams()
+{
+    btba_lfnet_params p;
+    btba_lfnet_params_default(&p);
+    return p;
+}
+
+std::vector<int> lfnetKeypoints(btba_workspace *ws, const btba_lfnet_params &params, int n_frames, int H, int W, const LfnetMapSet &maps,
+                                const float *photo_dev, const float *ori_dev, const LfnetBuffers &out)
+{
+    const size_t S = maps.score_dev.size();
+    if (maps.map_h.size() != S || maps.map_w.size() != S || maps.scale_factors.size() != S || n_frames < 1)
+        throw Error(BTBA_EINVAL, "lfnetKeypoints: one size and one scale factor per score map");
+    std::vector<int32_t> counts((size_t)n_frames);
+    const int rc = btba_lfnet_keypoints(ws, &params, n_frames, H, W, (int)S, maps.score_dev.data(), maps.map_h.data(), maps.map_w.data(),
+                                        maps.scale_factors.data(), photo_dev, ori_dev, out.max_heatmaps, out.max_scales, out.kpts_xy, out.n_kpts,
+                                        out.kpts, out.kpts_scale, out.kpts_ori, out.patches, counts.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_keypoints");
+    return std::vector<int>(counts.begin(), counts.end());
+}
+
+DetectedFeatures LfnetDetector::operator()(const uint8_t *, const float *gray_dev, int out_size) const
+{
+    const float *ori_dev = nullptr;
+    const LfnetMapSet maps = score_(gray_dev, out_size, ori_dev);
+    const int m = lfnetKeypoints(ws_, params_, 1, out_size, out_size, maps, gray_dev, ori_dev, out_)[0];
+    DetectedFeatures f;
+    f.kpts_dev = reinterpret_cast<float2 *>(out_.kpts);
+    f.n = m;
+    f.desc_dev = desc_(out_.patches, m, f.dim);
+    return f;
+}
+
 void DetectorFeatureManager::detectFeature(const std::shared_ptr<Frame> &frame)              // FeatureManager.cpp:811-908
 {
     prepareDetectorInputs(ws_, { frame }, bgr_, gray_, out_size_);

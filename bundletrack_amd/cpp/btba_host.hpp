@@ -328,6 +328,42 @@ private:
     int out_size_;
 };
 
+// LF-Net's keypoint head between its two conv nets (inference.py::build_multi_scale_deep_detector_3DNMS and build_patch_extraction)
+// on btba_lfnet_keypoints; the rules are in include/btba.h.  Every buffer is the caller's device memory.
+btba_lfnet_params lfnetParams();                                                 // btba_lfnet_params_default
+struct LfnetMapSet {                             // the score net's output for n frames
+    std::vector<const float *> score_dev;        // [S] device float [n][h_s][w_s]
+    std::vector<int32_t> map_h, map_w;           // [S]
+    std::vector<float> scale_factors;            // [S]
+};
+struct LfnetBuffers {                            // per frame: what btba_lfnet_keypoints writes, sizes in include/btba.h
+    float *max_heatmaps = nullptr, *max_scales = nullptr;            // [n][H][W]
+    int32_t *kpts_xy = nullptr, *n_kpts = nullptr;                   // [n][top_k][2], [n]
+    float *kpts = nullptr, *kpts_scale = nullptr, *kpts_ori = nullptr, *patches = nullptr;      // [n][top_k][2], [n][top_k], [n][top_k][2], [n][top_k][P][P]
+};
+// A, B and C for n_frames in one call.  Returns the keypoint counts (one host wait at the end); throws Error on a refusal.
+std::vector<int> lfnetKeypoints(btba_workspace *ws, const btba_lfnet_params &params, int n_frames, int H, int W, const LfnetMapSet &maps,
+                                const float *photo_dev, const float *ori_dev, const LfnetBuffers &out);
+
+// The detector DetectorFeatureManager takes, around the caller's two conv nets:
+//   score_net(gray_dev [S][S]) -> the score maps of one frame (LfnetMapSet) and ori_maps device float [S][S][2]
+//   desc_net(patches_dev [m][P][P], m) -> descriptors device float [m][dim]
+// with lfnetKeypoints in between; the keypoints returned are out.kpts (refined, in detector pixels).
+class LfnetDetector {
+public:
+    using ScoreFn = std::function<LfnetMapSet(const float *gray_dev, int out_size, const float *&ori_dev)>;
+    using DescFn = std::function<float *(const float *patches_dev, int m, int &dim)>;
+    LfnetDetector(btba_workspace *ws, ScoreFn score_net, DescFn desc_net, const btba_lfnet_params &params, const LfnetBuffers &out)
+        : ws_(ws), score_(std::move(score_net)), desc_(std::move(desc_net)), params_(params), out_(out) {}
+    DetectedFeatures operator()(const uint8_t *bgr_dev, const float *gray_dev, int out_size) const;
+private:
+    btba_workspace *ws_;
+    ScoreFn score_;
+    DescFn desc_;
+    btba_lfnet_params params_;
+    LfnetBuffers out_;
+};
+
 // SiftManager::findCorres (FeatureManager.cpp:173-240) with its map points on btba_corres_chain: NN, propagation along the map
 // points, RANSAC (ransac.max_iter / inlier_dist of yml), the map-point update and the FAIL gates for an ordered list of pairs in one
 // call, the frames' map points in a btba_mappoints on `ws` (a frame is registered at its first pair, by _id; forgetFrame frees its

@@ -25,6 +25,7 @@
 #include "btba_image.hpp"
 #include "btba_ingest.hpp"
 #include "btba_vos.hpp"
+#include "btba_lfnet.hpp"
 #include "btba_ransac.hpp"
 #include "btba_xorwow.hpp"
 #include "btba_match.hpp"
@@ -174,7 +175,7 @@ struct btba_workspace {
     std::vector<EventPair> events;                          // pending timed regions
     std::vector<hipEvent_t> event_pool;
     btba_stats stats{};
-    bool lds_attr_set = false, small_attr_set = false, mid_attr_set = false, vos_attr_set = false;
+    bool lds_attr_set = false, small_attr_set = false, mid_attr_set = false, vos_attr_set = false, lfnet_attr_set = false;
     int n_cus = 0;                     // compute units of the workspace's device (256 = all eight XCDs of an MI355X in SPX mode: what k_chain's item -> XCD mapping assumes)
     bool always_time_region = false;   // optimize_frames: ms_solve is part of its stats contract
     static constexpr int kMaxGroups = 8;
@@ -211,6 +212,7 @@ struct btba_workspace {
     DevBuf nocs;                                            // btba_nocs_errors: item words, boxes, step table, host-form poses and outputs
     DevBuf corres;                                          // btba_corres_chain: frame / pair tables, NN output, working lists, per-pair words
     DevBuf vos;                                             // btba_vos_propagate: the key splits' partial (m, l, acc) per item and target position
+    DevBuf lfnet;                                           // btba_lfnet_*: per-map moments, peak flags, the compacted peak list
     DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
@@ -2647,6 +2649,166 @@ int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_par
         if (n_max == 0) continue;
         k_detect_keypoints<<<dim3((n_max + 255) / 256, nf), 256, 0, ws->stream>>>(F);
         HIP_TRY(hipGetLastError());
+    }
+    return BTBA_OK;
+}
+
+void btba_lfnet_params_default(btba_lfnet_params *p)
+{
+    if (!p) return;
+    p->sm_ksize = 15; p->com_strength = 3.0f; p->score_com_strength = 100.0f; p->scale_com_strength = 100.0f;      // train_lfnet.py:1047-1189
+    p->nms_thresh = 0.0f; p->nms_ksize = 5;
+    p->top_k = 500;                                                   // run_server.py
+    p->pad_size = 16;                                                 // mso_resnet_detector.py:171: five-tap convolutions, three blocks
+    p->crop_radius = 16; p->soft_kpts = 1; p->kp_loc_size = 9; p->do_softmax_kp_refine = 1; p->kp_com_strength = 1.0f; p->patch_size = 32;
+}
+
+namespace {
+bool lfnet_params_ok(const btba_lfnet_params *p, int n_frames, int H, int W)
+{
+    if (!p || n_frames < 1 || H < 1 || W < 1 || H > BTBA_LFNET_MAX_SIZE || W > BTBA_LFNET_MAX_SIZE) return false;
+    if (p->sm_ksize < 1 || p->sm_ksize > BTBA_LFNET_MAX_KSIZE || p->sm_ksize % 2 == 0) return false;
+    if (p->nms_ksize < 1 || p->nms_ksize > BTBA_LFNET_MAX_KSIZE || p->nms_ksize % 2 == 0) return false;
+    if (p->top_k < 1 || p->top_k > BTBA_LFNET_MAX_TOP_K) return false;
+    const int m = std::min(H, W);
+    if (p->pad_size < 0 || p->crop_radius < 0 || 2 * (int64_t)p->pad_size >= m || 2 * (int64_t)p->crop_radius >= m) return false;
+    if (p->patch_size < 2 || p->patch_size > 64 || p->kp_loc_size < 2 || p->kp_loc_size > 64) return false;
+    return true;
+}
+
+// One layout for all three stages, so that a call of any of them leaves the others' regions where they were.
+struct LfnetScratch {
+    Scratch sc;
+    Scratch::Region<float2> stats;
+    Scratch::Region<uint8_t> peak;
+    Scratch::Region<int32_t> list_idx;
+    Scratch::Region<uint32_t> list_key;
+    LfnetScratch(int n_frames, int H, int W)
+        : stats(sc.add<float2>((size_t)n_frames * kLfnetMaxScales)), peak(sc.add<uint8_t>((size_t)n_frames * H * W)),
+          list_idx(sc.add<int32_t>((size_t)n_frames * H * W)), list_key(sc.add<uint32_t>((size_t)n_frames * H * W)) {}
+};
+
+int lfnet_heatmaps_enqueue(btba_workspace *ws, const btba_lfnet_params *prm, LfnetScratch &L, int n_frames, int H, int W, int S,
+                           const float *const *score_dev, const int32_t *map_h, const int32_t *map_w, const float *scale_factors,
+                           float *heat_dev, float *scales_dev)
+{
+    LfnetMaps M{};
+    for (int s = 0; s < S; s++) { M.p[s] = score_dev[s]; M.h[s] = map_h[s]; M.w[s] = map_w[s]; M.sf[s] = scale_factors[s]; }
+    const int h = prm->sm_ksize / 2;
+    int T = 16;
+    if (sizeof(float) * lfnet_heat_lds_floats(S, T, h) > 80 * 1024) T = 8;
+    const size_t lds = sizeof(float) * lfnet_heat_lds_floats(S, T, h);          // at most 122 KB (S = 16, k = 31)
+    if (!ws->lfnet_attr_set) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lfnet_heat), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ws->lfnet_attr_set = true;
+    }
+    k_lfnet_moments<<<dim3(S, n_frames), 256, 0, ws->stream>>>(M, L.stats);
+    HIP_TRY(hipGetLastError());
+    k_lfnet_heat<<<dim3((W + T - 1) / T, (H + T - 1) / T, n_frames), 256, lds, ws->stream>>>(
+        M, L.stats, S, H, W, T, h, prm->com_strength, prm->score_com_strength, prm->scale_com_strength, prm->pad_size, heat_dev, scales_dev);
+    HIP_TRY(hipGetLastError());
+    return BTBA_OK;
+}
+
+int lfnet_select_enqueue(btba_workspace *ws, const btba_lfnet_params *prm, LfnetScratch &L, int n_frames, int H, int W, const float *heat_dev,
+                         int32_t *kpts_xy_dev, int32_t *n_kpts_dev)
+{
+    k_lfnet_peaks<<<dim3((H * W + 255) / 256, n_frames), 256, 0, ws->stream>>>(heat_dev, H, W, prm->nms_thresh, prm->nms_ksize / 2, L.peak);
+    HIP_TRY(hipGetLastError());
+    k_lfnet_select<<<n_frames, kLfnetSelectThreads, 0, ws->stream>>>(heat_dev, L.peak, H, W, prm->crop_radius, prm->top_k, L.list_idx, L.list_key,
+                                                                     kpts_xy_dev, n_kpts_dev);
+    HIP_TRY(hipGetLastError());
+    return BTBA_OK;
+}
+
+int lfnet_crops_enqueue(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, const float *photo_dev, const float *ori_dev,
+                        const float *heat_dev, const float *scales_dev, const int32_t *kpts_xy_dev, const int32_t *n_kpts_dev,
+                        float *kpts_out_dev, float *kpts_scale_out_dev, float *kpts_ori_out_dev, float *patches_out_dev)
+{
+    k_lfnet_crops<<<dim3(prm->top_k, n_frames), 64, 0, ws->stream>>>(photo_dev, ori_dev, heat_dev, scales_dev, kpts_xy_dev, n_kpts_dev, H, W,
+                                                                     prm->top_k, prm->soft_kpts, prm->kp_loc_size, prm->do_softmax_kp_refine,
+                                                                     prm->kp_com_strength, prm->patch_size, kpts_out_dev, kpts_scale_out_dev,
+                                                                     kpts_ori_out_dev, patches_out_dev);
+    HIP_TRY(hipGetLastError());
+    return BTBA_OK;
+}
+
+bool lfnet_maps_ok(int S, const float *const *score_dev, const int32_t *map_h, const int32_t *map_w, const float *scale_factors)
+{
+    if (S < 1 || S > BTBA_LFNET_MAX_SCALES || !score_dev || !map_h || !map_w || !scale_factors) return false;
+    for (int s = 0; s < S; s++)
+        if (!score_dev[s] || misaligned(score_dev[s], 4) || map_h[s] < 1 || map_w[s] < 1 || map_h[s] > 4 * BTBA_LFNET_MAX_SIZE ||
+            map_w[s] > 4 * BTBA_LFNET_MAX_SIZE || (int64_t)map_h[s] * map_w[s] > INT32_MAX)
+            return false;
+    return true;
+}
+}  // namespace
+
+int btba_lfnet_heatmaps(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, int S, const float *const *score_dev,
+                        const int32_t *map_h, const int32_t *map_w, const float *scale_factors, float *max_heatmaps_dev, float *max_scales_dev)
+{
+    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !lfnet_maps_ok(S, score_dev, map_h, map_w, scale_factors) || !max_heatmaps_dev ||
+        !max_scales_dev || misaligned(max_heatmaps_dev, 4) || misaligned(max_scales_dev, 4))
+        return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+    LfnetScratch L(n_frames, H, W);
+    if (int rc = L.sc.bind(ws->lfnet)) return rc;
+    return lfnet_heatmaps_enqueue(ws, prm, L, n_frames, H, W, S, score_dev, map_h, map_w, scale_factors, max_heatmaps_dev, max_scales_dev);
+}
+
+int btba_lfnet_select(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, const float *heat_dev,
+                      int32_t *kpts_xy_dev, int32_t *n_kpts_dev)
+{
+    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !heat_dev || !kpts_xy_dev || !n_kpts_dev || misaligned(heat_dev, 4) ||
+        misaligned(kpts_xy_dev, 4) || misaligned(n_kpts_dev, 4))
+        return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+    LfnetScratch L(n_frames, H, W);
+    if (int rc = L.sc.bind(ws->lfnet)) return rc;
+    return lfnet_select_enqueue(ws, prm, L, n_frames, H, W, heat_dev, kpts_xy_dev, n_kpts_dev);
+}
+
+int btba_lfnet_crops(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, const float *photo_dev, const float *ori_dev,
+                     const float *heat_dev, const float *scales_dev, const int32_t *kpts_xy_dev, const int32_t *n_kpts_dev,
+                     float *kpts_out_dev, float *kpts_scale_out_dev, float *kpts_ori_out_dev, float *patches_out_dev)
+{
+    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !photo_dev || !ori_dev || !heat_dev || !scales_dev || !kpts_xy_dev || !n_kpts_dev ||
+        !kpts_out_dev || !kpts_scale_out_dev || !kpts_ori_out_dev || !patches_out_dev)
+        return BTBA_EINVAL;
+    for (const void *q : { (const void *)photo_dev, (const void *)ori_dev, (const void *)heat_dev, (const void *)scales_dev, (const void *)kpts_xy_dev,
+                           (const void *)n_kpts_dev, (const void *)kpts_out_dev, (const void *)kpts_scale_out_dev, (const void *)kpts_ori_out_dev,
+                           (const void *)patches_out_dev })
+        if (misaligned(q, 4)) return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+    return lfnet_crops_enqueue(ws, prm, n_frames, H, W, photo_dev, ori_dev, heat_dev, scales_dev, kpts_xy_dev, n_kpts_dev, kpts_out_dev,
+                               kpts_scale_out_dev, kpts_ori_out_dev, patches_out_dev);
+}
+
+int btba_lfnet_keypoints(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, int S, const float *const *score_dev,
+                         const int32_t *map_h, const int32_t *map_w, const float *scale_factors, const float *photo_dev, const float *ori_dev,
+                         float *max_heatmaps_dev, float *max_scales_dev, int32_t *kpts_xy_dev, int32_t *n_kpts_dev, float *kpts_out_dev,
+                         float *kpts_scale_out_dev, float *kpts_ori_out_dev, float *patches_out_dev, int32_t *n_kpts_host)
+{
+    // every argument is checked before the first HIP call
+    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !lfnet_maps_ok(S, score_dev, map_h, map_w, scale_factors) || !photo_dev || !ori_dev ||
+        !max_heatmaps_dev || !max_scales_dev || !kpts_xy_dev || !n_kpts_dev || !kpts_out_dev || !kpts_scale_out_dev || !kpts_ori_out_dev ||
+        !patches_out_dev)
+        return BTBA_EINVAL;
+    for (const void *q : { (const void *)photo_dev, (const void *)ori_dev, (const void *)max_heatmaps_dev, (const void *)max_scales_dev,
+                           (const void *)kpts_xy_dev, (const void *)n_kpts_dev, (const void *)kpts_out_dev, (const void *)kpts_scale_out_dev,
+                           (const void *)kpts_ori_out_dev, (const void *)patches_out_dev })
+        if (misaligned(q, 4)) return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+    LfnetScratch L(n_frames, H, W);
+    if (int rc = L.sc.bind(ws->lfnet)) return rc;
+    if (int rc = lfnet_heatmaps_enqueue(ws, prm, L, n_frames, H, W, S, score_dev, map_h, map_w, scale_factors, max_heatmaps_dev, max_scales_dev)) return rc;
+    if (int rc = lfnet_select_enqueue(ws, prm, L, n_frames, H, W, max_heatmaps_dev, kpts_xy_dev, n_kpts_dev)) return rc;
+    if (int rc = lfnet_crops_enqueue(ws, prm, n_frames, H, W, photo_dev, ori_dev, max_heatmaps_dev, max_scales_dev, kpts_xy_dev, n_kpts_dev,
+                                     kpts_out_dev, kpts_scale_out_dev, kpts_ori_out_dev, patches_out_dev))
+        return rc;
+    if (n_kpts_host) {
+        HIP_TRY(hipMemcpyAsync(n_kpts_host, n_kpts_dev, sizeof(int32_t) * (size_t)n_frames, hipMemcpyDeviceToHost, ws->stream));
+        HIP_TRY(hipStreamSynchronize(ws->stream));                   // the call's one host wait
     }
     return BTBA_OK;
 }

@@ -758,6 +758,94 @@ BTBA_API int btba_detector_inputs(btba_workspace *ws, const btba_detector_params
 BTBA_API int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_params *params, int n_frames, const float *roi_host,
                                               const float *const *kpts_in_dev, const int32_t *n_kpts, float *const *kpts_out_dev);
 
+/* ---- keypoint head (between the detector's two conv nets) ---------------------------------------------------------
+ * Replaces the non-learned stage of lf-net-release/run_server.py between its score net and its descriptor net:
+ * inference.py::build_multi_scale_deep_detector_3DNMS (:159-241) and build_patch_extraction (:243-262), on det_tools.py
+ * (instance_normalization, soft_nms_3d, soft_max_and_argmax_1d, end_of_frame_masks, non_max_suppression,
+ * make_top_k_sparse_tensor, extract_keypoints, batch_gather_keypoints, soft_argmax_2d) and spatial_transformer.py::transformer_crop.
+ * The two conv nets stay with the caller.  The photo is what btba_detector_inputs writes as grey.  All images are row-major.
+ *
+ * Stage A, btba_lfnet_heatmaps.  score_dev[s]: device float [n_frames][map_h[s]][map_w[s]], the score maps of scale s for all frames
+ * (each scale has its own size; the detector makes them at int(H / s + 0.5)); scale_factors, map_h, map_w: host [S].
+ *   per map   mean, var = the mean and the biased variance (tf.nn.moments), accumulated in fp64;
+ *             logit = x * inv - mean * inv, inv = 1 / sqrt(var + 1e-3), in fp32 (tf.nn.batch_normalization)
+ *   resize    to H x W as TF1's resize_images: src = dst * (in / (float)out); lower tap floor(src), upper min(lower + 1, in - 1);
+ *             top = tl + (tr - tl) * fx, bottom = bl + (br - bl) * fx, value = top + (bottom - top) * fy
+ *   soft_nms_3d, N(q) = all S scales x the sm_ksize x sm_ksize window of q, cut to the image:
+ *             M(q) = max over N(q);  e_s(q) = exp(com_strength * (logit_s(q) - M(q)));  p_s(q) = e_s(q) / (sum over N(q) of e + 1e-6)
+ *   soft_max_and_argmax_1d over the S values of a pixel, m = max_s p_s:
+ *             heat  = sum_s p_s * (a_s / (sum_s a_s + 1e-8)),                a_s = exp(score_com_strength * (p_s - m))
+ *             scale = sum_s scale_factors[s] * (b_s / (sum_s b_s + 1e-8)),   b_s = exp(scale_com_strength * (p_s - m))
+ *   max_heatmaps = heat where pad_size <= y < H - pad_size and pad_size <= x < W - pad_size, else 0;  max_scales = scale.
+ * Outputs: device float [n_frames][H][W] each.  Two launches for all frames; the main one makes a workgroup tile with its halo
+ * in LDS (btba_lfnet.hpp) and writes nothing full-size but the two outputs.  The fp32 summation order is the kernel's own; the
+ * tests hold it to bars measured from the reference's fp32 run against fp64.
+ *
+ * Stage B, btba_lfnet_select: exact on any fp32 heat map float [n_frames][H][W] without NaN.
+ *   works = heat < nms_thresh ? 0 : heat;  peak(q) = works(q) > works(r) for all nms_ksize^2 - 1 neighbours r, 0 outside the image
+ *   score = heat * peak * (crop_radius frame mask);  tf.nn.top_k(score over the flattened frame, top_k): equal values go to the
+ *   lower flat index;  of the chosen positions those that are peaks survive, in raster order.
+ * With fewer than top_k positive scores the zero scores fill up from flat index 0 on, so a zero-score peak (one between pad_size and
+ * crop_radius) survives if its flat index minus the number of nonzero scores before it is below top_k minus the positive count.
+ * Outputs: kpts_xy_dev int32 [n_frames][top_k][2] (x, y; slots past the count are 0) and n_kpts_dev int32 [n_frames].
+ *
+ * Stage C, btba_lfnet_crops.  photo_dev float [n][H][W]; ori_dev float [n][H][W][2] (cos, sin, as the detector gives them); heat_dev and
+ * scales_dev: stage A's outputs; kpts_xy_dev, n_kpts_dev: stage B's.  Per keypoint (kx, ky): s = scales[ky][kx], (c, sn) = ori[ky][kx];
+ *   transformer_crop(img, n, (px, py), a b / c d): g_i = -1 + i * (2 / (n - 1)); for row i, column j
+ *             x = (a g_j + b g_i) * n / 2 + px,  y = (c g_j + d g_i) * n / 2 + py;  x0 = clamp(floor(x)), x1 = clamp(floor(x) + 1) into
+ *             0 .. W - 1, y likewise;  value = (x1 - x)(y1 - y) I[y0][x0] + (x1 - x)(y - y0) I[y1][x0] + (x - x0)(y1 - y) I[y0][x1] +
+ *             (x - x0)(y - y0) I[y1][x1] -- the weights from the CLAMPED taps, so a sample outside the image is zero or an odd blend,
+ *             not the border pixel (the descriptor was trained on that)
+ *   soft_kpts: v = transformer_crop(heat, kp_loc_size, (kx, ky), s 0 / 0 s);  w = do_softmax_kp_refine ? exp(kp_com_strength *
+ *             (v - max v)) / (sum + 1e-8) : v;  (dx, dy) = sum w * (g_j, g_i);  kpt = (kx, ky) + (dx, dy) * s * kp_loc_size / 2
+ *             (without soft_kpts: kpt = (kx, ky) as floats)
+ *   patch   = transformer_crop(photo, patch_size, kpt, s c  -s sn / s sn  s c)
+ * Outputs: kpts_out_dev float [n][top_k][2], kpts_scale_out_dev float [n][top_k], kpts_ori_out_dev float [n][top_k][2],
+ * patches_out_dev float [n][top_k][patch_size][patch_size]; slots past n_kpts are written as zero.  One wave per keypoint slot.
+ *
+ * btba_lfnet_keypoints: A, B and C for n_frames in one call without a host wait in between; bit-identical to the three calls.
+ * With n_kpts_host non-NULL the counts are copied there and the call waits once at the end; otherwise it is asynchronous on the
+ * workspace stream, as the three stages are.  Scratch: 9 H W bytes per frame in the workspace.
+ * BTBA_EINVAL, decided before any GPU work: NULL ws, params, pointer or table entry, or one not aligned to 4 bytes; n_frames < 1; H or W
+ * outside 1 .. BTBA_LFNET_MAX_SIZE; a map size < 1; S outside 1 .. BTBA_LFNET_MAX_SCALES; sm_ksize or nms_ksize even or outside
+ * 1 .. BTBA_LFNET_MAX_KSIZE; top_k outside 1 .. BTBA_LFNET_MAX_TOP_K; pad_size or crop_radius negative, or twice one of them not below
+ * min(H, W); patch_size or kp_loc_size outside 2 .. 64. */
+#define BTBA_LFNET_MAX_SCALES 16
+#define BTBA_LFNET_MAX_KSIZE 31
+#define BTBA_LFNET_MAX_TOP_K 2048
+#define BTBA_LFNET_MAX_SIZE 8192
+typedef struct btba_lfnet_params {
+    int32_t sm_ksize;                /* 15: the scale-space soft-max window */
+    float com_strength;              /* 3 */
+    float score_com_strength;        /* 100 */
+    float scale_com_strength;        /* 100 */
+    float nms_thresh;                /* 0 */
+    int32_t nms_ksize;               /* 5 */
+    int32_t top_k;                   /* 500 */
+    int32_t pad_size;                /* 16: the detector's own border */
+    int32_t crop_radius;             /* 16 */
+    int32_t soft_kpts;               /* 1 */
+    int32_t kp_loc_size;             /* 9 */
+    int32_t do_softmax_kp_refine;    /* 1 */
+    float kp_com_strength;           /* 1 */
+    int32_t patch_size;              /* 32 */
+} btba_lfnet_params;
+BTBA_API void btba_lfnet_params_default(btba_lfnet_params *p);
+BTBA_API int btba_lfnet_heatmaps(btba_workspace *ws, const btba_lfnet_params *params, int n_frames, int H, int W, int S,
+                                 const float *const *score_dev, const int32_t *map_h, const int32_t *map_w, const float *scale_factors,
+                                 float *max_heatmaps_dev, float *max_scales_dev);
+BTBA_API int btba_lfnet_select(btba_workspace *ws, const btba_lfnet_params *params, int n_frames, int H, int W, const float *heat_dev,
+                               int32_t *kpts_xy_dev, int32_t *n_kpts_dev);
+BTBA_API int btba_lfnet_crops(btba_workspace *ws, const btba_lfnet_params *params, int n_frames, int H, int W, const float *photo_dev,
+                              const float *ori_dev, const float *heat_dev, const float *scales_dev, const int32_t *kpts_xy_dev,
+                              const int32_t *n_kpts_dev, float *kpts_out_dev, float *kpts_scale_out_dev, float *kpts_ori_out_dev,
+                              float *patches_out_dev);
+BTBA_API int btba_lfnet_keypoints(btba_workspace *ws, const btba_lfnet_params *params, int n_frames, int H, int W, int S,
+                                  const float *const *score_dev, const int32_t *map_h, const int32_t *map_w, const float *scale_factors,
+                                  const float *photo_dev, const float *ori_dev, float *max_heatmaps_dev, float *max_scales_dev,
+                                  int32_t *kpts_xy_dev, int32_t *n_kpts_dev, float *kpts_out_dev, float *kpts_scale_out_dev,
+                                  float *kpts_ori_out_dev, float *patches_out_dev, int32_t *n_kpts_host);
+
 /* ---- pose accuracy: ADD and ADD-S (the YCBInEOAT evaluation) -------------------------------------------------------
  * The per-frame errors the reference's evaluation averages into its AUC figures (scripts/eval_ycbineoat.py:54-163 with
  * scripts/Utils.py:69-95, add / adi), for many evaluations in one call.  One evaluation is a model point set x_0 .. x_{N-1}

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_lfnet_params_default", "btba_lfnet_heatmaps", "btba_lfnet_select", "btba_lfnet_crops", "btba_lfnet_keypoints",
+    "btba_lfnet_desc_config_default", "btba_lfnet_desc_model_create", "btba_lfnet_desc_model_destroy", "btba_lfnet_descriptors",
     "btba_mask_params_default", "btba_apply_masks",
     "btba_detector_params_default", "btba_detector_transform", "btba_detector_inputs", "btba_detector_keypoints_to_image",
     "btba_pose_errors", "btba_nocs_params_default", "btba_nocs_errors",
@@ -98,6 +99,22 @@ class LfnetParams(C.Structure):
                 ("nms_thresh", C.c_float), ("nms_ksize", C.c_int32), ("top_k", C.c_int32), ("pad_size", C.c_int32), ("crop_radius", C.c_int32),
                 ("soft_kpts", C.c_int32), ("kp_loc_size", C.c_int32), ("do_softmax_kp_refine", C.c_int32), ("kp_com_strength", C.c_float),
                 ("patch_size", C.c_int32)]
+
+
+class LfnetDescConfig(C.Structure):
+    """btba_lfnet_desc_config (include/btba.h)."""
+    _fields_ = [("patch_size", C.c_int32), ("depth", C.c_int32), ("channels", C.c_int32), ("fc_dim", C.c_int32), ("out_dim", C.c_int32),
+                ("activation", C.c_int32), ("leaky_alpha", C.c_float), ("norm", C.c_int32), ("bn_eps", C.c_float)]
+
+
+class LfnetDescLayer(C.Structure):
+    """btba_lfnet_desc_layer (include/btba.h): host float arrays, NULL where the layer has none."""
+    _fields_ = [(n, C.c_void_p) for n in ("weights", "biases", "gamma", "beta", "moving_mean", "moving_variance")]
+
+
+class LfnetDescWeights(C.Structure):
+    """btba_lfnet_desc_weights (include/btba.h)."""
+    _fields_ = [("conv", LfnetDescLayer * 4), ("fc1", LfnetDescLayer), ("fc2", LfnetDescLayer)]
 
 
 class DetectorParams(C.Structure):
@@ -172,6 +189,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 HOST_DRIVER = os.path.join(os.path.dirname(_PKG), "tests", "cpp", "host_driver")
+LFNET_DESC_DRIVER = os.path.join(os.path.dirname(_PKG), "tests", "cpp", "liblfnet_desc_driver.so")
 
 
 def build_host_cpp(force: bool = False, verbose: bool = False) -> str:
@@ -179,15 +197,21 @@ def build_host_cpp(force: bool = False, verbose: bool = False) -> str:
     root = os.path.dirname(_PKG)
     srcs = [os.path.join(root, "tests", "cpp", "host_driver.cpp"), os.path.join(_PKG, "cpp", "btba_host.cpp")]
     deps = srcs + [os.path.join(_PKG, "cpp", "btba_host.hpp"), HEADER, LIB_PATH]
-    if not force and os.path.exists(HOST_DRIVER) and os.path.getmtime(HOST_DRIVER) >= max(os.path.getmtime(d) for d in deps):
-        return HOST_DRIVER
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", HOST_DRIVER] + srcs + [
-        "-L" + _PKG, "-lbtba", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
-        "-Wl,-rpath," + _PKG, "-Wl,-rpath,$ORIGIN/../../bundletrack_amd", "-Wl,-rpath," + os.path.join(rocm, "lib")]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+    link = ["-L" + _PKG, "-lbtba", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
+            "-Wl,-rpath," + _PKG, "-Wl,-rpath,$ORIGIN/../../bundletrack_amd", "-Wl,-rpath," + os.path.join(rocm, "lib")]
+    common = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include")]
+    # the descriptor net's ctypes driver (tests/test_gpu_lfnet_desc.py): a shared library over the same host layer
+    desc_src = os.path.join(root, "tests", "cpp", "lfnet_desc_driver.cpp")
+    targets = [(HOST_DRIVER, srcs, []), (LFNET_DESC_DRIVER, [desc_src, srcs[1]], ["-fPIC", "-shared"])]
+    for out, sources, extra in targets:
+        newest = max(os.path.getmtime(d) for d in deps + sources)
+        if not force and os.path.exists(out) and os.path.getmtime(out) >= newest:
+            continue
+        cmd = common + extra + ["-o", out] + sources + link
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
     return HOST_DRIVER
 
 
@@ -285,6 +309,12 @@ def lib() -> C.CDLL:
         L.btba_lfnet_select.argtypes = [C.c_void_p, C.POINTER(LfnetParams), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
         L.btba_lfnet_crops.argtypes = [C.c_void_p, C.POINTER(LfnetParams), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
         L.btba_lfnet_keypoints.argtypes = [C.c_void_p, C.POINTER(LfnetParams), C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 15
+        L.btba_lfnet_desc_config_default.argtypes = [C.POINTER(LfnetDescConfig)]
+        L.btba_lfnet_desc_config_default.restype = None
+        L.btba_lfnet_desc_model_create.argtypes = [C.c_void_p, C.POINTER(LfnetDescConfig), C.POINTER(LfnetDescWeights), C.POINTER(C.c_void_p)]
+        L.btba_lfnet_desc_model_destroy.argtypes = [C.c_void_p]
+        L.btba_lfnet_desc_model_destroy.restype = None
+        L.btba_lfnet_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_match_params_default.argtypes = [C.POINTER(MatchParams)]
         L.btba_match_params_default.restype = None
         L.btba_match_capacity.argtypes = [C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
@@ -378,6 +408,11 @@ def vos_params(**kw) -> VosParams:
 def lfnet_params(**kw) -> LfnetParams:
     """btba_lfnet_params_default with fields overridden by keyword."""
     return _params(LfnetParams, "btba_lfnet_params_default", kw)
+
+
+def lfnet_desc_config(**kw) -> LfnetDescConfig:
+    """btba_lfnet_desc_config_default with fields overridden by keyword."""
+    return _params(LfnetDescConfig, "btba_lfnet_desc_config_default", kw)
 
 
 def detector_params(**kw) -> DetectorParams:

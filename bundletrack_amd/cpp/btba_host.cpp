@@ -873,6 +873,38 @@ DetectedFeatures LfnetDetector::operator()(const uint8_t *, const float *gray_de
     return f;
 }
 
+btba_lfnet_desc_config lfnetDescConfig()
+{
+    btba_lfnet_desc_config c;
+    btba_lfnet_desc_config_default(&c);
+    return c;
+}
+
+void lfnetDescriptors(btba_workspace *ws, const btba_lfnet_desc_model *model, int n_frames, int slots, const float *patches_dev,
+                      const int32_t *n_kpts_dev, float *desc_dev)
+{
+    const int rc = btba_lfnet_descriptors(ws, model, n_frames, slots, patches_dev, n_kpts_dev, desc_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_descriptors");
+}
+
+LfnetDescriptor::LfnetDescriptor(btba_workspace *ws, const btba_lfnet_desc_config &config, const btba_lfnet_desc_weights &weights)
+    : ws_(ws), config_(config)
+{
+    const int rc = btba_lfnet_desc_model_create(ws, &config, &weights, &model_);
+    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_desc_model_create");
+}
+
+LfnetDescriptor::~LfnetDescriptor() { btba_lfnet_desc_model_destroy(model_); }
+
+LfnetDetector::DescFn LfnetDescriptor::asDescNet(float *desc_dev) const
+{
+    return [this, desc_dev](const float *patches_dev, int m, int &dim) {
+        dim = config_.out_dim;
+        describe(1, m, patches_dev, nullptr, desc_dev);
+        return desc_dev;
+    };
+}
+
 void DetectorFeatureManager::detectFeature(const std::shared_ptr<Frame> &frame)              // FeatureManager.cpp:811-908
 {
     prepareDetectorInputs(ws_, { frame }, bgr_, gray_, out_size_);

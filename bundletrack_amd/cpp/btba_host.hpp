@@ -364,6 +364,34 @@ private:
     LfnetBuffers out_;
 };
 
+// LF-Net's descriptor net (models/simple_desc.py::get_model in inference) on btba_lfnet_descriptors; the rules are in include/btba.h.
+btba_lfnet_desc_config lfnetDescConfig();                                        // btba_lfnet_desc_config_default
+// patches_dev float [n_frames][slots][P][P] -> desc_dev float [n_frames][slots][out_dim]; n_kpts_dev int32 [n_frames] on the device or
+// nullptr for all slots.  Asynchronous on the workspace stream; throws Error on a refusal.
+void lfnetDescriptors(btba_workspace *ws, const btba_lfnet_desc_model *model, int n_frames, int slots, const float *patches_dev,
+                      const int32_t *n_kpts_dev, float *desc_dev);
+// A model on a workspace (created from host arrays in TensorFlow's layouts, destroyed with the object; move-only).  asDescNet gives
+// the LfnetDetector::DescFn that writes into the caller's desc_dev [top_k][out_dim].
+class LfnetDescriptor {
+public:
+    LfnetDescriptor(btba_workspace *ws, const btba_lfnet_desc_config &config, const btba_lfnet_desc_weights &weights);
+    ~LfnetDescriptor();
+    LfnetDescriptor(const LfnetDescriptor &) = delete;
+    LfnetDescriptor &operator=(const LfnetDescriptor &) = delete;
+    LfnetDescriptor(LfnetDescriptor &&o) noexcept : ws_(o.ws_), config_(o.config_), model_(o.model_) { o.model_ = nullptr; }
+    const btba_lfnet_desc_config &config() const { return config_; }
+    const btba_lfnet_desc_model *model() const { return model_; }
+    void describe(int n_frames, int slots, const float *patches_dev, const int32_t *n_kpts_dev, float *desc_dev) const
+    {
+        lfnetDescriptors(ws_, model_, n_frames, slots, patches_dev, n_kpts_dev, desc_dev);
+    }
+    LfnetDetector::DescFn asDescNet(float *desc_dev) const;
+private:
+    btba_workspace *ws_;
+    btba_lfnet_desc_config config_;
+    btba_lfnet_desc_model *model_ = nullptr;
+};
+
 // SiftManager::findCorres (FeatureManager.cpp:173-240) with its map points on btba_corres_chain: NN, propagation along the map
 // points, RANSAC (ransac.max_iter / inlier_dist of yml), the map-point update and the FAIL gates for an ordered list of pairs in one
 // call, the frames' map points in a btba_mappoints on `ws` (a frame is registered at its first pair, by _id; forgetFrame frees its

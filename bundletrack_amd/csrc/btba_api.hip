@@ -26,6 +26,7 @@
 #include "btba_ingest.hpp"
 #include "btba_vos.hpp"
 #include "btba_lfnet.hpp"
+#include "btba_lfnet_desc.hpp"
 #include "btba_ransac.hpp"
 #include "btba_xorwow.hpp"
 #include "btba_match.hpp"
@@ -213,6 +214,7 @@ struct btba_workspace {
     DevBuf corres;                                          // btba_corres_chain: frame / pair tables, NN output, working lists, per-pair words
     DevBuf vos;                                             // btba_vos_propagate: the key splits' partial (m, l, acc) per item and target position
     DevBuf lfnet;                                           // btba_lfnet_*: per-map moments, peak flags, the compacted peak list
+    DevBuf lfnet_desc;                                      // btba_lfnet_descriptors: two buffers of a chunk's widest layer
     DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
@@ -2809,6 +2811,171 @@ int btba_lfnet_keypoints(btba_workspace *ws, const btba_lfnet_params *prm, int n
     if (n_kpts_host) {
         HIP_TRY(hipMemcpyAsync(n_kpts_host, n_kpts_dev, sizeof(int32_t) * (size_t)n_frames, hipMemcpyDeviceToHost, ws->stream));
         HIP_TRY(hipStreamSynchronize(ws->stream));                   // the call's one host wait
+    }
+    return BTBA_OK;
+}
+
+void btba_lfnet_desc_config_default(btba_lfnet_desc_config *c)
+{
+    if (!c) return;
+    c->patch_size = 32; c->depth = 3; c->channels = 64; c->fc_dim = 512; c->out_dim = 256;      // simple_desc.py:10-14, run_server.py's checkpoint
+    c->activation = 0; c->leaky_alpha = 0.2f; c->norm = 0;
+    c->bn_eps = 1e-5f;                                                // tf_layer_utils.py:185
+}
+
+struct btba_lfnet_desc_model {
+    btba_workspace *ws = nullptr;
+    int device = 0;
+    btba_lfnet_desc_config cfg{};
+    struct Layer { size_t w = 0, scale = 0, shift = 0; int K = 0, N = 0; };      // offsets in floats into dev
+    Layer layers[BTBA_LFNET_DESC_MAX_DEPTH + 2];
+    int n_layers = 0;
+    size_t widest = 0;                     // floats per patch of the widest layer output
+    DevBuf dev;
+};
+
+namespace {
+bool desc_config_ok(const btba_lfnet_desc_config *c)
+{
+    if (!c || c->depth < 1 || c->depth > BTBA_LFNET_DESC_MAX_DEPTH || c->patch_size < 8 || c->patch_size > 64 || c->patch_size % (1 << c->depth)) return false;
+    if (c->channels < 16 || c->channels > 128 || c->channels % 16 || c->fc_dim < 16 || c->fc_dim > 1024 || c->fc_dim % 16) return false;
+    if (c->out_dim < 16 || c->out_dim > 512 || c->out_dim % 16 || c->activation < 0 || c->activation > 1 || c->norm < 0 || c->norm > 1) return false;
+    if (!std::isfinite(c->leaky_alpha) || !std::isfinite(c->bn_eps) || c->bn_eps < 0.0f) return false;
+    const int s = c->patch_size >> c->depth;
+    return (int64_t)s * s * (c->channels << (c->depth - 1)) <= 16384;
+}
+bool all_finite(const float *a, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+}  // namespace
+
+int btba_lfnet_desc_model_create(btba_workspace *ws, const btba_lfnet_desc_config *cfg, const btba_lfnet_desc_weights *wts, btba_lfnet_desc_model **out)
+{
+    if (out) *out = nullptr;
+    if (!ws || !wts || !out || !desc_config_ok(cfg)) return BTBA_EINVAL;
+    const int depth = cfg->depth, n_layers = depth + 2;
+    const btba_lfnet_desc_layer *src[BTBA_LFNET_DESC_MAX_DEPTH + 2];
+    int Ks[BTBA_LFNET_DESC_MAX_DEPTH + 2], Ns[BTBA_LFNET_DESC_MAX_DEPTH + 2];
+    size_t widest = 0;
+    for (int i = 0; i < depth; i++) {
+        src[i] = &wts->conv[i];
+        Ks[i] = 9 * (i ? cfg->channels << (i - 1) : 1);
+        Ns[i] = cfg->channels << i;
+        const size_t s = (size_t)(cfg->patch_size >> (i + 1));
+        widest = std::max(widest, s * s * Ns[i]);
+    }
+    const int flat = (cfg->patch_size >> depth) * (cfg->patch_size >> depth) * Ns[depth - 1];
+    src[depth] = &wts->fc1; Ks[depth] = flat; Ns[depth] = cfg->fc_dim;
+    src[depth + 1] = &wts->fc2; Ks[depth + 1] = cfg->fc_dim; Ns[depth + 1] = cfg->out_dim;
+    widest = std::max(widest, (size_t)std::max(cfg->fc_dim, cfg->out_dim));
+    for (int i = 0; i < n_layers; i++) {
+        const btba_lfnet_desc_layer &l = *src[i];
+        const size_t N = (size_t)Ns[i];
+        if (!l.weights || !all_finite(l.weights, (size_t)Ks[i] * N) || (l.biases && !all_finite(l.biases, N))) return BTBA_EINVAL;
+        if ((l.moving_mean == nullptr) != (l.moving_variance == nullptr)) return BTBA_EINVAL;
+        if (l.moving_mean) {
+            if (!all_finite(l.moving_mean, N) || !all_finite(l.moving_variance, N) || (l.gamma && !all_finite(l.gamma, N)) ||
+                (l.beta && !all_finite(l.beta, N)))
+                return BTBA_EINVAL;
+            for (size_t n = 0; n < N; n++)
+                if (!((double)l.moving_variance[n] + (double)cfg->bn_eps > 0.0)) return BTBA_EINVAL;
+        }
+    }
+    // every argument has been checked; the first HIP call follows
+    std::unique_ptr<btba_lfnet_desc_model> M(new (std::nothrow) btba_lfnet_desc_model());
+    if (!M) return BTBA_ENOMEM;
+    M->ws = ws; M->device = ws->device; M->cfg = *cfg; M->n_layers = n_layers; M->widest = widest;
+    auto pad64 = [](size_t n) { return (n + 63) & ~(size_t)63; };    // 256-byte regions: 16-byte loads of weight rows
+    size_t total = 0;
+    for (int i = 0; i < n_layers; i++) {
+        btba_lfnet_desc_model::Layer &L = M->layers[i];
+        L.K = Ks[i]; L.N = Ns[i];
+        L.w = total; total += pad64((size_t)Ks[i] * Ns[i]);
+        L.scale = total; total += pad64(Ns[i]);
+        L.shift = total; total += pad64(Ns[i]);
+    }
+    std::vector<float> host(total, 0.0f);
+    for (int i = 0; i < n_layers; i++) {
+        const btba_lfnet_desc_layer &l = *src[i];
+        const btba_lfnet_desc_model::Layer &L = M->layers[i];
+        std::memcpy(host.data() + L.w, l.weights, sizeof(float) * (size_t)L.K * L.N);      // [3][3][C_in][C_out] IS [K][N] in (ky, kx, c_in) order
+        for (int n = 0; n < L.N; n++) {
+            const double bias = l.biases ? (double)l.biases[n] : 0.0;
+            double scale = 1.0, shift = bias;
+            if (l.moving_mean) {
+                scale = (l.gamma ? (double)l.gamma[n] : 1.0) / std::sqrt((double)l.moving_variance[n] + (double)cfg->bn_eps);
+                shift = (l.beta ? (double)l.beta[n] : 0.0) + (bias - (double)l.moving_mean[n]) * scale;
+            }
+            host[L.scale + n] = (float)scale;
+            host[L.shift + n] = (float)shift;
+        }
+    }
+    DeviceGuard device_guard(ws);
+    if (int rc = M->dev.ensure(sizeof(float) * total)) return rc;
+    HIP_TRY(hipMemcpy(M->dev.p, host.data(), sizeof(float) * total, hipMemcpyHostToDevice));
+    *out = M.release();
+    return BTBA_OK;
+}
+
+void btba_lfnet_desc_model_destroy(btba_lfnet_desc_model *M)
+{
+    if (!M) return;
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
+    (void)hipDeviceSynchronize();                                     // delete frees the weights; no workspace access
+    delete M;
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+int btba_lfnet_descriptors(btba_workspace *ws, const btba_lfnet_desc_model *M, int n_frames, int slots, const float *patches_dev,
+                           const int32_t *n_kpts_dev, float *desc_dev)
+{
+    // the counts first: a model is not read before they are known to be sane
+    if (!ws || !M || n_frames < 0 || slots < 0 || slots > BTBA_LFNET_MAX_TOP_K || (int64_t)n_frames * slots > (1 << 24)) return BTBA_EINVAL;
+    const int total = n_frames * slots;
+    if (total == 0) return BTBA_OK;
+    if (!patches_dev || !desc_dev || misaligned(patches_dev, 4) || misaligned(desc_dev, 4) || misaligned(n_kpts_dev, 4) || M->ws != ws) return BTBA_EINVAL;
+    DeviceGuard device_guard(ws);
+    const btba_lfnet_desc_config &c = M->cfg;
+    const int chunk = std::min(total, kDescChunk), P = c.patch_size, depth = c.depth, D = c.out_dim;
+    Scratch sc;
+    Scratch::Region<float> b0 = sc.add<float>((size_t)chunk * M->widest), b1 = sc.add<float>((size_t)chunk * M->widest);
+    if (int rc = sc.bind(ws->lfnet_desc)) return rc;
+    float *buf[2] = { b0, b1 };
+    const float *W = M->dev.as<float>();
+    for (int p0 = 0; p0 < total; p0 += chunk) {
+        const int np = std::min(chunk, total - p0);
+        {
+            const btba_lfnet_desc_model::Layer &L = M->layers[0];
+            DescConv1 G{};
+            G.patches = patches_dev + (size_t)p0 * P * P; G.w = W + L.w; G.scale = W + L.scale; G.shift = W + L.shift; G.out = buf[0];
+            G.n_kpts = n_kpts_dev; G.n_patches = np; G.P = P; G.Ho = P / 2; G.pad = 0; G.C = L.N; G.act = c.activation; G.slots = slots;
+            G.patch0 = p0; G.alpha = c.leaky_alpha;
+            const int64_t threads = (int64_t)np * G.Ho * G.Ho * (L.N / 4);
+            k_desc_conv1<<<(unsigned)((threads + 255) / 256), 256, 0, ws->stream>>>(G);
+            HIP_TRY(hipGetLastError());
+        }
+        for (int i = 1; i < M->n_layers; i++) {
+            const btba_lfnet_desc_model::Layer &L = M->layers[i];
+            const bool conv = i < depth;
+            DescGemm G{};
+            G.in = buf[(i - 1) & 1]; G.out = buf[i & 1]; G.w = W + L.w; G.scale = W + L.scale; G.shift = W + L.shift; G.n_kpts = n_kpts_dev;
+            G.N = L.N; G.K = L.K; G.slots = slots; G.patch0 = p0; G.alpha = c.leaky_alpha;
+            if (conv) {               // an even input size: TensorFlow's SAME pads nothing before and one row and column after
+                G.Hi = G.Wi = P >> i; G.Ho = G.Wo = P >> (i + 1); G.Cin = L.K / 9; G.ks = 3; G.pad = 0; G.act = c.activation;
+            } else {
+                G.Hi = G.Wi = G.Ho = G.Wo = 1; G.Cin = L.K; G.ks = 1; G.pad = 0; G.act = i == depth ? c.activation : kDescActNone;
+            }
+            G.M = np * G.Ho * G.Wo;
+            k_desc_gemm<<<dim3((G.M + kDescBM - 1) / kDescBM, (G.N + kDescBN - 1) / kDescBN), 256, 0, ws->stream>>>(G);
+            HIP_TRY(hipGetLastError());
+        }
+        k_desc_finish<<<(np + 3) / 4, 256, 0, ws->stream>>>(buf[(M->n_layers - 1) & 1], desc_dev + (size_t)p0 * D, n_kpts_dev, np, D, c.norm == 0,
+                                                             slots, p0);
+        HIP_TRY(hipGetLastError());
     }
     return BTBA_OK;
 }

@@ -846,6 +846,72 @@ BTBA_API int btba_lfnet_keypoints(btba_workspace *ws, const btba_lfnet_params *p
                                   int32_t *kpts_xy_dev, int32_t *n_kpts_dev, float *kpts_out_dev, float *kpts_scale_out_dev,
                                   float *kpts_ori_out_dev, float *patches_out_dev, int32_t *n_kpts_host);
 
+/* ---- descriptor net (between the keypoint head's crops and the matcher) ---------------------------------------------
+ * LF-Net's descriptor net, lf-net-release/models/simple_desc.py::get_model on common/tf_layer_utils.py, in inference: `depth`
+ * stride-2 3 x 3 convolutions (1 -> channels -> 2 channels -> ...), each followed by batch norm and the activation, flatten, a
+ * fully connected layer to fc_dim with batch norm and the activation, a fully connected layer to out_dim, l2_normalize.  All of it in
+ * fp32 with fp32 accumulation (the convolutions from layer 2 on and the fully connected layers on v_mfma_f32_32x32x2_f32, whose result
+ * is a k-ordered fmaf chain; layer 1 on the vector ALU), every dot product in ONE fixed k order: a patch's descriptor is the same
+ * bits whatever the batch around it, its slot or its frame.
+ *
+ * The rules:
+ *   convolution   TensorFlow's SAME with stride 2 pads asymmetrically: out = ceil(in / 2), total = max((out - 1) * 2 + 3 - in, 0),
+ *                 before = total / 2 (integer division) and the rest after.  For an even size nothing is padded before and ONE row
+ *                 and ONE column after: output (oy, ox) reads input rows 2 oy .. 2 oy + 2 and columns 2 ox .. 2 ox + 2.
+ *                 weights [3][3][C_in][C_out]; the sum runs over (ky, kx, c_in) in that order.
+ *   batch norm    folded at model creation, in fp64 on the host and rounded once to fp32:
+ *                 scale = gamma / sqrt(moving_variance + bn_eps),  shift = beta + (bias - moving_mean) * scale;
+ *                 y = acc * scale + shift.  Without batch norm (NULL moving_*): scale = 1, shift = bias.
+ *   activation    0 relu: max(y, 0);  1 leaky relu: y >= 0 ? y : leaky_alpha * y
+ *   flatten       (h, w, c): the last convolution's NHWC output as it lies
+ *   l2_normalize  x * rsqrt(max(sum x^2, 1e-12)) over a descriptor
+ *
+ * btba_lfnet_desc_model_create checks the configuration and every array (finite values; moving_variance + bn_eps > 0), folds the batch
+ * norms, and uploads the weights in the [K][C_out] layout the kernels' B operand reads (K = 9 C_in or the fully connected layer's
+ * inputs).  It is the one call here that allocates and waits.  A model belongs to the workspace it was created with and must be
+ * destroyed before it.
+ * btba_lfnet_descriptors: patches_dev float [n_frames][slots][P][P] -> desc_dev float [n_frames][slots][out_dim].  n_kpts_dev: int32
+ * [n_frames] on the device, the number of leading slots of each frame that hold a patch (values outside 0 .. slots are clamped), or
+ * NULL for all.  Slots past the count are written as zero and their work is skipped.  Asynchronous on the workspace stream, no
+ * allocation once the workspace scratch has grown, no host wait.  n_frames * slots == 0 is success without a launch (the three device
+ * pointers are then not looked at).
+ * BTBA_EINVAL, decided before any GPU work.  create: NULL ws, config, weights or out; patch_size outside 8 .. 64 or not divisible by
+ * 2^depth; depth outside 1 .. 4; channels not a multiple of 16 in 16 .. 128; fc_dim not a multiple of 16 in 16 .. 1024; out_dim not a
+ * multiple of 16 in 16 .. 512; activation not 0 or 1; norm not 0 or 1; leaky_alpha or bn_eps not finite, bn_eps < 0; flatten size
+ * (patch_size / 2^depth)^2 * channels * 2^(depth - 1) above 16384; a NULL `weights` array of a used layer; only one of moving_mean and
+ * moving_variance given; a non-finite value; moving_variance + bn_eps <= 0.  descriptors: NULL ws, model, patches_dev or desc_dev, or
+ * one of the three device pointers not aligned to 4 bytes; n_frames or slots negative; slots above BTBA_LFNET_MAX_TOP_K; n_frames * slots above 2^24; a model created with another workspace. */
+#define BTBA_LFNET_DESC_MAX_DEPTH 4
+typedef struct btba_lfnet_desc_config {
+    int32_t patch_size;              /* 32 */
+    int32_t depth;                   /* 3: convolution layers */
+    int32_t channels;                /* 64: of layer 1; layer i has channels * 2^i */
+    int32_t fc_dim;                  /* 512 */
+    int32_t out_dim;                 /* 256 */
+    int32_t activation;              /* 0 relu, 1 leaky relu */
+    float leaky_alpha;               /* 0.2 */
+    int32_t norm;                    /* 0 l2norm, 1 none */
+    float bn_eps;                    /* 1e-5: _BATCH_NORM_EPSILON of tf_layer_utils.tf_batch_norm_act */
+} btba_lfnet_desc_config;
+/* One layer's arrays, host pointers in TensorFlow's own layouts: weights [3][3][C_in][C_out] or [in][out]; the others [C_out].
+ * NULL biases = none; NULL moving_mean and moving_variance = no batch norm on the layer (gamma and beta are then not read);
+ * NULL gamma = 1, NULL beta = 0. */
+typedef struct btba_lfnet_desc_layer {
+    const float *weights, *biases, *gamma, *beta, *moving_mean, *moving_variance;
+} btba_lfnet_desc_layer;
+typedef struct btba_lfnet_desc_weights {
+    btba_lfnet_desc_layer conv[BTBA_LFNET_DESC_MAX_DEPTH];     /* SimpleDesc/conv{i+1} and SimpleDesc/bn{i+1}; the first `depth` are read */
+    btba_lfnet_desc_layer fc1;                                 /* SimpleDesc/fc1 and SimpleDesc/fc-bn1 */
+    btba_lfnet_desc_layer fc2;                                 /* SimpleDesc/fc2: weights and biases (no activation follows) */
+} btba_lfnet_desc_weights;
+typedef struct btba_lfnet_desc_model btba_lfnet_desc_model;
+BTBA_API void btba_lfnet_desc_config_default(btba_lfnet_desc_config *c);
+BTBA_API int btba_lfnet_desc_model_create(btba_workspace *ws, const btba_lfnet_desc_config *config, const btba_lfnet_desc_weights *weights,
+                                          btba_lfnet_desc_model **out);
+BTBA_API void btba_lfnet_desc_model_destroy(btba_lfnet_desc_model *model);
+BTBA_API int btba_lfnet_descriptors(btba_workspace *ws, const btba_lfnet_desc_model *model, int n_frames, int slots,
+                                    const float *patches_dev, const int32_t *n_kpts_dev, float *desc_dev);
+
 /* ---- pose accuracy: ADD and ADD-S (the YCBInEOAT evaluation) -------------------------------------------------------
  * The per-frame errors the reference's evaluation averages into its AUC figures (scripts/eval_ycbineoat.py:54-163 with
  * scripts/Utils.py:69-95, add / adi), for many evaluations in one call.  One evaluation is a model point set x_0 .. x_{N-1}

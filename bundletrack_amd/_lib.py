@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -175,44 +176,64 @@ class BtbaError(RuntimeError):
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-pass-failed", "-fPIC", "-shared", "-fvisibility=hidden"]
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
+def build(force: bool = False, verbose: bool = False, out: str | None = None, extra_flags=()) -> str:
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU).
+
+    Every csrc/*.hip is one translation unit: compiled concurrently into build/<library name>/ beside the library, then linked.
+    `out` (another library path) and `extra_flags` (compile flags such as -save-temps or -DBTBA_REFERENCE_ORDER; temporaries land in
+    the object directory) are for developer A/B builds.  Anything in csrc/ or include/btba.h newer than the library rebuilds all of it.
+    """
+    out = os.path.abspath(out or LIB_PATH)
     srcs = [os.path.join(SRC_DIR, f) for f in os.listdir(SRC_DIR)] + [HEADER]
     newest = max(os.path.getmtime(s) for s in srcs)
-    if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
-        return LIB_PATH
-    cmd = ["hipcc"] + HIPCC_FLAGS + ["-o", LIB_PATH, os.path.join(SRC_DIR, "btba_api.hip")]
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= newest:
+        return out
+    units = sorted(s for s in srcs if s.endswith(".hip"))
+    obj_dir = os.path.join(os.path.dirname(out), "build", os.path.splitext(os.path.basename(out))[0])
+    os.makedirs(obj_dir, exist_ok=True)
+    objs = [os.path.join(obj_dir, os.path.splitext(os.path.basename(u))[0] + ".o") for u in units]
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd, cwd=obj_dir)
+
+    compile_flags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags)
+    jobs = min(len(units), 16, os.cpu_count() or 1, int(os.environ.get("MAX_JOBS") or 16))
+    with ThreadPoolExecutor(max(jobs, 1)) as pool:
+        list(pool.map(run, [["hipcc"] + compile_flags + ["-c", "-o", o, u] for u, o in zip(units, objs)]))
+    run(["hipcc"] + HIPCC_FLAGS + ["-o", out] + objs)
+    return out
+
+
+HOST_DRIVER = os.path.join(_ROOT, "tests", "cpp", "host_driver")
+LFNET_DESC_DRIVER = os.path.join(_ROOT, "tests", "cpp", "liblfnet_desc_driver.so")
+
+
+def build_driver(name: str, shared: bool = True, force: bool = False, verbose: bool = False) -> str:
+    """Compile tests/cpp/<name>.cpp together with the C++ host layer (bundletrack_amd/cpp) against libbtba.so: the shared library
+    tests/cpp/lib<name>.so, or with shared=False the program tests/cpp/<name>.  Rebuilt when older than a source, a header or the library."""
+    cpp = os.path.join(_ROOT, "tests", "cpp")
+    out = os.path.join(cpp, f"lib{name}.so" if shared else name)
+    srcs = [os.path.join(cpp, name + ".cpp"), os.path.join(_PKG, "cpp", "btba_host.cpp")]
+    deps = srcs + [os.path.join(_PKG, "cpp", "btba_host.hpp"), HEADER, LIB_PATH]
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
+        return out
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include")]
+    cmd += (["-fPIC", "-shared"] if shared else []) + ["-o", out] + srcs
+    cmd += ["-L" + _PKG, "-lbtba", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
+            "-Wl,-rpath," + _PKG, "-Wl,-rpath,$ORIGIN/../../bundletrack_amd", "-Wl,-rpath," + os.path.join(rocm, "lib")]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    return LIB_PATH
-
-
-HOST_DRIVER = os.path.join(os.path.dirname(_PKG), "tests", "cpp", "host_driver")
-LFNET_DESC_DRIVER = os.path.join(os.path.dirname(_PKG), "tests", "cpp", "liblfnet_desc_driver.so")
+    return out
 
 
 def build_host_cpp(force: bool = False, verbose: bool = False) -> str:
-    """Compile the C++ host layer (bundletrack_amd/cpp) and its test driver against libbtba.so."""
-    root = os.path.dirname(_PKG)
-    srcs = [os.path.join(root, "tests", "cpp", "host_driver.cpp"), os.path.join(_PKG, "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(_PKG, "cpp", "btba_host.hpp"), HEADER, LIB_PATH]
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    link = ["-L" + _PKG, "-lbtba", "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
-            "-Wl,-rpath," + _PKG, "-Wl,-rpath,$ORIGIN/../../bundletrack_amd", "-Wl,-rpath," + os.path.join(rocm, "lib")]
-    common = ["g++", "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include")]
-    # the descriptor net's ctypes driver (tests/test_gpu_lfnet_desc.py): a shared library over the same host layer
-    desc_src = os.path.join(root, "tests", "cpp", "lfnet_desc_driver.cpp")
-    targets = [(HOST_DRIVER, srcs, []), (LFNET_DESC_DRIVER, [desc_src, srcs[1]], ["-fPIC", "-shared"])]
-    for out, sources, extra in targets:
-        newest = max(os.path.getmtime(d) for d in deps + sources)
-        if not force and os.path.exists(out) and os.path.getmtime(out) >= newest:
-            continue
-        cmd = common + extra + ["-o", out] + sources + link
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    return HOST_DRIVER
+    """Compile the C++ host layer's test program (tests/cpp/host_driver) and the descriptor net's ctypes driver."""
+    build_driver("lfnet_desc_driver", force=force, verbose=verbose)
+    return build_driver("host_driver", shared=False, force=force, verbose=verbose)
 
 
 _lib = None

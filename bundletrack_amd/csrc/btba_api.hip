@@ -5,247 +5,17 @@
 // SolverBundling.cu:931-1003), re-designed for MI355X: no per-call allocation storm (grow-only
 // workspace), no per-iteration host sync (the dense pair list is static), three launches per
 // Gauss-Newton iteration, batches of independent instances in one grid.
-#include <hip/hip_runtime.h>
+//
+// This unit holds the workspace, the solver and the frame / correspondence pools; the other components' entry points are in
+// btba_api_{image,vos,lfnet,corres,eval}.hip.  What they share is btba_host_common.hpp.
 #include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <cstdlib>
-#include <new>
-#include <string>
-#include <map>
-#include <memory>
-#include <utility>
-#include <vector>
 
-#include "../../include/btba.h"
+#include "btba_host_common.hpp"
 #include "btba_kernels.hpp"
 #include "btba_solve_small.hpp"
 #include "btba_solve_mid.hpp"
-#include "btba_image.hpp"
-#include "btba_ingest.hpp"
-#include "btba_vos.hpp"
-#include "btba_lfnet.hpp"
-#include "btba_lfnet_desc.hpp"
-#include "btba_ransac.hpp"
-#include "btba_xorwow.hpp"
-#include "btba_match.hpp"
-#include "btba_mask.hpp"
-#include "btba_detect.hpp"
-#include "btba_eval.hpp"
-#include "btba_nocs.hpp"
-#include "btba_mappoints.hpp"
-#include "btba_window.hpp"
 
-using namespace btba;
-
-static thread_local int g_last_hip_error = 0;
-
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t e_ = (expr);                         \
-        if (e_ != hipSuccess) {                         \
-            g_last_hip_error = (int)e_;                 \
-            return BTBA_EHIP;                           \
-        }                                               \
-    } while (0)
-
-namespace {
-
-// Growable device memory that frees itself.  Move-only: a copy would be a second owner of p.
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept
-    {
-        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return BTBA_OK;
-        if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) { g_last_hip_error = (int)e; return BTBA_EHIP; } }
-        size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; p = nullptr; return e == hipErrorOutOfMemory ? BTBA_ENOMEM : BTBA_EHIP; }
-        cap = want;
-        return BTBA_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-// Growable pinned host memory that frees itself.  `want` is the capacity allocated when the block has to grow.
-struct PinBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    PinBuf() = default;
-    PinBuf(const PinBuf &) = delete;
-    PinBuf &operator=(const PinBuf &) = delete;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    int ensure(size_t bytes, size_t want = 0)
-    {
-        if (bytes <= cap) return BTBA_OK;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        if (!want) want = bytes + bytes / 2 + 4096;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; p = nullptr; return e == hipErrorOutOfMemory ? BTBA_ENOMEM : BTBA_EHIP; }
-        cap = want;
-        return BTBA_OK;
-    }
-};
-
-// The layout of one call's scratch in a DevBuf.  Regions are added in order; a present region takes its bytes rounded up to
-// 256, an absent one takes none and reads as nullptr.  After bind() a region converts to its typed device pointer.
-struct Scratch {
-    size_t bytes = 0;
-    unsigned char *base = nullptr;
-    template <class T> struct Region {
-        const Scratch *s; size_t off; bool present;
-        operator T *() const { return present ? reinterpret_cast<T *>(s->base + off) : nullptr; }
-    };
-    template <class T> Region<T> add(size_t count, bool present = true)
-    {
-        Region<T> r{ this, bytes, present };
-        if (present) bytes += (sizeof(T) * count + 255) & ~(size_t)255;
-        return r;
-    }
-    int bind(DevBuf &buf, size_t floor = 0) { int rc = buf.ensure(bytes > floor ? bytes : floor); base = buf.as<unsigned char>(); return rc; }
-};
-
-inline bool misaligned(const void *q, size_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
-
-struct EventPair { hipEvent_t a, b; int kind; };   // kind 0 dense, 1 sparse, 2 system, 3 solve region, 4 cache
-
-}  // namespace
-
-struct btba_workspace {
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
-    int device = 0;
-    DevBuf x, T, Tinv, sparse_part, dense_part, pairsum, dense_pairs, ptrs, big_A, solve_tab;
-    DevBuf corr, offsets, poses, campos, normals, nvalid;   // optimize_frames staging
-    DevBuf valid_lists, valid_counts;                       // per-frame lists of pixels with a depth (compact cache)
-    DevBuf block_ranges;                                    // per (frame, 8 x 8 block) usable depth range: dead-block test of the dense sweep
-    DevBuf chain_sync;                                      // chained launch: flags[B] + arrivals[n_gn][B] (zeroed before every launch), optional timeline
-    DevBuf chain_trace;
-    DevBuf corr24_tmp;                                      // re-layout of a call's EntryJ array written by its first iteration's sparse sweep (BTBA_OPT_RELAYOUT)
-    DevBuf live_blocks;                                     // BTBA_OPT_COUNT_LIVE: one uint64 the block-walk workgroups add their walked blocks to
-    bool count_live = false;
-    int *chain_error = nullptr;                             // pinned host word the chained launch's watchdog raises (checked at every host synchronisation)
-    bool chain_failed = false;                              // a watchdog fired on this workspace: chaining stays off from then on
-    bool chain_reported = false;                            // ... and an enqueue has already returned BTBA_ESCHED for it (the word itself is cleared only after a sync)
-    uint64_t chain_launches = 0;
-    // Developer / tuning switches.  Read from the environment ONCE, when the workspace is created (never on the solve path), and settable
-    // per workspace through btba_workspace_set_option (include/btba.h: BTBA_OPT_*).  None of them changes what is computed.
-    struct Tuning {
-        bool dense_order = true;       // BTBA_OPT_DENSE_ORDER   (env BTBA_NO_DENSE_ORDER=1 turns it off): dense pairs worked off heaviest first
-        bool tile_major = true;        // BTBA_OPT_TILE_MAJOR    (env BTBA_PAIR_MAJOR=1 turns it off): (band, pair) instead of (pair, band) work order
-        bool block_walk = true;        // BTBA_OPT_BLOCK_WALK    (env BTBA_NO_BLOCK_WALK=1): waves walk 8 x 8 blocks instead of 64 x 1 strips
-        bool block_skip = true;        // BTBA_OPT_BLOCK_SKIP    (env BTBA_NO_BLOCK_SKIP=1): provably dead blocks are not walked
-        int sparse_tail_256 = -1;      // BTBA_OPT_SPARSE_TAIL   (env BTBA_SPARSE_TAIL): share (x / 256) of the sparse items that close the fused launch; -1 = the library's choice
-        bool big_assembly = true;      // BTBA_OPT_BIG_ASSEMBLY  (env BTBA_NO_BIG_ASSEMBLY=1): many-workgroup reduction / assembly from 24 frames on
-        int overlap_groups = 2;        // BTBA_OPT_OVERLAP_GROUPS (env BTBA_GROUPS): instance groups of BTBA_FLAG_OVERLAP
-        bool overlap_equal_prio = false;   // BTBA_OPT_OVERLAP_EQUAL_PRIO (env BTBA_GROUP_PRIO=e...)
-        size_t keyed_corr_min_bytes = (size_t)1 << 20;   // BTBA_OPT_KEYED_CORR_MIN_BYTES (env of the same name): below it the keyed correspondence cache is not used
-        int chain = 0;                 // BTBA_OPT_CHAIN         (env BTBA_CHAIN): 1 = all Gauss-Newton iterations of a batch in ONE launch (k_chain) whenever the launch supports the solve; 0 (default) / -1 = the plain schedule
-        int corr_nt = -1;              // BTBA_OPT_CORR_NONTEMPORAL (env BTBA_CORR_NT): non-temporal correspondence loads  1 always, 0 never, -1 (default) the library's choice (corr_nt_auto)
-        int corr_nt_partial = 1;       // env BTBA_CORR_NT_PARTIAL=0 (developer): all instances stream non-temporally once the batch exceeds the cache, not only those that do not fit
-        long long last_level_cache = 224ll << 20;   // env BTBA_LLC_MB: what of the 256 MB memory-side cache a batch's frames + correspondences may fill before the stream is read non-temporally
-        bool relayout = false;         // BTBA_OPT_RELAYOUT (env BTBA_RELAYOUT=1 turns it on): a batch given as EntryJ is re-laid out to 24-byte records by its first iteration's sweep
-        int chain_group = 1;           // env BTBA_CHAIN_GROUP (developer A/B): instances per group of the chained launch's sequence (ChainDims::group)
-        int chain_sparse_period = 0;   // BTBA_OPT_CHAIN_SPARSE_PERIOD (env BTBA_CHAIN_PERIOD): 0 = an instance's sparse items follow its dense items, R >= 2 = every R-th item is a sparse one
-        int chain_timeout_ms = 500;    // BTBA_OPT_CHAIN_TIMEOUT_MS (env BTBA_CHAIN_TIMEOUT_MS): watchdog of the waits inside the chained launch
-        int chain_solve_prio = 0;      // env BTBA_CHAIN_SOLVE_PRIO (developer A/B): s_setprio of the solve items' waves
-        int chain_debug_skip = 0;      // env BTBA_CHAIN_DEBUG_SKIP (developer TIMING experiments, wrong results): ChainDims::debug_skip
-        bool solve_small = true;       // BTBA_OPT_SOLVE_SMALL (env BTBA_SOLVE_LEGACY=1 turns it off): k_solve_small for windows of <= 21 frames
-        int prepare_keep_T = 0;        // env BTBA_PREPARE_KEEP_T (developer / experiment builds): a solve's incoming matrices are its first iterate's T as they are (k_prepare)
-        int debug_lds_pad = 0;         // env BTBA_DEBUG_LDS_PAD (developer): extra dynamic LDS bytes per sweep workgroup -- what a larger LDS footprint costs the fused sweep
-        std::string chain_trace_file;  // env BTBA_CHAIN_TRACE_FILE (developer, scripts/chain_trace.py): every chained solve synchronises and dumps its workgroup timeline there
-    } tune;
-    std::vector<int32_t> dense_pairs_host;                  // what dense_pairs currently holds
-    int dense_pairs_frames = -1;
-    size_t dense_work_offset = 0;                           // ints into dense_pairs: the fused sweep's work table
-    int work_formula = 0;                                   // SolveDims::work_formula of that table
-    int solve_tab_frames = -1;                              // window size solve_tab was built for
-    std::vector<EventPair> events;                          // pending timed regions
-    std::vector<hipEvent_t> event_pool;
-    btba_stats stats{};
-    bool lds_attr_set = false, small_attr_set = false, mid_attr_set = false, vos_attr_set = false, lfnet_attr_set = false;
-    int n_cus = 0;                     // compute units of the workspace's device (256 = all eight XCDs of an MI355X in SPX mode: what k_chain's item -> XCD mapping assumes)
-    bool always_time_region = false;   // optimize_frames: ms_solve is part of its stats contract
-    static constexpr int kMaxGroups = 8;
-    uint64_t solves_enqueued = 0;      // rotates the sampled iteration of BTBA_FLAG_TIME_SAMPLED
-    hipStream_t aux_streams[kMaxGroups - 1] = {};  // groups 1 .. G-1 of a batch run here (software pipelining across instances)
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxGroups - 1] = {}, ev_order = nullptr;
-    // optimize_frames (round 6): the EntryJ / pose upload runs on a stream of its own while the frame cache is built on `stream`; small tables the cache build and
-    // the solve need (pointer tables, slot maps, valid counts) go through ONE pinned staging block, so that no call has to synchronise just to keep a local alive
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_copy = nullptr, ev_cache = nullptr;
-    PinBuf pin;
-    PinBuf pin_io;                                          // pinned: [poses out | poses in | pair offsets] of one optimize_frames call (small pageable copies cost ~10 us of host time each)
-    struct PendingSlot { int slot; uint64_t key; const float *depth, *normal; };
-    std::vector<PendingSlot> pool_pending;                  // frames cached by the call in flight: committed (live, n_valid) once their counts have come back
-
-    // persistent frame cache (btba_optimize_frames_keyed): compact (z, n) frames, their valid-pixel lists and counts
-    // live in pool slots that survive across calls; a keyframe is cached once, not once per BA call.
-    struct FrameSlot { uint64_t key = 0; const float *depth = nullptr, *normal = nullptr; uint64_t stamp = 0; bool live = false; int32_t n_valid = 0; };
-    DevBuf pool_zn, pool_lists, pool_counts, pool_nvalid, pool_map, pool_ranges;
-    size_t pool_map_offset = 0;                             // bytes into pool_map at which the window's frame -> slot map starts (behind the call's pointer table)
-    // keyed correspondence cache (BTBA_FLAG_KEYED_CORR): the EntryJ segment of a frame PAIR stays on the device under the pair's two
-    // frame keys; a sliding window then uploads only the new frame's K - 1 segments
-    struct CorrSeg { uint32_t off = 0, count = 0; };
-    DevBuf corr_pool, corr_desc, corr_stage_dev, corr_lens;   // pool of 24-byte correspondences; staging of a call's fresh EntryJ segments; the window's segment lengths
-    std::map<std::pair<uint64_t, uint64_t>, CorrSeg> corr_index;
-    size_t corr_pool_used = 0;                              // in entries
-    PinBuf corr_stage;                                      // pinned host staging of the segments uploaded by one call
-    DevBuf ransac;                                          // btba_ransac_pairs staging (points, samples, per-trial poses and counts, results)
-    DevBuf ransac_u;                                        // the reference's sample stream: n_trials x 3 uniforms (btba_xorwow.hpp), kept per (seed, n_trials)
-    std::vector<float> ransac_u_host;
-    DevBuf match;                                           // btba_match_pairs: tables, norms, candidate lists, selections, counts, host-form staging
-    DevBuf mask;                                            // btba_apply_masks: labels, counts, argmax keys, row extents, spans, hull stacks, ROI slots
-    DevBuf eval;                                            // btba_pose_errors: chunk tables, host-form poses and outputs, per-point minima
-    DevBuf nocs;                                            // btba_nocs_errors: item words, boxes, step table, host-form poses and outputs
-    DevBuf corres;                                          // btba_corres_chain: frame / pair tables, NN output, working lists, per-pair words
-    DevBuf vos;                                             // btba_vos_propagate: the key splits' partial (m, l, acc) per item and target position
-    DevBuf lfnet;                                           // btba_lfnet_*: per-map moments, peak flags, the compacted peak list
-    DevBuf lfnet_desc;                                      // btba_lfnet_descriptors: two buffers of a chunk's widest layer
-    DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
-    uint64_t ransac_u_seed = 0;
-    std::vector<FrameSlot> pool_slots;
-    int pool_H = 0, pool_W = 0, pool_npix = 0;
-    float pool_downscale = 0.0f, pool_K[9] = {0};
-    uint64_t pool_stamp = 0;
-    uint64_t pool_hits = 0, pool_misses = 0;
-
-    hipEvent_t get_event()
-    {
-        if (!event_pool.empty()) { hipEvent_t e = event_pool.back(); event_pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        return e;
-    }
-};
-
-// A workspace belongs to the device that was current when it was created.  A process that drives several GPUs from one thread
-// ("one process looping hipSetDevice") may call in with another device current: every entry point that takes a
-// workspace switches to the workspace's device for the duration of the call and back afterwards.
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(const btba_workspace *ws)
-    {
-        int cur = -1;
-        if (ws && hipGetDevice(&cur) == hipSuccess && cur != ws->device && hipSetDevice(ws->device) == hipSuccess) prev = cur;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+thread_local int btba_host::g_last_hip_error = 0;
 
 extern "C" {
 
@@ -616,8 +386,6 @@ static int pick_tiles(const btba_params *prm, int B, int Pd, int npix, bool list
     }
     return want;
 }
-
-static void scaled_intrinsics(int H, int W, int Hd, int Wd, const float *K, float intr[4], Mat4 *Kinv);
 
 struct ZnSpec {      // compact cache + the full-res geometry it encodes
     const float *zn = nullptr; int H = 0, W = 0; const float *K = nullptr;
@@ -1274,33 +1042,6 @@ int btba_solve_cached(btba_workspace *ws, const btba_params *params, int n_frame
                             max_corr_per_pair, dense_pairs, n_dense_pairs, poses_dev, trace_dev);
 }
 
-static void scaled_intrinsics(int H, int W, int Hd, int Wd, const float *K, float intr[4], Mat4 *Kinv)
-{
-    // CUDACache.cpp:20-24
-    intr[0] = K[0] * ((float)Wd / (float)W);
-    intr[1] = K[4] * ((float)Hd / (float)H);
-    intr[2] = K[2] * ((float)(Wd - 1) / (float)(W - 1));
-    intr[3] = K[5] * ((float)(Hd - 1) / (float)(H - 1));
-    // m_inputIntrinsicsInv (CUDACache.cpp:33): generic cofactor inverse of the 4x4 embedding of K, in fp32
-    const float m[16] = { K[0], K[1], K[2], 0, K[3], K[4], K[5], 0, K[6], K[7], K[8], 0, 0, 0, 0, 1 };
-    auto minor = [&](int r0, int r1, int r2, int c0, int c1, int c2) {
-        return m[4 * r0 + c0] * (m[4 * r1 + c1] * m[4 * r2 + c2] - m[4 * r1 + c2] * m[4 * r2 + c1])
-             - m[4 * r0 + c1] * (m[4 * r1 + c0] * m[4 * r2 + c2] - m[4 * r1 + c2] * m[4 * r2 + c0])
-             + m[4 * r0 + c2] * (m[4 * r1 + c0] * m[4 * r2 + c1] - m[4 * r1 + c1] * m[4 * r2 + c0]);
-    };
-    float adj[16];
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) {
-            int rr[3], cc[3], a = 0, b = 0;
-            for (int k = 0; k < 4; k++) { if (k != r) rr[a++] = k; if (k != c) cc[b++] = k; }
-            float mn = minor(rr[0], rr[1], rr[2], cc[0], cc[1], cc[2]);
-            adj[4 * c + r] = ((r + c) & 1) ? -mn : mn;
-        }
-    const float det = m[0] * adj[0] + m[1] * adj[4] + m[2] * adj[8] + m[3] * adj[12];
-    const float rdet = 1.0f / det;
-    for (int k = 0; k < 16; k++) Kinv->m[k] = adj[k] * rdet;
-}
-
 int btba_build_cache(btba_workspace *ws, int n_frames, int H, int W, const float *K, float image_downscale,
                      const float *const *depth_dev, const float *const *normal_dev,
                      float *campos_dev, float *normals_dev, int32_t *n_valid_dev, float *intr_out)
@@ -1849,235 +1590,6 @@ int btba_poses_to_matrices(btba_workspace *ws, int n, const float *x_dev, float 
     return BTBA_OK;
 }
 
-int btba_process_depth(btba_workspace *ws, int H, int W, const float *depth_in_dev, float *depth_out_dev,
-                       int erode_radius, float erode_diff, float erode_ratio, int bf_radius, float sigma_d, float sigma_r)
-{
-    DeviceGuard device_guard(ws);
-    if (!ws || H < 1 || W < 1 || !depth_in_dev || !depth_out_dev || depth_in_dev == depth_out_dev) return BTBA_EINVAL;
-    if (erode_radius < 0 || bf_radius < 0 || erode_radius + 2 * bf_radius > 16 || !(sigma_d > 0.0f) || !(sigma_r > 0.0f)) return BTBA_EINVAL;
-    DepthFilterParams P{ W, H, erode_radius, erode_diff, erode_ratio, bf_radius, sigma_d, sigma_r };
-    const int h = erode_radius + 2 * bf_radius;
-    const size_t lds = 2 * sizeof(float) * (size_t)(kTileW + 2 * h) * (kTileH + 2 * h);
-    const dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
-    if (erode_radius == 1 && bf_radius == 2) k_process_depth<1, 2><<<grid, 256, lds, ws->stream>>>(P, depth_in_dev, depth_out_dev);        // the tracker's stencils, unrolled
-    else k_process_depth<-1, -1><<<grid, 256, lds, ws->stream>>>(P, depth_in_dev, depth_out_dev);
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-int btba_depth_to_normals(btba_workspace *ws, int H, int W, const float *K, const float *depth_dev, float *normals_dev, float *xyz_dev)
-{
-    DeviceGuard device_guard(ws);
-    if (!ws || H < 1 || W < 1 || !K || !depth_dev || !normals_dev) return BTBA_EINVAL;
-    float intr[4];
-    Mat4 Kinv;
-    scaled_intrinsics(H, W, H, W, K, intr, &Kinv);       // only the generic cofactor inverse of the 4x4 embedding is used
-    k_depth_to_normals<<<dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, ws->stream>>>(W, H, Kinv, depth_dev, reinterpret_cast<float4 *>(normals_dev), reinterpret_cast<float4 *>(xyz_dev));
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-void btba_ingest_params_default(btba_ingest_params *p)
-{
-    if (!p) return;
-    p->depth_format = 0;
-    p->erode_radius = 1; p->erode_diff = 0.001f; p->erode_ratio = 0.8f;          // config_ycbineoat.yml:9-16
-    p->bf_radius = 2; p->sigma_d = 2.0f; p->sigma_r = 100000.0f;
-}
-
-int btba_ingest_frames(btba_workspace *ws, const btba_ingest_params *prm, int n_frames, int H, int W, const float *K,
-                       const void *const *depth_in_dev, const uint8_t *const *bgr_in_dev, float *const *depth_out_dev,
-                       float *const *normal_out_dev, uint8_t *const *color_out_dev, float *const *depth_raw_out_dev,
-                       float *const *xyz_out_dev)
-{
-    // every argument is checked before the first HIP call
-    if (!ws || !prm || n_frames < 1 || H < 1 || W < 1 || !K || !depth_in_dev || !depth_out_dev || !normal_out_dev) return BTBA_EINVAL;
-    if (prm->depth_format < 0 || prm->depth_format > 1) return BTBA_EINVAL;
-    if (prm->erode_radius < 0 || prm->bf_radius < 0 || prm->erode_radius + 2 * prm->bf_radius > 16 || !(prm->sigma_d > 0.0f) || !(prm->sigma_r > 0.0f))
-        return BTBA_EINVAL;
-    const size_t n_px = (size_t)H * W, in_bytes = n_px * (prm->depth_format == 0 ? sizeof(uint16_t) : sizeof(float));
-    for (int f = 0; f < n_frames; f++) {
-        const void *in = depth_in_dev[f];
-        const uint8_t *bgr = bgr_in_dev ? bgr_in_dev[f] : nullptr;
-        uint8_t *color = color_out_dev ? color_out_dev[f] : nullptr;
-        float *raw = depth_raw_out_dev ? depth_raw_out_dev[f] : nullptr, *xyz = xyz_out_dev ? xyz_out_dev[f] : nullptr;
-        if (!in || !depth_out_dev[f] || !normal_out_dev[f] || (color && !bgr)) return BTBA_EINVAL;
-        if (misaligned(in, prm->depth_format == 0 ? 2 : 4) || misaligned(depth_out_dev[f], 4) || misaligned(normal_out_dev[f], 16) ||
-            misaligned(color, 4) || misaligned(raw, 4) || misaligned(xyz, 16))
-            return BTBA_EINVAL;
-        auto overlaps_input = [&](const void *q, size_t bytes) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(q);
-            return q && a < b + bytes && b < a + in_bytes;
-        };
-        if (overlaps_input(depth_out_dev[f], 4 * n_px) || overlaps_input(normal_out_dev[f], 16 * n_px) || overlaps_input(color, 4 * n_px) ||
-            overlaps_input(raw, 4 * n_px) || overlaps_input(xyz, 16 * n_px))
-            return BTBA_EINVAL;
-    }
-    DeviceGuard device_guard(ws);
-    DepthFilterParams P{ W, H, prm->erode_radius, prm->erode_diff, prm->erode_ratio, prm->bf_radius, prm->sigma_d, prm->sigma_r };
-    const int h = P.erode_radius + 2 * P.bf_radius;
-    const size_t lds = 2 * sizeof(float) * (size_t)(kTileW + 2 * h) * (kTileH + 2 * h);
-    float intr[4];
-    Mat4 Kinv;
-    scaled_intrinsics(H, W, H, W, K, intr, &Kinv);       // btba_depth_to_normals' inverse
-    for (int b0 = 0; b0 < n_frames; b0 += kIngestChunk) {
-        const int nf = std::min(kIngestChunk, n_frames - b0);
-        IngestDepthFrames D{};
-        IngestMapFrames M{};
-        for (int z = 0; z < nf; z++) {
-            const int f = b0 + z;
-            D.in[z] = depth_in_dev[f];
-            D.out[z] = depth_out_dev[f];
-            D.raw[z] = depth_raw_out_dev ? depth_raw_out_dev[f] : nullptr;
-            M.depth[z] = depth_out_dev[f];
-            M.normals[z] = reinterpret_cast<float4 *>(normal_out_dev[f]);
-            M.xyz[z] = xyz_out_dev ? reinterpret_cast<float4 *>(xyz_out_dev[f]) : nullptr;
-            M.color[z] = color_out_dev ? reinterpret_cast<uint32_t *>(color_out_dev[f]) : nullptr;
-            M.bgr[z] = M.color[z] ? bgr_in_dev[f] : nullptr;
-        }
-        const dim3 grid_d((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH, nf);
-        if (prm->depth_format == 0) launch_ingest_depth<uint16_t>(P, D, grid_d, lds, ws->stream);
-        else launch_ingest_depth<float>(P, D, grid_d, lds, ws->stream);
-        HIP_TRY(hipGetLastError());
-        k_ingest_maps<<<dim3((W + 63) / 64, (H + 3) / 4, nf), dim3(64, 4), 0, ws->stream>>>(W, H, Kinv, M);
-        HIP_TRY(hipGetLastError());
-    }
-    return BTBA_OK;
-}
-
-void btba_vos_params_default(btba_vos_params *p)
-{
-    if (!p) return;
-    p->ref_num = 9; p->range = 40;                                                // run_video.py:42-52
-    p->sigma_dense = 8.0f; p->sigma_sparse = 21.0f; p->temperature = 1.0f;
-    p->continuous_frames = 4; p->sparse_after = 15;                               // lib/predict.py:48-49
-}
-
-static bool vos_params_ok(const btba_vos_params *p)
-{
-    return p && p->continuous_frames >= 1 && p->ref_num >= p->continuous_frames - 1 && p->ref_num >= 1 && p->ref_num <= BTBA_VOS_MAX_REF &&
-           p->range >= 0 && p->sparse_after >= 0 && p->sigma_dense > 0.0f && p->sigma_sparse > 0.0f && std::isfinite(p->temperature);
-}
-
-int btba_vos_sample_frames(const btba_vos_params *p, int frame_idx, int32_t *idx_out, int32_t *n_out, int32_t *n_dense_out)
-{
-    if (!vos_params_ok(p) || frame_idx < 1 || !idx_out || !n_out || !n_dense_out) return BTBA_EINVAL;
-    int n = 0;
-    if (frame_idx <= p->ref_num) {
-        for (int i = 0; i < frame_idx; i++) idx_out[n++] = i;
-    } else {
-        const int dense_num = p->continuous_frames - 1, sparse_num = p->ref_num - dense_num;
-        const int ref_end = frame_idx - dense_num - 1, ref_start = std::max(ref_end - p->range, 0);
-        // np.linspace(ref_start, ref_end, sparse_num).astype(int): start + i * step in double, product and sum rounded separately, the last element the stop itself
-        const double delta = (double)ref_end - (double)ref_start;
-        const int div = sparse_num - 1;
-        const double step = div > 0 ? delta / (double)div : 0.0;
-        for (int i = 0; i < sparse_num; i++) {
-            volatile double prod = div > 0 ? (step == 0.0 ? ((double)i / (double)div) * delta : (double)i * step) : (double)i * delta;
-            double y = prod + (double)ref_start;
-            if (sparse_num > 1 && i == sparse_num - 1) y = (double)ref_end;
-            idx_out[n++] = (int32_t)y;
-        }
-        for (int j = 0; j < dense_num; j++) idx_out[n++] = frame_idx - dense_num + j;
-    }
-    *n_out = n;
-    *n_dense_out = frame_idx > p->sparse_after ? std::min(p->continuous_frames, n) : n;       // predict:48-55: [-4:] of fewer than four is all of them
-    return BTBA_OK;
-}
-
-int btba_vos_first_labels(btba_workspace *ws, int H, int W, int d, const uint8_t *label_dev, float *labels_out_dev)
-{
-    if (!ws || H < 1 || W < 1 || d < 2 || d > BTBA_VOS_MAX_CLASSES || !label_dev || !labels_out_dev || misaligned(labels_out_dev, 4)) return BTBA_EINVAL;
-    const int Hd = (H + 7) / 8, Wd = (W + 7) / 8;
-    if ((int64_t)Hd * Wd > BTBA_VOS_MAX_POSITIONS) return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    k_vos_first_labels<<<dim3((Wd + 63) / 64, (Hd + 3) / 4), dim3(64, 4), 0, ws->stream>>>(H, W, Hd, Wd, d, label_dev, labels_out_dev);
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-int btba_vos_masks(btba_workspace *ws, int d, int Hd, int Wd, int H, int W, const float *pred_dev, uint8_t *mask_out_dev)
-{
-    if (!ws || d < 2 || d > BTBA_VOS_MAX_CLASSES || Hd < 1 || Wd < 1 || H < 1 || W < 1 || (int64_t)Hd * Wd > BTBA_VOS_MAX_POSITIONS ||
-        (int64_t)H * W > INT32_MAX || !pred_dev || !mask_out_dev || misaligned(pred_dev, 4))
-        return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    k_vos_masks<<<dim3((W + 63) / 64, (H + 3) / 4), dim3(64, 4), 0, ws->stream>>>(d, Hd, Wd, H, W, pred_dev, mask_out_dev);
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-int btba_vos_inputs(btba_workspace *ws, int n_frames, int H, int W, const uint8_t *const *bgr_dev, float *rgb_out_dev)
-{
-    if (!ws || n_frames < 1 || H < 1 || W < 1 || (int64_t)H * W > INT32_MAX / 4 || !bgr_dev || !rgb_out_dev || misaligned(rgb_out_dev, 4)) return BTBA_EINVAL;
-    for (int f = 0; f < n_frames; f++)
-        if (!bgr_dev[f]) return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    const int n_px = H * W;
-    for (int f0 = 0; f0 < n_frames; f0 += kVosInputChunk) {
-        const int nf = std::min(kVosInputChunk, n_frames - f0);
-        VosInputFrames F{};
-        for (int z = 0; z < nf; z++) F.bgr[z] = bgr_dev[f0 + z];
-        k_vos_inputs<<<dim3((n_px + 255) / 256, nf), 256, 0, ws->stream>>>(n_px, F, rgb_out_dev, f0);
-        HIP_TRY(hipGetLastError());
-    }
-    return BTBA_OK;
-}
-
-int btba_vos_propagate(btba_workspace *ws, const btba_vos_params *prm, int n_items, int C, int d, int Hd, int Wd, const int32_t *n_ref,
-                       const int32_t *n_dense, const float *const *ref_feat_dev, const float *const *ref_label_dev,
-                       const float *const *target_dev, float *const *pred_out_dev, float *const *onehot_out_dev)
-{
-    // every argument is checked before the first HIP call
-    if (!ws || !vos_params_ok(prm) || n_items < 1 || !n_ref || !n_dense || !ref_feat_dev || !ref_label_dev || !target_dev || !pred_out_dev) return BTBA_EINVAL;
-    if (C < 8 || C > BTBA_VOS_MAX_CHANNELS || C % 8 != 0 || d < 2 || d > BTBA_VOS_MAX_CLASSES || Hd < 1 || Wd < 1 || (int64_t)Hd * Wd > BTBA_VOS_MAX_POSITIONS)
-        return BTBA_EINVAL;
-    size_t k = 0;
-    for (int b = 0; b < n_items; b++) {
-        if (n_ref[b] < 1 || n_ref[b] > BTBA_VOS_MAX_REF || n_dense[b] < 0 || n_dense[b] > n_ref[b]) return BTBA_EINVAL;
-        if (!target_dev[b] || !pred_out_dev[b] || misaligned(target_dev[b], 4) || misaligned(pred_out_dev[b], 4) ||
-            (onehot_out_dev && misaligned(onehot_out_dev[b], 4)))
-            return BTBA_EINVAL;
-        for (int r = 0; r < n_ref[b]; r++, k++)
-            if (!ref_feat_dev[k] || !ref_label_dev[k] || misaligned(ref_feat_dev[k], 4) || misaligned(ref_label_dev[k], 4)) return BTBA_EINVAL;
-    }
-    DeviceGuard device_guard(ws);
-    const int HW = Hd * Wd, NQ = C <= 256 ? 4 : 2, QT = 32 * NQ;
-    Scratch sc;
-    auto part = sc.add<float>(vos_part_floats(HW, d) * (size_t)n_items);
-    if (int rc = sc.bind(ws->vos)) return rc;
-    const size_t lds = sizeof(float) * std::max((size_t)C * QT, (size_t)kVosWaves * (2 + kVosMaxClasses) * QT);       // at most 128 KB
-    if (!ws->vos_attr_set) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vos_partial<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vos_partial<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        ws->vos_attr_set = true;
-    }
-    const float sd2 = prm->sigma_dense * prm->sigma_dense, ss2 = prm->sigma_sparse * prm->sigma_sparse;
-    k = 0;
-    for (int b0 = 0; b0 < n_items; b0 += kVosChunk) {
-        const int nb = std::min(kVosChunk, n_items - b0);
-        VosItems I{};
-        int max_split = 1;
-        for (int z = 0; z < nb; z++) {
-            const int b = b0 + z;
-            for (int r = 0; r < n_ref[b]; r++, k++) { I.ref[z][r] = ref_feat_dev[k]; I.lab[z][r] = ref_label_dev[k]; }
-            I.tgt[z] = target_dev[b];
-            I.pred[z] = pred_out_dev[b];
-            I.onehot[z] = onehot_out_dev ? onehot_out_dev[b] : nullptr;
-            I.n_ref[z] = n_ref[b]; I.n_dense[z] = n_dense[b];
-            I.n_split[z] = vos_splits(HW, n_ref[b], QT);
-            max_split = std::max(max_split, (int)I.n_split[z]);
-        }
-        const dim3 grid((HW + QT - 1) / QT, max_split, nb);
-        if (NQ == 4) k_vos_partial<4><<<grid, 64 * kVosWaves, lds, ws->stream>>>(I, C, d, Hd, Wd, prm->temperature, sd2, ss2, part, b0);
-        else k_vos_partial<2><<<grid, 64 * kVosWaves, lds, ws->stream>>>(I, C, d, Hd, Wd, prm->temperature, sd2, ss2, part, b0);
-        HIP_TRY(hipGetLastError());
-        k_vos_merge<<<dim3((HW + 255) / 256, nb), 256, 0, ws->stream>>>(I, d, HW, part, b0);
-        HIP_TRY(hipGetLastError());
-    }
-    return BTBA_OK;
-}
-
 int btba_build_cache_zn(btba_workspace *ws, int n_frames, int H, int W, const float *K, float image_downscale,
                         const float *const *depth_dev, const float *const *normal_dev, float *zn_dev, int32_t *n_valid_dev, float *intr_out)
 {
@@ -2186,1395 +1698,4 @@ int btba_solve_batch_zn_aux(btba_workspace *ws, const btba_params *params, int n
                          pair_offsets_dev, max_corr_per_pair, dense_pairs, dense_pairs ? n_dense_pairs : -1, poses_dev, trace_dev, nullptr, c24);
 }
 
-
-// ---- correspondence RANSAC ---------------------------------------------------------
-// the reference's per-trial cuRAND streams = one table of uniforms for all pairs; rebuilt only when the seed changes or
-// more trials are asked for than the table holds (a longer table for the same seed starts with the shorter one)
-static int ransac_uniform_table(btba_workspace *ws, uint64_t seed, int n_trials)
-{
-    if (ws->ransac_u_host.size() >= 3 * (size_t)n_trials && ws->ransac_u_seed == seed) return BTBA_OK;
-    HIP_TRY(hipStreamSynchronize(ws->stream));      // an earlier call's kernels / upload may still be using the old table
-    ws->ransac_u_host.assign(3 * (size_t)n_trials, 0.0f);
-    xorwow::ransac_uniform_table(seed, n_trials, ws->ransac_u_host.data());
-    ws->ransac_u_seed = seed;
-    int rc;
-    if ((rc = ws->ransac_u.ensure(12 * (size_t)n_trials))) return rc;
-    HIP_TRY(hipMemcpyAsync(ws->ransac_u.p, ws->ransac_u_host.data(), 12 * (size_t)n_trials, hipMemcpyHostToDevice, ws->stream));
-    return BTBA_OK;
-}
-
-// vote + extraction for D.n_pairs pairs whose point counts are on the DEVICE (offsets[p] .. offsets[p + 1]); `best` zeroed by the caller.
-// Asynchronous on the workspace stream: btba_ransac_pairs_ex and btba_corres_chain (one pair per call, its count written by an earlier kernel).
-static int ransac_enqueue(btba_workspace *ws, const RansacDims &D, const float4 *dA, const float4 *dB, const int *d_offsets, const int *dS, float *d_pose,
-                          int *d_cnt, unsigned long long *d_best, int *d_ids, int *d_nin, int *d_bt, float *d_bp)
-{
-    k_ransac_vote<<<dim3((D.n_trials + 255) / 256, D.n_pairs), 256, 0, ws->stream>>>(D, dA, dB, d_offsets, dS, ws->ransac_u.as<float>(), d_pose, d_cnt, d_best);
-    k_ransac_extract<<<D.n_pairs, 256, 0, ws->stream>>>(D, dA, dB, d_offsets, d_pose, d_best, d_ids, d_nin, d_bt, d_bp);
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-int btba_ransac_pairs_ex(btba_workspace *ws, int hypothesis, int device_resident, int n_pairs, const float *ptsA, const float *ptsB, const int32_t *n_pts,
-                         int n_trials, float dist_thres, const int32_t *samples, uint64_t seed,
-                         int32_t *inlier_ids_out, int32_t *n_inliers_out, int32_t *best_trial_out, float *best_pose_out,
-                         int32_t *trial_counts_out, float *trial_poses_out)
-{
-    DeviceGuard device_guard(ws);
-    if (!ws || n_pairs < 1 || !n_pts || n_trials < 1 || !(dist_thres >= 0.0f) || !inlier_ids_out || !n_inliers_out) return BTBA_EINVAL;
-    const bool draw_hash = (hypothesis & BTBA_RANSAC_DRAW_HASH) != 0;
-    hypothesis &= ~BTBA_RANSAC_DRAW_HASH;
-    if (hypothesis != BTBA_RANSAC_REFERENCE_SVD && hypothesis != BTBA_RANSAC_HORN) return BTBA_EINVAL;
-    std::vector<int32_t> offsets(n_pairs + 1, 0);
-    for (int p = 0; p < n_pairs; p++) {
-        if (n_pts[p] < 0) return BTBA_EINVAL;
-        offsets[p + 1] = offsets[p] + n_pts[p];
-    }
-    const size_t T = (size_t)offsets[n_pairs], NT = (size_t)n_pairs * n_trials;
-    if (T && (!ptsA || !ptsB)) return BTBA_EINVAL;
-    const bool dev = device_resident != 0;
-    Scratch S;
-    const auto s_a = S.add<float4>(T ? T : 1, !dev), s_b = S.add<float4>(T ? T : 1, !dev);
-    const auto s_off = S.add<int>((size_t)n_pairs + 1);
-    const auto s_smp = S.add<int>((samples && !dev) ? 3 * NT : 1);      // (absent: one word)
-    const auto s_pose = S.add<float>(12 * NT);
-    const auto s_cnt = S.add<int>(NT);
-    const auto s_best = S.add<unsigned long long>((size_t)n_pairs);
-    const auto s_ids = S.add<int>(T ? T : 1, !dev);
-    const auto s_nin = S.add<int>((size_t)n_pairs), s_bt = S.add<int>((size_t)n_pairs);
-    const auto s_bp = S.add<float>(16 * (size_t)n_pairs);
-    int rc;
-    if ((rc = S.bind(ws->ransac, 256))) return rc;
-    if (T && !dev) {
-        HIP_TRY(hipMemcpyAsync(s_a, ptsA, 16 * T, hipMemcpyHostToDevice, ws->stream));
-        HIP_TRY(hipMemcpyAsync(s_b, ptsB, 16 * T, hipMemcpyHostToDevice, ws->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(s_off, offsets.data(), 4 * (size_t)(n_pairs + 1), hipMemcpyHostToDevice, ws->stream));
-    HIP_TRY(hipStreamSynchronize(ws->stream));          // `offsets` is a local (16 B per pair: the only host wait of the device-resident form)
-    if (samples && !dev) HIP_TRY(hipMemcpyAsync(s_smp, samples, 12 * NT, hipMemcpyHostToDevice, ws->stream));
-    HIP_TRY(hipMemsetAsync(s_best, 0, 8 * (size_t)n_pairs, ws->stream));
-    if (!samples && !draw_hash && (rc = ransac_uniform_table(ws, seed, n_trials))) return rc;
-    RansacDims D{};
-    D.n_pairs = n_pairs; D.n_trials = n_trials; D.dist_thres = dist_thres; D.seed = seed; D.hypothesis = hypothesis;
-    D.draw = samples ? 1 : (draw_hash ? 0 : 2);
-    const float4 *dA = dev ? reinterpret_cast<const float4 *>(ptsA) : s_a;
-    const float4 *dB = dev ? reinterpret_cast<const float4 *>(ptsB) : s_b;
-    const int *dS = (samples && dev) ? samples : s_smp;
-    // device-resident: results go straight to the caller's device buffers (the optional per-trial tables too)
-    int *d_ids = dev ? inlier_ids_out : s_ids;
-    int *d_nin = dev ? n_inliers_out : s_nin;
-    int *d_bt = (dev && best_trial_out) ? best_trial_out : s_bt;
-    float *d_bp = (dev && best_pose_out) ? best_pose_out : s_bp;
-    int *d_cnt = (dev && trial_counts_out) ? trial_counts_out : s_cnt;
-    float *d_pose = (dev && trial_poses_out) ? trial_poses_out : s_pose;
-    if ((rc = ransac_enqueue(ws, D, dA, dB, s_off, dS, d_pose, d_cnt, s_best, d_ids, d_nin, d_bt, d_bp))) return rc;
-    if (dev) return BTBA_OK;                          // asynchronous on the workspace stream
-    // the inlier lists are written only up to each pair's count: fetch counts first, ids after
-    HIP_TRY(hipMemcpyAsync(n_inliers_out, d_nin, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost, ws->stream));
-    if (T) HIP_TRY(hipMemcpyAsync(inlier_ids_out, d_ids, 4 * T, hipMemcpyDeviceToHost, ws->stream));
-    if (best_trial_out) HIP_TRY(hipMemcpyAsync(best_trial_out, d_bt, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost, ws->stream));
-    if (best_pose_out) HIP_TRY(hipMemcpyAsync(best_pose_out, d_bp, 64 * (size_t)n_pairs, hipMemcpyDeviceToHost, ws->stream));
-    if (trial_counts_out) HIP_TRY(hipMemcpyAsync(trial_counts_out, d_cnt, 4 * NT, hipMemcpyDeviceToHost, ws->stream));
-    if (trial_poses_out) HIP_TRY(hipMemcpyAsync(trial_poses_out, d_pose, 48 * NT, hipMemcpyDeviceToHost, ws->stream));
-    HIP_TRY(hipStreamSynchronize(ws->stream));
-    return BTBA_OK;
-}
-
-int btba_ransac_pairs(btba_workspace *ws, int n_pairs, const float *ptsA_host, const float *ptsB_host, const int32_t *n_pts,
-                      int n_trials, float dist_thres, const int32_t *samples_host, uint64_t seed,
-                      int32_t *inlier_ids_out, int32_t *n_inliers_out, int32_t *best_trial_out, float *best_pose_out,
-                      int32_t *trial_counts_out, float *trial_poses_out)
-{
-    DeviceGuard device_guard(ws);
-    return btba_ransac_pairs_ex(ws, BTBA_RANSAC_REFERENCE_SVD, 0, n_pairs, ptsA_host, ptsB_host, n_pts, n_trials, dist_thres, samples_host, seed,
-                                inlier_ids_out, n_inliers_out, best_trial_out, best_pose_out, trial_counts_out, trial_poses_out);
-}
-
-int btba_ransac_reference_uniforms(uint64_t seed, int n_trials, float *u_out)
-{
-    if (n_trials < 0 || (n_trials && !u_out)) return BTBA_EINVAL;
-    xorwow::ransac_uniform_table(seed, n_trials, u_out);
-    return BTBA_OK;
-}
-
-void btba_match_params_default(btba_match_params *p)
-{
-    if (!p) return;
-    p->k = 5;                                                         // FeatureManager.cpp:262 (k_near)
-    p->mutual = 1;                                                    // config_ycbineoat.yml:47
-    p->max_dist_neighbor = 0.03f;
-    p->cos_max_normal_neighbor = (float)std::cos(45.0f / 180.0 * M_PI);
-    p->max_dist_no_neighbor = 0.02f;
-    p->cos_max_normal_no_neighbor = (float)std::cos(45.0f / 180.0 * M_PI);
-    p->min_z = 0.1f;                                                  // FeatureManager.cpp:319
-}
-
-int btba_match_capacity(const btba_match_params *prm, int n_frames, int H, int W, int D, const int32_t *n_kpts,
-                        int n_pairs, const int32_t *pairs, int64_t *capacity_out)
-{
-    if (!prm || prm->k < 1 || prm->k > kMatchKMax || n_frames < 1 || H < 1 || W < 1 || D < 4 || D > kMatchMaxD || D % 4 || !n_kpts || n_pairs < 0 ||
-        (n_pairs && !pairs) || !capacity_out)
-        return BTBA_EINVAL;
-    for (int f = 0; f < n_frames; f++)
-        if (n_kpts[f] < 0 || n_kpts[f] > kMatchMaxKpts) return BTBA_EINVAL;
-    int64_t cap = 0;
-    for (int p = 0; p < n_pairs; p++) {
-        const int a = pairs[2 * p], b = pairs[2 * p + 1];
-        if (a < 0 || a >= n_frames || b < 0 || b >= n_frames || a == b) return BTBA_EINVAL;
-        cap += n_kpts[a] + (prm->mutual ? n_kpts[b] : 0);
-    }
-    if (cap > INT_MAX) return BTBA_EINVAL;                            // query and output positions are int32 on the device
-    *capacity_out = cap;
-    return BTBA_OK;
-}
-
-// every pointer argument btba_match_pairs / btba_corres_chain read before their first HIP call
-static int match_check_frames(const btba_match_params *prm, int n_frames, int H, int W, int D, const int32_t *n_kpts, int n_pairs, const int32_t *pairs,
-                              const float *K, const float *const *desc_dev, const float *const *kpts_dev, const float *const *depth_dev,
-                              const float *const *normal_dev, const float *poses, const int32_t *frame_ids, int64_t *cap)
-{
-    int rc = btba_match_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, cap);
-    if (rc) return rc;
-    if (!K || !desc_dev || !kpts_dev || !depth_dev || !normal_dev || !poses || !frame_ids) return BTBA_EINVAL;
-    std::vector<char> used(n_frames, 0);
-    for (int p = 0; p < n_pairs; p++) used[pairs[2 * p]] = used[pairs[2 * p + 1]] = 1;
-    for (int f = 0; f < n_frames; f++)
-        if (used[f] && n_kpts[f] > 0 &&
-            (!desc_dev[f] || !kpts_dev[f] || !depth_dev[f] || !normal_dev[f] || misaligned(desc_dev[f], 16) || misaligned(kpts_dev[f], 8) || misaligned(normal_dev[f], 16)))
-            return BTBA_EINVAL;
-    return BTBA_OK;
-}
-
-// The matcher's launches for validated arguments, asynchronous on the workspace stream.  The host tables stay in E until the
-// caller has synchronised; E.d_cnt / E.d_off are the per-pair counts and offsets (device, in ws->match).
-struct MatchEnqueue {
-    std::vector<MatchFrame> fr;
-    std::vector<MatchPair> pt;
-    int *d_cnt = nullptr, *d_off = nullptr;
-    btba_match *d_out = nullptr;
-    float4 *d_pa = nullptr, *d_pb = nullptr;
-};
-
-static int match_enqueue(btba_workspace *ws, const btba_match_params *prm, bool dev, int n_frames, int H, int W, const float *K,
-                         const float *const *desc_dev, int D, const float *const *kpts_dev, const int32_t *n_kpts, const float *const *depth_dev,
-                         const float *const *normal_dev, const float *poses, const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
-                         btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, MatchEnqueue &E)
-{
-    std::vector<char> used(n_frames, 0);
-    for (int p = 0; p < n_pairs; p++) used[pairs[2 * p]] = used[pairs[2 * p + 1]] = 1;
-    // host tables: frames, pairs (thresholds chosen by frame ids, FeatureManager.cpp:259)
-    std::vector<MatchFrame> &fr = E.fr;
-    fr.assign(n_frames, MatchFrame{});
-    int n_norms = 0, max_n = 0;
-    for (int f = 0; f < n_frames; f++) {
-        MatchFrame &m = fr[f];
-        m = MatchFrame{};
-        m.n = used[f] ? n_kpts[f] : 0;
-        m.desc = desc_dev[f]; m.kpts = reinterpret_cast<const float2 *>(kpts_dev[f]);
-        m.depth = depth_dev[f]; m.normal = reinterpret_cast<const float4 *>(normal_dev[f]);
-        m.norm_off = n_norms;
-        n_norms += m.n;
-        max_n = std::max(max_n, m.n);
-        for (int k = 0; k < 12; k++) m.pose[k] = poses[16 * f + k];
-    }
-    std::vector<MatchPair> &pt = E.pt;
-    pt.assign(n_pairs, MatchPair{});
-    int qbase = 0, max_q = 0;
-    for (int p = 0; p < n_pairs; p++) {
-        const int a = pairs[2 * p], b = pairs[2 * p + 1];
-        const bool neighbor = std::abs((long long)frame_ids[a] - (long long)frame_ids[b]) == 1;
-        pt[p] = MatchPair{ a, b, qbase, 0, neighbor ? prm->max_dist_neighbor : prm->max_dist_no_neighbor,
-                           neighbor ? prm->cos_max_normal_neighbor : prm->cos_max_normal_no_neighbor, 0.0f, 0.0f };
-        const int nq = fr[a].n + (prm->mutual ? fr[b].n : 0);
-        qbase += nq;
-        max_q = std::max(max_q, nq);
-    }
-    const size_t Q = (size_t)qbase;
-    const size_t Q1 = Q ? Q : 1;
-    Scratch S;
-    const auto dF = S.add<MatchFrame>(n_frames);
-    const auto dP = S.add<MatchPair>(n_pairs);
-    const auto d_nrm = S.add<float>(n_norms ? n_norms : 1);
-    const auto d_cand = S.add<MatchCand>(prm->k * Q1);
-    const auto d_sel = S.add<int>(Q1), d_pos = S.add<int>(Q1);
-    const auto s_cnt = S.add<int>(n_pairs), s_off = S.add<int>(n_pairs);
-    const auto s_out = S.add<btba_match>(Q1, !dev);
-    const auto s_pa = S.add<float4>(Q1, !dev && ptsA_model_out), s_pb = S.add<float4>(Q1, !dev && ptsB_model_out);
-    int rc;
-    if ((rc = S.bind(ws->match))) return rc;
-    HIP_TRY(hipMemcpyAsync(dF, fr.data(), sizeof(MatchFrame) * n_frames, hipMemcpyHostToDevice, ws->stream));
-    HIP_TRY(hipMemcpyAsync(dP, pt.data(), sizeof(MatchPair) * n_pairs, hipMemcpyHostToDevice, ws->stream));
-
-    MatchDims M{};
-    M.W = W; M.H = H; M.D = D; M.k = prm->k; M.mutual = prm->mutual ? 1 : 0; M.min_z = prm->min_z;
-    float intr[4];
-    scaled_intrinsics(H, W, H, W, K, intr, &M.Kinv);                 // btba_depth_to_normals' inverse: the same camera-space points
-    int *d_cnt = s_cnt, *d_off = s_off;
-    btba_match *d_out = dev ? matches_out : s_out;
-    float4 *d_pa = dev ? reinterpret_cast<float4 *>(ptsA_model_out) : s_pa;      // (nullptr when the caller wants no points)
-    float4 *d_pb = dev ? reinterpret_cast<float4 *>(ptsB_model_out) : s_pb;
-    if (max_n > 0) {
-        k_match_norms<<<dim3((max_n + 255) / 256, n_frames), 256, 0, ws->stream>>>(dF, D, d_nrm);
-        k_match_topk<<<dim3(n_pairs, (max_n + kMatchRows - 1) / kMatchRows, 1 + M.mutual), 256, 0, ws->stream>>>(M, dF, dP, d_nrm, d_cand);
-    }
-    k_match_select<<<n_pairs, 256, 0, ws->stream>>>(M, dF, dP, d_cand, d_sel, d_pos, d_cnt);
-    k_match_offsets<<<1, 256, 0, ws->stream>>>(n_pairs, d_cnt, d_off);
-    if (max_q > 0)
-        k_match_pack<<<dim3(n_pairs, (max_q + 255) / 256), 256, 0, ws->stream>>>(M, dF, dP, d_cand, d_sel, d_pos, d_off, d_out, d_pa, d_pb);
-    HIP_TRY(hipGetLastError());
-    E.d_cnt = d_cnt; E.d_off = d_off; E.d_out = d_out; E.d_pa = d_pa; E.d_pb = d_pb;
-    return BTBA_OK;
-}
-
-int btba_match_pairs(btba_workspace *ws, const btba_match_params *prm, int device_resident, int n_frames, int H, int W,
-                     const float *K, const float *const *desc_dev, int D, const float *const *kpts_dev,
-                     const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev, const float *poses,
-                     const int32_t *frame_ids, int n_pairs, const int32_t *pairs,
-                     btba_match *matches_out, float *ptsA_model_out, float *ptsB_model_out, int32_t *n_out)
-{
-    // every argument is checked before the first HIP call
-    int64_t cap = 0;
-    int rc = match_check_frames(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, K, desc_dev, kpts_dev, depth_dev, normal_dev, poses, frame_ids, &cap);
-    if (rc) return rc;
-    if (!ws || (n_pairs && !n_out) || (cap && !matches_out)) return BTBA_EINVAL;
-    if (n_pairs == 0) return BTBA_OK;
-    DeviceGuard device_guard(ws);
-    const bool dev = device_resident != 0;
-    MatchEnqueue E;
-    if ((rc = match_enqueue(ws, prm, dev, n_frames, H, W, K, desc_dev, D, kpts_dev, n_kpts, depth_dev, normal_dev, poses, frame_ids, n_pairs, pairs,
-                            matches_out, ptsA_model_out, ptsB_model_out, E)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(n_out, E.d_cnt, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, ws->stream));
-    HIP_TRY(hipStreamSynchronize(ws->stream));                       // n_out valid; the host tables in E may go
-    if (!dev) {
-        size_t total = 0;
-        for (int p = 0; p < n_pairs; p++) total += (size_t)n_out[p];
-        if (total) {
-            HIP_TRY(hipMemcpyAsync(matches_out, E.d_out, sizeof(btba_match) * total, hipMemcpyDeviceToHost, ws->stream));
-            if (E.d_pa) HIP_TRY(hipMemcpyAsync(ptsA_model_out, E.d_pa, 16 * total, hipMemcpyDeviceToHost, ws->stream));
-            if (E.d_pb) HIP_TRY(hipMemcpyAsync(ptsB_model_out, E.d_pb, 16 * total, hipMemcpyDeviceToHost, ws->stream));
-            HIP_TRY(hipStreamSynchronize(ws->stream));
-        }
-    }
-    return BTBA_OK;
-}
-
-void btba_mask_params_default(btba_mask_params *p)
-{
-    if (!p) return;
-    p->largest_component_hull = 0;                                    // config_ycbineoat.yml: data_dir without "NOCS"
-    p->dilate = 5;                                                    // Frame.cpp:310 (MORPH_RECT 5 x 5)
-}
-
-int btba_apply_masks(btba_workspace *ws, const btba_mask_params *prm, int n_frames, int H, int W,
-                     const uint8_t *const *mask_dev, float *const *depth_dev, float *const *normal_dev,
-                     uint8_t *const *color_dev, uint8_t *const *mask_out_dev, float *roi_out)
-{
-    // every argument is checked before the first HIP call
-    if (!ws || !prm || prm->dilate < 1 || prm->dilate > 2 * kMaskMaxR + 1 || prm->dilate % 2 == 0 || n_frames < 1 || H < 1 || W < 1 ||
-        (int64_t)H * W >= ((int64_t)1 << 31) || !mask_dev || !depth_dev || !normal_dev)
-        return BTBA_EINVAL;
-    for (int f = 0; f < n_frames; f++)
-        if (!mask_dev[f] || !depth_dev[f] || !normal_dev[f] || misaligned(normal_dev[f], 16) ||
-            (color_dev && color_dev[f] && misaligned(color_dev[f], 4)) ||
-            (mask_out_dev && mask_out_dev[f] && static_cast<const void *>(mask_out_dev[f]) == static_cast<const void *>(mask_dev[f])))
-            return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    const bool hull = prm->largest_component_hull != 0;
-    const int r = prm->dilate / 2, chunk = std::min(n_frames, kMaskChunk);
-    const size_t HW = (size_t)H * W;
-    Scratch S;
-    const auto s_roi = S.add<int>(4 * (size_t)n_frames, roi_out != nullptr);
-    const auto s_lab = S.add<int>(chunk * HW, hull), s_cnt = S.add<int>(chunk * HW, hull);
-    const auto s_best = S.add<unsigned long long>(chunk, hull);
-    const auto s_rows = S.add<int2>(chunk * (size_t)H, hull), s_span = S.add<int2>(chunk * (size_t)H, hull);
-    const auto s_stk = S.add<int2>(chunk * (4 * (size_t)H + 2), hull && H > kHullLdsMaxH);
-    int rc;
-    if ((rc = S.bind(ws->mask, 256))) return rc;
-    int *d_roi = s_roi, *d_lab = s_lab, *d_cnt = s_cnt;
-    unsigned long long *d_best = s_best;
-    int2 *d_rows = s_rows, *d_span = s_span, *d_stk = s_stk;
-    if (d_roi) HIP_TRY(hipMemsetAsync(d_roi, 0, sizeof(int) * 4 * n_frames, ws->stream));      // the zero start of k_mask_apply's ROI encoding
-    const dim3 lgrid((W + kLabelTile - 1) / kLabelTile, (H + kLabelTile - 1) / kLabelTile, 1), lblock(kLabelTile, kLabelTile);
-    const dim3 agrid((W + kMaskTileW - 1) / kMaskTileW, (H + kMaskTileH - 1) / kMaskTileH, 1), ablock(kMaskTileW, 4);
-    const size_t hull_lds = H <= kHullLdsMaxH ? sizeof(int2) * (5 * (size_t)H + 2) : 0;
-    for (int b0 = 0; b0 < n_frames; b0 += kMaskChunk) {
-        const int nf = std::min(kMaskChunk, n_frames - b0);
-        MaskFrames F{};
-        for (int z = 0; z < nf; z++) {
-            F.mask[z] = mask_dev[b0 + z];
-            F.depth[z] = depth_dev[b0 + z];
-            F.normal[z] = reinterpret_cast<float4 *>(normal_dev[b0 + z]);
-            F.color[z] = color_dev ? reinterpret_cast<uchar4 *>(color_dev[b0 + z]) : nullptr;
-            F.mask_out[z] = mask_out_dev ? mask_out_dev[b0 + z] : nullptr;
-        }
-        dim3 lg = lgrid, ag = agrid;
-        lg.z = ag.z = nf;
-        if (hull) {
-            k_mask_label_local<<<lg, lblock, 0, ws->stream>>>(W, H, F, d_lab, d_cnt, d_best);
-            k_mask_label_merge<<<lg, lblock, 0, ws->stream>>>(W, H, d_lab);
-            k_mask_label_count<<<lg, lblock, 0, ws->stream>>>(W, H, d_lab, d_cnt);
-            k_mask_argmax<<<dim3((unsigned)((HW + 255) / 256), nf), 256, 0, ws->stream>>>((int)HW, d_cnt, d_best);
-            k_mask_rows<<<dim3((H + 3) / 4, nf), 256, 0, ws->stream>>>(W, H, d_lab, d_best, d_rows);
-            k_mask_hull<<<nf, 256, hull_lds, ws->stream>>>(W, H, d_rows, d_stk, d_span);
-            k_mask_apply<true><<<ag, ablock, 0, ws->stream>>>(W, H, r, F, d_span, d_roi, b0);
-        } else {
-            k_mask_apply<false><<<ag, ablock, 0, ws->stream>>>(W, H, r, F, nullptr, d_roi, b0);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    if (roi_out) {
-        std::vector<int> h(4 * (size_t)n_frames);
-        HIP_TRY(hipMemcpyAsync(h.data(), d_roi, sizeof(int) * h.size(), hipMemcpyDeviceToHost, ws->stream));
-        HIP_TRY(hipStreamSynchronize(ws->stream));
-        for (int f = 0; f < n_frames; f++) {
-            roi_out[4 * f + 0] = (float)(9999 - h[4 * f + 0]);
-            roi_out[4 * f + 1] = (float)h[4 * f + 1];
-            roi_out[4 * f + 2] = (float)(9999 - h[4 * f + 2]);
-            roi_out[4 * f + 3] = (float)h[4 * f + 3];
-        }
-    }
-    return BTBA_OK;
-}
-
 }  // extern "C"
-
-// ---- detector front end (btba_detect.hpp) ----------------------------------------------------------------------
-namespace {
-struct DetRoi { int umin, vmin, wc, hc; };
-
-// the ROI rules shared by the three entry points: integral, non-negative, below 2^24 (exact in float), at least 1 x 1 after the
-// crop, and inside the H x W image when that is known (H > 0)
-bool det_roi(const float *r, int H, int W, DetRoi &o)
-{
-    for (int q = 0; q < 4; q++)
-        if (!(r[q] >= 0.0f && r[q] < 16777216.0f) || r[q] != std::floor(r[q])) return false;
-    o.umin = (int)r[0];
-    o.vmin = (int)r[2];
-    o.wc = (int)(r[1] - r[0]);
-    o.hc = (int)(r[3] - r[2]);
-    if (o.wc < 1 || o.hc < 1) return false;
-    return H <= 0 || ((int64_t)o.umin + o.wc <= W && (int64_t)o.vmin + o.hc <= H);
-}
-
-bool det_params_ok(const btba_detector_params *p)
-{
-    return p && p->out_size >= 4 && p->out_size <= kDetMaxSize && p->out_size % 4 == 0;
-}
-
-// Lfnet::detectFeature's forward_transform (scale * translation, formed by Eigen's 3 x 3 product) and Eigen's cofactor inverse
-// of it, in fp32 (include/btba.h)
-void det_transform(int S, const float *roi, const DetRoi &r, float *fwd, float *bwd)
-{
-#pragma clang fp contract(off)
-    const float s = (float)S / (float)std::max(r.wc, r.hc);
-    const float su = s * roi[0], sv = s * roi[2];
-    const float F[9] = { s, 0.0f, 0.0f - su, 0.0f, s, 0.0f - sv, 0.0f, 0.0f, 1.0f };
-    const float det = s * s, invdet = 1.0f / det, r00 = s * invdet;
-    const float B[9] = { r00, 0.0f, (su * s) * invdet, 0.0f, r00, (sv * s) * invdet, 0.0f, 0.0f, det * invdet };
-    if (fwd) std::memcpy(fwd, F, sizeof F);
-    if (bwd) std::memcpy(bwd, B, sizeof B);
-}
-}  // namespace
-
-extern "C" {
-
-void btba_detector_params_default(btba_detector_params *p)
-{
-    if (!p) return;
-    p->out_size = 400;                                                // Lfnet::detectFeature's H_input = W_input (FeatureManager.cpp:851-852)
-}
-
-int btba_detector_transform(const btba_detector_params *prm, const float *roi, float *fwd, float *bwd)
-{
-    DetRoi r;
-    if (!det_params_ok(prm) || !roi || !fwd || !bwd || !det_roi(roi, 0, 0, r)) return BTBA_EINVAL;
-    det_transform(prm->out_size, roi, r, fwd, bwd);
-    return BTBA_OK;
-}
-
-int btba_detector_inputs(btba_workspace *ws, const btba_detector_params *prm, int n_frames, int H, int W,
-                         const uint8_t *const *color_dev, const float *roi_host, uint8_t *bgr_out_dev, float *gray_out_dev)
-{
-    // every argument is checked before the first HIP call
-    if (!ws || !det_params_ok(prm) || n_frames < 1 || H < 1 || W < 1 || !color_dev || !roi_host ||
-        misaligned(bgr_out_dev, 4) || misaligned(gray_out_dev, 16))
-        return BTBA_EINVAL;
-    std::vector<DetRoi> rois(n_frames);
-    for (int f = 0; f < n_frames; f++)
-        if (!color_dev[f] || misaligned(color_dev[f], 4) || !det_roi(roi_host + 4 * f, H, W, rois[f])) return BTBA_EINVAL;
-    if (!bgr_out_dev && !gray_out_dev) return BTBA_OK;
-    DeviceGuard device_guard(ws);
-    const int S = prm->out_size;
-    const dim3 block(64, 4), grid((S + 255) / 256, S / 4, 1);
-    for (int b0 = 0; b0 < n_frames; b0 += kDetChunk) {
-        const int nf = std::min(kDetChunk, n_frames - b0);
-        DetectFrames F{};
-        for (int z = 0; z < nf; z++) {
-            const DetRoi &r = rois[b0 + z];
-            F.color[z] = reinterpret_cast<const uchar4 *>(color_dev[b0 + z]) + ((size_t)r.vmin * W + r.umin);
-            F.wc[z] = r.wc;
-            F.hc[z] = r.hc;
-        }
-        dim3 g = grid;
-        g.z = nf;
-        k_detect_inputs<<<g, block, 0, ws->stream>>>(W, S, F, b0, bgr_out_dev, gray_out_dev);
-        HIP_TRY(hipGetLastError());
-    }
-    return BTBA_OK;
-}
-
-int btba_detector_keypoints_to_image(btba_workspace *ws, const btba_detector_params *prm, int n_frames, const float *roi_host,
-                                     const float *const *kpts_in_dev, const int32_t *n_kpts, float *const *kpts_out_dev)
-{
-    if (!ws || !det_params_ok(prm) || n_frames < 1 || !roi_host || !kpts_in_dev || !n_kpts || !kpts_out_dev) return BTBA_EINVAL;
-    std::vector<float> bwd(9 * (size_t)n_frames);
-    for (int f = 0; f < n_frames; f++) {
-        DetRoi r;
-        if (n_kpts[f] < 0 || n_kpts[f] > kDetMaxKpts || (n_kpts[f] > 0 && (!kpts_in_dev[f] || !kpts_out_dev[f])) ||
-            misaligned(kpts_in_dev[f], 8) || misaligned(kpts_out_dev[f], 8) || !det_roi(roi_host + 4 * f, 0, 0, r))
-            return BTBA_EINVAL;
-        det_transform(prm->out_size, roi_host + 4 * f, r, nullptr, bwd.data() + 9 * f);
-    }
-    DeviceGuard device_guard(ws);
-    for (int b0 = 0; b0 < n_frames; b0 += kDetChunk) {
-        const int nf = std::min(kDetChunk, n_frames - b0);
-        KptFrames F{};
-        int n_max = 0;
-        for (int z = 0; z < nf; z++) {
-            const float *B = bwd.data() + 9 * (b0 + z);
-            F.in[z] = reinterpret_cast<const float2 *>(kpts_in_dev[b0 + z]);
-            F.out[z] = reinterpret_cast<float2 *>(kpts_out_dev[b0 + z]);
-            F.n[z] = n_kpts[b0 + z];
-            F.r00[z] = B[0]; F.r02[z] = B[2]; F.r11[z] = B[4]; F.r12[z] = B[5];
-            n_max = std::max(n_max, F.n[z]);
-        }
-        if (n_max == 0) continue;
-        k_detect_keypoints<<<dim3((n_max + 255) / 256, nf), 256, 0, ws->stream>>>(F);
-        HIP_TRY(hipGetLastError());
-    }
-    return BTBA_OK;
-}
-
-void btba_lfnet_params_default(btba_lfnet_params *p)
-{
-    if (!p) return;
-    p->sm_ksize = 15; p->com_strength = 3.0f; p->score_com_strength = 100.0f; p->scale_com_strength = 100.0f;      // train_lfnet.py:1047-1189
-    p->nms_thresh = 0.0f; p->nms_ksize = 5;
-    p->top_k = 500;                                                   // run_server.py
-    p->pad_size = 16;                                                 // mso_resnet_detector.py:171: five-tap convolutions, three blocks
-    p->crop_radius = 16; p->soft_kpts = 1; p->kp_loc_size = 9; p->do_softmax_kp_refine = 1; p->kp_com_strength = 1.0f; p->patch_size = 32;
-}
-
-namespace {
-bool lfnet_params_ok(const btba_lfnet_params *p, int n_frames, int H, int W)
-{
-    if (!p || n_frames < 1 || H < 1 || W < 1 || H > BTBA_LFNET_MAX_SIZE || W > BTBA_LFNET_MAX_SIZE) return false;
-    if (p->sm_ksize < 1 || p->sm_ksize > BTBA_LFNET_MAX_KSIZE || p->sm_ksize % 2 == 0) return false;
-    if (p->nms_ksize < 1 || p->nms_ksize > BTBA_LFNET_MAX_KSIZE || p->nms_ksize % 2 == 0) return false;
-    if (p->top_k < 1 || p->top_k > BTBA_LFNET_MAX_TOP_K) return false;
-    const int m = std::min(H, W);
-    if (p->pad_size < 0 || p->crop_radius < 0 || 2 * (int64_t)p->pad_size >= m || 2 * (int64_t)p->crop_radius >= m) return false;
-    if (p->patch_size < 2 || p->patch_size > 64 || p->kp_loc_size < 2 || p->kp_loc_size > 64) return false;
-    return true;
-}
-
-// One layout for all three stages, so that a call of any of them leaves the others' regions where they were.
-struct LfnetScratch {
-    Scratch sc;
-    Scratch::Region<float2> stats;
-    Scratch::Region<uint8_t> peak;
-    Scratch::Region<int32_t> list_idx;
-    Scratch::Region<uint32_t> list_key;
-    LfnetScratch(int n_frames, int H, int W)
-        : stats(sc.add<float2>((size_t)n_frames * kLfnetMaxScales)), peak(sc.add<uint8_t>((size_t)n_frames * H * W)),
-          list_idx(sc.add<int32_t>((size_t)n_frames * H * W)), list_key(sc.add<uint32_t>((size_t)n_frames * H * W)) {}
-};
-
-int lfnet_heatmaps_enqueue(btba_workspace *ws, const btba_lfnet_params *prm, LfnetScratch &L, int n_frames, int H, int W, int S,
-                           const float *const *score_dev, const int32_t *map_h, const int32_t *map_w, const float *scale_factors,
-                           float *heat_dev, float *scales_dev)
-{
-    LfnetMaps M{};
-    for (int s = 0; s < S; s++) { M.p[s] = score_dev[s]; M.h[s] = map_h[s]; M.w[s] = map_w[s]; M.sf[s] = scale_factors[s]; }
-    const int h = prm->sm_ksize / 2;
-    int T = 16;
-    if (sizeof(float) * lfnet_heat_lds_floats(S, T, h) > 80 * 1024) T = 8;
-    const size_t lds = sizeof(float) * lfnet_heat_lds_floats(S, T, h);          // at most 122 KB (S = 16, k = 31)
-    if (!ws->lfnet_attr_set) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lfnet_heat), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ws->lfnet_attr_set = true;
-    }
-    k_lfnet_moments<<<dim3(S, n_frames), 256, 0, ws->stream>>>(M, L.stats);
-    HIP_TRY(hipGetLastError());
-    k_lfnet_heat<<<dim3((W + T - 1) / T, (H + T - 1) / T, n_frames), 256, lds, ws->stream>>>(
-        M, L.stats, S, H, W, T, h, prm->com_strength, prm->score_com_strength, prm->scale_com_strength, prm->pad_size, heat_dev, scales_dev);
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-int lfnet_select_enqueue(btba_workspace *ws, const btba_lfnet_params *prm, LfnetScratch &L, int n_frames, int H, int W, const float *heat_dev,
-                         int32_t *kpts_xy_dev, int32_t *n_kpts_dev)
-{
-    k_lfnet_peaks<<<dim3((H * W + 255) / 256, n_frames), 256, 0, ws->stream>>>(heat_dev, H, W, prm->nms_thresh, prm->nms_ksize / 2, L.peak);
-    HIP_TRY(hipGetLastError());
-    k_lfnet_select<<<n_frames, kLfnetSelectThreads, 0, ws->stream>>>(heat_dev, L.peak, H, W, prm->crop_radius, prm->top_k, L.list_idx, L.list_key,
-                                                                     kpts_xy_dev, n_kpts_dev);
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-int lfnet_crops_enqueue(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, const float *photo_dev, const float *ori_dev,
-                        const float *heat_dev, const float *scales_dev, const int32_t *kpts_xy_dev, const int32_t *n_kpts_dev,
-                        float *kpts_out_dev, float *kpts_scale_out_dev, float *kpts_ori_out_dev, float *patches_out_dev)
-{
-    k_lfnet_crops<<<dim3(prm->top_k, n_frames), 64, 0, ws->stream>>>(photo_dev, ori_dev, heat_dev, scales_dev, kpts_xy_dev, n_kpts_dev, H, W,
-                                                                     prm->top_k, prm->soft_kpts, prm->kp_loc_size, prm->do_softmax_kp_refine,
-                                                                     prm->kp_com_strength, prm->patch_size, kpts_out_dev, kpts_scale_out_dev,
-                                                                     kpts_ori_out_dev, patches_out_dev);
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-bool lfnet_maps_ok(int S, const float *const *score_dev, const int32_t *map_h, const int32_t *map_w, const float *scale_factors)
-{
-    if (S < 1 || S > BTBA_LFNET_MAX_SCALES || !score_dev || !map_h || !map_w || !scale_factors) return false;
-    for (int s = 0; s < S; s++)
-        if (!score_dev[s] || misaligned(score_dev[s], 4) || map_h[s] < 1 || map_w[s] < 1 || map_h[s] > 4 * BTBA_LFNET_MAX_SIZE ||
-            map_w[s] > 4 * BTBA_LFNET_MAX_SIZE || (int64_t)map_h[s] * map_w[s] > INT32_MAX)
-            return false;
-    return true;
-}
-}  // namespace
-
-int btba_lfnet_heatmaps(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, int S, const float *const *score_dev,
-                        const int32_t *map_h, const int32_t *map_w, const float *scale_factors, float *max_heatmaps_dev, float *max_scales_dev)
-{
-    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !lfnet_maps_ok(S, score_dev, map_h, map_w, scale_factors) || !max_heatmaps_dev ||
-        !max_scales_dev || misaligned(max_heatmaps_dev, 4) || misaligned(max_scales_dev, 4))
-        return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    LfnetScratch L(n_frames, H, W);
-    if (int rc = L.sc.bind(ws->lfnet)) return rc;
-    return lfnet_heatmaps_enqueue(ws, prm, L, n_frames, H, W, S, score_dev, map_h, map_w, scale_factors, max_heatmaps_dev, max_scales_dev);
-}
-
-int btba_lfnet_select(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, const float *heat_dev,
-                      int32_t *kpts_xy_dev, int32_t *n_kpts_dev)
-{
-    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !heat_dev || !kpts_xy_dev || !n_kpts_dev || misaligned(heat_dev, 4) ||
-        misaligned(kpts_xy_dev, 4) || misaligned(n_kpts_dev, 4))
-        return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    LfnetScratch L(n_frames, H, W);
-    if (int rc = L.sc.bind(ws->lfnet)) return rc;
-    return lfnet_select_enqueue(ws, prm, L, n_frames, H, W, heat_dev, kpts_xy_dev, n_kpts_dev);
-}
-
-int btba_lfnet_crops(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, const float *photo_dev, const float *ori_dev,
-                     const float *heat_dev, const float *scales_dev, const int32_t *kpts_xy_dev, const int32_t *n_kpts_dev,
-                     float *kpts_out_dev, float *kpts_scale_out_dev, float *kpts_ori_out_dev, float *patches_out_dev)
-{
-    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !photo_dev || !ori_dev || !heat_dev || !scales_dev || !kpts_xy_dev || !n_kpts_dev ||
-        !kpts_out_dev || !kpts_scale_out_dev || !kpts_ori_out_dev || !patches_out_dev)
-        return BTBA_EINVAL;
-    for (const void *q : { (const void *)photo_dev, (const void *)ori_dev, (const void *)heat_dev, (const void *)scales_dev, (const void *)kpts_xy_dev,
-                           (const void *)n_kpts_dev, (const void *)kpts_out_dev, (const void *)kpts_scale_out_dev, (const void *)kpts_ori_out_dev,
-                           (const void *)patches_out_dev })
-        if (misaligned(q, 4)) return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    return lfnet_crops_enqueue(ws, prm, n_frames, H, W, photo_dev, ori_dev, heat_dev, scales_dev, kpts_xy_dev, n_kpts_dev, kpts_out_dev,
-                               kpts_scale_out_dev, kpts_ori_out_dev, patches_out_dev);
-}
-
-int btba_lfnet_keypoints(btba_workspace *ws, const btba_lfnet_params *prm, int n_frames, int H, int W, int S, const float *const *score_dev,
-                         const int32_t *map_h, const int32_t *map_w, const float *scale_factors, const float *photo_dev, const float *ori_dev,
-                         float *max_heatmaps_dev, float *max_scales_dev, int32_t *kpts_xy_dev, int32_t *n_kpts_dev, float *kpts_out_dev,
-                         float *kpts_scale_out_dev, float *kpts_ori_out_dev, float *patches_out_dev, int32_t *n_kpts_host)
-{
-    // every argument is checked before the first HIP call
-    if (!ws || !lfnet_params_ok(prm, n_frames, H, W) || !lfnet_maps_ok(S, score_dev, map_h, map_w, scale_factors) || !photo_dev || !ori_dev ||
-        !max_heatmaps_dev || !max_scales_dev || !kpts_xy_dev || !n_kpts_dev || !kpts_out_dev || !kpts_scale_out_dev || !kpts_ori_out_dev ||
-        !patches_out_dev)
-        return BTBA_EINVAL;
-    for (const void *q : { (const void *)photo_dev, (const void *)ori_dev, (const void *)max_heatmaps_dev, (const void *)max_scales_dev,
-                           (const void *)kpts_xy_dev, (const void *)n_kpts_dev, (const void *)kpts_out_dev, (const void *)kpts_scale_out_dev,
-                           (const void *)kpts_ori_out_dev, (const void *)patches_out_dev })
-        if (misaligned(q, 4)) return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    LfnetScratch L(n_frames, H, W);
-    if (int rc = L.sc.bind(ws->lfnet)) return rc;
-    if (int rc = lfnet_heatmaps_enqueue(ws, prm, L, n_frames, H, W, S, score_dev, map_h, map_w, scale_factors, max_heatmaps_dev, max_scales_dev)) return rc;
-    if (int rc = lfnet_select_enqueue(ws, prm, L, n_frames, H, W, max_heatmaps_dev, kpts_xy_dev, n_kpts_dev)) return rc;
-    if (int rc = lfnet_crops_enqueue(ws, prm, n_frames, H, W, photo_dev, ori_dev, max_heatmaps_dev, max_scales_dev, kpts_xy_dev, n_kpts_dev,
-                                     kpts_out_dev, kpts_scale_out_dev, kpts_ori_out_dev, patches_out_dev))
-        return rc;
-    if (n_kpts_host) {
-        HIP_TRY(hipMemcpyAsync(n_kpts_host, n_kpts_dev, sizeof(int32_t) * (size_t)n_frames, hipMemcpyDeviceToHost, ws->stream));
-        HIP_TRY(hipStreamSynchronize(ws->stream));                   // the call's one host wait
-    }
-    return BTBA_OK;
-}
-
-void btba_lfnet_desc_config_default(btba_lfnet_desc_config *c)
-{
-    if (!c) return;
-    c->patch_size = 32; c->depth = 3; c->channels = 64; c->fc_dim = 512; c->out_dim = 256;      // simple_desc.py:10-14, run_server.py's checkpoint
-    c->activation = 0; c->leaky_alpha = 0.2f; c->norm = 0;
-    c->bn_eps = 1e-5f;                                                // tf_layer_utils.py:185
-}
-
-struct btba_lfnet_desc_model {
-    btba_workspace *ws = nullptr;
-    int device = 0;
-    btba_lfnet_desc_config cfg{};
-    struct Layer { size_t w = 0, scale = 0, shift = 0; int K = 0, N = 0; };      // offsets in floats into dev
-    Layer layers[BTBA_LFNET_DESC_MAX_DEPTH + 2];
-    int n_layers = 0;
-    size_t widest = 0;                     // floats per patch of the widest layer output
-    DevBuf dev;
-};
-
-namespace {
-bool desc_config_ok(const btba_lfnet_desc_config *c)
-{
-    if (!c || c->depth < 1 || c->depth > BTBA_LFNET_DESC_MAX_DEPTH || c->patch_size < 8 || c->patch_size > 64 || c->patch_size % (1 << c->depth)) return false;
-    if (c->channels < 16 || c->channels > 128 || c->channels % 16 || c->fc_dim < 16 || c->fc_dim > 1024 || c->fc_dim % 16) return false;
-    if (c->out_dim < 16 || c->out_dim > 512 || c->out_dim % 16 || c->activation < 0 || c->activation > 1 || c->norm < 0 || c->norm > 1) return false;
-    if (!std::isfinite(c->leaky_alpha) || !std::isfinite(c->bn_eps) || c->bn_eps < 0.0f) return false;
-    const int s = c->patch_size >> c->depth;
-    return (int64_t)s * s * (c->channels << (c->depth - 1)) <= 16384;
-}
-bool all_finite(const float *a, size_t n)
-{
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-}  // namespace
-
-int btba_lfnet_desc_model_create(btba_workspace *ws, const btba_lfnet_desc_config *cfg, const btba_lfnet_desc_weights *wts, btba_lfnet_desc_model **out)
-{
-    if (out) *out = nullptr;
-    if (!ws || !wts || !out || !desc_config_ok(cfg)) return BTBA_EINVAL;
-    const int depth = cfg->depth, n_layers = depth + 2;
-    const btba_lfnet_desc_layer *src[BTBA_LFNET_DESC_MAX_DEPTH + 2];
-    int Ks[BTBA_LFNET_DESC_MAX_DEPTH + 2], Ns[BTBA_LFNET_DESC_MAX_DEPTH + 2];
-    size_t widest = 0;
-    for (int i = 0; i < depth; i++) {
-        src[i] = &wts->conv[i];
-        Ks[i] = 9 * (i ? cfg->channels << (i - 1) : 1);
-        Ns[i] = cfg->channels << i;
-        const size_t s = (size_t)(cfg->patch_size >> (i + 1));
-        widest = std::max(widest, s * s * Ns[i]);
-    }
-    const int flat = (cfg->patch_size >> depth) * (cfg->patch_size >> depth) * Ns[depth - 1];
-    src[depth] = &wts->fc1; Ks[depth] = flat; Ns[depth] = cfg->fc_dim;
-    src[depth + 1] = &wts->fc2; Ks[depth + 1] = cfg->fc_dim; Ns[depth + 1] = cfg->out_dim;
-    widest = std::max(widest, (size_t)std::max(cfg->fc_dim, cfg->out_dim));
-    for (int i = 0; i < n_layers; i++) {
-        const btba_lfnet_desc_layer &l = *src[i];
-        const size_t N = (size_t)Ns[i];
-        if (!l.weights || !all_finite(l.weights, (size_t)Ks[i] * N) || (l.biases && !all_finite(l.biases, N))) return BTBA_EINVAL;
-        if ((l.moving_mean == nullptr) != (l.moving_variance == nullptr)) return BTBA_EINVAL;
-        if (l.moving_mean) {
-            if (!all_finite(l.moving_mean, N) || !all_finite(l.moving_variance, N) || (l.gamma && !all_finite(l.gamma, N)) ||
-                (l.beta && !all_finite(l.beta, N)))
-                return BTBA_EINVAL;
-            for (size_t n = 0; n < N; n++)
-                if (!((double)l.moving_variance[n] + (double)cfg->bn_eps > 0.0)) return BTBA_EINVAL;
-        }
-    }
-    // every argument has been checked; the first HIP call follows
-    std::unique_ptr<btba_lfnet_desc_model> M(new (std::nothrow) btba_lfnet_desc_model());
-    if (!M) return BTBA_ENOMEM;
-    M->ws = ws; M->device = ws->device; M->cfg = *cfg; M->n_layers = n_layers; M->widest = widest;
-    auto pad64 = [](size_t n) { return (n + 63) & ~(size_t)63; };    // 256-byte regions: 16-byte loads of weight rows
-    size_t total = 0;
-    for (int i = 0; i < n_layers; i++) {
-        btba_lfnet_desc_model::Layer &L = M->layers[i];
-        L.K = Ks[i]; L.N = Ns[i];
-        L.w = total; total += pad64((size_t)Ks[i] * Ns[i]);
-        L.scale = total; total += pad64(Ns[i]);
-        L.shift = total; total += pad64(Ns[i]);
-    }
-    std::vector<float> host(total, 0.0f);
-    for (int i = 0; i < n_layers; i++) {
-        const btba_lfnet_desc_layer &l = *src[i];
-        const btba_lfnet_desc_model::Layer &L = M->layers[i];
-        std::memcpy(host.data() + L.w, l.weights, sizeof(float) * (size_t)L.K * L.N);      // [3][3][C_in][C_out] IS [K][N] in (ky, kx, c_in) order
-        for (int n = 0; n < L.N; n++) {
-            const double bias = l.biases ? (double)l.biases[n] : 0.0;
-            double scale = 1.0, shift = bias;
-            if (l.moving_mean) {
-                scale = (l.gamma ? (double)l.gamma[n] : 1.0) / std::sqrt((double)l.moving_variance[n] + (double)cfg->bn_eps);
-                shift = (l.beta ? (double)l.beta[n] : 0.0) + (bias - (double)l.moving_mean[n]) * scale;
-            }
-            host[L.scale + n] = (float)scale;
-            host[L.shift + n] = (float)shift;
-        }
-    }
-    DeviceGuard device_guard(ws);
-    if (int rc = M->dev.ensure(sizeof(float) * total)) return rc;
-    HIP_TRY(hipMemcpy(M->dev.p, host.data(), sizeof(float) * total, hipMemcpyHostToDevice));
-    *out = M.release();
-    return BTBA_OK;
-}
-
-void btba_lfnet_desc_model_destroy(btba_lfnet_desc_model *M)
-{
-    if (!M) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
-    (void)hipDeviceSynchronize();                                     // delete frees the weights; no workspace access
-    delete M;
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-int btba_lfnet_descriptors(btba_workspace *ws, const btba_lfnet_desc_model *M, int n_frames, int slots, const float *patches_dev,
-                           const int32_t *n_kpts_dev, float *desc_dev)
-{
-    // the counts first: a model is not read before they are known to be sane
-    if (!ws || !M || n_frames < 0 || slots < 0 || slots > BTBA_LFNET_MAX_TOP_K || (int64_t)n_frames * slots > (1 << 24)) return BTBA_EINVAL;
-    const int total = n_frames * slots;
-    if (total == 0) return BTBA_OK;
-    if (!patches_dev || !desc_dev || misaligned(patches_dev, 4) || misaligned(desc_dev, 4) || misaligned(n_kpts_dev, 4) || M->ws != ws) return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    const btba_lfnet_desc_config &c = M->cfg;
-    const int chunk = std::min(total, kDescChunk), P = c.patch_size, depth = c.depth, D = c.out_dim;
-    Scratch sc;
-    Scratch::Region<float> b0 = sc.add<float>((size_t)chunk * M->widest), b1 = sc.add<float>((size_t)chunk * M->widest);
-    if (int rc = sc.bind(ws->lfnet_desc)) return rc;
-    float *buf[2] = { b0, b1 };
-    const float *W = M->dev.as<float>();
-    for (int p0 = 0; p0 < total; p0 += chunk) {
-        const int np = std::min(chunk, total - p0);
-        {
-            const btba_lfnet_desc_model::Layer &L = M->layers[0];
-            DescConv1 G{};
-            G.patches = patches_dev + (size_t)p0 * P * P; G.w = W + L.w; G.scale = W + L.scale; G.shift = W + L.shift; G.out = buf[0];
-            G.n_kpts = n_kpts_dev; G.n_patches = np; G.P = P; G.Ho = P / 2; G.pad = 0; G.C = L.N; G.act = c.activation; G.slots = slots;
-            G.patch0 = p0; G.alpha = c.leaky_alpha;
-            const int64_t threads = (int64_t)np * G.Ho * G.Ho * (L.N / 4);
-            k_desc_conv1<<<(unsigned)((threads + 255) / 256), 256, 0, ws->stream>>>(G);
-            HIP_TRY(hipGetLastError());
-        }
-        for (int i = 1; i < M->n_layers; i++) {
-            const btba_lfnet_desc_model::Layer &L = M->layers[i];
-            const bool conv = i < depth;
-            DescGemm G{};
-            G.in = buf[(i - 1) & 1]; G.out = buf[i & 1]; G.w = W + L.w; G.scale = W + L.scale; G.shift = W + L.shift; G.n_kpts = n_kpts_dev;
-            G.N = L.N; G.K = L.K; G.slots = slots; G.patch0 = p0; G.alpha = c.leaky_alpha;
-            if (conv) {               // an even input size: TensorFlow's SAME pads nothing before and one row and column after
-                G.Hi = G.Wi = P >> i; G.Ho = G.Wo = P >> (i + 1); G.Cin = L.K / 9; G.ks = 3; G.pad = 0; G.act = c.activation;
-            } else {
-                G.Hi = G.Wi = G.Ho = G.Wo = 1; G.Cin = L.K; G.ks = 1; G.pad = 0; G.act = i == depth ? c.activation : kDescActNone;
-            }
-            G.M = np * G.Ho * G.Wo;
-            k_desc_gemm<<<dim3((G.M + kDescBM - 1) / kDescBM, (G.N + kDescBN - 1) / kDescBN), 256, 0, ws->stream>>>(G);
-            HIP_TRY(hipGetLastError());
-        }
-        k_desc_finish<<<(np + 3) / 4, 256, 0, ws->stream>>>(buf[(M->n_layers - 1) & 1], desc_dev + (size_t)p0 * D, n_kpts_dev, np, D, c.norm == 0,
-                                                             slots, p0);
-        HIP_TRY(hipGetLastError());
-    }
-    return BTBA_OK;
-}
-
-int btba_pose_errors(btba_workspace *ws, int device_resident, int n_models, const float *const *model_pts_dev, const int32_t *n_pts,
-                     int n_evals, const int32_t *model_index, const float *poses_pred, const float *poses_gt,
-                     float *add_out, float *adds_out)
-{
-    // every argument is checked before the first HIP call
-    if (!ws || n_models < 1 || !model_pts_dev || !n_pts || n_evals < 0) return BTBA_EINVAL;
-    for (int m = 0; m < n_models; m++)
-        if (!model_pts_dev[m] || misaligned(model_pts_dev[m], 4) || n_pts[m] < 1 || n_pts[m] > BTBA_EVAL_MAX_POINTS)
-            return BTBA_EINVAL;
-    if (n_evals == 0) return BTBA_OK;
-    if (!model_index || !poses_pred || !poses_gt || !add_out || !adds_out) return BTBA_EINVAL;
-    for (int e = 0; e < n_evals; e++)
-        if (model_index[e] < 0 || model_index[e] >= n_models) return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-
-    // chunks: at most kEvalChunkEvals evaluations and kEvalScratchPoints per-point minima each
-    std::vector<EvalRec> rec(n_evals);
-    std::vector<int> chunk_start{ 0 };
-    int64_t pts_in_chunk = 0, max_chunk_pts = 0;
-    for (int e = 0; e < n_evals; e++) {
-        const int n = n_pts[model_index[e]];
-        if (e > chunk_start.back() && (pts_in_chunk + n > kEvalScratchPoints || e - chunk_start.back() >= kEvalChunkEvals)) {
-            chunk_start.push_back(e);
-            pts_in_chunk = 0;
-        }
-        rec[e] = EvalRec{ model_pts_dev[model_index[e]], n, (int)pts_in_chunk };
-        pts_in_chunk += n;
-        max_chunk_pts = std::max(max_chunk_pts, pts_in_chunk);
-    }
-    chunk_start.push_back(n_evals);
-    const int max_chunk = std::min(n_evals, kEvalChunkEvals);
-    const bool dev = device_resident != 0;
-    Scratch S;
-    const auto s_rec = S.add<EvalRec>(max_chunk);
-    const auto s_pp = S.add<float>(16 * (size_t)max_chunk, !dev), s_pg = S.add<float>(16 * (size_t)max_chunk, !dev);
-    const auto s_out = S.add<float>(2 * (size_t)max_chunk, !dev);
-    const auto s_min = S.add<unsigned>((size_t)max_chunk_pts);
-    int rc = S.bind(ws->eval);
-    if (rc) return rc;
-    EvalRec *d_rec = s_rec;
-    unsigned *d_min = s_min;
-    for (size_t c = 0; c + 1 < chunk_start.size(); c++) {
-        const int e0 = chunk_start[c], ne = chunk_start[c + 1] - e0;
-        int max_n = 0;
-        for (int e = e0; e < e0 + ne; e++) max_n = std::max(max_n, rec[e].n);
-        const float *pp = poses_pred + 16 * (size_t)e0, *pg = poses_gt + 16 * (size_t)e0;
-        float *oa = add_out + e0, *os = adds_out + e0;
-        HIP_TRY(hipMemcpyAsync(d_rec, rec.data() + e0, sizeof(EvalRec) * ne, hipMemcpyHostToDevice, ws->stream));
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(s_pp, pp, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
-            HIP_TRY(hipMemcpyAsync(s_pg, pg, sizeof(float) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
-            pp = s_pp;
-            pg = s_pg;
-            oa = s_out;
-            os = oa + max_chunk;
-        }
-        // split the candidates when evaluations x query tiles cannot fill the chip (the result does not depend on it)
-        const int tiles = (max_n + kEvalQTile - 1) / kEvalQTile;
-        const int64_t wgs = (int64_t)ne * tiles;
-        int splits = 1;
-        if (wgs < 2048) splits = (int)std::min<int64_t>((2048 + wgs - 1) / wgs, (max_n + kEvalCTile - 1) / kEvalCTile);
-        int per = (max_n + splits - 1) / splits;
-        per = (per + kEvalCTile - 1) / kEvalCTile * kEvalCTile;
-        splits = (max_n + per - 1) / per;
-        if (splits > 1) HIP_TRY(hipMemsetAsync(d_min, 0xff, sizeof(unsigned) * (size_t)(rec[e0 + ne - 1].off + rec[e0 + ne - 1].n), ws->stream));
-        k_eval_nn<<<dim3(ne, tiles, splits), kEvalThreads, 0, ws->stream>>>(d_rec, pp, pg, per, splits > 1 ? 1 : 0, d_min);
-        k_eval_reduce<<<ne, kEvalRedThreads, 0, ws->stream>>>(d_rec, pp, pg, d_min, oa, os);
-        HIP_TRY(hipGetLastError());
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(add_out + e0, oa, sizeof(float) * ne, hipMemcpyDeviceToHost, ws->stream));
-            HIP_TRY(hipMemcpyAsync(adds_out + e0, os, sizeof(float) * ne, hipMemcpyDeviceToHost, ws->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host tables above may go
-    return BTBA_OK;
-}
-
-void btba_nocs_params_default(btba_nocs_params *p)
-{
-    if (!p) return;
-    p->rot_thresh_deg = 5.0;
-    p->shift_thresh = 50.0;
-    p->iou_thresh = 0.25;
-    p->n_sym_steps = 20;
-    p->flip_z180_pred = 1;
-    p->normalize_columns = 1;
-    p->clamp_acos = 0;
-}
-
-int btba_nocs_errors(btba_workspace *ws, const btba_nocs_params *params_in, int device_resident, int n_boxes, const double *boxes,
-                     int n_evals, const int32_t *class_id, const int32_t *handle_visible, const int32_t *box_index,
-                     const double *poses_pred, const double *poses_gt, double *theta_deg_out, double *shift_out, double *iou_out)
-{
-    // every argument is checked before the first HIP call
-    btba_nocs_params prm;
-    if (params_in) prm = *params_in; else btba_nocs_params_default(&prm);
-    if (!ws || !boxes || n_boxes < 1 || n_boxes > (1 << 30) || n_evals < 0 || prm.n_sym_steps < 1 || prm.n_sym_steps > kNocsMaxSteps) return BTBA_EINVAL;
-    if (n_evals == 0) return BTBA_OK;
-    if (!class_id || !box_index || !poses_pred || !poses_gt || !theta_deg_out || !shift_out || !iou_out) return BTBA_EINVAL;
-    const bool dev = device_resident != 0;
-    if (dev && (misaligned(poses_pred, 8) || misaligned(poses_gt, 8) || misaligned(theta_deg_out, 8) || misaligned(shift_out, 8) || misaligned(iou_out, 8)))
-        return BTBA_EINVAL;
-    std::vector<int32_t> meta(n_evals);                     // box_index << 1 | rotation-symmetric
-    for (int e = 0; e < n_evals; e++) {
-        const int32_t c = class_id[e];
-        if (c < 1 || c > 6 || box_index[e] < 0 || box_index[e] >= n_boxes) return BTBA_EINVAL;
-        const bool sym = c == 1 || c == 2 || c == 4 || (c == 6 && handle_visible && handle_visible[e] == 0);
-        meta[e] = box_index[e] << 1 | (sym ? 1 : 0);
-    }
-    double table[2 * kNocsMaxSteps] = {};                   // (cos, sin) of ((2 pi) i) / n_sym_steps: the bits every item rotates by
-    for (int i = 0; i < prm.n_sym_steps; i++) {
-        const double a = 2.0 * M_PI * (double)i / (double)prm.n_sym_steps;
-        table[2 * i] = std::cos(a);
-        table[2 * i + 1] = std::sin(a);
-    }
-    const int flags = (prm.flip_z180_pred ? kNocsFlip : 0) | (prm.normalize_columns ? kNocsNormalize : 0) | (prm.clamp_acos ? kNocsClamp : 0);
-    DeviceGuard device_guard(ws);
-
-    const int max_chunk = std::min(n_evals, kNocsChunkItems);
-    Scratch S;
-    const auto s_meta = S.add<int32_t>(max_chunk);
-    const auto s_box = S.add<double>(24 * (size_t)n_boxes);
-    const auto s_tab = S.add<double>(2 * kNocsMaxSteps);
-    const auto s_pp = S.add<double>(16 * (size_t)max_chunk, !dev), s_pg = S.add<double>(16 * (size_t)max_chunk, !dev);
-    const auto s_out = S.add<double>(3 * (size_t)max_chunk, !dev);
-    int rc = S.bind(ws->nocs);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(s_box, boxes, sizeof(double) * 24 * (size_t)n_boxes, hipMemcpyHostToDevice, ws->stream));
-    HIP_TRY(hipMemcpyAsync(s_tab, table, sizeof(table), hipMemcpyHostToDevice, ws->stream));
-    for (int e0 = 0; e0 < n_evals; e0 += kNocsChunkItems) {
-        const int ne = std::min(kNocsChunkItems, n_evals - e0);
-        const double *pp = poses_pred + 16 * (size_t)e0, *pg = poses_gt + 16 * (size_t)e0;
-        double *ot = theta_deg_out + e0, *os = shift_out + e0, *oi = iou_out + e0;
-        HIP_TRY(hipMemcpyAsync(s_meta, meta.data() + e0, sizeof(int32_t) * ne, hipMemcpyHostToDevice, ws->stream));
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(s_pp, pp, sizeof(double) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
-            HIP_TRY(hipMemcpyAsync(s_pg, pg, sizeof(double) * 16 * ne, hipMemcpyHostToDevice, ws->stream));
-            pp = s_pp;
-            pg = s_pg;
-            ot = s_out;
-            os = ot + max_chunk;
-            oi = os + max_chunk;
-        }
-        k_nocs_errors<<<(ne + kNocsItems - 1) / kNocsItems, kNocsThreads, 0, ws->stream>>>(ne, s_meta, s_box, pp, pg, s_tab, prm.n_sym_steps, flags, ot, os, oi);
-        HIP_TRY(hipGetLastError());
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(theta_deg_out + e0, ot, sizeof(double) * ne, hipMemcpyDeviceToHost, ws->stream));
-            HIP_TRY(hipMemcpyAsync(shift_out + e0, os, sizeof(double) * ne, hipMemcpyDeviceToHost, ws->stream));
-            HIP_TRY(hipMemcpyAsync(iou_out + e0, oi, sizeof(double) * ne, hipMemcpyDeviceToHost, ws->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host tables above may go
-    return BTBA_OK;
-}
-
-int btba_window_layout(int n_windows, int n_frames, const int32_t *seg_counts, const int32_t *newframe_index, int32_t min_fm_edges_newframe,
-                       int64_t *corr_stride_out, uint32_t *max_corr_per_pair_out, uint32_t *pair_offsets_out,
-                       int64_t *n_edges_newframe_out, int32_t *run_ba_out)
-{
-    if (n_windows < 1 || n_frames < 2 || n_frames > BTBA_MAX_FRAMES || !seg_counts || !newframe_index) return BTBA_EINVAL;
-    const int P = n_frames * (n_frames - 1) / 2;
-    int64_t stride = 0;
-    int32_t longest = 0;
-    for (int w = 0; w < n_windows; w++) {                             // validate everything before the first output is written
-        if (newframe_index[w] < 0 || newframe_index[w] >= n_frames) return BTBA_EINVAL;
-        int64_t total = 0;
-        for (int p = 0; p < P; p++) {
-            const int32_t c = seg_counts[(size_t)w * P + p];
-            if (c < 0) return BTBA_EINVAL;
-            total += c;
-            longest = std::max(longest, c);
-        }
-        if (total > (int64_t)UINT32_MAX) return BTBA_EINVAL;
-        stride = std::max(stride, total);
-    }
-    for (int w = 0; w < n_windows; w++) {
-        const int32_t *cnt = seg_counts + (size_t)w * P;
-        const int nf = newframe_index[w];
-        int64_t edges = 0;
-        uint32_t at = 0;
-        int p = 0;
-        for (int i = 0; i < n_frames; i++)
-            for (int j = i + 1; j < n_frames; j++, p++) {
-                if (pair_offsets_out) pair_offsets_out[(size_t)w * (P + 1) + p] = at;
-                at += (uint32_t)cnt[p];
-                if (i == nf || j == nf) edges += cnt[p];
-            }
-        if (pair_offsets_out) pair_offsets_out[(size_t)w * (P + 1) + P] = at;
-        if (n_edges_newframe_out) n_edges_newframe_out[w] = edges;
-        if (run_ba_out) run_ba_out[w] = edges > (int64_t)min_fm_edges_newframe ? 1 : 0;
-    }
-    if (corr_stride_out) *corr_stride_out = stride;
-    if (max_corr_per_pair_out) *max_corr_per_pair_out = (uint32_t)longest;
-    return BTBA_OK;
-}
-
-int btba_marshal_windows(btba_workspace *ws, int n_windows, int n_frames, const btba_match *matches_dev, int64_t n_records,
-                         const uint32_t *segments_dev, uint32_t max_corr_per_pair, int64_t corr_stride,
-                         btba_entryj *corr_dev, uint32_t *pair_offsets_dev, float *corr24_dev)
-{
-    if (!ws || n_windows < 1 || n_windows > 65535 || n_frames < 2 || n_frames > BTBA_MAX_FRAMES || n_records < 0 || n_records > (int64_t)UINT32_MAX ||
-        (!matches_dev && n_records) || !segments_dev || !corr_dev || !pair_offsets_dev || corr_stride < 1)
-        return BTBA_EINVAL;
-    if (misaligned(matches_dev, 16) || misaligned(segments_dev, 8) || misaligned(corr_dev, 16) ||
-        misaligned(pair_offsets_dev, 4) || misaligned(corr24_dev, 8))
-        return BTBA_EINVAL;
-    DeviceGuard device_guard(ws);
-    const int P = n_frames * (n_frames - 1) / 2;
-    const unsigned tiles = std::max(1u, (max_corr_per_pair + (unsigned)kWinThreads - 1u) / (unsigned)kWinThreads);      // tile 0 also writes the offsets
-    k_window_marshal<<<dim3(tiles, (unsigned)P, (unsigned)n_windows), kWinThreads, 0, ws->stream>>>(
-        n_frames, P, segments_dev, reinterpret_cast<const unsigned char *>(matches_dev), (unsigned long long)n_records, (unsigned long long)corr_stride,
-        reinterpret_cast<uint4 *>(corr_dev), pair_offsets_dev, reinterpret_cast<float2 *>(corr24_dev));
-    HIP_TRY(hipGetLastError());
-    return BTBA_OK;
-}
-
-int btba_procrustes_pairs(btba_workspace *ws, int device_resident, int n_pairs, const btba_match *matches_dev, int64_t n_records,
-                          const int32_t *segments, const float *posesA, const float *posesB, float *pose_out, float *err_out, double *moments_out)
-{
-    // every argument is checked before the first HIP call
-    if (!ws || n_pairs < 0 || n_records < 0 || n_records > (int64_t)UINT32_MAX) return BTBA_EINVAL;
-    if (n_pairs == 0) return BTBA_OK;
-    if (!segments || !posesA || !posesB || !pose_out || !err_out || (!matches_dev && n_records) || misaligned(matches_dev, 8))
-        return BTBA_EINVAL;
-    std::vector<KabschRec> rec(n_pairs);
-    for (int e = 0; e < n_pairs; e++) {
-        const int64_t off = segments[2 * e], n = segments[2 * e + 1];
-        if (off < 0 || n < 0 || off + n > n_records) return BTBA_EINVAL;
-        rec[e] = KabschRec{ (uint32_t)off, (int32_t)n };
-    }
-    DeviceGuard device_guard(ws);
-    const bool dev = device_resident != 0;
-    const size_t np = (size_t)n_pairs;
-    Scratch S;
-    const auto s_rec = S.add<KabschRec>(np);
-    const auto s_mom = S.add<double>(16 * np, !(moments_out && dev));
-    const auto s_pa = S.add<float>(16 * np, !dev), s_pb = S.add<float>(16 * np, !dev), s_out = S.add<float>(16 * np, !dev);
-    const auto s_err = S.add<float>(np, !dev);
-    int rc = S.bind(ws->window);
-    if (rc) return rc;
-    KabschRec *d_rec = s_rec;
-    double *d_mom = moments_out && dev ? moments_out : s_mom;
-    const float *pa = posesA, *pb = posesB;
-    float *po = pose_out, *pe = err_out;
-    HIP_TRY(hipMemcpyAsync(d_rec, rec.data(), sizeof(KabschRec) * np, hipMemcpyHostToDevice, ws->stream));
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(s_pa, posesA, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
-        HIP_TRY(hipMemcpyAsync(s_pb, posesB, sizeof(float) * 16 * np, hipMemcpyHostToDevice, ws->stream));
-        pa = s_pa;
-        pb = s_pb;
-        po = s_out;
-        pe = s_err;
-    }
-    const unsigned char *recs = reinterpret_cast<const unsigned char *>(matches_dev);
-    k_kabsch_moments<<<n_pairs, kKabschThreads, 0, ws->stream>>>(d_rec, recs, pa, pb, d_mom);
-    k_kabsch_solve<<<n_pairs, kKabschThreads, 0, ws->stream>>>(d_rec, recs, pa, pb, d_mom, po, pe);
-    HIP_TRY(hipGetLastError());
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(pose_out, po, sizeof(float) * 16 * np, hipMemcpyDeviceToHost, ws->stream));
-        HIP_TRY(hipMemcpyAsync(err_out, pe, sizeof(float) * np, hipMemcpyDeviceToHost, ws->stream));
-        if (moments_out) HIP_TRY(hipMemcpyAsync(moments_out, d_mom, sizeof(double) * 16 * np, hipMemcpyDeviceToHost, ws->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ws->stream));                       // the host table above may go
-    return BTBA_OK;
-}
-
-}  // extern "C"
-
-// ---- map-point memory and the tracker's findCorres (btba_mappoints.hpp) ------------------------------------------------------
-struct btba_mappoints {
-    btba_workspace *ws = nullptr;
-    int device = 0;                        // the workspace's device: destroy does not touch the workspace (it may be gone already)
-    struct Slot { bool live = false; int n = 0; DevBuf data; };     // data: kpts float2[n] | canon int[n] | order int[n] | map int[n]
-    std::vector<Slot> slots;
-    int slot_cap = 0, mp_cap = 0;
-    DevBuf table;                          // MpSlot[slot_cap]
-    DevBuf img;                            // int [mp_cap][slot_cap]
-    DevBuf stamp, stack;                   // int [mp_cap] each
-    DevBuf hdr;                            // kMpNext, kMpTop, kMpErr
-    int64_t live_known = 0;                // live map points at the last host synchronisation of forget
-    int64_t bound = 0;                     // upper bound of live map points: live_known + keypoints of every slot that may still create some
-    bool broken = false;                   // the device allocator's guard fired (unreachable while capacity >= bound): the memory is unusable
-};
-
-namespace {
-constexpr int kMpMaxSlots = 1024;
-constexpr int64_t kMpMaxImgInts = (int64_t)1 << 28;     // 1 GiB of img rows
-
-size_t mp_slot_bytes(int n) { return (size_t)n * 8 + 3 * (size_t)n * 4 + 64; }
-MpSlot mp_slot_view(btba_mappoints::Slot &s)
-{
-    MpSlot v{};
-    unsigned char *b = s.data.as<unsigned char>();
-    v.kpts = reinterpret_cast<const float2 *>(b);
-    v.canon = reinterpret_cast<const int *>(b + (size_t)s.n * 8);
-    v.order = reinterpret_cast<const int *>(b + (size_t)s.n * 12);
-    v.map = reinterpret_cast<int *>(b + (size_t)s.n * 16);
-    v.n = s.n;
-    return v;
-}
-
-// grow img / stamp / stack / the slot table to (slots, points); contents kept, new entries -1.  Synchronous.
-int mp_grow(btba_mappoints *M, int slots, int points)
-{
-    if (slots <= M->slot_cap && points <= M->mp_cap) return BTBA_OK;
-    hipStream_t st = M->ws->stream;
-    const int ns = std::max(slots, M->slot_cap), np = std::max(points, M->mp_cap);
-    if ((int64_t)ns * np > kMpMaxImgInts || ns > kMpMaxSlots) return BTBA_ENOMEM;
-    DevBuf img, stamp, stack, table;
-    int rc;
-    if ((rc = img.ensure((size_t)ns * np * 4)) || (rc = stamp.ensure((size_t)np * 4)) || (rc = stack.ensure((size_t)np * 4)) ||
-        (rc = table.ensure(sizeof(MpSlot) * ns)))
-        return rc;
-    HIP_TRY(hipMemsetAsync(img.p, 0xFF, (size_t)ns * np * 4, st));
-    HIP_TRY(hipMemsetAsync(stamp.p, 0xFF, (size_t)np * 4, st));
-    HIP_TRY(hipMemsetAsync(table.p, 0, sizeof(MpSlot) * ns, st));
-    if (M->mp_cap && M->slot_cap) {
-        HIP_TRY(hipMemcpy2DAsync(img.p, (size_t)ns * 4, M->img.p, (size_t)M->slot_cap * 4, (size_t)M->slot_cap * 4, M->mp_cap, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(stack.p, M->stack.p, (size_t)M->mp_cap * 4, hipMemcpyDeviceToDevice, st));
-    }
-    if (M->slot_cap) HIP_TRY(hipMemcpyAsync(table.p, M->table.p, sizeof(MpSlot) * M->slot_cap, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    M->img = std::move(img); M->stamp = std::move(stamp); M->stack = std::move(stack); M->table = std::move(table);
-    M->slot_cap = ns; M->mp_cap = np;
-    return BTBA_OK;
-}
-}  // namespace
-
-int btba_mappoints_create(btba_workspace *ws, btba_mappoints **out)
-{
-    if (!ws || !out) return BTBA_EINVAL;
-    *out = nullptr;
-    DeviceGuard device_guard(ws);
-    btba_mappoints *M = new (std::nothrow) btba_mappoints;
-    if (!M) return BTBA_ENOMEM;
-    M->ws = ws;
-    M->device = ws->device;
-    int rc;
-    if ((rc = M->hdr.ensure(16))) { delete M; return rc; }
-    hipError_t e = hipMemsetAsync(M->hdr.p, 0, 16, ws->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ws->stream);
-    if (e != hipSuccess) { g_last_hip_error = (int)e; delete M; return BTBA_EHIP; }
-    *out = M;
-    return BTBA_OK;
-}
-
-void btba_mappoints_destroy(btba_mappoints *M)
-{
-    if (!M) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
-    (void)hipDeviceSynchronize();                                     // delete frees the buffers; no workspace access
-    delete M;
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-int btba_mappoints_register_frame(btba_mappoints *M, int n_kpts, const float *kpts_dev, int32_t *slot_out)
-{
-    if (!M || !slot_out || n_kpts < 0 || n_kpts > kMatchMaxKpts || (n_kpts && !kpts_dev) || misaligned(kpts_dev, 8)) return BTBA_EINVAL;
-    if (M->broken) return BTBA_ENOMEM;
-    DeviceGuard device_guard(M->ws);
-    hipStream_t st = M->ws->stream;
-    int slot = 0;
-    while (slot < (int)M->slots.size() && M->slots[slot].live) slot++;
-    int rc;
-    // capacity first: a failure here leaves the memory as it was
-    if ((rc = mp_grow(M, slot + 1 > M->slot_cap ? std::max(2 * M->slot_cap, std::max(slot + 1, 16)) : M->slot_cap,
-                      M->bound + n_kpts > M->mp_cap ? (int)std::min<int64_t>(std::max<int64_t>(2 * (int64_t)M->mp_cap, M->bound + n_kpts + 1024), INT_MAX) : M->mp_cap)))
-        return rc;
-    btba_mappoints::Slot fresh;
-    if ((rc = fresh.data.ensure(mp_slot_bytes(n_kpts)))) return rc;
-    fresh.n = n_kpts;
-    MpSlot v = mp_slot_view(fresh);
-    int *bad = reinterpret_cast<int *>(fresh.data.as<unsigned char>() + (size_t)n_kpts * 20);
-    HIP_TRY(hipMemsetAsync(bad, 0, 4, st));
-    if (n_kpts) {
-        HIP_TRY(hipMemcpyAsync(const_cast<float2 *>(v.kpts), kpts_dev, (size_t)n_kpts * 8, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemsetAsync(const_cast<int *>(v.order), 0xFF, (size_t)n_kpts * 4, st));
-        const int g = (n_kpts + 255) / 256;
-        k_mp_canon<<<g, 256, 0, st>>>(v.kpts, n_kpts, const_cast<int *>(v.canon), bad);
-        k_mp_order<<<g, 256, 0, st>>>(v.kpts, n_kpts, v.canon, const_cast<int *>(v.order), v.map);
-        HIP_TRY(hipGetLastError());
-    }
-    int bad_h = 0;
-    HIP_TRY(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad_h) return BTBA_EINVAL;                                   // a non-finite keypoint
-    HIP_TRY(hipMemcpy(M->table.as<MpSlot>() + slot, &v, sizeof(MpSlot), hipMemcpyHostToDevice));
-    if (slot == (int)M->slots.size()) M->slots.emplace_back();
-    fresh.live = true;
-    M->slots[slot] = std::move(fresh);
-    M->bound += n_kpts;
-    *slot_out = slot;
-    return BTBA_OK;
-}
-
-int btba_mappoints_forget_frame(btba_mappoints *M, int32_t slot)
-{
-    if (!M || slot < 0 || slot >= (int)M->slots.size() || !M->slots[slot].live) return BTBA_EINVAL;
-    if (M->broken) return BTBA_ENOMEM;
-    DeviceGuard device_guard(M->ws);
-    hipStream_t st = M->ws->stream;
-    if (M->mp_cap) {
-        k_mp_forget<<<1, 256, 0, st>>>(slot, M->slot_cap, M->img.as<int>(), M->hdr.as<int>(), M->stack.as<int>());
-        HIP_TRY(hipGetLastError());
-    }
-    int h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, M->hdr.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    M->slots[slot] = btba_mappoints::Slot{};
-    MpSlot dead{};
-    HIP_TRY(hipMemcpy(M->table.as<MpSlot>() + slot, &dead, sizeof(MpSlot), hipMemcpyHostToDevice));
-    M->live_known = h[kMpNext] - h[kMpTop];
-    M->bound = M->live_known;
-    for (auto &s : M->slots)
-        if (s.live) M->bound += s.n;
-    return BTBA_OK;
-}
-
-int btba_mappoints_export(btba_mappoints *M, int32_t *dims_out, int32_t *slot_n_out, int32_t *canon_out, int32_t *map_out, int32_t *img_out)
-{
-    if (!M || !dims_out) return BTBA_EINVAL;
-    DeviceGuard device_guard(M->ws);
-    hipStream_t st = M->ws->stream;
-    int h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, M->hdr.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int S = (int)M->slots.size();
-    int64_t total = 0;
-    for (auto &s : M->slots) total += s.live ? s.n : 0;
-    dims_out[0] = S; dims_out[1] = h[kMpNext]; dims_out[2] = (int32_t)total; dims_out[3] = h[kMpErr];
-    if (slot_n_out)
-        for (int k = 0; k < S; k++) slot_n_out[k] = M->slots[k].live ? M->slots[k].n : -1;
-    int64_t off = 0;
-    for (int k = 0; k < S; k++) {
-        btba_mappoints::Slot &s = M->slots[k];
-        if (!s.live || !s.n) continue;
-        MpSlot v = mp_slot_view(s);
-        if (canon_out) HIP_TRY(hipMemcpyAsync(canon_out + off, v.canon, (size_t)s.n * 4, hipMemcpyDeviceToHost, st));
-        if (map_out) HIP_TRY(hipMemcpyAsync(map_out + off, v.map, (size_t)s.n * 4, hipMemcpyDeviceToHost, st));
-        off += s.n;
-    }
-    if (img_out && h[kMpNext] && S)
-        HIP_TRY(hipMemcpy2DAsync(img_out, (size_t)S * 4, M->img.p, (size_t)M->slot_cap * 4, (size_t)S * 4, h[kMpNext], hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return BTBA_OK;
-}
-
-void btba_corres_params_default(btba_corres_params *p)
-{
-    if (!p) return;
-    p->n_trials = 2000;                                               // ransac.max_iter (btba::Config::ransac_max_iter)
-    p->dist_thres = 0.01f;                                            // ransac.inlier_dist
-    p->hypothesis = BTBA_RANSAC_REFERENCE_SVD;
-    p->pad = 0;
-    p->seed = 0;                                                      // the reference's literal curand_init seed
-}
-
-int btba_corres_chain_capacity(const btba_match_params *prm, int n_frames, int H, int W, int D, const int32_t *n_kpts,
-                               int n_pairs, const int32_t *pairs, int64_t *capacity_out)
-{
-    int64_t nn = 0;
-    int rc = btba_match_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, &nn);
-    if (rc) return rc;
-    std::vector<std::pair<int, int>> seen;
-    seen.reserve(n_pairs);
-    int64_t cap = nn;
-    for (int p = 0; p < n_pairs; p++) {
-        const int a = pairs[2 * p], b = pairs[2 * p + 1];
-        seen.emplace_back(std::min(a, b), std::max(a, b));
-        cap += n_kpts[a];                                             // propagated matches: at most one per key of A
-    }
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return BTBA_EINVAL;     // a frame pair twice
-    if (cap > INT_MAX) return BTBA_EINVAL;
-    *capacity_out = cap;
-    return BTBA_OK;
-}
-
-int btba_corres_chain(btba_workspace *ws, btba_mappoints *M, const btba_match_params *prm, const btba_corres_params *rprm, int device_resident,
-                      int n_frames, int H, int W, const float *K, const float *const *desc_dev, int D, const float *const *kpts_dev,
-                      const int32_t *n_kpts, const float *const *depth_dev, const float *const *normal_dev, const float *poses,
-                      const int32_t *frame_ids, const int32_t *slots, int32_t *status, int n_pairs, const int32_t *pairs,
-                      btba_match *matches_out, int32_t *n_out, int32_t *stage_counts_out)
-{
-    // every argument is checked before the first HIP call
-    int64_t cap = 0, cap_nn = 0;
-    int rc = btba_corres_chain_capacity(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, &cap);
-    if (rc) return rc;
-    if ((rc = match_check_frames(prm, n_frames, H, W, D, n_kpts, n_pairs, pairs, K, desc_dev, kpts_dev, depth_dev, normal_dev, poses, frame_ids, &cap_nn)))
-        return rc;
-    if (!ws || !M || M->ws != ws || !rprm || !slots || !status || (n_pairs && !n_out) || (cap && !matches_out)) return BTBA_EINVAL;
-    if (M->broken || M->bound > M->mp_cap) return BTBA_ENOMEM;         // before any launch: nothing changes
-    const int hyp = rprm->hypothesis & ~BTBA_RANSAC_DRAW_HASH;
-    if (rprm->n_trials < 1 || !(rprm->dist_thres >= 0.0f) || (hyp != BTBA_RANSAC_REFERENCE_SVD && hyp != BTBA_RANSAC_HORN)) return BTBA_EINVAL;
-    std::vector<int> slot_user(M->slots.size(), -1);
-    for (int p = 0; p < n_pairs; p++)
-        for (int s = 0; s < 2; s++) {
-            const int f = pairs[2 * p + s], sl = slots[f];
-            if (sl < 0 || sl >= (int)M->slots.size() || !M->slots[sl].live || M->slots[sl].n != n_kpts[f]) return BTBA_EINVAL;
-            if (slot_user[sl] >= 0 && slot_user[sl] != f) return BTBA_EINVAL;    // two frames of the call on one slot
-            slot_user[sl] = f;
-        }
-    for (int p = 0; p < n_pairs; p++)
-        if (frame_ids[pairs[2 * p]] <= frame_ids[pairs[2 * p + 1]]) return BTBA_EINVAL;   // A is the newer frame
-    if (n_pairs == 0) return BTBA_OK;
-    DeviceGuard device_guard(ws);
-    hipStream_t st = ws->stream;
-
-    // host tables (alive until the final synchronisation)
-    std::vector<CorresFrame> cf(n_frames);
-    for (int f = 0; f < n_frames; f++) {
-        cf[f] = CorresFrame{};
-        cf[f].depth = depth_dev[f];
-        for (int k = 0; k < 12; k++) cf[f].pose[k] = poses[16 * f + k];
-        cf[f].slot = slots[f];
-    }
-    std::vector<CorresPair> cp(n_pairs);
-    int64_t base = 0;
-    for (int p = 0; p < n_pairs; p++) {
-        const int a = pairs[2 * p], b = pairs[2 * p + 1];
-        cp[p] = CorresPair{ a, b, std::abs((long long)frame_ids[a] - (long long)frame_ids[b]) == 1 ? 1 : 0, (int)base };
-        base += n_kpts[a] + (prm->mutual ? n_kpts[b] : 0) + n_kpts[a];
-    }
-    const size_t L = (size_t)std::max<int64_t>(base, 1), Nn = (size_t)std::max<int64_t>(cap_nn, 1), NT = (size_t)rprm->n_trials;
-    const bool dev = device_resident != 0;
-    const size_t np = (size_t)n_pairs, n_res = (size_t)n_frames + 1 + 2 * np + 4 * np;      // status | out_off | n_out | stage
-    Scratch S;
-    const auto dF = S.add<CorresFrame>(n_frames);
-    const auto dP = S.add<CorresPair>(np);
-    const auto d_nn = S.add<btba_match>(Nn);
-    const auto s_npa = S.add<float4>(Nn), s_npb = S.add<float4>(Nn);
-    const auto s_list = S.add<btba_match>(L);
-    const auto s_la = S.add<float4>(L), s_lb = S.add<float4>(L);
-    const auto s_ids = S.add<int>(L), d_ump = S.add<int>(L), d_ua = S.add<int>(L);
-    const auto s_out = S.add<btba_match>((size_t)std::max<int64_t>(cap, 1), !dev);
-    const auto s_meta = S.add<int>(2 * np), s_roff = S.add<int>(2 * np);
-    const auto s_best = S.add<unsigned long long>(np);
-    const auto s_nin = S.add<int>(np), s_bt = S.add<int>(np);
-    const auto s_bp = S.add<float>(16 * np), s_tp = S.add<float>(12 * NT);
-    const auto s_tc = S.add<int>(NT);
-    const auto s_res = S.add<int>(n_res + 4);                          // ... | hdr copy
-    if ((rc = S.bind(ws->corres))) return rc;
-    if (!(rprm->hypothesis & BTBA_RANSAC_DRAW_HASH) && (rc = ransac_uniform_table(ws, rprm->seed, rprm->n_trials))) return rc;
-    int *d_status = s_res, *d_outoff = d_status + n_frames, *d_nout = d_outoff + n_pairs + 1, *d_stage = d_nout + n_pairs;
-    HIP_TRY(hipMemcpyAsync(dF, cf.data(), sizeof(CorresFrame) * n_frames, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dP, cp.data(), sizeof(CorresPair) * n_pairs, hipMemcpyHostToDevice, st));
-    std::vector<int32_t> st_in(status, status + n_frames);
-    HIP_TRY(hipMemcpyAsync(d_status, st_in.data(), 4 * (size_t)n_frames, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_outoff, 0, 4, st));
-
-    // NN for every pair at once (it reads no map state)
-    float4 *d_npa = s_npa, *d_npb = s_npb;
-    MatchEnqueue E;
-    if ((rc = match_enqueue(ws, prm, true, n_frames, H, W, K, desc_dev, D, kpts_dev, n_kpts, depth_dev, normal_dev, poses, frame_ids, n_pairs, pairs,
-                            d_nn, reinterpret_cast<float *>(d_npa), reinterpret_cast<float *>(d_npb), E)))
-        return rc;
-
-    CorresDims Cd{};
-    Cd.W = W; Cd.H = H; Cd.slot_cap = M->slot_cap; Cd.mp_cap = M->mp_cap;
-    float intr[4];
-    scaled_intrinsics(H, W, H, W, K, intr, &Cd.Kinv);
-    RansacDims Rd{};
-    Rd.n_pairs = 1; Rd.n_trials = rprm->n_trials; Rd.dist_thres = rprm->dist_thres; Rd.seed = rprm->seed; Rd.hypothesis = hyp;
-    Rd.draw = (rprm->hypothesis & BTBA_RANSAC_DRAW_HASH) ? 0 : 2;
-    btba_match *d_list = s_list, *d_out = dev ? matches_out : s_out;
-    float4 *d_la = s_la, *d_lb = s_lb;
-    int *d_ids = s_ids, *d_meta = s_meta, *d_roff = s_roff, *d_nin = s_nin, *d_bt = s_bt, *d_tc = s_tc;
-    unsigned long long *d_best = s_best;
-    float *d_bp = s_bp, *d_tp = s_tp;
-    const MpSlot *dS = M->table.as<MpSlot>();
-    // per pair, in order: propagation, RANSAC (vote + inlier list), update + gates.  No host synchronisation in between.
-    for (int p = 0; p < n_pairs; p++) {
-        const int bs = cp[p].base;
-        k_corres_prop<<<1, 256, 0, st>>>(Cd, p, dF, dP, dS, M->img.as<int>(), d_nn, d_npa, d_npb, E.d_cnt, E.d_off,
-                                         d_status, d_list, d_la, d_lb, d_meta, d_roff, d_best, d_stage);
-        if ((rc = ransac_enqueue(ws, Rd, d_la + bs, d_lb + bs, d_roff + 2 * p, nullptr, d_tp, d_tc, d_best + p, d_ids + bs, d_nin + p, d_bt + p, d_bp + 16 * p)))
-            return rc;
-        k_corres_update<<<1, 256, 0, st>>>(Cd, p, dF, dP, dS, M->img.as<int>(), M->stamp.as<int>(), M->hdr.as<int>(), M->stack.as<int>(), d_status,
-                                           d_list, d_meta, d_ids, d_nin, d_ump, d_ua, d_out, d_outoff, d_nout, d_stage);
-    }
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> res(n_res);
-    int hdr[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(res.data(), d_status, 4 * res.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hdr, M->hdr.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                              // the chain's one host synchronisation
-    if (hdr[kMpErr]) { M->broken = true; return BTBA_ENOMEM; }     // unreachable (capacity >= bound, checked above); should it fire, the memory is unusable
-    std::memcpy(status, res.data(), 4 * (size_t)n_frames);
-    const int32_t *r_off = res.data() + n_frames, *r_nout = r_off + n_pairs + 1, *r_stage = r_nout + n_pairs;
-    std::memcpy(n_out, r_nout, 4 * (size_t)n_pairs);
-    if (stage_counts_out) std::memcpy(stage_counts_out, r_stage, 16 * (size_t)n_pairs);
-    if (!dev && r_off[n_pairs]) {
-        HIP_TRY(hipMemcpyAsync(matches_out, d_out, sizeof(btba_match) * (size_t)r_off[n_pairs], hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return BTBA_OK;
-}

@@ -362,4 +362,16 @@ __device__ __forceinline__ void block_reduce_store(float (&acc)[NV], float *lds_
     }
 }
 
+// canonical pair index -> (i, j), i < j, outer i
+__device__ __forceinline__ void pair_from_index(int p, int n, int &i, int &j)
+{
+    int ii = 0, rem = p;
+    while (rem >= n - 1 - ii) { rem -= n - 1 - ii; ii++; }
+    i = ii; j = ii + 1 + rem;
+}
+
+// The C24 correspondence layout (btba_kernels.hpp, sparse sweep): groups of 64 entries as three planes of float2.
+// float2 index of entry E's first plane (the other two follow at + 64 and + 128); E counts entries from the start of the array
+__device__ __forceinline__ size_t corr24_index(size_t E) { return (E >> 6) * 192 + (E & 63); }
+
 }  // namespace btba

@@ -195,12 +195,7 @@ __device__ __forceinline__ void depth_to_normals_pixel(int W, int H, const Mat4 
     normals[o] = res;
 }
 
-// grid (ceil(W/64), ceil(H/4)) x (64, 4).  normals (and optionally the xyz map) for one frame.
-__global__ void __launch_bounds__(256) k_depth_to_normals(int W, int H, Mat4 Kinv, const float *__restrict__ depth, float4 *__restrict__ normals, float4 *__restrict__ xyz_out)
-{
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= W || y >= H) return;
-    depth_to_normals_pixel(W, H, Kinv, depth, normals, xyz_out, x, y);
-}
+// (k_depth_to_normals, the per-frame kernel over depth_to_normals_pixel, is in btba_ingest.hpp: this header is shared by two host
+// units -- ingest and matching -- and so defines no non-template kernel)
 
 }  // namespace btba

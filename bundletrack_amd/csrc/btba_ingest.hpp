@@ -57,6 +57,14 @@ inline void launch_ingest_depth(const DepthFilterParams &P, const IngestDepthFra
     else k_ingest_depth<-1, -1, TIn><<<grid, 256, lds, stream>>>(P, F);
 }
 
+// grid (ceil(W/64), ceil(H/4)) x (64, 4).  normals (and optionally the xyz map) for one frame.
+__global__ void __launch_bounds__(256) k_depth_to_normals(int W, int H, Mat4 Kinv, const float *__restrict__ depth, float4 *__restrict__ normals, float4 *__restrict__ xyz_out)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= W || y >= H) return;
+    depth_to_normals_pixel(W, H, Kinv, depth, normals, xyz_out, x, y);
+}
+
 __global__ void __launch_bounds__(256) k_ingest_maps(int W, int H, Mat4 Kinv, const IngestMapFrames F)
 {
     const int z = blockIdx.z;

@@ -106,13 +106,6 @@ struct SolveDims {
 
 __device__ __forceinline__ size_t frame_slot_of(const SolveDims &D, size_t f) { return D.frame_slot ? (size_t)D.frame_slot[f] : f; }
 
-// canonical pair index -> (i, j), i < j, outer i
-__device__ __forceinline__ void pair_from_index(int p, int n, int &i, int &j)
-{
-    int ii = 0, rem = p;
-    while (rem >= n - 1 - ii) { rem -= n - 1 - ii; ii++; }
-    i = ii; j = ii + 1 + rem;
-}
 __device__ __forceinline__ int pair_index(int i, int j, int n) { return i * n - i * (i + 1) / 2 + (j - i - 1); }
 
 __device__ __forceinline__ Mat4 load_mat4(const float *p)
@@ -300,8 +293,6 @@ __global__ void __launch_bounds__(kBlock) k_pack_zn(size_t total, const float4 *
 //            (pos_i.x, pos_i.y)[64], (pos_i.z, pos_j.x)[64], (pos_j.y, pos_j.z)[64] -- so that each of a wave's three 8-byte loads covers 512
 //            contiguous bytes: plain 24-byte records, three loads at stride 24, touch every cache line three times and measured SLOWER than
 //            EntryJ on the masked launch although they move a quarter less (52.0 vs 49.9 us, gpurun_out/r03_13).
-// float2 index of entry E's first plane (the other two follow at + 64 and + 128); E counts entries from the start of the array
-__device__ __forceinline__ size_t corr24_index(size_t E) { return (E >> 6) * 192 + (E & 63); }
 template <bool C24, bool NT>
 __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const float4 *__restrict__ corr, const uint32_t *__restrict__ pair_offsets,
                                                   const float *__restrict__ T, float *__restrict__ partials, int chunk, int p, int b, float *red)

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <climits>
 
+#include "../../include/btba.h"
 #include "btba_device.hpp"
 #include "btba_image.hpp"
 

@@ -33,6 +33,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "btba_device.hpp"
 
 namespace btba {
 

@@ -1,5 +1,6 @@
 """Per-kernel register / LDS / scratch usage of a libbtba build (hipcc -Rpass-analysis=kernel-resource-usage), no GPU needed.
 usage: python scripts/dev/resource_usage.py [filter-substring] [-- extra hipcc flags]"""
+import os
 import re
 import subprocess
 import sys
@@ -7,9 +8,10 @@ import sys
 args = sys.argv[1:]
 extra = args[args.index("--") + 1:] if "--" in args else []
 flt = [a for a in (args[:args.index("--")] if "--" in args else args)]
-cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-pass-failed", "-fPIC", "-shared", "-fvisibility=hidden",
-       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/btba_ru.so", "bundletrack_amd/csrc/btba_api.hip"] + extra
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+# the library's own build, one unit at a time so that the units' remarks do not interleave
+cmd = [sys.executable, "-c", "import sys; from bundletrack_amd import _lib; _lib.build(force=True, out='/tmp/btba_ru/libbtba.so', extra_flags=sys.argv[1:])",
+       "-Rpass-analysis=kernel-resource-usage"] + extra
+out = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, MAX_JOBS="1")).stderr
 cur, rows = None, {}
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)

@@ -74,12 +74,11 @@ def ckdtree_ms(name):
 
 
 def valu_per_pair():
-    """VALU instructions per (query, candidate) pair in k_eval_nn's inner loop, from the -save-temps ISA of btba_api.hip."""
+    """VALU instructions per (query, candidate) pair in k_eval_nn's inner loop, from the -save-temps ISA of btba_api_eval.hip."""
+    from bundletrack_amd import _lib
     with tempfile.TemporaryDirectory() as d:
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-Wno-pass-failed", "-fPIC", "-shared", "-save-temps",
-                        "-o", os.path.join(d, "lib.so"), os.path.join(ROOT, "bundletrack_amd", "csrc", "btba_api.hip")], cwd=d, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        isa = open(glob.glob(os.path.join(d, "*gfx950*.s"))[0]).read()
+        _lib.build(force=True, out=os.path.join(d, "lib.so"), extra_flags=["-save-temps"])
+        isa = open(glob.glob(os.path.join(d, "build", "lib", "btba_api_eval-*gfx950*.s"))[0]).read()
     body = isa[isa.index("_ZN4btba9k_eval_nn"):]
     body = body[:body.index("s_endpgm")]
     blocks = re.split(r"\n\.LBB\d+_\d+:", body)

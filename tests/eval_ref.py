@@ -10,7 +10,7 @@ import numpy as np
 
 from bundletrack_amd import synthetic as S
 
-from match_ref import HERE, ROOT, _build
+from match_ref import HERE, _build
 
 _host = None
 
@@ -125,16 +125,8 @@ def driver():
     """tests/cpp/libeval_driver.so: btba::poseErrors and btba::vocapAuc of the C++ host layer, linked against libbtba.so."""
     global _driver
     if _driver is None:
-        import subprocess
         from bundletrack_amd import _lib
-        so = os.path.join(HERE, "cpp", "libeval_driver.so")
-        srcs = [os.path.join(HERE, "cpp", "eval_driver.cpp"), os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.cpp")]
-        deps = srcs + [os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-            pkg = os.path.dirname(_lib.LIB_PATH)
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] +
-                                  srcs + ["-L" + pkg, "-lbtba", "-Wl,-rpath," + pkg])
+        so = _lib.build_driver("eval_driver")
         _driver = C.CDLL(so)
         _driver.pose_errors_driver.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]

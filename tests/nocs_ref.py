@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from match_ref import HERE, ROOT, _build
+from match_ref import HERE, _build
 
 GOLDEN = os.path.join(HERE, "golden", "nocs", "nocs_reference.npz")
 CLASS_NAMES = ("BG", "bottle", "bowl", "camera", "can", "laptop", "mug")
@@ -228,16 +228,8 @@ def driver():
     """tests/cpp/libnocs_driver.so: btba::nocsErrors and btba::nocsReport of the C++ host layer, linked against libbtba.so."""
     global _driver
     if _driver is None:
-        import subprocess
         from bundletrack_amd import _lib
-        so = os.path.join(HERE, "cpp", "libnocs_driver.so")
-        srcs = [os.path.join(HERE, "cpp", "nocs_driver.cpp"), os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.cpp")]
-        deps = srcs + [os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-            rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-            pkg = os.path.dirname(_lib.LIB_PATH)
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] +
-                                  srcs + ["-L" + pkg, "-lbtba", "-Wl,-rpath," + pkg])
+        so = _lib.build_driver("nocs_driver")
         _driver = C.CDLL(so)
         _driver.nocs_errors_driver.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

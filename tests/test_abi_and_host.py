@@ -2,6 +2,7 @@
 declares, host helpers behave, and the caller-side logic (marshalling, keyframe memory) matches the
 reference's rules.  No compute kernel is launched here."""
 import ctypes as C
+import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +17,13 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(L, name), name
     assert L.btba_version() == 105
+
+
+def test_defined_btba_symbols_are_exactly_the_declared_ones():
+    """The library is several translation units: a helper that crosses units must stay hidden, and no unit may drop an entry point."""
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = sorted(ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("btba_"))
+    assert defined == _lib.declared_symbols()
 
 
 def test_struct_sizes_match_header():

@@ -335,17 +335,7 @@ def test_workspace_destroy_returns_the_chain_scratch(scene):
 
 def _session_driver():
     import ctypes as C
-    import os
-    import subprocess
-    from match_ref import HERE, ROOT
-    so = os.path.join(HERE, "cpp", "libcorres_driver.so")
-    srcs = [os.path.join(HERE, "cpp", "corres_driver.cpp"), os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] + srcs +
-                              ["-L" + pkg, "-lbtba", "-Wl,-rpath," + pkg, "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(rocm, "lib")])
+    so = _lib.build_driver("corres_driver")
     f = C.CDLL(so).corres_session
     f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 5 + \
                  [C.c_int, C.c_void_p, C.c_int64]

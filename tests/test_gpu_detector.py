@@ -5,8 +5,6 @@ round trip; determinism and the asynchronous form; the depth -> normals -> mask 
 back-mapping -> matching chain; the Python Bundler's detector step; and the C++ DetectorFeatureManager.  One module-scoped
 workspace, one C++ driver library loaded in-process (no child processes)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,9 +15,6 @@ from bundletrack_amd import _lib
 from bundletrack_amd import synthetic as S
 
 import detector_ref as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 @pytest.fixture(scope="module")
@@ -344,14 +339,7 @@ def test_python_bundler_detector_skips_tiny_roi_and_fails_on_exception(ws):
 
 
 def _driver():
-    so = os.path.join(HERE, "cpp", "libdetector_driver.so")
-    srcs = [os.path.join(HERE, "cpp", "detector_driver.cpp"), os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] + srcs +
-                              ["-L" + pkg, "-lbtba", "-Wl,-rpath," + pkg])
+    so = _lib.build_driver("detector_driver")
     f = C.CDLL(so).detector_driver
     f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
     return f

@@ -262,17 +262,7 @@ def test_python_bundler_ingests_frames_that_bring_only_their_images(ws, tmp_path
 
 
 def _driver():
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    so = os.path.join(here, "cpp", "libingest_driver.so")
-    srcs = [os.path.join(here, "cpp", "ingest_driver.cpp"), os.path.join(root, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(root, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] + srcs +
-                              ["-L" + pkg, "-lbtba", "-Wl,-rpath," + pkg])
+    so = _lib.build_driver("ingest_driver")
     f = C.CDLL(so).ingest_driver
     f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9
     return f

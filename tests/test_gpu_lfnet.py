@@ -4,7 +4,6 @@ the restatement on the device's own heat maps and on made-up ones; stage C again
 against the three calls and the stored reference keypoints; the argument checks; LfnetDetector inside a Bundler session; the C++
 host.  One module-scoped workspace.  All figures are printed before they are asserted."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -15,9 +14,6 @@ from bundletrack_amd import _lib
 from bundletrack_amd import lfnet
 
 import lfnet_ref as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 @pytest.fixture(scope="module")
@@ -399,15 +395,7 @@ def test_lfnet_detector_inside_a_bundler_session(ws):
 
 
 def _lfnet_driver():
-    import subprocess
-    so = os.path.join(HERE, "cpp", "liblfnet_driver.so")
-    srcs = [os.path.join(HERE, "cpp", "lfnet_driver.cpp"), os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] + srcs +
-                              ["-L" + pkg, "-lbtba", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + pkg])
+    so = _lib.build_driver("lfnet_driver")
     lib = C.CDLL(so)
     lib.lfnet_keypoints_driver.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 8
     lib.lfnet_detector_driver.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 9

@@ -4,8 +4,6 @@ a batch of mixed frames across two launch chunks; determinism; the asynchronous 
 depth -> normals -> mask -> matching chain; the Python Bundler's ROI gate; and the C++ host layer.  One module-scoped workspace,
 one C++ driver library loaded in-process (no child processes)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,9 +14,6 @@ from bundletrack_amd import _lib
 from bundletrack_amd import synthetic as S
 
 import mask_ref as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 @pytest.fixture(scope="module")
@@ -279,14 +274,7 @@ def test_python_bundler_segments_frames_and_fails_a_tiny_roi(ws):
 
 
 def _driver():
-    so = os.path.join(HERE, "cpp", "libmask_driver.so")
-    srcs = [os.path.join(HERE, "cpp", "mask_driver.cpp"), os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] + srcs +
-                              ["-L" + pkg, "-lbtba", "-Wl,-rpath," + pkg])
+    so = _lib.build_driver("mask_driver")
     f = C.CDLL(so).mask_driver
     f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
     return f

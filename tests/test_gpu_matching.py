@@ -2,8 +2,6 @@
 btba_depth_to_normals, deterministic, equal in both buffer forms, chained into RANSAC, the C++ host layer, and recall of planted
 correspondences.  One module-scoped workspace, no subprocesses."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +11,7 @@ pytestmark = pytest.mark.gpu
 from bundletrack_amd import _lib
 from bundletrack_amd import synthetic as S
 
-from match_ref import HERE, ROOT, HostFrame, restate, scene_frames
+from match_ref import HostFrame, restate, scene_frames
 
 
 @pytest.fixture(scope="module")
@@ -186,14 +184,7 @@ def test_recall_of_planted_correspondences(ws):
 
 
 def _driver():
-    so = os.path.join(HERE, "cpp", "libmatch_driver.so")
-    srcs = [os.path.join(HERE, "cpp", "match_driver.cpp"), os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] + srcs +
-                              ["-L" + pkg, "-lbtba", "-Wl,-rpath," + pkg])
+    so = _lib.build_driver("match_driver")
     f = C.CDLL(so).match_driver
     f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

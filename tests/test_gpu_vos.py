@@ -258,17 +258,7 @@ def test_session_step_by_step(ws, rng):
 
 
 def _vos_driver():
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    so = os.path.join(here, "cpp", "libvos_driver.so")
-    srcs = [os.path.join(here, "cpp", "vos_driver.cpp"), os.path.join(root, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(root, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", so] + srcs +
-                              ["-L" + pkg, "-lbtba", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + pkg])
+    so = _lib.build_driver("vos_driver")
     lib = C.CDLL(so)
     lib.vos_session_driver.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7
     lib.vos_bundler_driver.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 11

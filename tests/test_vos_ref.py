@@ -71,17 +71,7 @@ def test_sample_frames_equal_the_reference(golden, ref_num, rng, tmp_path):
 
 
 def _host_program():
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    exe = os.path.join(here, "cpp", "vos_host")
-    srcs = [os.path.join(here, "cpp", "vos_host.cpp"), os.path.join(root, "bundletrack_amd", "cpp", "btba_host.cpp")]
-    deps = srcs + [os.path.join(root, "bundletrack_amd", "cpp", "btba_host.hpp"), _lib.HEADER, _lib.LIB_PATH]
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
-        rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-        pkg = os.path.dirname(_lib.LIB_PATH)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-o", exe] + srcs +
-                              ["-L" + pkg, "-lbtba", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + pkg,
-                               "-Wl,-rpath," + os.path.join(rocm, "lib")])
+    exe = _lib.build_driver("vos_host", shared=False)
     return exe
 
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """How much of the HIP path's disagreement with the oracle's DECISIONS is due to its 1-ulp reciprocal / reciprocal square root (v_rcp_f32, v_rsq_f32:
-the counterpart of the reference's own -use_fast_math, CMakeLists.txt:7) and how much to its re-ordered arithmetic?  GPU box, one library per process:
+the counterpart of the reference's own -use_fast_math, CMakeLists.txt:7) and how much to its re-ordered arithmetic?  GPU box, one library per process
+(the experiment library is a call of bundletrack_amd._lib.build(out=..., extra_flags=[...]), like tests/tools/reference_order_experiment.py's):
 
     BTBA_LIB_PATH=build/ab/exactdiv.so python tests/tools/exact_div_experiment.py 120 > gpurun_out/exact_div_exact.jsonl
                                        python tests/tools/exact_div_experiment.py 120 > gpurun_out/exact_div_product.jsonl

@@ -2,7 +2,7 @@
 """Is the ORDER of the per-pixel arithmetic what makes the HIP path's accept decisions differ from the oracle's?  (round 4's verdict, "prove the
 arithmetic-order explanation".)  GPU box, one library per process:
 
-    hipcc ... -DBTBA_REFERENCE_ORDER -ffp-contract=off -o build/ab/reforder.so bundletrack_amd/csrc/btba_api.hip        (a TEST-ONLY build, never the product)
+    python -c "from bundletrack_amd import _lib; _lib.build(out='build/ab/reforder.so', extra_flags=['-DBTBA_REFERENCE_ORDER', '-ffp-contract=off'])"        (a TEST-ONLY build, never the product)
     BTBA_LIB_PATH=build/ab/reforder.so python tests/tools/reference_order_experiment.py 120 > gpurun_out/reforder.jsonl
                                        python tests/tools/reference_order_experiment.py 120 > gpurun_out/product.jsonl
 

@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = [
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_lfnet_params_default", "btba_lfnet_heatmaps", "btba_lfnet_select", "btba_lfnet_crops", "btba_lfnet_keypoints",
     "btba_lfnet_desc_config_default", "btba_lfnet_desc_model_create", "btba_lfnet_desc_model_destroy", "btba_lfnet_descriptors",
+    "btba_lfnet_det_config_default", "btba_lfnet_det_scales", "btba_lfnet_det_model_create", "btba_lfnet_det_model_destroy", "btba_lfnet_det_map_size",
+    "btba_lfnet_det_map_sizes", "btba_lfnet_det_pad_size", "btba_lfnet_scores",
     "btba_mask_params_default", "btba_apply_masks",
     "btba_detector_params_default", "btba_detector_transform", "btba_detector_inputs", "btba_detector_keypoints_to_image",
     "btba_pose_errors", "btba_nocs_params_default", "btba_nocs_errors",
@@ -116,6 +118,23 @@ class LfnetDescLayer(C.Structure):
 class LfnetDescWeights(C.Structure):
     """btba_lfnet_desc_weights (include/btba.h)."""
     _fields_ = [("conv", LfnetDescLayer * 4), ("fc1", LfnetDescLayer), ("fc2", LfnetDescLayer)]
+
+
+class LfnetDetConfig(C.Structure):
+    """btba_lfnet_det_config (include/btba.h)."""
+    _fields_ = [("channels", C.c_int32), ("ksize", C.c_int32), ("blocks", C.c_int32), ("num_scales", C.c_int32),
+                ("scale_factors", C.c_double * 16), ("activation", C.c_int32), ("leaky_alpha", C.c_float), ("bn_eps", C.c_float)]
+
+
+class LfnetDetBlock(C.Structure):
+    """btba_lfnet_det_block (include/btba.h)."""
+    _fields_ = [("pre_bn", LfnetDescLayer), ("conv1", LfnetDescLayer), ("conv2", LfnetDescLayer)]
+
+
+class LfnetDetWeights(C.Structure):
+    """btba_lfnet_det_weights (include/btba.h)."""
+    _fields_ = [("init_conv", LfnetDescLayer), ("block", LfnetDetBlock * 8), ("fin_bn", LfnetDescLayer), ("score_conv", LfnetDescLayer * 16),
+                ("ori_conv", LfnetDescLayer)]
 
 
 class DetectorParams(C.Structure):
@@ -208,6 +227,7 @@ def build(force: bool = False, verbose: bool = False, out: str | None = None, ex
 
 HOST_DRIVER = os.path.join(_ROOT, "tests", "cpp", "host_driver")
 LFNET_DESC_DRIVER = os.path.join(_ROOT, "tests", "cpp", "liblfnet_desc_driver.so")
+LFNET_DET_DRIVER = os.path.join(_ROOT, "tests", "cpp", "liblfnet_det_driver.so")
 
 
 def build_driver(name: str, shared: bool = True, force: bool = False, verbose: bool = False) -> str:
@@ -231,8 +251,9 @@ def build_driver(name: str, shared: bool = True, force: bool = False, verbose: b
 
 
 def build_host_cpp(force: bool = False, verbose: bool = False) -> str:
-    """Compile the C++ host layer's test program (tests/cpp/host_driver) and the descriptor net's ctypes driver."""
+    """Compile the C++ host layer's test program (tests/cpp/host_driver) and the two LF-Net nets' ctypes drivers."""
     build_driver("lfnet_desc_driver", force=force, verbose=verbose)
+    build_driver("lfnet_det_driver", force=force, verbose=verbose)
     return build_driver("host_driver", shared=False, force=force, verbose=verbose)
 
 
@@ -336,6 +357,16 @@ def lib() -> C.CDLL:
         L.btba_lfnet_desc_model_destroy.argtypes = [C.c_void_p]
         L.btba_lfnet_desc_model_destroy.restype = None
         L.btba_lfnet_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_lfnet_det_config_default.argtypes = [C.POINTER(LfnetDetConfig)]
+        L.btba_lfnet_det_config_default.restype = None
+        L.btba_lfnet_det_scales.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p]
+        L.btba_lfnet_det_model_create.argtypes = [C.c_void_p, C.POINTER(LfnetDetConfig), C.POINTER(LfnetDetWeights), C.POINTER(C.c_void_p)]
+        L.btba_lfnet_det_model_destroy.argtypes = [C.c_void_p]
+        L.btba_lfnet_det_model_destroy.restype = None
+        L.btba_lfnet_det_map_size.argtypes = [C.c_double, C.c_int]
+        L.btba_lfnet_det_map_sizes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.btba_lfnet_det_pad_size.argtypes = [C.c_void_p]
+        L.btba_lfnet_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_match_params_default.argtypes = [C.POINTER(MatchParams)]
         L.btba_match_params_default.restype = None
         L.btba_match_capacity.argtypes = [C.POINTER(MatchParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
@@ -434,6 +465,20 @@ def lfnet_params(**kw) -> LfnetParams:
 def lfnet_desc_config(**kw) -> LfnetDescConfig:
     """btba_lfnet_desc_config_default with fields overridden by keyword."""
     return _params(LfnetDescConfig, "btba_lfnet_desc_config_default", kw)
+
+
+def lfnet_det_config(**kw) -> LfnetDetConfig:
+    """btba_lfnet_det_config_default with fields overridden by keyword; scale_factors: a sequence, which also sets num_scales."""
+    sf = kw.pop("scale_factors", None)
+    p = _params(LfnetDetConfig, "btba_lfnet_det_config_default", kw)
+    if sf is not None:
+        sf = [float(s) for s in sf]
+        if not 1 <= len(sf) <= 16:
+            raise ValueError("1 .. 16 scale factors")
+        p.num_scales = len(sf)
+        for i in range(16):
+            p.scale_factors[i] = sf[i] if i < len(sf) else 0.0
+    return p
 
 
 def detector_params(**kw) -> DetectorParams:

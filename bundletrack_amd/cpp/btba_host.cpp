@@ -905,6 +905,60 @@ LfnetDetector::DescFn LfnetDescriptor::asDescNet(float *desc_dev) const
     };
 }
 
+btba_lfnet_det_config lfnetDetConfig()
+{
+    btba_lfnet_det_config c;
+    btba_lfnet_det_config_default(&c);
+    return c;
+}
+
+std::vector<double> lfnetDetScales(double min_scale, double max_scale, int num_scales)
+{
+    std::vector<double> out((size_t)std::max(num_scales, 1));
+    const int rc = btba_lfnet_det_scales(min_scale, max_scale, num_scales, out.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_det_scales");
+    return out;
+}
+
+LfnetScoreNet::LfnetScoreNet(btba_workspace *ws, const btba_lfnet_det_config &config, const btba_lfnet_det_weights &weights)
+    : ws_(ws), config_(config)
+{
+    const int rc = btba_lfnet_det_model_create(ws, &config, &weights, &model_);
+    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_det_model_create");
+}
+
+LfnetScoreNet::~LfnetScoreNet() { btba_lfnet_det_model_destroy(model_); }
+
+LfnetMapSet LfnetScoreNet::mapSet(int H, int W, const std::vector<float *> &score_dev) const
+{
+    const size_t S = (size_t)config_.num_scales;
+    if (score_dev.size() != S) throw Error(BTBA_EINVAL, "LfnetScoreNet: one score buffer per scale");
+    LfnetMapSet maps;
+    maps.score_dev.assign(score_dev.begin(), score_dev.end());
+    maps.map_h.resize(S);
+    maps.map_w.resize(S);
+    const int rc = btba_lfnet_det_map_sizes(model_, H, W, maps.map_h.data(), maps.map_w.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_det_map_sizes");
+    for (size_t j = 0; j < S; j++) maps.scale_factors.push_back((float)config_.scale_factors[j]);
+    return maps;
+}
+
+void LfnetScoreNet::scores(int n_frames, int H, int W, const float *photo_dev, const std::vector<float *> &score_dev, float *ori_dev) const
+{
+    if (score_dev.size() != (size_t)config_.num_scales) throw Error(BTBA_EINVAL, "LfnetScoreNet: one score buffer per scale");
+    const int rc = btba_lfnet_scores(ws_, model_, n_frames, H, W, photo_dev, score_dev.data(), ori_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_scores");
+}
+
+LfnetDetector::ScoreFn LfnetScoreNet::asScoreNet(std::vector<float *> score_dev, float *ori_dev) const
+{
+    return [this, score_dev, ori_dev](const float *gray_dev, int out_size, const float *&ori_out) {
+        scores(1, out_size, out_size, gray_dev, score_dev, ori_dev);
+        ori_out = ori_dev;
+        return mapSet(out_size, out_size, score_dev);
+    };
+}
+
 void DetectorFeatureManager::detectFeature(const std::shared_ptr<Frame> &frame)              // FeatureManager.cpp:811-908
 {
     prepareDetectorInputs(ws_, { frame }, bgr_, gray_, out_size_);

@@ -392,6 +392,32 @@ private:
     btba_lfnet_desc_model *model_ = nullptr;
 };
 
+// LF-Net's detector net (models/mso_resnet_detector.py::get_model in inference) on btba_lfnet_scores; the rules are in include/btba.h.
+btba_lfnet_det_config lfnetDetConfig();                                          // btba_lfnet_det_config_default
+std::vector<double> lfnetDetScales(double min_scale, double max_scale, int num_scales);      // btba_lfnet_det_scales
+// A model on a workspace (created from host arrays in TensorFlow's layouts, destroyed with the object; move-only).  scores() fills the
+// caller's maps.score_dev[j] (device float [n][map_h[j]][map_w[j]], sizes from mapSet) and ori_dev [n][H][W][2], asynchronously on the
+// workspace stream.  asScoreNet gives the LfnetDetector::ScoreFn that writes one frame into the caller's buffers.
+class LfnetScoreNet {
+public:
+    LfnetScoreNet(btba_workspace *ws, const btba_lfnet_det_config &config, const btba_lfnet_det_weights &weights);
+    ~LfnetScoreNet();
+    LfnetScoreNet(const LfnetScoreNet &) = delete;
+    LfnetScoreNet &operator=(const LfnetScoreNet &) = delete;
+    LfnetScoreNet(LfnetScoreNet &&o) noexcept : ws_(o.ws_), config_(o.config_), model_(o.model_) { o.model_ = nullptr; }
+    const btba_lfnet_det_config &config() const { return config_; }
+    const btba_lfnet_det_model *model() const { return model_; }
+    int padSize() const { return btba_lfnet_det_pad_size(model_); }
+    // the map sizes and scale factors for H x W frames over the caller's per-scale buffers
+    LfnetMapSet mapSet(int H, int W, const std::vector<float *> &score_dev) const;
+    void scores(int n_frames, int H, int W, const float *photo_dev, const std::vector<float *> &score_dev, float *ori_dev) const;
+    LfnetDetector::ScoreFn asScoreNet(std::vector<float *> score_dev, float *ori_dev) const;
+private:
+    btba_workspace *ws_;
+    btba_lfnet_det_config config_;
+    btba_lfnet_det_model *model_ = nullptr;
+};
+
 // SiftManager::findCorres (FeatureManager.cpp:173-240) with its map points on btba_corres_chain: NN, propagation along the map
 // points, RANSAC (ransac.max_iter / inlier_dist of yml), the map-point update and the FAIL gates for an ordered list of pairs in one
 // call, the frames' map points in a btba_mappoints on `ws` (a frame is registered at its first pair, by _id; forgetFrame frees its

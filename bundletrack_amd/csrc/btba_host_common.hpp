@@ -157,7 +157,7 @@ struct btba_workspace {
     std::vector<EventPair> events;                          // pending timed regions
     std::vector<hipEvent_t> event_pool;
     btba_stats stats{};
-    bool lds_attr_set = false, small_attr_set = false, mid_attr_set = false, vos_attr_set = false, lfnet_attr_set = false;
+    bool lds_attr_set = false, small_attr_set = false, mid_attr_set = false, vos_attr_set = false, lfnet_attr_set = false, lfnet_det_attr_set = false;
     int n_cus = 0;                     // compute units of the workspace's device (256 = all eight XCDs of an MI355X in SPX mode: what k_chain's item -> XCD mapping assumes)
     bool always_time_region = false;   // optimize_frames: ms_solve is part of its stats contract
     static constexpr int kMaxGroups = 8;
@@ -196,6 +196,7 @@ struct btba_workspace {
     DevBuf vos;                                             // btba_vos_propagate: the key splits' partial (m, l, acc) per item and target position
     DevBuf lfnet;                                           // btba_lfnet_*: per-map moments, peak flags, the compacted peak list
     DevBuf lfnet_desc;                                      // btba_lfnet_descriptors: two buffers of a chunk's widest layer
+    DevBuf lfnet_det;                                       // btba_lfnet_scores: the residual stream and conv1's output of a pass, NHWC
     DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;

@@ -139,6 +139,15 @@ class LfnetDetector:
         self.params = _params(params)
         self.last = None                                   # the last call's lfnet_keypoints result
 
+    @classmethod
+    def from_models(cls, ws, score_net, desc_net, params=None):
+        """The detector around the two device nets: score_net an lfnet_det.LfnetScoreNet, whose scale_factors and pad_size the
+        keypoint head takes (pad_size overrides the one in `params`), desc_net an lfnet_desc.LfnetDescriptor (or any desc_net)."""
+        import copy
+        p = copy.copy(_params(params))
+        p.pad_size = int(score_net.pad_size)
+        return cls(ws, score_net, desc_net, score_net.scale_factors, p)
+
     def __call__(self, bgr, gray):
         import torch
         with torch.no_grad():

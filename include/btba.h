@@ -912,6 +912,87 @@ BTBA_API void btba_lfnet_desc_model_destroy(btba_lfnet_desc_model *model);
 BTBA_API int btba_lfnet_descriptors(btba_workspace *ws, const btba_lfnet_desc_model *model, int n_frames, int slots,
                                     const float *patches_dev, const int32_t *n_kpts_dev, float *desc_dev);
 
+/* ---- detector net (before the keypoint head) ------------------------------------------------------------------------
+ * LF-Net's detector net, lf-net-release/models/mso_resnet_detector.py::get_model on common/tf_layer_utils.py, in inference: the grey
+ * photo to the per-scale score maps btba_lfnet_heatmaps takes and the orientation map btba_lfnet_crops takes.  photo_dev float
+ * [n][H][W] is used as it is (run_server.py normalises the photo into a variable nobody reads).  C = channels, k = ksize; NHWC,
+ * fp32 operands with fp32 accumulation; the C -> C convolutions on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain), the thin ends
+ * (1 -> C, C -> 1, C -> 2) on the vector ALU; every output element is ONE chain over (ky, kx, c_in) in that order, so a frame's
+ * results are the same bits whatever the batch, the frame's place in it or the pass.
+ *
+ * The rules:
+ *   convolution   k x k, stride 1, SAME: k / 2 zeros on every side, plus bias.  The zeros pad the tensor AFTER batch norm and
+ *                 activation: a tap outside the image contributes 0, not act(shift).
+ *   init_conv     1 -> C.
+ *   block i       x <- conv2(act(mid-bn(conv1(act(pre-bn(x)))))) + x, i = 1 .. blocks; both convolutions C -> C; the shortcut is
+ *                 the block's input before pre-bn.
+ *   features      f = act(fin-bn(x))
+ *   score map j   h_j = (int)((float)H * (float)(1.0 / s_j) + 0.5f), w_j likewise (fp32, as tf.cast(base_height_f * inv_s + 0.5,
+ *                 tf.int32)); f resized to h_j x w_j per channel by TF1's resize_images (stage A's rule above: src = dst * (in /
+ *                 (float)out), lower tap floor(src), upper min(lower + 1, in - 1), top / bottom / value lerps in that order); then
+ *                 score_conv_j, C -> 1, no activation.  float [n][h_j][w_j].
+ *   orientation   ori_conv, C -> 2, then l2_normalize over the two channels: x * rsqrt(max(x0^2 + x1^2, 1e-12)).  float [n][H][W][2].
+ *   batch norm    tf.layers.batch_normalization with epsilon bn_eps.  mid-bn is folded into conv1 with its bias at model creation
+ *                 as the descriptor net's are (fp64 on the host, rounded once).  pre-bn and fin-bn sit behind the residual sum:
+ *                 each is a per-channel pair scale = gamma / sqrt(moving_variance + bn_eps), shift = beta - moving_mean * scale
+ *                 (fp64, rounded once), y = x * scale + shift.
+ *   activation    0 relu, 1 leaky relu with leaky_alpha (as the descriptor net's)
+ *   pad_size      (2 blocks + 2) * (k / 2): the reference's num_conv * (conv_ksize // 2), 16 for the release net; what
+ *                 btba_lfnet_params.pad_size takes.
+ *   scale factors np.exp(np.linspace(log(max_scale), log(min_scale), num_scales)) in double, largest first; num_scales == 1: [1.0].
+ *
+ * btba_lfnet_det_model_create checks the configuration and every array, folds the batch norms and uploads.  It is the one call here
+ * that allocates and waits.  A model belongs to the workspace it was created with and must be destroyed before it.
+ * btba_lfnet_det_scales, btba_lfnet_det_map_size, btba_lfnet_det_map_sizes, btba_lfnet_det_pad_size: host helpers, no GPU work.
+ * map_size is the rule above for one side and one scale factor; map_sizes applies it to a model's factors and writes num_scales
+ * entries; pad_size returns -1 for a NULL model.
+ * btba_lfnet_scores: score_dev is a HOST table of num_scales device pointers, score_dev[j] float [n][h_j][w_j]; ori_dev float
+ * [n][H][W][2].  Asynchronous on the workspace stream, no host wait, no allocation once the workspace scratch has grown.  Frames are
+ * worked in passes of at most BTBA_LFNET_DET_PASS_PIXELS frame-pixels (a larger single frame is a pass of its own): the scratch is
+ * two NHWC buffers of 4 C bytes per pixel of a pass.  n_frames == 0 is success without a launch.
+ * BTBA_EINVAL, decided before any GPU work: a NULL argument or table entry, a device pointer not aligned to 4 bytes; channels not a
+ * multiple of 16 in 16 .. 64; ksize not 3 or 5; blocks outside 1 .. BTBA_LFNET_DET_MAX_BLOCKS; num_scales outside 1 ..
+ * BTBA_LFNET_MAX_SCALES; a scale factor not finite or <= 0; n_frames negative; H, W or a map size outside 1 .. BTBA_LFNET_MAX_SIZE;
+ * activation not 0 or 1; leaky_alpha or bn_eps not finite, bn_eps < 0; a NULL `weights` array of a convolution; only one of
+ * moving_mean and moving_variance given; a non-finite value; moving_variance + bn_eps <= 0; a model created with another workspace. */
+#define BTBA_LFNET_DET_MAX_BLOCKS 8
+#define BTBA_LFNET_DET_PASS_PIXELS (1 << 20)
+typedef struct btba_lfnet_det_config {
+    int32_t channels;                /* 16 */
+    int32_t ksize;                   /* 5 */
+    int32_t blocks;                  /* 3 */
+    int32_t num_scales;              /* 5 */
+    double scale_factors[BTBA_LFNET_MAX_SCALES];   /* sqrt(2) .. 1 / sqrt(2), largest first; the first num_scales are read */
+    int32_t activation;              /* 1: 0 relu, 1 leaky relu */
+    float leaky_alpha;               /* 0.2 */
+    float bn_eps;                    /* 1e-5 */
+} btba_lfnet_det_config;
+/* Host arrays in TensorFlow's layouts under the checkpoint's names (btba_lfnet_desc_layer's NULL rules).  A record that stands for
+ * a batch norm alone (pre_bn, fin_bn) is read for gamma, beta, moving_mean and moving_variance only. */
+typedef struct btba_lfnet_det_block {
+    btba_lfnet_desc_layer pre_bn;    /* ConvOnlyResNet/block-{i}/pre-bn */
+    btba_lfnet_desc_layer conv1;     /* .../conv1/{weights [k][k][C][C], biases} and .../mid-bn */
+    btba_lfnet_desc_layer conv2;     /* .../conv2/{weights, biases} */
+} btba_lfnet_det_block;
+typedef struct btba_lfnet_det_weights {
+    btba_lfnet_desc_layer init_conv;                              /* ConvOnlyResNet/init_conv: weights [k][k][1][C], biases */
+    btba_lfnet_det_block block[BTBA_LFNET_DET_MAX_BLOCKS];        /* block-{i+1}; the first `blocks` are read */
+    btba_lfnet_desc_layer fin_bn;                                 /* ConvOnlyResNet/fin-bn */
+    btba_lfnet_desc_layer score_conv[BTBA_LFNET_MAX_SCALES];      /* score_conv_{j}: weights [k][k][C][1], biases [1] */
+    btba_lfnet_desc_layer ori_conv;                               /* ori_conv: weights [k][k][C][2], biases [2] */
+} btba_lfnet_det_weights;
+typedef struct btba_lfnet_det_model btba_lfnet_det_model;
+BTBA_API void btba_lfnet_det_config_default(btba_lfnet_det_config *c);
+BTBA_API int btba_lfnet_det_scales(double min_scale, double max_scale, int num_scales, double *out);
+BTBA_API int btba_lfnet_det_model_create(btba_workspace *ws, const btba_lfnet_det_config *config, const btba_lfnet_det_weights *weights,
+                                         btba_lfnet_det_model **out);
+BTBA_API void btba_lfnet_det_model_destroy(btba_lfnet_det_model *model);
+BTBA_API int btba_lfnet_det_map_size(double scale_factor, int size);      /* one side of one map; -1 for a bad argument */
+BTBA_API int btba_lfnet_det_map_sizes(const btba_lfnet_det_model *model, int H, int W, int32_t *map_h, int32_t *map_w);
+BTBA_API int btba_lfnet_det_pad_size(const btba_lfnet_det_model *model);
+BTBA_API int btba_lfnet_scores(btba_workspace *ws, const btba_lfnet_det_model *model, int n_frames, int H, int W, const float *photo_dev,
+                               float *const *score_dev, float *ori_dev);
+
 /* ---- pose accuracy: ADD and ADD-S (the YCBInEOAT evaluation) -------------------------------------------------------
  * The per-frame errors the reference's evaluation averages into its AUC figures (scripts/eval_ycbineoat.py:54-163 with
  * scripts/Utils.py:69-95, add / adi), for many evaluations in one call.  One evaluation is a model point set x_0 .. x_{N-1}

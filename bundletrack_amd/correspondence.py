@@ -11,18 +11,20 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from ._lfnet_model import Handle
 from ._lib import MATCH_DTYPE, CorresParams, check, corres_params, lib, match_params
 from .matching import _MATCH_WORDS, _dims, _frame_tables, params_from_config
 
 
-class MapPointMemory:
+class MapPointMemory(Handle):
     """btba_mappoints on a workspace: frame slots and map points on the device."""
+    _destroy = "btba_mappoints_destroy"
 
     def __init__(self, ws):
         self.ws = ws
         h = C.c_void_p()
         check(lib().btba_mappoints_create(ws.handle, C.byref(h)), "btba_mappoints_create")
-        self.handle = h
+        self._h = h
 
     def register_frame(self, kpts_gpu) -> int:
         """Copy a frame's keypoints (float32 CUDA [n, 2], or None) into a free slot; returns the slot."""
@@ -56,18 +58,6 @@ class MapPointMemory:
             out["canon"][s], out["map"][s] = canon[off:off + n].copy(), mp[off:off + n].copy()
             off += n
         return out
-
-    def close(self) -> None:
-        if getattr(self, "handle", None) is not None and self.handle.value:
-            lib().btba_mappoints_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 @dataclass
 class ChainResult:

@@ -887,15 +887,6 @@ void lfnetDescriptors(btba_workspace *ws, const btba_lfnet_desc_model *model, in
     if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_descriptors");
 }
 
-LfnetDescriptor::LfnetDescriptor(btba_workspace *ws, const btba_lfnet_desc_config &config, const btba_lfnet_desc_weights &weights)
-    : ws_(ws), config_(config)
-{
-    const int rc = btba_lfnet_desc_model_create(ws, &config, &weights, &model_);
-    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_desc_model_create");
-}
-
-LfnetDescriptor::~LfnetDescriptor() { btba_lfnet_desc_model_destroy(model_); }
-
 LfnetDetector::DescFn LfnetDescriptor::asDescNet(float *desc_dev) const
 {
     return [this, desc_dev](const float *patches_dev, int m, int &dim) {
@@ -919,15 +910,6 @@ std::vector<double> lfnetDetScales(double min_scale, double max_scale, int num_s
     if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_det_scales");
     return out;
 }
-
-LfnetScoreNet::LfnetScoreNet(btba_workspace *ws, const btba_lfnet_det_config &config, const btba_lfnet_det_weights &weights)
-    : ws_(ws), config_(config)
-{
-    const int rc = btba_lfnet_det_model_create(ws, &config, &weights, &model_);
-    if (rc != BTBA_OK) throw Error(rc, "btba_lfnet_det_model_create");
-}
-
-LfnetScoreNet::~LfnetScoreNet() { btba_lfnet_det_model_destroy(model_); }
 
 LfnetMapSet LfnetScoreNet::mapSet(int H, int W, const std::vector<float *> &score_dev) const
 {

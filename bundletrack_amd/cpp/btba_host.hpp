@@ -364,6 +364,31 @@ private:
     LfnetBuffers out_;
 };
 
+// What LfnetDescriptor and LfnetScoreNet are built on: a model of the library on a workspace, created from a configuration and host
+// arrays by `create` (named `where` in the Error of a refusal) and destroyed with the object by `destroy`; move-only.
+template <class Config, class Model> class LfnetModelHolder {
+public:
+    LfnetModelHolder(const LfnetModelHolder &) = delete;
+    LfnetModelHolder &operator=(const LfnetModelHolder &) = delete;
+    LfnetModelHolder(LfnetModelHolder &&o) noexcept : ws_(o.ws_), config_(o.config_), model_(o.model_), destroy_(o.destroy_) { o.model_ = nullptr; }
+    ~LfnetModelHolder() { destroy_(model_); }
+    const Config &config() const { return config_; }
+    const Model *model() const { return model_; }
+protected:
+    template <class Weights>
+    LfnetModelHolder(btba_workspace *ws, const Config &config, const Weights &weights,
+                     int (*create)(btba_workspace *, const Config *, const Weights *, Model **), void (*destroy)(Model *), const char *where)
+        : ws_(ws), config_(config), destroy_(destroy)
+    {
+        const int rc = create(ws, &config, &weights, &model_);
+        if (rc != BTBA_OK) throw Error(rc, where);
+    }
+    btba_workspace *ws_;
+    Config config_;
+    Model *model_ = nullptr;
+    void (*destroy_)(Model *);
+};
+
 // LF-Net's descriptor net (models/simple_desc.py::get_model in inference) on btba_lfnet_descriptors; the rules are in include/btba.h.
 btba_lfnet_desc_config lfnetDescConfig();                                        // btba_lfnet_desc_config_default
 // patches_dev float [n_frames][slots][P][P] -> desc_dev float [n_frames][slots][out_dim]; n_kpts_dev int32 [n_frames] on the device or
@@ -372,24 +397,15 @@ void lfnetDescriptors(btba_workspace *ws, const btba_lfnet_desc_model *model, in
                       const int32_t *n_kpts_dev, float *desc_dev);
 // A model on a workspace (created from host arrays in TensorFlow's layouts, destroyed with the object; move-only).  asDescNet gives
 // the LfnetDetector::DescFn that writes into the caller's desc_dev [top_k][out_dim].
-class LfnetDescriptor {
+class LfnetDescriptor : public LfnetModelHolder<btba_lfnet_desc_config, btba_lfnet_desc_model> {
 public:
-    LfnetDescriptor(btba_workspace *ws, const btba_lfnet_desc_config &config, const btba_lfnet_desc_weights &weights);
-    ~LfnetDescriptor();
-    LfnetDescriptor(const LfnetDescriptor &) = delete;
-    LfnetDescriptor &operator=(const LfnetDescriptor &) = delete;
-    LfnetDescriptor(LfnetDescriptor &&o) noexcept : ws_(o.ws_), config_(o.config_), model_(o.model_) { o.model_ = nullptr; }
-    const btba_lfnet_desc_config &config() const { return config_; }
-    const btba_lfnet_desc_model *model() const { return model_; }
+    LfnetDescriptor(btba_workspace *ws, const btba_lfnet_desc_config &config, const btba_lfnet_desc_weights &weights)
+        : LfnetModelHolder(ws, config, weights, btba_lfnet_desc_model_create, btba_lfnet_desc_model_destroy, "btba_lfnet_desc_model_create") {}
     void describe(int n_frames, int slots, const float *patches_dev, const int32_t *n_kpts_dev, float *desc_dev) const
     {
         lfnetDescriptors(ws_, model_, n_frames, slots, patches_dev, n_kpts_dev, desc_dev);
     }
     LfnetDetector::DescFn asDescNet(float *desc_dev) const;
-private:
-    btba_workspace *ws_;
-    btba_lfnet_desc_config config_;
-    btba_lfnet_desc_model *model_ = nullptr;
 };
 
 // LF-Net's detector net (models/mso_resnet_detector.py::get_model in inference) on btba_lfnet_scores; the rules are in include/btba.h.
@@ -398,24 +414,15 @@ std::vector<double> lfnetDetScales(double min_scale, double max_scale, int num_s
 // A model on a workspace (created from host arrays in TensorFlow's layouts, destroyed with the object; move-only).  scores() fills the
 // caller's maps.score_dev[j] (device float [n][map_h[j]][map_w[j]], sizes from mapSet) and ori_dev [n][H][W][2], asynchronously on the
 // workspace stream.  asScoreNet gives the LfnetDetector::ScoreFn that writes one frame into the caller's buffers.
-class LfnetScoreNet {
+class LfnetScoreNet : public LfnetModelHolder<btba_lfnet_det_config, btba_lfnet_det_model> {
 public:
-    LfnetScoreNet(btba_workspace *ws, const btba_lfnet_det_config &config, const btba_lfnet_det_weights &weights);
-    ~LfnetScoreNet();
-    LfnetScoreNet(const LfnetScoreNet &) = delete;
-    LfnetScoreNet &operator=(const LfnetScoreNet &) = delete;
-    LfnetScoreNet(LfnetScoreNet &&o) noexcept : ws_(o.ws_), config_(o.config_), model_(o.model_) { o.model_ = nullptr; }
-    const btba_lfnet_det_config &config() const { return config_; }
-    const btba_lfnet_det_model *model() const { return model_; }
+    LfnetScoreNet(btba_workspace *ws, const btba_lfnet_det_config &config, const btba_lfnet_det_weights &weights)
+        : LfnetModelHolder(ws, config, weights, btba_lfnet_det_model_create, btba_lfnet_det_model_destroy, "btba_lfnet_det_model_create") {}
     int padSize() const { return btba_lfnet_det_pad_size(model_); }
     // the map sizes and scale factors for H x W frames over the caller's per-scale buffers
     LfnetMapSet mapSet(int H, int W, const std::vector<float *> &score_dev) const;
     void scores(int n_frames, int H, int W, const float *photo_dev, const std::vector<float *> &score_dev, float *ori_dev) const;
     LfnetDetector::ScoreFn asScoreNet(std::vector<float *> score_dev, float *ori_dev) const;
-private:
-    btba_workspace *ws_;
-    btba_lfnet_det_config config_;
-    btba_lfnet_det_model *model_ = nullptr;
 };
 
 // SiftManager::findCorres (FeatureManager.cpp:173-240) with its map points on btba_corres_chain: NN, propagation along the map

@@ -470,15 +470,7 @@ int btba_mappoints_create(btba_workspace *ws, btba_mappoints **out)
     return BTBA_OK;
 }
 
-void btba_mappoints_destroy(btba_mappoints *M)
-{
-    if (!M) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
-    (void)hipDeviceSynchronize();                                     // delete frees the buffers; no workspace access
-    delete M;
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
+void btba_mappoints_destroy(btba_mappoints *M) { destroy_on_device(M); }
 
 int btba_mappoints_register_frame(btba_mappoints *M, int n_kpts, const float *kpts_dev, int32_t *slot_out)
 {

@@ -173,15 +173,12 @@ void btba_lfnet_desc_config_default(btba_lfnet_desc_config *c)
     c->bn_eps = 1e-5f;                                                // tf_layer_utils.py:185
 }
 
-struct btba_lfnet_desc_model {
-    btba_workspace *ws = nullptr;
-    int device = 0;
+struct btba_lfnet_desc_model : LfnetModelBase {
     btba_lfnet_desc_config cfg{};
     struct Layer { size_t w = 0, scale = 0, shift = 0; int K = 0, N = 0; };      // offsets in floats into dev
     Layer layers[BTBA_LFNET_DESC_MAX_DEPTH + 2];
     int n_layers = 0;
     size_t widest = 0;                     // floats per patch of the widest layer output
-    DevBuf dev;
 };
 
 namespace {
@@ -193,12 +190,6 @@ bool desc_config_ok(const btba_lfnet_desc_config *c)
     if (!std::isfinite(c->leaky_alpha) || !std::isfinite(c->bn_eps) || c->bn_eps < 0.0f) return false;
     const int s = c->patch_size >> c->depth;
     return (int64_t)s * s * (c->channels << (c->depth - 1)) <= 16384;
-}
-bool all_finite(const float *a, size_t n)
-{
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(a[i])) return false;
-    return true;
 }
 }  // namespace
 
@@ -221,64 +212,31 @@ int btba_lfnet_desc_model_create(btba_workspace *ws, const btba_lfnet_desc_confi
     src[depth] = &wts->fc1; Ks[depth] = flat; Ns[depth] = cfg->fc_dim;
     src[depth + 1] = &wts->fc2; Ks[depth + 1] = cfg->fc_dim; Ns[depth + 1] = cfg->out_dim;
     widest = std::max(widest, (size_t)std::max(cfg->fc_dim, cfg->out_dim));
-    for (int i = 0; i < n_layers; i++) {
-        const btba_lfnet_desc_layer &l = *src[i];
-        const size_t N = (size_t)Ns[i];
-        if (!l.weights || !all_finite(l.weights, (size_t)Ks[i] * N) || (l.biases && !all_finite(l.biases, N))) return BTBA_EINVAL;
-        if ((l.moving_mean == nullptr) != (l.moving_variance == nullptr)) return BTBA_EINVAL;
-        if (l.moving_mean) {
-            if (!all_finite(l.moving_mean, N) || !all_finite(l.moving_variance, N) || (l.gamma && !all_finite(l.gamma, N)) ||
-                (l.beta && !all_finite(l.beta, N)))
-                return BTBA_EINVAL;
-            for (size_t n = 0; n < N; n++)
-                if (!((double)l.moving_variance[n] + (double)cfg->bn_eps > 0.0)) return BTBA_EINVAL;
-        }
-    }
+    for (int i = 0; i < n_layers; i++)
+        if (!lfnet_conv_ok(*src[i], (size_t)Ks[i], (size_t)Ns[i]) || !lfnet_bn_ok(*src[i], (size_t)Ns[i], cfg->bn_eps)) return BTBA_EINVAL;
     // every argument has been checked; the first HIP call follows
     std::unique_ptr<btba_lfnet_desc_model> M(new (std::nothrow) btba_lfnet_desc_model());
     if (!M) return BTBA_ENOMEM;
     M->ws = ws; M->device = ws->device; M->cfg = *cfg; M->n_layers = n_layers; M->widest = widest;
-    auto pad64 = [](size_t n) { return (n + 63) & ~(size_t)63; };    // 256-byte regions: 16-byte loads of weight rows
-    size_t total = 0;
+    LfnetArena A;
     for (int i = 0; i < n_layers; i++) {
         btba_lfnet_desc_model::Layer &L = M->layers[i];
         L.K = Ks[i]; L.N = Ns[i];
-        L.w = total; total += pad64((size_t)Ks[i] * Ns[i]);
-        L.scale = total; total += pad64(Ns[i]);
-        L.shift = total; total += pad64(Ns[i]);
+        L.w = A.take((size_t)L.K * L.N); L.scale = A.take(L.N); L.shift = A.take(L.N);
     }
-    std::vector<float> host(total, 0.0f);
+    A.fill();
     for (int i = 0; i < n_layers; i++) {
-        const btba_lfnet_desc_layer &l = *src[i];
         const btba_lfnet_desc_model::Layer &L = M->layers[i];
-        std::memcpy(host.data() + L.w, l.weights, sizeof(float) * (size_t)L.K * L.N);      // [3][3][C_in][C_out] IS [K][N] in (ky, kx, c_in) order
-        for (int n = 0; n < L.N; n++) {
-            const double bias = l.biases ? (double)l.biases[n] : 0.0;
-            double scale = 1.0, shift = bias;
-            if (l.moving_mean) {
-                scale = (l.gamma ? (double)l.gamma[n] : 1.0) / std::sqrt((double)l.moving_variance[n] + (double)cfg->bn_eps);
-                shift = (l.beta ? (double)l.beta[n] : 0.0) + (bias - (double)l.moving_mean[n]) * scale;
-            }
-            host[L.scale + n] = (float)scale;
-            host[L.shift + n] = (float)shift;
-        }
+        A.put(L.w, src[i]->weights, (size_t)L.K * L.N);              // [3][3][C_in][C_out] IS [K][N] in (ky, kx, c_in) order
+        lfnet_fold(*src[i], src[i]->biases, L.N, cfg->bn_eps, A.at(L.scale), A.at(L.shift));
     }
     DeviceGuard device_guard(ws);
-    if (int rc = M->dev.ensure(sizeof(float) * total)) return rc;
-    HIP_TRY(hipMemcpy(M->dev.p, host.data(), sizeof(float) * total, hipMemcpyHostToDevice));
+    if (int rc = M->upload(A)) return rc;
     *out = M.release();
     return BTBA_OK;
 }
 
-void btba_lfnet_desc_model_destroy(btba_lfnet_desc_model *M)
-{
-    if (!M) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
-    (void)hipDeviceSynchronize();                                     // delete frees the weights; no workspace access
-    delete M;
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
+void btba_lfnet_desc_model_destroy(btba_lfnet_desc_model *M) { destroy_on_device(M); }
 
 int btba_lfnet_descriptors(btba_workspace *ws, const btba_lfnet_desc_model *M, int n_frames, int slots, const float *patches_dev,
                            const int32_t *n_kpts_dev, float *desc_dev)
@@ -317,7 +275,7 @@ int btba_lfnet_descriptors(btba_workspace *ws, const btba_lfnet_desc_model *M, i
             if (conv) {               // an even input size: TensorFlow's SAME pads nothing before and one row and column after
                 G.Hi = G.Wi = P >> i; G.Ho = G.Wo = P >> (i + 1); G.Cin = L.K / 9; G.ks = 3; G.pad = 0; G.act = c.activation;
             } else {
-                G.Hi = G.Wi = G.Ho = G.Wo = 1; G.Cin = L.K; G.ks = 1; G.pad = 0; G.act = i == depth ? c.activation : kDescActNone;
+                G.Hi = G.Wi = G.Ho = G.Wo = 1; G.Cin = L.K; G.ks = 1; G.pad = 0; G.act = i == depth ? c.activation : kLfnetActNone;
             }
             G.M = np * G.Ho * G.Wo;
             k_desc_gemm<<<dim3((G.M + kDescBM - 1) / kDescBM, (G.N + kDescBN - 1) / kDescBN), 256, 0, ws->stream>>>(G);

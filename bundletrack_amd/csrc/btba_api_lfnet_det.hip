@@ -20,49 +20,9 @@ bool det_config_ok(const btba_lfnet_det_config *c)
     return true;
 }
 
-bool det_finite(const float *a, size_t n)
-{
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
-// the batch-norm arrays of a record: absent, or complete enough and sane
-bool det_bn_ok(const btba_lfnet_desc_layer &l, size_t N, float eps)
-{
-    if ((l.moving_mean == nullptr) != (l.moving_variance == nullptr)) return false;
-    if (!l.moving_mean) return true;
-    if (!det_finite(l.moving_mean, N) || !det_finite(l.moving_variance, N) || (l.gamma && !det_finite(l.gamma, N)) || (l.beta && !det_finite(l.beta, N)))
-        return false;
-    for (size_t n = 0; n < N; n++)
-        if (!((double)l.moving_variance[n] + (double)eps > 0.0)) return false;
-    return true;
-}
-
-bool det_conv_ok(const btba_lfnet_desc_layer &l, size_t K, size_t N)
-{
-    return l.weights && det_finite(l.weights, K * N) && (!l.biases || det_finite(l.biases, N));
-}
-
-// (scale, shift) of y = x * scale + shift for the batch norm of `l` behind a bias (bias NULL: none), fp64 rounded once
-void det_fold(const btba_lfnet_desc_layer &l, const float *bias, int N, float eps, float *scale, float *shift)
-{
-    for (int n = 0; n < N; n++) {
-        const double b = bias ? (double)bias[n] : 0.0;
-        double sc = 1.0, sh = b;
-        if (l.moving_mean) {
-            sc = (l.gamma ? (double)l.gamma[n] : 1.0) / std::sqrt((double)l.moving_variance[n] + (double)eps);
-            sh = (l.beta ? (double)l.beta[n] : 0.0) + (b - (double)l.moving_mean[n]) * sc;
-        }
-        scale[n] = (float)sc;
-        shift[n] = (float)sh;
-    }
-}
 }  // namespace
 
-struct btba_lfnet_det_model {
-    btba_workspace *ws = nullptr;
-    int device = 0;
+struct btba_lfnet_det_model : LfnetModelBase {
     btba_lfnet_det_config cfg{};
     struct Pair { size_t scale = 0, shift = 0; };                    // offsets in floats into dev
     struct Block { Pair pre, mid, out; size_t w1 = 0, w2 = 0; };
@@ -71,7 +31,6 @@ struct btba_lfnet_det_model {
     Pair fin;
     size_t score_w[BTBA_LFNET_MAX_SCALES] = {}, ori_w = 0;
     float score_b[BTBA_LFNET_MAX_SCALES] = {}, ori_b[2] = {};
-    DevBuf dev;
 };
 
 namespace {
@@ -144,68 +103,61 @@ int btba_lfnet_det_model_create(btba_workspace *ws, const btba_lfnet_det_config 
     if (!ws || !wts || !out || !det_config_ok(cfg)) return BTBA_EINVAL;
     const int C = cfg->channels, k = cfg->ksize, kk = k * k, S = cfg->num_scales;
     const size_t N = (size_t)C;
-    if (!det_conv_ok(wts->init_conv, (size_t)kk, N) || !det_bn_ok(wts->fin_bn, N, cfg->bn_eps) || !det_conv_ok(wts->ori_conv, (size_t)kk * C, 2))
+    const float eps = cfg->bn_eps;
+    if (!lfnet_conv_ok(wts->init_conv, (size_t)kk, N) || !lfnet_bn_ok(wts->fin_bn, N, eps) || !lfnet_conv_ok(wts->ori_conv, (size_t)kk * C, 2))
         return BTBA_EINVAL;
     for (int i = 0; i < cfg->blocks; i++) {
         const btba_lfnet_det_block &b = wts->block[i];
-        if (!det_bn_ok(b.pre_bn, N, cfg->bn_eps) || !det_conv_ok(b.conv1, (size_t)kk * C, N) || !det_bn_ok(b.conv1, N, cfg->bn_eps) ||
-            !det_conv_ok(b.conv2, (size_t)kk * C, N))
+        if (!lfnet_bn_ok(b.pre_bn, N, eps) || !lfnet_conv_ok(b.conv1, (size_t)kk * C, N) || !lfnet_bn_ok(b.conv1, N, eps) ||
+            !lfnet_conv_ok(b.conv2, (size_t)kk * C, N))
             return BTBA_EINVAL;
     }
     for (int j = 0; j < S; j++)
-        if (!det_conv_ok(wts->score_conv[j], (size_t)kk * C, 1)) return BTBA_EINVAL;
+        if (!lfnet_conv_ok(wts->score_conv[j], (size_t)kk * C, 1)) return BTBA_EINVAL;
     // every argument has been checked; the first HIP call follows
     std::unique_ptr<btba_lfnet_det_model> M(new (std::nothrow) btba_lfnet_det_model());
     if (!M) return BTBA_ENOMEM;
     M->ws = ws; M->device = ws->device; M->cfg = *cfg;
-    size_t total = 0;
-    auto take = [&](size_t n) { const size_t at = total; total += (n + 63) & ~(size_t)63; return at; };      // 256-byte regions
-    auto take_pair = [&](btba_lfnet_det_model::Pair &p) { p.scale = take(N); p.shift = take(N); };
-    M->init_w = take((size_t)kk * C); M->init_b = take(N);
+    LfnetArena A;
+    auto take_pair = [&](btba_lfnet_det_model::Pair &p) { p.scale = A.take(N); p.shift = A.take(N); };
+    M->init_w = A.take((size_t)kk * C); M->init_b = A.take(N);
     for (int i = 0; i < cfg->blocks; i++) {
         btba_lfnet_det_model::Block &B = M->blocks[i];
-        take_pair(B.pre); B.w1 = take((size_t)kk * C * C); take_pair(B.mid); B.w2 = take((size_t)kk * C * C); take_pair(B.out);
+        take_pair(B.pre); B.w1 = A.take((size_t)kk * C * C); take_pair(B.mid); B.w2 = A.take((size_t)kk * C * C); take_pair(B.out);
     }
     take_pair(M->fin);
-    for (int j = 0; j < S; j++) M->score_w[j] = take((size_t)kk * C);
-    M->ori_w = take((size_t)kk * C * 2);
-    std::vector<float> host(total, 0.0f);
-    float *h = host.data();
-    std::memcpy(h + M->init_w, wts->init_conv.weights, sizeof(float) * (size_t)kk * C);          // [k][k][1][C] IS [k * k][C]
-    if (wts->init_conv.biases) std::memcpy(h + M->init_b, wts->init_conv.biases, sizeof(float) * N);
-    btba_lfnet_desc_layer no_bn{};
+    for (int j = 0; j < S; j++) M->score_w[j] = A.take((size_t)kk * C);
+    M->ori_w = A.take((size_t)kk * C * 2);
+    A.fill();
+    auto fold = [&](const btba_lfnet_desc_layer &bn, const float *bias, const btba_lfnet_det_model::Pair &p) {
+        lfnet_fold(bn, bias, C, eps, A.at(p.scale), A.at(p.shift));
+    };
+    A.put(M->init_w, wts->init_conv.weights, (size_t)kk * C);                                    // [k][k][1][C] IS [k * k][C]
+    if (wts->init_conv.biases) A.put(M->init_b, wts->init_conv.biases, N);
+    const btba_lfnet_desc_layer no_bn{};
     for (int i = 0; i < cfg->blocks; i++) {
         const btba_lfnet_det_block &b = wts->block[i];
         const btba_lfnet_det_model::Block &B = M->blocks[i];
-        det_fold(b.pre_bn, nullptr, C, cfg->bn_eps, h + B.pre.scale, h + B.pre.shift);
-        std::memcpy(h + B.w1, b.conv1.weights, sizeof(float) * (size_t)kk * C * C);              // [k][k][C][C] IS [K][N] in (ky, kx, c_in) order
-        det_fold(b.conv1, b.conv1.biases, C, cfg->bn_eps, h + B.mid.scale, h + B.mid.shift);
-        std::memcpy(h + B.w2, b.conv2.weights, sizeof(float) * (size_t)kk * C * C);
-        det_fold(no_bn, b.conv2.biases, C, cfg->bn_eps, h + B.out.scale, h + B.out.shift);
+        fold(b.pre_bn, nullptr, B.pre);
+        A.put(B.w1, b.conv1.weights, (size_t)kk * C * C);                                        // [k][k][C][C] IS [K][N] in (ky, kx, c_in) order
+        fold(b.conv1, b.conv1.biases, B.mid);
+        A.put(B.w2, b.conv2.weights, (size_t)kk * C * C);
+        fold(no_bn, b.conv2.biases, B.out);
     }
-    det_fold(wts->fin_bn, nullptr, C, cfg->bn_eps, h + M->fin.scale, h + M->fin.shift);
+    fold(wts->fin_bn, nullptr, M->fin);
     for (int j = 0; j < S; j++) {
-        std::memcpy(h + M->score_w[j], wts->score_conv[j].weights, sizeof(float) * (size_t)kk * C);
+        A.put(M->score_w[j], wts->score_conv[j].weights, (size_t)kk * C);
         M->score_b[j] = wts->score_conv[j].biases ? wts->score_conv[j].biases[0] : 0.0f;
     }
-    std::memcpy(h + M->ori_w, wts->ori_conv.weights, sizeof(float) * (size_t)kk * C * 2);
+    A.put(M->ori_w, wts->ori_conv.weights, (size_t)kk * C * 2);
     for (int o = 0; o < 2; o++) M->ori_b[o] = wts->ori_conv.biases ? wts->ori_conv.biases[o] : 0.0f;
     DeviceGuard device_guard(ws);
-    if (int rc = M->dev.ensure(sizeof(float) * total)) return rc;
-    HIP_TRY(hipMemcpy(M->dev.p, host.data(), sizeof(float) * total, hipMemcpyHostToDevice));
+    if (int rc = M->upload(A)) return rc;
     *out = M.release();
     return BTBA_OK;
 }
 
-void btba_lfnet_det_model_destroy(btba_lfnet_det_model *M)
-{
-    if (!M) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess || prev == M->device || hipSetDevice(M->device) != hipSuccess) prev = -1;
-    (void)hipDeviceSynchronize();                                     // delete frees the weights; no workspace access
-    delete M;
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
+void btba_lfnet_det_model_destroy(btba_lfnet_det_model *M) { destroy_on_device(M); }
 
 int btba_lfnet_det_map_size(double scale_factor, int size)
 {
@@ -270,7 +222,7 @@ int btba_lfnet_scores(btba_workspace *ws, const btba_lfnet_det_model *M, int n_f
             G.shift = Wd + B.mid.shift; G.shortcut = nullptr; G.out = t; G.out_act = c.activation;
             if (int rc = det_conv_enqueue(ws, C, ks, G, grid)) return rc;
             G.in = t; G.w = Wd + B.w2; G.in_scale = G.in_shift = nullptr; G.scale = Wd + B.out.scale; G.shift = Wd + B.out.shift;
-            G.shortcut = x; G.out = x; G.out_act = kDetActNone;          // in place: a lane reads and writes its own elements only
+            G.shortcut = x; G.out = x; G.out_act = kLfnetActNone;          // in place: a lane reads and writes its own elements only
             if (int rc = det_conv_enqueue(ws, C, ks, G, grid)) return rc;
         }
         DetHead G{};

@@ -15,6 +15,7 @@
 
 #include "../../include/btba.h"
 #include "btba_device.hpp"
+#include "btba_lfnet_weights.hpp"
 
 // The types below are members of btba_workspace, which every unit sees: a named namespace, hidden, instead of an anonymous one per unit.
 namespace btba_host __attribute__((visibility("hidden"))) {
@@ -228,6 +229,30 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
+
+// What a model handle of either LF-Net net starts with: its workspace, that workspace's device and the arena's device copy.
+struct LfnetModelBase {
+    btba_workspace *ws = nullptr;
+    int device = 0;
+    DevBuf dev;
+    int upload(const LfnetArena &a)
+    {
+        if (int rc = dev.ensure(sizeof(float) * a.total)) return rc;
+        HIP_TRY(hipMemcpy(dev.p, a.host.data(), sizeof(float) * a.total, hipMemcpyHostToDevice));
+        return BTBA_OK;
+    }
+};
+
+// The destroy of a handle with a `device` member that owns device memory and is not part of a workspace.
+template <class M> void destroy_on_device(M *m)
+{
+    if (!m) return;
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess || prev == m->device || hipSetDevice(m->device) != hipSuccess) prev = -1;
+    (void)hipDeviceSynchronize();                                     // delete frees the buffers; no workspace access
+    delete m;
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
 
 inline void scaled_intrinsics(int H, int W, int Hd, int Wd, const float *K, float intr[4], Mat4 *Kinv)
 {

@@ -25,13 +25,13 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/btba.h"
+#include "btba_lfnet_net.hpp"
 
 namespace btba {
 
 constexpr int kDescBM = 64, kDescBN = 64, kDescKT = 16;
 constexpr int kDescAStride = kDescBM + 4;        // [k][row] image of the A tile: the four k-quads of a row land in four different bank groups
 constexpr int kDescChunk = 2048;                 // patches per pass over the layers: bounds the scratch (two buffers of the widest layer)
-constexpr int kDescActRelu = 0, kDescActLeaky = 1, kDescActNone = 2;
 
 typedef float desc_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -41,13 +41,6 @@ __device__ inline bool desc_live(const int32_t *__restrict__ n_kpts, int slots, 
     if (!n_kpts) return true;
     const int f = g / slots;
     return g - f * slots < n_kpts[f];
-}
-
-__device__ inline float desc_act(float v, int act, float alpha)
-{
-    if (act == kDescActRelu) return fmaxf(v, 0.0f);
-    if (act == kDescActLeaky) return v >= 0.0f ? v : alpha * v;
-    return v;
 }
 
 struct DescConv1 {
@@ -78,11 +71,7 @@ __global__ void __launch_bounds__(256) k_desc_conv1(const DescConv1 G)
             acc.x = fmaf(x, w.x, acc.x); acc.y = fmaf(x, w.y, acc.y); acc.z = fmaf(x, w.z, acc.z); acc.w = fmaf(x, w.w, acc.w);
         }
     }
-    const float4 sc = *reinterpret_cast<const float4 *>(G.scale + c), sh = *reinterpret_cast<const float4 *>(G.shift + c);
-    float4 o;
-    o.x = desc_act(fmaf(acc.x, sc.x, sh.x), G.act, G.alpha); o.y = desc_act(fmaf(acc.y, sc.y, sh.y), G.act, G.alpha);
-    o.z = desc_act(fmaf(acc.z, sc.z, sh.z), G.act, G.alpha); o.w = desc_act(fmaf(acc.w, sc.w, sh.w), G.act, G.alpha);
-    *reinterpret_cast<float4 *>(G.out + (size_t)pos * G.C + c) = o;
+    *reinterpret_cast<float4 *>(G.out + (size_t)pos * G.C + c) = lfnet_bn_act4(acc, G.scale, G.shift, c, G.act, G.alpha);
 }
 
 struct DescGemm {
@@ -150,7 +139,7 @@ __global__ void __launch_bounds__(256) k_desc_gemm(const DescGemm G)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m < G.M) G.out[(size_t)m * G.N + n] = desc_act(fmaf(acc[r], sc, sh), G.act, G.alpha);
+        if (m < G.M) G.out[(size_t)m * G.N + n] = lfnet_act(fmaf(acc[r], sc, sh), G.act, G.alpha);
     }
 }
 

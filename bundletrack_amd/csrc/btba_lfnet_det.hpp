@@ -29,30 +29,15 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/btba.h"
+#include "btba_lfnet_net.hpp"
 
 namespace btba {
 
 constexpr int kDetTile = 16;
-constexpr int kDetActRelu = 0, kDetActLeaky = 1, kDetActNone = 2;
 
 typedef float det_f32x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline int det_lds_floats(int C, int ks) { const int r = kDetTile + 2 * (ks / 2); return r * r * (C + 4); }
-
-__device__ inline float det_act(float v, int act, float alpha)
-{
-    if (act == kDetActRelu) return fmaxf(v, 0.0f);
-    if (act == kDetActLeaky) return v >= 0.0f ? v : alpha * v;
-    return v;
-}
-
-__device__ inline float4 det_bn_act(float4 v, const float *__restrict__ scale, const float *__restrict__ shift, int c, int act, float alpha)
-{
-    const float4 sc = *reinterpret_cast<const float4 *>(scale + c), sh = *reinterpret_cast<const float4 *>(shift + c);
-    v.x = det_act(fmaf(v.x, sc.x, sh.x), act, alpha); v.y = det_act(fmaf(v.y, sc.y, sh.y), act, alpha);
-    v.z = det_act(fmaf(v.z, sc.z, sh.z), act, alpha); v.w = det_act(fmaf(v.w, sc.w, sh.w), act, alpha);
-    return v;
-}
 
 struct DetInit {
     const float *photo;                          // [frames][H][W]
@@ -112,7 +97,7 @@ __global__ void __launch_bounds__(256) k_det_conv(const DetConv G)
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (gy >= 0 && gy < G.H && gx >= 0 && gx < G.W) {
             v = *reinterpret_cast<const float4 *>(img + ((size_t)gy * G.W + gx) * C + 4 * q);
-            if (G.in_scale) v = det_bn_act(v, G.in_scale, G.in_shift, 4 * q, G.act, G.alpha);
+            if (G.in_scale) v = lfnet_bn_act4(v, G.in_scale, G.in_shift, 4 * q, G.act, G.alpha);
         }
         *reinterpret_cast<float4 *>(det_lds + p * PS + 4 * q) = v;
     }
@@ -156,7 +141,7 @@ __global__ void __launch_bounds__(256) k_det_conv(const DetConv G)
                 const int gx = x0 + lk * 4 + r;
                 if (gx >= G.W) continue;
                 const size_t o = (frame + (size_t)gy * G.W + gx) * C + n;
-                float v = det_act(fmaf(acc[mt][nt][r], sc, sh), G.out_act, G.alpha);
+                float v = lfnet_act(fmaf(acc[mt][nt][r], sc, sh), G.out_act, G.alpha);
                 if (G.shortcut) v += G.shortcut[o];
                 G.out[o] = v;
             }
@@ -193,7 +178,7 @@ __global__ void __launch_bounds__(256) k_det_head(const DetHead G)
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (my >= 0 && my < G.h && mx >= 0 && mx < G.w_out) {
             auto feat = [&](int yy, int xx) {
-                return det_bn_act(*reinterpret_cast<const float4 *>(img + ((size_t)yy * G.W + xx) * C + c), G.fscale, G.fshift, c, G.act, G.alpha);
+                return lfnet_bn_act4(*reinterpret_cast<const float4 *>(img + ((size_t)yy * G.W + xx) * C + c), G.fscale, G.fshift, c, G.act, G.alpha);
             };
             if (same) {
                 v = feat(my, mx);

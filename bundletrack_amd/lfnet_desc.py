@@ -9,15 +9,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LfnetDescLayer, LfnetDescWeights, check, lfnet_desc_config, lib
+from ._lfnet_model import BN_FIELDS, NpzModel, WeightMarshal, resolve_config
+from ._lib import LfnetDescWeights, check, lfnet_desc_config, lib
 
 MAX_DEPTH, MAX_SLOTS = 4, 2048             # BTBA_LFNET_DESC_MAX_DEPTH, BTBA_LFNET_MAX_TOP_K
 SCOPE = "SimpleDesc"
-_BN = ("gamma", "beta", "moving_mean", "moving_variance")
-
-
-def _config(config):
-    return lfnet_desc_config() if config is None else (lfnet_desc_config(**config) if isinstance(config, dict) else config)
 
 
 def layer_scopes(depth: int):
@@ -33,7 +29,7 @@ def expected_names(depth: int, perform_bn: bool = True, use_bias: bool = True, s
         if use_bias:
             names.append(f"{scope}/{layer}/biases")
         if bn and perform_bn:
-            names += [f"{scope}/{bn}/{k}" for k in _BN]
+            names += [f"{scope}/{bn}/{k}" for k in BN_FIELDS]
     return names
 
 
@@ -57,7 +53,7 @@ def config_from_weights(weights, scope: str = SCOPE, **over):
     return lfnet_desc_config(**cfg)
 
 
-class LfnetDescriptor:
+class LfnetDescriptor(NpzModel):
     """A descriptor model on a workspace.  weights: a mapping from the checkpoint's variable names (SimpleDesc/conv1/weights,
     SimpleDesc/conv1/biases, SimpleDesc/bn1/gamma, .../beta, .../moving_mean, .../moving_variance, SimpleDesc/fc1/weights,
     SimpleDesc/fc-bn1/..., SimpleDesc/fc2/weights, SimpleDesc/fc2/biases) to arrays in TensorFlow's layouts.  A layer's `weights`
@@ -66,34 +62,23 @@ class LfnetDescriptor:
 
     Callable as desc_net: (patches [m, 1, P, P] or [m, P, P]) -> [m, D]."""
 
+    _destroy = "btba_lfnet_desc_model_destroy"
+    _default_config, _expected_names, _config_from_weights = staticmethod(lfnet_desc_config), staticmethod(expected_names), staticmethod(config_from_weights)
+
     def __init__(self, ws, weights, config=None, scope: str = SCOPE):
-        self.ws, self.config = ws, _config(config)
+        self.ws, self.config = ws, resolve_config(lfnet_desc_config, config)
         cfg = self.config
-        W = LfnetDescWeights()
-        keep = []                                          # the host arrays must outlive the create call
-
-        def arr(name, shape):
-            if name not in weights:
-                return None
-            a = np.ascontiguousarray(weights[name], np.float32)
-            if tuple(a.shape) != tuple(shape):
-                raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(a.shape)}")
-            keep.append(a)
-            return a.ctypes.data
-
-        def fill(layer: LfnetDescLayer, name, bn, wshape):
-            if f"{scope}/{name}/weights" not in weights:
-                raise KeyError(f"descriptor weights: missing {scope}/{name}/weights; expected {expected_names(int(cfg.depth), scope=scope)}")
-            n = wshape[-1]
-            layer.weights = arr(f"{scope}/{name}/weights", wshape)
-            layer.biases = arr(f"{scope}/{name}/biases", (n,))
-            if bn:
-                for k in _BN:
-                    setattr(layer, k, arr(f"{scope}/{bn}/{k}", (n,)))
-
         depth = int(cfg.depth)
         if not 1 <= depth <= MAX_DEPTH:
             raise ValueError(f"depth {depth} outside 1 .. {MAX_DEPTH}")
+        W = LfnetDescWeights()
+        m = WeightMarshal(weights, scope, "descriptor", expected_names(depth, scope=scope))
+
+        def fill(layer, name, bn, wshape):
+            m.conv(layer, name, wshape)
+            if bn:
+                m.bn(layer, bn, wshape[-1])
+
         c_in = 1
         for i, (name, bn) in enumerate(layer_scopes(depth)[:depth]):
             c_out = int(cfg.channels) << i
@@ -105,37 +90,17 @@ class LfnetDescriptor:
         h = C.c_void_p()
         check(lib().btba_lfnet_desc_model_create(ws.handle, C.byref(cfg), C.byref(W), C.byref(h)), "btba_lfnet_desc_model_create")
         self._h = h
-        del keep
+
+    @staticmethod
+    def _counts(cfg, have, scope, over):
+        return (int(cfg.depth) if cfg is not None else max(sum(f"{scope}/conv{i + 1}/weights" in have for i in range(MAX_DEPTH)), 1),)
 
     @classmethod
     def from_npz(cls, ws, path, config=None, perform_bn: bool = True, use_bias: bool = True, scope: str = SCOPE, **over):
         """A model from an .npz whose arrays are named as the checkpoint names its variables (INTEGRATION.md has the TF1 export).
         Every variable of get_model(perform_bn=..., use_bias=...) must be there: a missing one is an error that lists them all.
         Without `config` the shape fields come from the arrays; `over` sets activation, leaky_alpha, norm, bn_eps."""
-        with np.load(path) as z:
-            have = {k: z[k] for k in z.files}
-        depth = int(_config(config).depth) if config is not None else max(sum(f"{scope}/conv{i + 1}/weights" in have for i in range(MAX_DEPTH)), 1)
-        want = expected_names(depth, perform_bn, use_bias, scope)
-        missing = [n for n in want if n not in have]
-        if missing:
-            raise KeyError(f"{path}: missing {missing}; expected the arrays {want}")
-        cfg = _config(config) if config is not None else config_from_weights(have, scope, **over)
-        return cls(ws, {n: have[n] for n in want}, cfg, scope)
-
-    @property
-    def handle(self):
-        return self._h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().btba_lfnet_desc_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return cls._from_npz(ws, path, config, perform_bn, use_bias, scope, over)
 
     def describe(self, patches, n_kpts=None):
         """patches: float32 CUDA [n, K, P, P]; n_kpts: int32 CUDA [n] or None (all slots).  Returns desc float32 [n, K, D]; slots

@@ -10,15 +10,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LfnetDescLayer, LfnetDetWeights, check, lfnet_det_config, lib
+from ._lfnet_model import BN_FIELDS, NpzModel, WeightMarshal, resolve_config
+from ._lib import LfnetDetWeights, check, lfnet_det_config, lib
 
 MAX_BLOCKS, MAX_SCALES = 8, 16             # BTBA_LFNET_DET_MAX_BLOCKS, BTBA_LFNET_MAX_SCALES
 SCOPE = "ConvOnlyResNet"
-_BN = ("gamma", "beta", "moving_mean", "moving_variance")
-
-
-def _config(config):
-    return lfnet_det_config() if config is None else (lfnet_det_config(**config) if isinstance(config, dict) else config)
 
 
 def detector_scales(min_scale: float, max_scale: float, num_scales: int) -> np.ndarray:
@@ -40,7 +36,7 @@ def expected_names(blocks: int, num_scales: int, perform_bn: bool = True, use_bi
 
     def bn(name):
         if perform_bn:
-            names.extend(f"{scope}/{name}/{k}" for k in _BN)
+            names.extend(f"{scope}/{name}/{k}" for k in BN_FIELDS)
 
     conv("init_conv")
     for i in range(1, blocks + 1):
@@ -77,7 +73,7 @@ def config_from_weights(weights, scope: str = SCOPE, **over):
     return lfnet_det_config(**cfg)
 
 
-class LfnetScoreNet:
+class LfnetScoreNet(NpzModel):
     """A detector model on a workspace.  weights: a mapping from the checkpoint's variable names (ConvOnlyResNet/init_conv/weights,
     ConvOnlyResNet/block-1/pre-bn/gamma, .../conv1/weights, .../mid-bn/moving_mean, ConvOnlyResNet/fin-bn/..., .../score_conv_0/weights,
     .../ori_conv/biases, ...) to arrays in TensorFlow's layouts.  A convolution's `weights` must be there; absent biases mean none,
@@ -86,72 +82,47 @@ class LfnetScoreNet:
 
     Callable as score_net: gray [n, 1, H, W] -> (list of S maps [n, h_j, w_j], ori [n, H, W, 2])."""
 
+    _destroy = "btba_lfnet_det_model_destroy"
+    _default_config, _expected_names, _config_from_weights = staticmethod(lfnet_det_config), staticmethod(expected_names), staticmethod(config_from_weights)
+
     def __init__(self, ws, weights, config=None, scope: str = SCOPE):
-        self.ws, self.config = ws, _config(config)
+        self.ws, self.config = ws, resolve_config(lfnet_det_config, config)
         cfg = self.config
         Cn, k, blocks, S = int(cfg.channels), int(cfg.ksize), int(cfg.blocks), int(cfg.num_scales)
         if not 1 <= blocks <= MAX_BLOCKS or not 1 <= S <= MAX_SCALES:
             raise ValueError(f"blocks {blocks} outside 1 .. {MAX_BLOCKS} or num_scales {S} outside 1 .. {MAX_SCALES}")
         W = LfnetDetWeights()
-        keep = []                                          # the host arrays must outlive the create call
-
-        def arr(name, shape):
-            if name not in weights:
-                return None
-            a = np.ascontiguousarray(weights[name], np.float32)
-            if tuple(a.shape) != tuple(shape):
-                raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(a.shape)}")
-            keep.append(a)
-            return a.ctypes.data
-
-        def conv(layer: LfnetDescLayer, name, c_in, c_out):
-            if f"{scope}/{name}/weights" not in weights:
-                raise KeyError(f"detector weights: missing {scope}/{name}/weights; expected {expected_names(blocks, S, scope=scope)}")
-            layer.weights = arr(f"{scope}/{name}/weights", (k, k, c_in, c_out))
-            layer.biases = arr(f"{scope}/{name}/biases", (c_out,))
-
-        def bn(layer: LfnetDescLayer, name):
-            for f in _BN:
-                setattr(layer, f, arr(f"{scope}/{name}/{f}", (Cn,)))
-
-        conv(W.init_conv, "init_conv", 1, Cn)
+        m = WeightMarshal(weights, scope, "detector", expected_names(blocks, S, scope=scope))
+        m.conv(W.init_conv, "init_conv", (k, k, 1, Cn))
         for i in range(blocks):
             b = W.block[i]
-            bn(b.pre_bn, f"block-{i + 1}/pre-bn")
-            conv(b.conv1, f"block-{i + 1}/conv1", Cn, Cn)
-            bn(b.conv1, f"block-{i + 1}/mid-bn")
-            conv(b.conv2, f"block-{i + 1}/conv2", Cn, Cn)
-        bn(W.fin_bn, "fin-bn")
+            m.bn(b.pre_bn, f"block-{i + 1}/pre-bn", Cn)
+            m.conv(b.conv1, f"block-{i + 1}/conv1", (k, k, Cn, Cn))
+            m.bn(b.conv1, f"block-{i + 1}/mid-bn", Cn)
+            m.conv(b.conv2, f"block-{i + 1}/conv2", (k, k, Cn, Cn))
+        m.bn(W.fin_bn, "fin-bn", Cn)
         for j in range(S):
-            conv(W.score_conv[j], f"score_conv_{j}", Cn, 1)
-        conv(W.ori_conv, "ori_conv", Cn, 2)
+            m.conv(W.score_conv[j], f"score_conv_{j}", (k, k, Cn, 1))
+        m.conv(W.ori_conv, "ori_conv", (k, k, Cn, 2))
         h = C.c_void_p()
         check(lib().btba_lfnet_det_model_create(ws.handle, C.byref(cfg), C.byref(W), C.byref(h)), "btba_lfnet_det_model_create")
         self._h = h
-        del keep
+
+    @staticmethod
+    def _counts(cfg, have, scope, over):
+        if cfg is not None:
+            return int(cfg.blocks), int(cfg.num_scales)
+        blocks = max(sum(f"{scope}/block-{i + 1}/conv1/weights" in have for i in range(MAX_BLOCKS)), 1)
+        if "scale_factors" in over:
+            return blocks, len(over["scale_factors"])
+        return blocks, max(sum(f"{scope}/score_conv_{j}/weights" in have for j in range(MAX_SCALES)), 1)
 
     @classmethod
     def from_npz(cls, ws, path, config=None, perform_bn: bool = True, use_bias: bool = True, scope: str = SCOPE, **over):
         """A model from an .npz whose arrays are named as the checkpoint names its variables (INTEGRATION.md has the TF1 export).
         Every variable of get_model(perform_bn=..., use_bias=...) must be there: a missing one is an error that lists them all.
         Without `config` the shape fields come from the arrays; `over` sets scale_factors, activation, leaky_alpha, bn_eps."""
-        with np.load(path) as z:
-            have = {k: z[k] for k in z.files}
-        if config is not None:
-            blocks, scales = int(_config(config).blocks), int(_config(config).num_scales)
-        else:
-            blocks = max(sum(f"{scope}/block-{i + 1}/conv1/weights" in have for i in range(MAX_BLOCKS)), 1)
-            scales = len(over["scale_factors"]) if "scale_factors" in over else max(sum(f"{scope}/score_conv_{j}/weights" in have for j in range(MAX_SCALES)), 1)
-        want = expected_names(blocks, scales, perform_bn, use_bias, scope)
-        missing = [n for n in want if n not in have]
-        if missing:
-            raise KeyError(f"{path}: missing {missing}; expected the arrays {want}")
-        cfg = _config(config) if config is not None else config_from_weights(have, scope, **over)
-        return cls(ws, {n: have[n] for n in want}, cfg, scope)
-
-    @property
-    def handle(self):
-        return self._h
+        return cls._from_npz(ws, path, config, perform_bn, use_bias, scope, over)
 
     @property
     def scale_factors(self):
@@ -167,17 +138,6 @@ class LfnetScoreNet:
         mh, mw = np.zeros(S, np.int32), np.zeros(S, np.int32)
         check(lib().btba_lfnet_det_map_sizes(self._h, int(H), int(W), mh.ctypes.data, mw.ctypes.data), "btba_lfnet_det_map_sizes")
         return mh, mw
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().btba_lfnet_det_model_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def scores(self, photo):
         """photo: float32 CUDA [n, H, W] or [n, 1, H, W].  Returns (list of S score maps float32 [n, h_j, w_j], ori float32

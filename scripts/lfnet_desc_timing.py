@@ -46,7 +46,7 @@ def main():
     layers = []
     for layer, bn in R.layer_scopes(cfg["depth"]):
         w = weights[f"SimpleDesc/{layer}/weights"]
-        scale, shift = R.fold(weights, layer, bn, w.shape[-1], cfg["bn_eps"])
+        scale, shift = R.fold(weights, R.SCOPE, bn, w.shape[-1], cfg["bn_eps"], weights.get(f"{R.SCOPE}/{layer}/biases"))
         wt = torch.from_numpy(w).cuda()
         layers.append((wt.permute(3, 2, 0, 1).contiguous() if w.ndim == 4 else wt, torch.from_numpy(scale.astype(np.float32)).cuda(),
                        torch.from_numpy(shift.astype(np.float32)).cuda()))

@@ -50,7 +50,7 @@ def main():
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
     conv_w = lambda name: dev(weights[f"ConvOnlyResNet/{name}/weights"]).permute(3, 2, 0, 1).contiguous()
     bias = lambda name: weights.get(f"ConvOnlyResNet/{name}/biases")
-    pair = lambda name, n, b=None: tuple(dev(v)[None, :, None, None] for v in R.bn_pair(weights, name, n, cfg["bn_eps"], b))
+    pair = lambda name, n, b=None: tuple(dev(v)[None, :, None, None] for v in R.N.fold(weights, R.SCOPE, name, n, cfg["bn_eps"], b))
     init = (conv_w("init_conv"), pair("none", Cn, bias("init_conv")))
     blocks = []
     for i in range(1, cfg["blocks"] + 1):

@@ -21,7 +21,6 @@ Two places where a group is not get_model's text as it stands: get_model asks fo
 the store hands out the stored, narrower array (Store.get_variable); and get_model switches batch norm and biases for all layers at
 once, so the group without them (c) has neither in any layer."""
 import contextlib
-import importlib.util
 import os
 import sys
 import types
@@ -29,13 +28,16 @@ import types
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 import lfnet_desc_ref as R  # noqa: E402
 import lfnet_ref  # noqa: E402
+from ref_loader import load_under_stand_ins  # noqa: E402
 
 F32 = np.float32
+REFERENCE_FILES = (("common.tf_layer_utils", "common/tf_layer_utils.py"), ("common.tf_train_utils", "common/tf_train_utils.py"))
 
 
 class Dim(int):
@@ -167,23 +169,8 @@ def reference_modules(store):
     det_tools.instance_normalization = instance_normalization
     common = types.ModuleType("common")
     common.__path__ = []
-    names = ("tensorflow", "det_tools", "common", "common.tf_layer_utils", "common.tf_train_utils", "simple_desc")
-    saved = {k: sys.modules.get(k) for k in names}
-    sys.modules.update(tensorflow=make_tensorflow(store), det_tools=det_tools, common=common)
-    mods = {}
-    try:
-        for name, path in (("common.tf_layer_utils", "common/tf_layer_utils.py"), ("common.tf_train_utils", "common/tf_train_utils.py"),
-                           ("simple_desc", "models/simple_desc.py")):
-            spec = importlib.util.spec_from_file_location(name, os.path.join(root, path))
-            mods[name] = importlib.util.module_from_spec(spec)
-            sys.modules[name] = mods[name]
-            spec.loader.exec_module(mods[name])
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    mods = load_under_stand_ins(root, REFERENCE_FILES + (("simple_desc", "models/simple_desc.py"),),
+                                dict(tensorflow=make_tensorflow(store), det_tools=det_tools, common=common))
     return mods["simple_desc"], mods["common.tf_train_utils"]
 
 
@@ -207,8 +194,8 @@ def main():
     out = {}
     for g, (name, over, (perform_bn, use_bias), m) in enumerate(R.GROUPS):
         cfg = R.config(**over)
-        q = R.make_model(31000 + g, cfg, perform_bn, use_bias)
-        pq, pm = R.make_patches(32000 + g, m, cfg["patch_size"])
+        q = R.make_model(R.MODEL_SEED + g, cfg, perform_bn, use_bias)
+        pq, pm = R.make_patches(R.PATCH_SEED + g, m, cfg["patch_size"])
         weights, patches = R.model_weights(q), R.levels(pq, pm)
         ref_desc, ref_raw = run_reference(weights, cfg, perform_bn, use_bias, patches)
         d64, r64 = R.forward(weights, cfg, patches, np.float64)

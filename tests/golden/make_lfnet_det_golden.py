@@ -20,7 +20,6 @@ prints values stored here).  Only inputs and results are stored:
                                over the pixels whose fp64 raw norm is at least 0.05 x the frame's largest)
 The file is written only if the restatement in fp32 mode is inside the bars and at most 1 % of any frame's pixels are left out of
 the orientation comparison."""
-import importlib.util
 import os
 import sys
 import types
@@ -35,6 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import lfnet_det_ref as R  # noqa: E402
 import lfnet_ref  # noqa: E402
 import make_lfnet_desc_golden as D  # noqa: E402
+from ref_loader import load_under_stand_ins  # noqa: E402
 
 F32 = np.float32
 t = D.t
@@ -127,23 +127,8 @@ def reference_modules(store):
         return None
     common = types.ModuleType("common")
     common.__path__ = []
-    names = ("tensorflow", "common", "common.tf_layer_utils", "common.tf_train_utils", "mso_resnet_detector")
-    saved = {k: sys.modules.get(k) for k in names}
-    sys.modules.update(tensorflow=make_tensorflow(store), common=common)
-    mods = {}
-    try:
-        for name, path in (("common.tf_layer_utils", "common/tf_layer_utils.py"), ("common.tf_train_utils", "common/tf_train_utils.py"),
-                           ("mso_resnet_detector", "models/mso_resnet_detector.py")):
-            spec = importlib.util.spec_from_file_location(name, os.path.join(root, path))
-            mods[name] = importlib.util.module_from_spec(spec)
-            sys.modules[name] = mods[name]
-            spec.loader.exec_module(mods[name])
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    mods = load_under_stand_ins(root, D.REFERENCE_FILES + (("mso_resnet_detector", "models/mso_resnet_detector.py"),),
+                                dict(tensorflow=make_tensorflow(store), common=common))
     return mods["mso_resnet_detector"], mods["common.tf_train_utils"]
 
 
@@ -169,8 +154,8 @@ def main():
     out = {}
     for g, (name, over, (perform_bn, use_bias), (n, H, W), big_beta) in enumerate(R.GROUPS):
         cfg = R.config(**over)
-        q = R.make_model(41000 + g, cfg, perform_bn, use_bias, big_beta)
-        pq, pm = R.make_photos(42000 + g, n, H, W)
+        q = R.make_model(R.MODEL_SEED + g, cfg, perform_bn, use_bias, big_beta)
+        pq, pm = R.make_photos(R.PHOTO_SEED + g, n, H, W)
         weights, photos = R.model_weights(q), R.levels(pq, pm)
         ref_maps, ref_ori, ref_sf, ref_pad = run_reference(weights, cfg, perform_bn, use_bias, photos)
         assert np.array_equal(ref_sf, np.asarray(cfg["scale_factors"])) and ref_pad == R.pad_size(cfg)

@@ -18,7 +18,6 @@ A seed is taken only if every peak and top-k decision of the case has an fp64 ma
 samples on the crop's discontinuity is at most 0.5 %, and the restatement's stage B on the reference's heat map gives the
 reference's keypoints; the file is written only if the reference's own fp32 result is inside the bars."""
 import contextlib
-import importlib.util
 import os
 import sys
 import types
@@ -26,10 +25,12 @@ import types
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 import lfnet_ref as R  # noqa: E402
+from ref_loader import load_under_stand_ins  # noqa: E402
 
 F32 = np.float32
 
@@ -224,21 +225,8 @@ def reference_modules():
         return None
     utils = types.ModuleType("utils")
     utils.embed_breakpoint = lambda *a, **k: None
-    saved = {k: sys.modules.get(k) for k in ("tensorflow", "cv2", "utils", "det_tools", "spatial_transformer", "inference")}
-    sys.modules.update(tensorflow=make_tensorflow(), cv2=types.ModuleType("cv2"), utils=utils)
-    mods = {}
-    try:
-        for name in ("spatial_transformer", "det_tools", "inference"):
-            spec = importlib.util.spec_from_file_location(name, os.path.join(root, name + ".py"))
-            mods[name] = importlib.util.module_from_spec(spec)
-            sys.modules[name] = mods[name]
-            spec.loader.exec_module(mods[name])
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    mods = load_under_stand_ins(root, [(name, name + ".py") for name in ("spatial_transformer", "det_tools", "inference")],
+                                dict(tensorflow=make_tensorflow(), cv2=types.ModuleType("cv2"), utils=utils))
     return mods["inference"], mods["det_tools"]
 
 

@@ -11,6 +11,9 @@ import os
 
 import numpy as np
 
+from lfnet_net_ref import activate, bn_levels, fold, levels, model_weights  # noqa: F401
+import lfnet_net_ref as N
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "lfnet_desc", "lfnet_desc_reference.npz")
 SCOPE = "SimpleDesc"
@@ -20,7 +23,7 @@ DEFAULTS = dict(patch_size=32, depth=3, channels=64, fc_dim=512, out_dim=256, ac
 GROUPS = (("a", dict(patch_size=16, depth=2, channels=16, fc_dim=32, out_dim=16, activation=0, norm=0), (True, True), 5),
           ("b", dict(patch_size=32, depth=3, channels=16, fc_dim=64, out_dim=32, activation=1, leaky_alpha=0.2, norm=1), (True, True), 5),
           ("c", dict(patch_size=32, depth=3, channels=32, fc_dim=128, out_dim=64, activation=0, norm=0), (False, False), 5))
-_BN = ("gamma", "beta", "moving_mean", "moving_variance")
+MODEL_SEED, PATCH_SEED = 31000, 32000      # + the group's index: the seeds of the golden file's models and patches
 
 
 def config(**over):
@@ -66,22 +69,6 @@ def dense(x, w, dtype):
     return out
 
 
-def fold(weights, layer, bn, n, eps):
-    """(scale, shift) of include/btba.h in fp64."""
-    g = lambda name, default: np.asarray(weights[name], np.float64) if name in weights else np.full(n, default, np.float64)
-    bias = g(f"{SCOPE}/{layer}/biases", 0.0)
-    if bn is None or f"{SCOPE}/{bn}/moving_mean" not in weights:
-        return np.ones(n), bias
-    scale = g(f"{SCOPE}/{bn}/gamma", 1.0) / np.sqrt(g(f"{SCOPE}/{bn}/moving_variance", 1.0) + np.float64(np.float32(eps)))
-    return scale, g(f"{SCOPE}/{bn}/beta", 0.0) + (bias - g(f"{SCOPE}/{bn}/moving_mean", 0.0)) * scale
-
-
-def activate(y, cfg):
-    if cfg["activation"] == 0:
-        return np.maximum(y, 0)
-    return np.where(y >= 0, y, y * y.dtype.type(np.float32(cfg["leaky_alpha"])))
-
-
 def flatten(x):
     """(h, w, c): NHWC as it lies."""
     return np.ascontiguousarray(x).reshape(x.shape[0], -1)
@@ -106,7 +93,7 @@ def forward(weights, cfg, patches, dtype=np.float64):
         if i == depth:
             x = flatten(x)
         acc = conv(x, w, dtype) if i < depth else dense(x, w, dtype)
-        scale, shift = fold(weights, layer, bn, w.shape[-1], cfg["bn_eps"])
+        scale, shift = fold(weights, SCOPE, bn, w.shape[-1], cfg["bn_eps"], weights.get(f"{SCOPE}/{layer}/biases"))
         y = acc * scale.astype(dtype) + shift.astype(dtype)
         x = activate(y, cfg) if i <= depth else y
     return (l2_normalize(x, dtype) if cfg["norm"] == 0 else x), x
@@ -120,10 +107,6 @@ def error(desc, raw, desc64, raw64, cfg):
 
 
 # ---- seeded models and patches on int8 levels ---------------------------------------------------------------------------
-
-def levels(q, mult):
-    return (np.asarray(q).astype(np.float32) * np.float32(mult)).astype(np.float32)
-
 
 def make_model(seed, cfg, perform_bn=True, use_bias=True):
     """{name: (int8 levels, fp32 multiplier)}: weights uniform with He's bound, moving variances in [0.5, 2], gammas in [0.64, 1.27]."""
@@ -142,15 +125,8 @@ def make_model(seed, cfg, perform_bn=True, use_bias=True):
         if use_bias:
             q[f"{SCOPE}/{layer}/biases"] = (rs.integers(-127, 128, n).astype(np.int8), np.float32(1.0 / 512.0))
         if bn and perform_bn:
-            q[f"{SCOPE}/{bn}/gamma"] = (rs.integers(64, 128, n).astype(np.int8), np.float32(0.01))
-            q[f"{SCOPE}/{bn}/beta"] = (rs.integers(-127, 128, n).astype(np.int8), np.float32(1.0 / 512.0))
-            q[f"{SCOPE}/{bn}/moving_mean"] = (rs.integers(-127, 128, n).astype(np.int8), np.float32(1.0 / 512.0))
-            q[f"{SCOPE}/{bn}/moving_variance"] = (rs.integers(32, 128, n).astype(np.int8), np.float32(1.0 / 64.0))
+            q.update((f"{SCOPE}/{bn}/{k}", v) for k, v in bn_levels(rs, n).items())
     return q
-
-
-def model_weights(q):
-    return {name: levels(*v) for name, v in q.items()}
 
 
 def make_patches(seed, m, P):
@@ -170,6 +146,4 @@ def load_golden():
 
 def group_model(z, name):
     """The stored model and patches of a group as fp32: (weights, patches [m, P, P])."""
-    pre = f"{name}/"
-    w = {k[len(pre):]: levels(z[k], z[k + "@mult"]) for k in z.files if k.startswith(pre + SCOPE) and not k.endswith("@mult")}
-    return w, levels(z[f"{name}/patches"], z[f"{name}/patches@mult"])
+    return N.group_model(z, name, SCOPE, "patches")

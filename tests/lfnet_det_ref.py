@@ -12,12 +12,14 @@ import os
 
 import numpy as np
 
+from lfnet_net_ref import BN as _BN, activate, bn_levels, levels, model_weights  # noqa: F401
+import lfnet_net_ref as N
 from lfnet_ref import resize_taps
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "lfnet_det", "lfnet_det_reference.npz")
 SCOPE = "ConvOnlyResNet"
-_BN = ("gamma", "beta", "moving_mean", "moving_variance")
+MODEL_SEED, PHOTO_SEED = 41000, 42000      # + the group's index: the seeds of the golden file's models and photos
 ORI_FLOOR, ORI_CAP = 0.05, 0.01            # pixels whose fp64 raw norm is below ORI_FLOOR x the frame's largest are not compared; at most ORI_CAP of a frame
 
 
@@ -81,22 +83,6 @@ def conv(x, w, dtype):
     return out
 
 
-def bn_pair(weights, name, n, eps, bias=None):
-    """(scale, shift) of include/btba.h in fp64 for the batch norm `name` behind `bias`; (1, bias) where the norm is absent."""
-    g = lambda key, default: np.asarray(weights[key], np.float64) if key in weights else np.full(n, default, np.float64)
-    b = np.zeros(n) if bias is None else np.asarray(bias, np.float64)
-    if f"{SCOPE}/{name}/moving_mean" not in weights:
-        return np.ones(n), b
-    scale = g(f"{SCOPE}/{name}/gamma", 1.0) / np.sqrt(g(f"{SCOPE}/{name}/moving_variance", 1.0) + np.float64(np.float32(eps)))
-    return scale, g(f"{SCOPE}/{name}/beta", 0.0) + (b - g(f"{SCOPE}/{name}/moving_mean", 0.0)) * scale
-
-
-def activate(y, cfg):
-    if cfg["activation"] == 0:
-        return np.maximum(y, 0)
-    return np.where(y >= 0, y, y * y.dtype.type(np.float32(cfg["leaky_alpha"])))
-
-
 def resize(x, h, w, dtype):
     """TF1's resize_images on NHWC: top, bottom and value lerps in that order."""
     ya, yb, fy = resize_taps(x.shape[1], h, dtype)
@@ -116,6 +102,7 @@ def forward(weights, cfg, photos, dtype=np.float64, pad_before_bn=False):
     bias = lambda name: weights.get(f"{SCOPE}/{name}/biases")
     W = lambda name: weights[f"{SCOPE}/{name}/weights"]
     affine = lambda v, pair: v * pair[0].astype(dtype) + pair[1].astype(dtype)
+    bn_pair = lambda name, n, b=None: N.fold(weights, SCOPE, name, n, eps, b)
 
     def conv_of(v, pair, name):
         """conv(act(bn(v))) with the zeros after (right) or before (wrong) the norm and activation."""
@@ -126,20 +113,20 @@ def forward(weights, cfg, photos, dtype=np.float64, pad_before_bn=False):
         return conv(vp, W(name), dtype)[:, h:-h, h:-h]
 
     x = np.asarray(photos, dtype)[..., None]
-    x = affine(conv(x, W("init_conv"), dtype), bn_pair(weights, "none", C, eps, bias("init_conv")))
+    x = affine(conv(x, W("init_conv"), dtype), bn_pair(None, C, bias("init_conv")))
     for i in range(1, cfg["blocks"] + 1):
         b = f"block-{i}"
-        t = conv_of(x, bn_pair(weights, f"{b}/pre-bn", C, eps), f"{b}/conv1")
-        t = activate(affine(t, bn_pair(weights, f"{b}/mid-bn", C, eps, bias(f"{b}/conv1"))), cfg)
-        x = affine(conv(t, W(f"{b}/conv2"), dtype), bn_pair(weights, "none", C, eps, bias(f"{b}/conv2"))) + x
-    fin = bn_pair(weights, "fin-bn", C, eps)
+        t = conv_of(x, bn_pair(f"{b}/pre-bn", C), f"{b}/conv1")
+        t = activate(affine(t, bn_pair(f"{b}/mid-bn", C, bias(f"{b}/conv1"))), cfg)
+        x = affine(conv(t, W(f"{b}/conv2"), dtype), bn_pair(None, C, bias(f"{b}/conv2"))) + x
+    fin = bn_pair("fin-bn", C)
     f = activate(affine(x, fin), cfg)
     H, Wd = x.shape[1:3]
     maps = []
     for j, (h, w) in enumerate(map_sizes(cfg, H, Wd)):
         r = f if (h, w) == (H, Wd) else resize(f, h, w, dtype)
-        maps.append(affine(conv(r, W(f"score_conv_{j}"), dtype), bn_pair(weights, "none", 1, eps, bias(f"score_conv_{j}")))[..., 0])
-    raw = affine(conv(f, W("ori_conv"), dtype), bn_pair(weights, "none", 2, eps, bias("ori_conv")))
+        maps.append(affine(conv(r, W(f"score_conv_{j}"), dtype), bn_pair(None, 1, bias(f"score_conv_{j}")))[..., 0])
+    raw = affine(conv(f, W("ori_conv"), dtype), bn_pair(None, 2, bias("ori_conv")))
     ss = raw[..., :1] * raw[..., :1] + raw[..., 1:] * raw[..., 1:]
     unit = raw * (dtype(1.0) / np.sqrt(np.maximum(ss, dtype(1e-12))))
     return maps, raw, unit
@@ -165,10 +152,6 @@ def error(maps, unit, maps64, raw64, unit64):
 
 
 # ---- seeded models and photos on int8 levels ----------------------------------------------------------------------------
-
-def levels(q, mult):
-    return (np.asarray(q).astype(np.float32) * np.float32(mult)).astype(np.float32)
-
 
 def layer_shapes(cfg):
     """(name, weight shape, batch-norm name or None) of every convolution and (None, None, name) of every free-standing batch norm,
@@ -200,19 +183,8 @@ def make_model(seed, cfg, perform_bn=True, use_bias=True, big_beta=False):
             elif use_bias:
                 q[f"{SCOPE}/{name}/biases"] = (rs.integers(-127, 128, n).astype(np.int8), np.float32(1.0 / 512.0))
         if bn and perform_bn:
-            free = name is None
-            q[f"{SCOPE}/{bn}/gamma"] = (rs.integers(64, 128, C).astype(np.int8), np.float32(0.01))
-            if free and big_beta:
-                q[f"{SCOPE}/{bn}/beta"] = ((rs.integers(64, 128, C) * rs.choice([-1, 1], C)).astype(np.int8), np.float32(1.0 / 128.0))
-            else:
-                q[f"{SCOPE}/{bn}/beta"] = (rs.integers(-127, 128, C).astype(np.int8), np.float32(1.0 / 512.0))
-            q[f"{SCOPE}/{bn}/moving_mean"] = (rs.integers(-127, 128, C).astype(np.int8), np.float32(1.0 / 512.0))
-            q[f"{SCOPE}/{bn}/moving_variance"] = (rs.integers(32, 128, C).astype(np.int8), np.float32(1.0 / 64.0))
+            q.update((f"{SCOPE}/{bn}/{k}", v) for k, v in bn_levels(rs, C, big_beta and name is None).items())
     return q
-
-
-def model_weights(q):
-    return {name: levels(*v) for name, v in q.items()}
 
 
 def make_photos(seed, n, H, W):
@@ -235,6 +207,4 @@ def load_golden():
 
 def group_model(z, name):
     """The stored model and photos of a group as fp32: (weights, photos [n, H, W])."""
-    pre = f"{name}/"
-    w = {k[len(pre):]: levels(z[k], z[k + "@mult"]) for k in z.files if k.startswith(pre + SCOPE) and not k.endswith("@mult")}
-    return w, levels(z[f"{name}/photos"], z[f"{name}/photos@mult"])
+    return N.group_model(z, name, SCOPE, "photos")

@@ -3,12 +3,16 @@ the reference's own numbers (tests/golden/lfnet_desc/lfnet_desc_reference.npz, m
 tests/golden/make_lfnet_desc_golden.py) within the stored bars, TensorFlow's SAME rule and the flatten order by hand, every
 BTBA_EINVAL that is decided before any GPU work, from_npz's missing-name error and the struct sizes.  No GPU."""
 import ctypes as C
+import itertools
+import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
 
 import lfnet_desc_ref as R
+import lfnet_net_ref
 from bundletrack_amd import _lib, lfnet_desc
 
 
@@ -40,6 +44,17 @@ def test_fp64_restatement_meets_the_reference_under_the_stored_bars(golden):
         else:
             assert np.array_equal(d64, r64)
     assert n == 15
+
+
+def test_the_seeds_reproduce_the_stored_levels(golden):
+    for g, (name, over, (perform_bn, use_bias), m) in enumerate(R.GROUPS):
+        cfg = R.config(**over)
+        q = dict(R.make_model(R.MODEL_SEED + g, cfg, perform_bn, use_bias), patches=R.make_patches(R.PATCH_SEED + g, m, cfg["patch_size"]))
+        stored = {k for k in golden.files if k.startswith(f"{name}/{R.SCOPE}/") and not k.endswith("@mult")} | {f"{name}/patches"}
+        assert stored == {f"{name}/{k}" for k in q}
+        for k, (lv, mult) in q.items():
+            got, got_mult = golden[f"{name}/{k}"], golden[f"{name}/{k}@mult"]
+            assert got.dtype == np.int8 and got_mult.dtype == np.float32 and np.array_equal(got, lv) and got_mult == mult, (name, k)
 
 
 def test_a_wrong_padding_rule_or_flatten_order_is_far_outside_the_bars(golden):
@@ -193,6 +208,74 @@ def test_create_rejects_bad_arguments_before_any_gpu_work():
     W, keep = _host_weights(cfg0)
     keep["SimpleDesc/bn2/moving_variance"][3] = 0.0
     assert create(W=W, bn_eps=0.0) == E
+
+
+def test_weights_layer_verdicts_and_fold_bits_under_sanitizers(tmp_path):
+    """bundletrack_amd/csrc/btba_lfnet_weights.hpp alone, in tests/cpp/lfnet_weights_host.cpp built with AddressSanitizer and
+    UBSan: the verdicts of lfnet_conv_ok and lfnet_bn_ok are the rules of include/btba.h, lfnet_fold's bits are float32 of
+    lfnet_net_ref.fold, and the sanitizers report nothing (the arrays are heap blocks of exactly N, or K * N, floats)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "lfnet_weights_host")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                           "-I", os.path.join(root, "include"), os.path.join(root, "tests", "cpp", "lfnet_weights_host.cpp"), "-o", exe])
+    names = ("weights", "biases") + lfnet_net_ref.BN
+    K = 9
+    cases = []                                              # (N, eps, {array name: float32 array})
+
+    def arrays(N, have, seed):
+        rs = np.random.default_rng(seed)
+        a = dict(weights=rs.standard_normal(K * N), biases=rs.standard_normal(N), gamma=rs.uniform(0.5, 1.5, N), beta=rs.standard_normal(N),
+                 moving_mean=rs.standard_normal(N), moving_variance=rs.uniform(0.5, 2.0, N))
+        return {k: v.astype(np.float32) for k, v in a.items() if k in have}
+
+    bn_sets = (lfnet_net_ref.BN, ("moving_mean", "moving_variance"), ())
+    for N, bn, bias in itertools.product((16, 2), bn_sets, (True, False)):
+        have = ("weights",) + (("biases",) if bias else ()) + tuple(bn)
+        cases.append((N, 1e-5, arrays(N, have, len(cases))))
+        for name in have:                                   # one NaN in the last element of each array in turn
+            a = arrays(N, have, len(cases))
+            a[name][-1] = np.nan
+            cases.append((N, 1e-5, a))
+    for N in (16, 2):
+        a = arrays(N, names, len(cases))
+        a["moving_variance"][-1] = 0.0                      # variance + eps == 0, with and without an eps
+        cases.append((N, 0.0, a))
+        a = arrays(N, names, len(cases))
+        a["moving_variance"][-1] = -np.float32(1e-5)
+        cases.append((N, 1e-5, a))
+        for only in ("moving_mean", "moving_variance"):     # one moving array without the other
+            cases.append((N, 1e-5, arrays(N, ("weights", "biases", "gamma", "beta", only), len(cases))))
+        cases.append((N, 1e-5, arrays(N, names[1:], len(cases))))      # no weights
+    assert len(cases) == 2 * (27 + 5)                      # per size: 6 layouts and a NaN per array of each, 5 refusals more
+
+    bits = lambda a: " ".join(f"{b:08x}" for b in np.asarray(a, np.float32).reshape(-1).view(np.uint32))
+    text = "".join(f"{K} {N} {bits(eps)} " + " ".join(str(int(k in a)) for k in names) + " " + " ".join(bits(a[k]) for k in names if k in a) + "\n"
+                   for N, eps, a in cases)
+    run = subprocess.run([exe], input=text, capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", (run.returncode, run.stderr[-2000:])
+    lines = run.stdout.splitlines()
+    assert len(lines) == len(cases)
+    n_ok = 0
+    for (N, eps, a), line in zip(cases, lines):
+        finite = lambda k: bool(np.isfinite(a[k]).all())
+        conv_ok = "weights" in a and finite("weights") and ("biases" not in a or finite("biases"))
+        bn_ok = ("moving_mean" in a) == ("moving_variance" in a)
+        if bn_ok and "moving_mean" in a:
+            bn_ok = all(finite(k) for k in lfnet_net_ref.BN if k in a) and \
+                bool((a["moving_variance"].astype(np.float64) + np.float64(np.float32(eps)) > 0.0).all())
+        words = line.split()
+        assert (int(words[0]), int(words[1])) == (int(conv_ok), int(bn_ok)), (N, eps, sorted(a), line[:40])
+        if not bn_ok:
+            assert len(words) == 2
+            continue
+        got = np.array([int(w, 16) for w in words[2:]], np.uint32).view(np.float32).reshape(2, N)
+        w = {f"S/bn/{k}": a[k] for k in lfnet_net_ref.BN if k in a}
+        want = np.stack(lfnet_net_ref.fold(w, "S", "bn", N, eps, a.get("biases"))).astype(np.float32)
+        np.testing.assert_array_equal(got, want)           # NaN (a refused bias) equals NaN
+        if conv_ok:
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (N, eps, sorted(a))
+            n_ok += 1
+    assert n_ok == 2 * 3 * 2                                # every accepted layout at both sizes
 
 
 def test_descriptors_rejects_bad_arguments_before_any_gpu_work():

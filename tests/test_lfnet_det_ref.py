@@ -44,6 +44,16 @@ def test_restatement_meets_the_reference_under_the_stored_bars(golden):
         assert np.abs(np.sqrt((u64 ** 2).sum(-1)) - 1.0).max() < 1e-12
 
 
+def test_the_seeds_reproduce_the_stored_levels(golden):
+    for g, (name, over, (perform_bn, use_bias), (n, H, W), big_beta) in enumerate(R.GROUPS):
+        q = dict(R.make_model(R.MODEL_SEED + g, R.config(**over), perform_bn, use_bias, big_beta), photos=R.make_photos(R.PHOTO_SEED + g, n, H, W))
+        stored = {k for k in golden.files if k.startswith(f"{name}/{R.SCOPE}/") and not k.endswith("@mult")} | {f"{name}/photos"}
+        assert stored == {f"{name}/{k}" for k in q}
+        for k, (lv, mult) in q.items():
+            got, got_mult = golden[f"{name}/{k}"], golden[f"{name}/{k}@mult"]
+            assert got.dtype == np.int8 and got_mult.dtype == np.float32 and np.array_equal(got, lv) and got_mult == mult, (name, k)
+
+
 def test_pad_size_map_sizes_and_scale_factors_are_the_reference_runs(golden):
     for name, over, _, (n, H, W), _ in R.GROUPS:
         cfg = R.config(**over)

@@ -1,5 +1,5 @@
-"""Where a PCG step of k_solve_small goes (developer build -DBTBA_SOLVE_PCG_STAMPS from the sources with
-`git apply scripts/dev/pcg_stamps.patch` applied: the trace's eight clock slots = seven points inside step 1, wave 0's view).
+"""Where a PCG step of k_solve_small / k_solve_mid goes (developer build -DBTBA_SOLVE_PCG_STAMPS from the sources with
+`git apply scripts/dev/pcg_stamps.patch` applied -- it stamps pcg() of btba_solve_phases.hpp: the trace's eight clock slots = seven points inside step 1, wave 0's view).
     BTBA_LIB_PATH=build/ab/pcg_stamps.so python scripts/dev/pcg_stamps.py"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

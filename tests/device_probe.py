@@ -1,6 +1,6 @@
 """Build and load tests/hip/libbtba_probe.so (tests/hip/btba_probe.hip): the product's device functions, one element per thread.
 
-Staleness rule of the tests/cpp drivers: rebuilt when it is missing or older than its sources (the probe, the two product headers and
+Staleness rule of the tests/cpp drivers: rebuilt when it is missing or older than its sources (the probe, the product headers it includes and
 the flags in bundletrack_amd/_lib.py) and hipcc is on PATH; otherwise the existing file is used; neither possible is an error."""
 import ctypes as C
 import os
@@ -12,7 +12,7 @@ from bundletrack_amd import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hip", "btba_probe.hip")
 SO = os.path.join(HERE, "hip", "libbtba_probe.so")
-DEPS = [SRC, os.path.join(_lib.SRC_DIR, "btba_device.hpp"), os.path.join(_lib.SRC_DIR, "btba_svd3.hpp"), os.path.abspath(_lib.__file__)]
+DEPS = [SRC] + [os.path.join(_lib.SRC_DIR, h) for h in ("btba_device.hpp", "btba_svd3.hpp", "btba_solve_phases.hpp", "btba_kernels.hpp")] + [os.path.abspath(_lib.__file__)]
 
 # name -> argument types (device pointers as c_void_p); every launcher returns the hipError_t
 SIGNATURES = {
@@ -24,6 +24,7 @@ SIGNATURES = {
     "probe_div": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
     "probe_sqrt": [C.c_int, C.c_void_p, C.c_void_p, C.c_int],
     "probe_mat_inverse": [C.c_void_p, C.c_void_p, C.c_int],
+    "probe_inverse16": [C.c_int, C.c_void_p, C.c_void_p, C.c_int],
     "probe_huber_weight": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
     "probe_sincos": [C.c_void_p, C.c_void_p, C.c_int],
     "probe_sweep": [C.c_int, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],

@@ -2,14 +2,14 @@
 //
 // It includes the product headers unchanged and is compiled with the flags of libbtba.so (bundletrack_amd/_lib.py: HIPCC_FLAGS),
 // so every function below runs exactly as the kernels run it.  Nothing is restated here: each kernel calls one product function
-// per element (one wave per case for the reductions).  The one composition is the solver's update of btba_solve_small.hpp
-// (phase 4): Log(Exp(delta) C) with C = Exp(x) whose last row is reset to constants.
+// per element (one wave per case for the reductions, sixteen lanes per matrix for the solve kernels' inverse).
 //
 // Every launcher takes device pointers (torch tensors on cuda:0), launches, synchronises and returns the hipError_t.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../bundletrack_amd/csrc/btba_device.hpp"
+#include "../../bundletrack_amd/csrc/btba_solve_phases.hpp"
 #include "../../bundletrack_amd/csrc/btba_svd3.hpp"
 
 using namespace btba;
@@ -18,8 +18,8 @@ using namespace btba;
 
 namespace {
 
-constexpr int kBlock = 256;
-inline unsigned n_blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+constexpr int kProbeBlock = 256;
+inline unsigned n_blocks(int64_t n) { return (unsigned)((n + kProbeBlock - 1) / kProbeBlock); }
 inline int finish() { hipError_t e = hipGetLastError(); if (e != hipSuccess) return (int)e; return (int)hipDeviceSynchronize(); }
 __device__ __forceinline__ int64_t gid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
@@ -64,19 +64,29 @@ template <bool F> __global__ void k_ln_rotation(const float *R, float *w, int n)
     for (int k = 0; k < 3; k++) w[3 * i + k] = o[k];
 }
 
-// d = (dW, dT) as the solver's delta record holds them per frame, x = (rot, trans): out = Log(Exp(dW, dT) Exp(x))
-template <bool F> __global__ void k_update(const float *d, const float *x, float *out, int n)
+// d = (dW, dT) as the solver's delta record holds them per frame, x = (rot, trans), T = Exp(x) from an earlier launch (as the solve kernels
+// find it): out = Log(Exp(dW, dT) Exp(x)) by their update_frame, which takes the delta as the PCG leaves it ([trans, rot]) and T from LDS
+template <bool F> __global__ void __launch_bounds__(kProbeBlock) k_update(const float *d, const float *x, const float *T, float *out, int n)
 {
+    __shared__ __attribute__((aligned(16))) float Tk[kProbeBlock][16];
     const int64_t i = gid();
     if (i >= n) return;
-    const float dW[3] = { d[6 * i], d[6 * i + 1], d[6 * i + 2] }, dT[3] = { d[6 * i + 3], d[6 * i + 4], d[6 * i + 5] };
-    const float xr[3] = { x[6 * i], x[6 * i + 1], x[6 * i + 2] }, xt[3] = { x[6 * i + 3], x[6 * i + 4], x[6 * i + 5] };
-    const Mat4 U = pose_to_matrix<F>(dW, dT);
-    Mat4 C = pose_to_matrix<F>(xr, xt);
-    C.m[12] = 0.0f; C.m[13] = 0.0f; C.m[14] = 0.0f; C.m[15] = 1.0f;
-    float rot[3], trans[3];
-    matrix_to_pose<F>(mat_mul(U, C), rot, trans);
+    for (int k = 0; k < 16; k++) Tk[threadIdx.x][k] = T[16 * i + k];
+    const float dk[6] = { d[6 * i + 3], d[6 * i + 4], d[6 * i + 5], d[6 * i], d[6 * i + 1], d[6 * i + 2] };
+    float rot[3] = { x[6 * i], x[6 * i + 1], x[6 * i + 2] }, trans[3] = { x[6 * i + 3], x[6 * i + 4], x[6 * i + 5] };
+    update_frame<F>(true, dk, Tk[threadIdx.x], rot, trans);
     for (int k = 0; k < 3; k++) { out[6 * i + k] = rot[k]; out[6 * i + 3 + k] = trans[k]; }
+}
+
+// matrix c on lanes 16 c .. 16 c + 15: lane e writes entry e of its inverse
+template <bool F> __global__ void __launch_bounds__(kProbeBlock) k_inverse16(const float *M, float *out, int n)
+{
+    __shared__ __attribute__((aligned(16))) float m[kProbeBlock];
+    const int64_t i = gid(), last = 16 * (int64_t)n - 1;
+    m[threadIdx.x] = M[i < last ? i : last];                  // (the groups behind the last matrix run along and store nothing)
+    __syncthreads();
+    const float v = inverse_on_sixteen_lanes<F>(m + (threadIdx.x & ~15u), threadIdx.x);
+    if (i <= last) out[i] = v;
 }
 
 __global__ void k_mat_inverse(const float *M, float *out, int n)
@@ -222,35 +232,54 @@ template <int NV> __global__ void __launch_bounds__(256) k_block_reduce(const fl
 }  // namespace
 
 // ---- launchers ----------------------------------------------------------------------------------------------------
-#define PROBE_F(kernel, ...) do { if (fast) hipLaunchKernelGGL(kernel<true>, dim3(n_blocks(n)), dim3(kBlock), 0, 0, __VA_ARGS__); \
-                                  else hipLaunchKernelGGL(kernel<false>, dim3(n_blocks(n)), dim3(kBlock), 0, 0, __VA_ARGS__); } while (0)
+#define PROBE_F(kernel, ...) do { if (fast) hipLaunchKernelGGL(kernel<true>, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, __VA_ARGS__); \
+                                  else hipLaunchKernelGGL(kernel<false>, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, __VA_ARGS__); } while (0)
 
 PROBE_API int probe_pose_to_matrix(int fast, const float *x, float *M, int n) { if (n <= 0) return 0; PROBE_F(k_pose_to_matrix, x, M, n); return finish(); }
 PROBE_API int probe_matrix_to_pose(int fast, const float *M, float *x, int n) { if (n <= 0) return 0; PROBE_F(k_matrix_to_pose, M, x, n); return finish(); }
 PROBE_API int probe_exp_rotation(int fast, const float *w, float *R, int n) { if (n <= 0) return 0; PROBE_F(k_exp_rotation, w, R, n); return finish(); }
 PROBE_API int probe_ln_rotation(int fast, const float *R, float *w, int n) { if (n <= 0) return 0; PROBE_F(k_ln_rotation, R, w, n); return finish(); }
-PROBE_API int probe_update(int fast, const float *d, const float *x, float *out, int n) { if (n <= 0) return 0; PROBE_F(k_update, d, x, out, n); return finish(); }
+PROBE_API int probe_update(int fast, const float *d, const float *x, float *out, int n)
+{
+    if (n <= 0) return 0;
+    float *T = nullptr;                                      // Exp(x), by a launch of its own
+    hipError_t e = hipMalloc(&T, (size_t)n * 16 * sizeof(float));
+    if (e != hipSuccess) return (int)e;
+    PROBE_F(k_pose_to_matrix, x, T, n);
+    PROBE_F(k_update, d, x, T, out, n);
+    const int rc = finish();
+    hipFree(T);
+    return rc;
+}
 PROBE_API int probe_div(int fast, const float *a, const float *b, float *out, int n) { if (n <= 0) return 0; PROBE_F(k_div, a, b, out, n); return finish(); }
 PROBE_API int probe_sqrt(int fast, const float *x, float *out, int n) { if (n <= 0) return 0; PROBE_F(k_sqrt, x, out, n); return finish(); }
+
+PROBE_API int probe_inverse16(int fast, const float *M, float *out, int n_mat)
+{
+    if (n_mat <= 0) return 0;
+    const int64_t n = 16 * (int64_t)n_mat;
+    PROBE_F(k_inverse16, M, out, n_mat);
+    return finish();
+}
 
 PROBE_API int probe_mat_inverse(const float *M, float *out, int n)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_mat_inverse, dim3(n_blocks(n)), dim3(kBlock), 0, 0, M, out, n);
+    hipLaunchKernelGGL(k_mat_inverse, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, M, out, n);
     return finish();
 }
 
 PROBE_API int probe_huber_weight(const float *e, const float *delta, float *out, int n)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_huber, dim3(n_blocks(n)), dim3(kBlock), 0, 0, e, delta, out, n);
+    hipLaunchKernelGGL(k_huber, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, e, delta, out, n);
     return finish();
 }
 
 PROBE_API int probe_sincos(const float *x, float *out, int n)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_sincos, dim3(n_blocks(n)), dim3(kBlock), 0, 0, x, out, n);
+    hipLaunchKernelGGL(k_sincos, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, x, out, n);
     return finish();
 }
 
@@ -258,28 +287,28 @@ PROBE_API int probe_sincos(const float *x, float *out, int n)
 PROBE_API int probe_sweep(int which, uint32_t lo_bits, int64_t n, const float *xs, unsigned *stat, float *bad, int n_bad)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_sweep, dim3(n_blocks(n)), dim3(kBlock), 0, 0, which, lo_bits, n, xs, stat, bad, n_bad);
+    hipLaunchKernelGGL(k_sweep, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, which, lo_bits, n, xs, stat, bad, n_bad);
     return finish();
 }
 
 PROBE_API int probe_rsqrt(int refined, const float *x, float *out, int n)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_rsqrt, dim3(n_blocks(n)), dim3(kBlock), 0, 0, refined, x, out, n);
+    hipLaunchKernelGGL(k_rsqrt, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, refined, x, out, n);
     return finish();
 }
 
 PROBE_API int probe_svd(const float *A, float *U, float *s, float *V, int n)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_svd, dim3(n_blocks(n)), dim3(kBlock), 0, 0, A, U, s, V, n);
+    hipLaunchKernelGGL(k_svd, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, A, U, s, V, n);
     return finish();
 }
 
 PROBE_API int probe_procrustes(const float *src4, const float *dst4, const int *off, float *pose16, int *ok, int n)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_procrustes, dim3(n_blocks(n)), dim3(kBlock), 0, 0, (const float4 *)src4, (const float4 *)dst4, off, pose16, ok, n);
+    hipLaunchKernelGGL(k_procrustes, dim3(n_blocks(n)), dim3(kProbeBlock), 0, 0, (const float4 *)src4, (const float4 *)dst4, off, pose16, ok, n);
     return finish();
 }
 

@@ -3,7 +3,7 @@
 - SE(3) (btba_device.hpp), both flavours of division and square root: every output component within A e_oracle + B ulp(scale) of the
   float64 truth (tests/se3_ref.py), e_oracle being the CPU oracle's own error (the oracle is bit-exact with the reference).
 - The bit-for-bit claims of the comments: sincosf = sinf / cosf, se3_sqrt(x / 4) = se3_sqrt(x) / 2, v_rcp_f32 / v_sqrt_f32 within 1 ulp,
-  huber_weight = the oracle's, mat_inverse within a few ulps.
+  huber_weight = the oracle's, mat_inverse and the solve kernels' sixteen-lane inverse within a few ulps.
 - The 3x3 approximate SVD and procrustes (btba_svd3.hpp): the device build equal to the host build, bit for bit, and to the
   reference's own procrustesKernel where oracle/_ref/libbtba_ref_ransac.so exists.
 - The wave64 reductions: bit-exact against a float32 restatement of the documented DPP / permlane tree.
@@ -349,6 +349,32 @@ def test_mat_inverse(probe, oracle):
     rel = np.abs(got - inv).max((1, 2)) / (np.abs(inv).max((1, 2)) * kappa * 2.0 ** -24)
     print(f"mat_inverse on general 4x4 (cond up to {kappa.max():.1e}): worst max|err| / (cond eps max|inv|) = {rel.max():.2f}")
     assert rel.max() <= 64          # the CPU oracle (the same cofactor formula, no contraction) measures 29 on these inputs
+
+
+INVERSE16_FAST_ULPS = 6.0           # twice the measured worst, 3.00 (the IEEE flavour measures 3.00 as well)
+
+
+@pytest.fixture(scope="module")
+def exp_inverse_cases(oracle):
+    """test_mat_inverse's Exp-output cases: the matrices, the oracle's inverses, max(1, |t|)"""
+    _, rot, trans = _se3_cases(14)
+    M = _oracle_exp(oracle, rot, trans)
+    want = np.stack([oracle.mat4_inverse(m) for m in M])
+    return M, want, np.maximum(1.0, np.linalg.norm(trans, axis=1))[:, None, None]
+
+
+@pytest.mark.parametrize("fast", [0, 1])
+def test_inverse_on_sixteen_lanes(probe, exp_inverse_cases, fast):
+    """The solve kernels' inverse (btba_solve_phases.hpp: one adjugate entry per lane, sixteen lanes per matrix) against the oracle's
+    float4x4::getInverse.  IEEE flavour: test_mat_inverse's bar.  Fast flavour (the kernels' default): 1 / det is v_rcp_f32, 1 ulp off
+    in every entry."""
+    M, want, scale = exp_inverse_cases
+    n = len(M)
+    out = _empty(n, 16)
+    _call(probe.probe_inverse16, fast, _dev(M.reshape(n, 16)), out, n)
+    ulps = np.abs(out.cpu().numpy().reshape(n, 4, 4).astype(np.float64) - want) / _ulp(scale)
+    print(f"inverse_on_sixteen_lanes<{'fast' if fast else 'ieee'}> on Exp outputs: worst {ulps.max():.2f} ulps of max(1, |t|) from the oracle")
+    assert ulps.max() <= (INVERSE16_FAST_ULPS if fast else 4)
 
 
 # ---- the 3x3 SVD: device build = host build -----------------------------------------------------------------------

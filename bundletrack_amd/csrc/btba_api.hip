@@ -12,6 +12,8 @@
 
 #include "btba_host_common.hpp"
 #include "btba_kernels.hpp"
+#include "btba_solve_general.hpp"
+#include "btba_chain.hpp"
 #include "btba_solve_small.hpp"
 #include "btba_solve_mid.hpp"
 
@@ -518,7 +520,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
         ws->dense_pairs_frames = N;
     }
     // tables of k_system_solve that depend on the window size only: canonical pair p -> (i << 8 | j), then the 72
-    // descriptors of the sparse 6x6 block entries (btba_kernels.hpp: sparse_entry_descriptor)
+    // descriptors of the sparse 6x6 block entries (btba_solve_general.hpp: sparse_entry_descriptor)
     if (ws->solve_tab_frames != N) {
         const size_t lut16 = ((size_t)P + 288 + 3) & ~(size_t)3;           // a second, 16-byte aligned copy of the descriptors (k_solve_small loads them as int4)
         std::vector<int32_t> tab(lut16 + 288);
@@ -579,13 +581,13 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     D.trace_record = L.record_floats; D.tr_x = L.off_x; D.tr_T = L.off_T; D.tr_rhs = L.off_rhs; D.tr_prec = L.off_precond;
     D.tr_pcg = L.off_pcg; D.tr_delta = L.off_delta; D.tr_dpair = L.off_dense_pair; D.tr_A = L.off_A; D.tr_clk = L.off_clk;
 
-    const size_t n = 6 * (size_t)N, ld = 4 * (((n + 3) / 4) | 1);
+    const size_t n = 6 * (size_t)N, ld = (size_t)solve_row_floats(N);
     // the 6N x 6N matrix lives in the CU's LDS when it fits (N <= BTBA_MAX_FRAMES_LDS with the default pair list); larger
     // windows (up to the reference's 85 frames) keep it in an L2-resident global scratch and run the multi-wave PCG
-    const size_t lds_rest = (6 * ld + 16 + 16 * (size_t)N + 4 * (size_t)D.n_dense_pairs + (size_t)N + 1 + (size_t)P + 288 + (((size_t)P + 3) & ~(size_t)3) + ((6 * (size_t)N + 3) & ~(size_t)3)) * sizeof(float);
+    // (the layout of k_system_solve's LDS: btba_solve_layout.hpp)
     const size_t lds_limit = 160 * 1024;
-    const bool a_global = n * ld * sizeof(float) + lds_rest > lds_limit;
-    const size_t lds_core = (a_global ? 0 : n * ld * sizeof(float)) + lds_rest;
+    const bool a_global = sizeof(float) * SolveLayout(N, D.n_dense_pairs, false, false).total > lds_limit;
+    const size_t lds_core = sizeof(float) * SolveLayout(N, D.n_dense_pairs, a_global, false).total;
     const size_t lds_pairs = ((size_t)P * kSparseVals + (size_t)D.n_dense_pairs * kDenseVals) * sizeof(float);
     D.pairsum_in_lds = (lds_core + lds_pairs <= 64 * 1024) ? 1 : 0;   // keep two workgroups per CU when it fits
     if (!D.pairsum_in_lds && lds_core + lds_pairs <= lds_limit && B <= 256) D.pairsum_in_lds = 1;
@@ -646,7 +648,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
         HIP_TRY(hipMemsetAsync(ws->dense_part.p, 0, sizeof(float) * (size_t)B * (Pd > 0 ? Pd : 1) * kDenseVals, ws->stream));
     }
     const bool compaction = use_zn && use_dense && (prm->flags & BTBA_FLAG_COMPACTION);
-    // The chained launch (btba_kernels.hpp: k_chain): all Gauss-Newton iterations in ONE launch, the system solves handed over inside it.
+    // The chained launch (btba_chain.hpp: k_chain): all Gauss-Newton iterations in ONE launch, the system solves handed over inside it.
     // Same sums in the same order as the plain schedule; taken for the batches it pays for and the configurations it is written for.
     const int chain_lay = zn_layout == 1 ? (compaction ? 3 : 1) : 0;
     // Only on request (BTBA_OPT_CHAIN = 1).  Measured at c3 x 32 on one box (profiles/r04/chain_experiments.json): the chained launch with two tiles
@@ -658,7 +660,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     const bool chain = chain_lay != 0 && !ws->chain_failed && ws->n_cus == 256 && ws->tune.chain > 0 && use_sparse && use_dense && !wsi && !wdi
                        && !trace && !atomic_sums && !a_global && !D.pre_assembled && N <= kChainMaxFrames && chunks <= kChainMaxParts && tiles <= kChainMaxParts
                        && !(prm->flags & (BTBA_FLAG_NO_FUSE | BTBA_FLAG_OVERLAP)) && !Z.frame_slot
-                       && lds_rest + 16 + sizeof(float) * chain_region_floats(N) <= kChainLdsBytes;      // (c3's 15 frames are the largest window whose solve fits a sweep workgroup's LDS share)
+                       && sizeof(float) * SolveLayout(N, D.n_dense_pairs, true, true).total <= kChainLdsBytes;      // (c3's 15 frames are the largest window whose solve fits a sweep workgroup's LDS share)
     // Fresh matches arrive as EntryJ (32 B, the wire format).  A solve reads them once per Gauss-Newton iteration; with BTBA_OPT_RELAYOUT the FIRST
     // iteration's sparse sweep writes 24-byte records as the entries pass by (SolveDims::corr24_out) and the other iterations stream those -- no separate
     // pack pass (btba_pack_correspondences24: 65 us + a launch at c3 x 32, 7 % of a step).  Measured (profiles/r04/relayout.json): the first launch's
@@ -796,7 +798,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     const size_t lut_bytes = sizeof(float) * (size_t)((Wd + Hd + 3) & ~3) + (zn_layout == 1 ? sizeof(float4) * (size_t)(Wd + Hd) : 0) + blist_bytes + (size_t)ws->tune.debug_lds_pad;         // coordinate look-up tables of the compact dense sweep (+ its list of live blocks)
     if (chain) {
         // ONE launch: 8 XCD sequences x n_gn iterations x (instances of the XCD) x (sweep items + 1 solve item)
-        const size_t chain_lds = std::max(lut_bytes, lds_rest + 16 + sizeof(float) * chain_region_floats(N));
+        const size_t chain_lds = std::max(lut_bytes, sizeof(float) * SolveLayout(N, D.n_dense_pairs, true, true).total);
         const unsigned per_inst = Cn.items_d + Cn.items_s + 1u;
         const unsigned grid = 8u * (unsigned)prm->n_gn_iters * Cn.inst_per_xcd * per_inst;
         if (!ws->tune.chain_trace_file.empty()) {          // developer: timeline of the launch (scripts/chain_trace.py)

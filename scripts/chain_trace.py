@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Workgroup timeline of ONE chained launch (btba_kernels.hpp: k_chain).  Run on the GPU box:
+"""Workgroup timeline of ONE chained launch (btba_chain.hpp: k_chain).  Run on the GPU box:
 
     BTBA_CHAIN_TRACE_FILE=gpurun_out/chain.bin python scripts/chain_trace.py [--masked] [--instances 32] [--out gpurun_out/chain_trace.json]
 

@@ -609,6 +609,38 @@ def test_edge_shapes_through_the_boundary(gpu, oracle):
     assert max(max(S.pose_error(poses_nodepth[k], p2[k])) for k in range(pb.n_frames)) < 2e-6
 
 
+def test_pre_assembled_system_loaded_back_into_lds(gpu, oracle):
+    """k_system_solve on a system that k_big_reduce + k_big_assemble built in the global scratch and whose matrix still fits LDS: it is
+    loaded back for the one-wave PCG.  The library's defaults send 22 ... 31 frames to k_solve_mid, and a traced solve keeps the assembly on
+    one workgroup, so only BTBA_OPT_SOLVE_SMALL = 0 without a trace takes this path.  N = 24, the smallest window it is taken for, on the
+    frames of the N = 31 case above (128 x 96 -> 32 x 24 cache, 12 matches per pair): against the oracle under that case's bar, and
+    against the same window assembled by the one workgroup under the bar of the N = 40 comparison above."""
+    Ks = S.NOCS_K.copy(); Ks[:2] *= 0.2
+    pb = S.make_problem(24, 12, seed=96, background=False, H=96, W=128, K=Ks, rot_step_deg=(5.0, 6.0))
+    d = [gpu.torch.from_numpy(pb.depth[k]).to(gpu.dev) for k in range(pb.n_frames)]
+    n = [gpu.torch.from_numpy(pb.normals[k]).to(gpu.dev) for k in range(pb.n_frames)]
+    caches = [oracle.build_cache(pb.depth[k], pb.normals[k], pb.K, pb.downscale) for k in range(pb.n_frames)]
+    ref = oracle.solve(np.stack([c["campos"] for c in caches]), np.stack([c["normals"] for c in caches]), caches[0]["intr"], pb.corr, pb.poses_init)
+    opt = gpu.OptimizerGpu(workspace=gpu.ws)
+    poses = {}
+    try:
+        gpu.ws.set_option(_lib.OPT_SOLVE_SMALL, 0)
+        for big in (1, 0):
+            gpu.ws.set_option(_lib.OPT_BIG_ASSEMBLY, big)
+            poses[big] = pb.poses_init.copy()
+            opt.optimizeFrames(pb.corr, None, pb.n_frames, pb.H, pb.W, d, None, n, poses[big], pb.K)
+    finally:
+        gpu.ws.set_option(_lib.OPT_BIG_ASSEMBLY, 1)
+        gpu.ws.set_option(_lib.OPT_SOLVE_SMALL, 1)
+    for big in (1, 0):
+        worst = max(max(S.pose_error(poses[big][k], ref.poses[k])) for k in range(pb.n_frames))
+        print(f"N=24, big assembly {big}: worst pose diff against the oracle {worst:.2e}")
+        assert np.isfinite(poses[big]).all() and worst < 5e-4, (big, worst)
+    d_paths = max(max(S.pose_error(poses[1][k], poses[0][k])) for k in range(pb.n_frames))
+    print(f"N=24: many-workgroup assembly vs one workgroup: worst pose diff {d_paths:.2e}")
+    assert 0 < d_paths < 5e-5 or np.array_equal(poses[1], poses[0]), d_paths
+
+
 def test_strided_tensors_are_refused(gpu):
     from bundletrack_amd.optimizer import _dev_ptr
     t = gpu.torch.zeros((4, 6, 8, 4), device=gpu.dev)

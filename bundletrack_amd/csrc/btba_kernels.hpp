@@ -317,22 +317,31 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
     for (int k = 0; k < kSparseVals; k++) acc[k] = 0.0f;
 
     const float delta2 = D.robust_delta * D.robust_delta;
-    auto accumulate = [&](bool valid, float pix, float piy, float piz, float pjx, float pjy, float pjz) {
-        const float m = valid ? 1.0f : 0.0f;
+    int n_valid = 0;                                  // valid entries of this WAVE (scalar register); joins the record as acc[0] behind the loop
+    // One correspondence.  all_valid (wave-uniform): every entry of the wave's trip is valid -- in real windows almost every trip -- and nothing is masked.
+    // Otherwise an invalid / out-of-range slot contributes exact zeros (its payload may be anything, even NaN) through the selects in the two blocks behind
+    // wave-uniform branches; with every entry valid those selects return their first operand, so both ways are the same arithmetic and the same bits.
+    // (The empty asm keeps each block a branch: speculated, its selects would run on every trip again.)
+    auto accumulate = [&](const bool all_valid, bool valid, float pix, float piy, float piz, float pjx, float pjy, float pjz) {
         float wix, wiy, wiz, wjx, wjy, wjz;
         xform_point(Ti, pix, piy, piz, wix, wiy, wiz);
         xform_point(Tj, pjx, pjy, pjz, wjx, wjy, wjz);
-        // an invalid / out-of-range slot contributes exact zeros (its payload may be anything, even NaN)
-        wix = m != 0.0f ? wix : 0.0f; wiy = m != 0.0f ? wiy : 0.0f; wiz = m != 0.0f ? wiz : 0.0f;
-        wjx = m != 0.0f ? wjx : 0.0f; wjy = m != 0.0f ? wjy : 0.0f; wjz = m != 0.0f ? wjz : 0.0f;
+        if (!all_valid) {
+            asm volatile("");
+            wix = valid ? wix : 0.0f; wiy = valid ? wiy : 0.0f; wiz = valid ? wiz : 0.0f;
+            wjx = valid ? wjx : 0.0f; wjy = valid ? wjy : 0.0f; wjz = valid ? wjz : 0.0f;
+        }
         const float rx = wix - wjx, ry = wiy - wjy, rz = wiz - wjz;
         const float e2 = rx * rx + ry * ry + rz * rz;
 #ifdef BTBA_EXACT_DIV
-        const float rho = m * ((e2 <= delta2) ? 1.0f : D.robust_delta / sqrtf(e2));
+        float rho = (e2 <= delta2) ? 1.0f : D.robust_delta / sqrtf(e2);
 #else
-        const float rho = m * ((e2 <= delta2) ? 1.0f : D.robust_delta * __builtin_amdgcn_rsqf(e2));
+        float rho = (e2 <= delta2) ? 1.0f : D.robust_delta * __builtin_amdgcn_rsqf(e2);
 #endif
-        acc[0] += m;
+        if (!all_valid) {
+            asm volatile("");
+            rho = valid ? rho : 0.0f;                 // (a masked slot has e2 = 0: rho was 1)
+        }
         acc[1] += wix; acc[2] += wiy; acc[3] += wiz;
         acc[4] += wjx; acc[5] += wjy; acc[6] += wjz;
         acc[7] += wix * wix; acc[8] += wix * wiy; acc[9] += wix * wiz; acc[10] += wiy * wiy; acc[11] += wiy * wiz; acc[12] += wiz * wiz;
@@ -347,6 +356,15 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
         acc[38] += rho * (wiy * wiy + wiz * wiz); acc[39] += rho * (wix * wix + wiz * wiz); acc[40] += rho * (wix * wix + wiy * wiy);
         acc[41] += rho * (wjy * wjy + wjz * wjz); acc[42] += rho * (wjx * wjx + wjz * wjz); acc[43] += rho * (wjx * wjx + wjy * wjy);
     };
+    // One trip's two correspondences.  The count is a popcount of the two valid masks (the ballots of single comparisons, AND-ed in scalar registers).
+    auto accumulate_pair = [&](bool valid_a, bool live_b, bool valid_b, float ax, float ay, float az, float aX, float aY, float aZ,
+                               float bx, float by, float bz, float bX, float bY, float bZ) {
+        const unsigned long long ma = __builtin_amdgcn_ballot_w64(valid_a), mb = __builtin_amdgcn_ballot_w64(live_b) & __builtin_amdgcn_ballot_w64(valid_b);
+        n_valid += __popcll(ma) + __popcll(mb);
+        const bool all_valid = (ma & mb) == ~0ull;
+        accumulate(all_valid, valid_a, ax, ay, az, aX, aY, aZ);
+        accumulate(all_valid, live_b && valid_b, bx, by, bz, bX, bY, bZ);
+    };
     // two correspondences per lane per trip (entries e and e + 256: every load instruction of a wave covers consecutive entries), all of
     // their loads in flight together
     if (C24) {
@@ -359,14 +377,15 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
             const bool live2 = e2 < hi;
             const float2 *qa = cb + corr24_index(e_base + e), *qb = cb + corr24_index(e_base + (live2 ? e2 : e));
             const float2 a0 = ld_stream_f2<NT>(qa), a1 = ld_stream_f2<NT>(qa + 64), a2 = ld_stream_f2<NT>(qa + 128), b0 = ld_stream_f2<NT>(qb), b1 = ld_stream_f2<NT>(qb + 64), b2 = ld_stream_f2<NT>(qb + 128);
-            accumulate(__float_as_uint(a0.x) != 0xFFFFFFFFu, a0.x, a0.y, a1.x, a1.y, a2.x, a2.y);
-            accumulate(live2 && __float_as_uint(b0.x) != 0xFFFFFFFFu, b0.x, b0.y, b1.x, b1.y, b2.x, b2.y);
+            accumulate_pair(__float_as_uint(a0.x) != 0xFFFFFFFFu, live2, __float_as_uint(b0.x) != 0xFFFFFFFFu,
+                            a0.x, a0.y, a1.x, a1.y, a2.x, a2.y, b0.x, b0.y, b1.x, b1.y, b2.x, b2.y);
         }
     } else {
         const float4 *cb = corr + 2 * (size_t)b * D.corr_stride;
         bool misplaced = false;                       // an entry whose (imgIdx_i, imgIdx_j) is not this segment's pair
         float2 *const c24 = D.corr24_out;             // (wave-uniform) the re-layout of the first iteration: k_pack_corr24_batch's records, written as the entries pass by
         const size_t e_out = (size_t)D.corr_entry0 + (size_t)b * (size_t)D.corr_stride;
+        // the entry's order check and re-layout (its sums: accumulate_pair)
         auto entry = [&](const float4 &q0, const float4 &q1, bool live, uint32_t e) {
             // q0 = (imgIdx_i, imgIdx_j, pos_i.x, pos_i.y)  q1 = (pos_i.z, pos_j.x, pos_j.y, pos_j.z)
             const bool valid = live && __float_as_uint(q0.x) != 0xFFFFFFFFu;      // EntryJ::isValid
@@ -377,7 +396,6 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
                 o[64] = make_float2(q1.x, q1.y);
                 o[128] = make_float2(q1.z, q1.w);
             }
-            accumulate(valid, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w);
         };
         for (uint32_t e = lo + tid; e < hi; e += 2 * kBlock) {
             const uint32_t e2 = e + kBlock;
@@ -386,9 +404,12 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
             const float4 a0 = ld_stream_f4<NT>(cb + 2 * (size_t)e), a1 = ld_stream_f4<NT>(cb + 2 * (size_t)e + 1), b0 = ld_stream_f4<NT>(cb + 2 * (size_t)e2c), b1 = ld_stream_f4<NT>(cb + 2 * (size_t)e2c + 1);
             entry(a0, a1, true, e);
             entry(b0, b1, live2, e2c);
+            accumulate_pair(__float_as_uint(a0.x) != 0xFFFFFFFFu, live2, __float_as_uint(b0.x) != 0xFFFFFFFFu,
+                            a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w);
         }
         if (D.order_flag && misplaced) atomicOr(D.order_flag, 1);
     }
+    acc[0] = (tid & 63u) == 0u ? (float)n_valid : 0.0f;         // an integer far below 2^24: the float the per-lane counts summed to
     float *out = partials + ((unsigned)b * D.sp_stride + (unsigned)(D.atomic_sums ? p : p * D.sparse_chunks + chunk) * (unsigned)kSparseVals);
     block_reduce_store<kSparseVals, 4>(acc, red, out, D.atomic_sums ? 1 : D.publish ? 2 : 0);
 }
@@ -982,8 +1003,6 @@ template <int IMM> __device__ __forceinline__ float4 gather16_imm(const char *ba
 // arithmetic (exact below 2^24) instead of costing a vector add behind every float -> int conversion
 __device__ __forceinline__ unsigned lds_address(const void *p) { return (unsigned)(unsigned long)(const __attribute__((address_space(3))) char *)p; }
 __device__ __forceinline__ float2 lds_f32x2_abs(unsigned addr) { const __attribute__((address_space(3))) float *q = (const __attribute__((address_space(3))) float *)(unsigned long)addr; return make_float2(q[0], q[1]); }
-// opaque copy: keeps a value in a VGPR the compiler cannot see through
-__device__ __forceinline__ unsigned opaque_vgpr(unsigned x) { asm volatile("" : "+v"(x)); return x; }
 // v_min_f32 as the hardware does it: fminf() makes the compiler canonicalise its operands first (v_max_f32 x, x, x -- a half-rate
 // instruction per operand, repeated in the loop even for loop invariants); the operands here are never signalling NaNs
 __device__ __forceinline__ float min_raw(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -1209,6 +1228,7 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
     float acc[kDenseVals];
 #pragma unroll
     for (int k = 0; k < kDenseVals; k++) acc[k] = 0.0f;
+    int n_ok = 0;                                         // accepted pixels of this WAVE (scalar register); joins the record as acc[27] behind the walk
 
     const char *tap_row0 = reinterpret_cast<const char *>(zn_t), *tap_row1 = tap_row0 + C.row16;
     const float lut_addr_f = (float)lds_address(lut), ybase4_abs = C.ybase4 + lut_addr_f;
@@ -1227,7 +1247,9 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         const float u = qx * C.fx * rqz + C.cx, v = qy * C.fy * rqz + C.cy;
         const float uc = clamp0_s(u, C.wm1), vc = clamp0_s(v, C.hm1);      // NaN -> 0: addresses stay in the frame
         const bool valid = src_ok & (fabsf(u - uc) < 0.5f) & (fabsf(v - vc) < 0.5f);
-        if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return;
+        // (the wave's mask of `valid`, AND-ed from the ballots of the single tests: see ok_mask below)
+        const unsigned long long valid_mask = __builtin_amdgcn_ballot_w64(src_ok) & __builtin_amdgcn_ballot_w64(fabsf(u - uc) < 0.5f) & __builtin_amdgcn_ballot_w64(fabsf(v - vc) < 0.5f);
+        if (valid_mask == 0ull) return;
         // rotate the normal (only the waves that go on need it: half of the block trips end above)
         const float nqx = C.R[0] * zs.y + C.R[1] * zs.z + C.R[2] * zs.w;
         const float nqy = C.R[3] * zs.y + C.R[4] * zs.z + C.R[5] * zs.w;
@@ -1241,7 +1263,7 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         // Lanes that already failed the in-image / source-depth tests (8.8 % in the trips that go on, clustered along block edges: profiles/r06/sweep_census.json) issue no
         // taps.  The texture addresser's service time per gather is exposed almost in full (profiles/r06/bound_probes.json: one more 16-byte gather per trip = +13.4 us
         // per launch, linear) and it skips idle quads (profiles/r06/taps_exec.json: same bits, -1.5 % on the launch).  The registers of those lanes stay undefined
-        // and are never used: `ok` contains `valid`, and `keep` zeroes everything a rejected lane contributes (an AND: NaN-safe).
+        // and are never used: `ok` contains `valid`, and nothing behind `ok` runs for a rejected lane.
         float4 z00, z10, z01, z11;
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wconditional-uninitialized"
@@ -1269,36 +1291,41 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         const float dx = qx - cix, dy = qy - ciy, dz = qz - ciz;
         const float dist2 = fma_nd(dz, dz, fma_nd(dx, dx, dy * dy));
         const float dn = fma_nd(nqz, niz, fma_nd(nqx, nix, nqy * niy));
-        const bool ok = valid & ((__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits) & (dn >= C.normal_thresh) & (dist2 <= C.dist2_thresh);
-        // rejected pixels contribute exact zeros: AND with 0 / ~0 (one select, then 2-cycle v_and_b32; NaN-safe, unlike a multiply)
-        const unsigned keep = opaque_vgpr(ok ? 0xFFFFFFFFu : 0u);
-        auto masked = [keep](float x) { return __uint_as_float(__float_as_uint(x) & keep); };
-        // SIGNS: the row is accumulated as a+ = [n_i ; n_i x q] and the residual as res+ = (q - c_i) . n_i, i.e. a = D a+ with
-        // D = diag(-1, -1, -1, 1, 1, 1) and res = -res+ (SolverBundlingDenseUtil.h:78-110, LieDerivUtil.h:228-273).  Then S = D S+ D and
-        // g = -D g+ : exact sign changes of whole sums, applied once per workgroup in the epilogue instead of four negations per pixel.
-        const float res = masked(fma_nd(dz, niz, fma_nd(dx, nix, dy * niy)));
-        // Huber (SolverBundlingUtil.h:24-40) times the dense weight: rho' = 1 for e <= delta^2, delta / sqrt(e) above  <=>  min(1, delta rsq(e)).
-        // Not masked: a rejected pixel has res = 0, rsq(0) = inf, min(w, inf) = w -- finite, and it multiplies a masked (zero) row.
-        const float wgt = min_raw_s(C.wdelta * fast_rsq(res * res), C.w_dense);
-        const float mx = masked(nix), my = masked(niy), mz = masked(niz);
-        const float a[6] = { mx, my, mz, my * qz - mz * qy, mz * qx - mx * qz, mx * qy - my * qx };
-        int k = 0;
-        // acc += wa_r * a_c is a read-modify-write FMA: it issues at full rate only when its two multiplicands sit in VGPRs of
-        // different parity (profiles/r02/valu_calibration.md).  (wa_r, a_r) held as an aligned register PAIR puts every wa in an
-        // even and every a in an odd register, whatever the allocator does with the rest.
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        f2v pr[6];
+        // the accept mask of the wave, AND-ed from the ballots of the single tests (a ballot of one comparison is the comparison's own scalar result; the
+        // ballot of a combined flag is lowered through a select and a second compare)
+        const unsigned long long ok_mask = valid_mask & __builtin_amdgcn_ballot_w64((__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits)
+                                         & __builtin_amdgcn_ballot_w64(dn >= C.normal_thresh) & __builtin_amdgcn_ballot_w64(dist2 <= C.dist2_thresh);
+        // Rejected pixels contribute NOTHING: the count is a popcount of the wave's accept mask in a scalar register, and the residual, the weight, the row
+        // and the 27 accumulates run under the exec mask of `ok` like the taps above.  A sum that is not added to equals the sum that got + 0.0f (the
+        // accumulators start at + 0.0f and so never hold - 0.0f), so every sum keeps its bits; a rejected lane's blend -- undefined taps, a NaN or inf target
+        // normal -- is never read past `ok`.
+        n_ok += __popcll(ok_mask);
+        if (__builtin_amdgcn_inverse_ballot_w64(ok_mask)) {
+            // SIGNS: the row is accumulated as a+ = [n_i ; n_i x q] and the residual as res+ = (q - c_i) . n_i, i.e. a = D a+ with
+            // D = diag(-1, -1, -1, 1, 1, 1) and res = -res+ (SolverBundlingDenseUtil.h:78-110, LieDerivUtil.h:228-273).  Then S = D S+ D and
+            // g = -D g+ : exact sign changes of whole sums, applied once per workgroup in the epilogue instead of four negations per pixel.
+            const float res = fma_nd(dz, niz, fma_nd(dx, nix, dy * niy));
+            // Huber (SolverBundlingUtil.h:24-40) times the dense weight: rho' = 1 for e <= delta^2, delta / sqrt(e) above  <=>  min(1, delta rsq(e))
+            // (res = 0: rsq(0) = inf, min(inf, w) = w).
+            const float wgt = min_raw_s(C.wdelta * fast_rsq(res * res), C.w_dense);
+            const float a[6] = { nix, niy, niz, niy * qz - niz * qy, niz * qx - nix * qz, nix * qy - niy * qx };
+            int k = 0;
+            // acc += wa_r * a_c is a read-modify-write FMA: it issues at full rate only when its two multiplicands sit in VGPRs of
+            // different parity (profiles/r02/valu_calibration.md).  (wa_r, a_r) held as an aligned register PAIR puts every wa in an
+            // even and every a in an odd register, whatever the allocator does with the rest.
+            typedef float f2v __attribute__((ext_vector_type(2)));
+            f2v pr[6];
 #pragma unroll
-        for (int r = 0; r < 6; r++) { pr[r] = (f2v){ wgt * a[r], a[r] }; asm volatile("" : "+v"(pr[r])); }
-        f2v rr = (f2v){ wgt, res };
-        asm volatile("" : "+v"(rr));
+            for (int r = 0; r < 6; r++) { pr[r] = (f2v){ wgt * a[r], a[r] }; asm volatile("" : "+v"(pr[r])); }
+            f2v rr = (f2v){ wgt, res };
+            asm volatile("" : "+v"(rr));
 #pragma unroll
-        for (int r = 0; r < 6; r++) {
+            for (int r = 0; r < 6; r++) {
 #pragma unroll
-            for (int c = r; c < 6; c++) acc[k++] += pr[r].x * pr[c].y;
-            acc[21 + r] += pr[r].x * rr.y;
+                for (int c = r; c < 6; c++) acc[k++] += pr[r].x * pr[c].y;
+                acc[21 + r] += pr[r].x * rr.y;
+            }
         }
-        acc[27] += masked(1.0f);
     };
 
     if (WALK == 2) {
@@ -1385,6 +1412,8 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
             pixel(zs, 4u * ox, 4u * oy);                  // 4-byte table offsets -> 16-byte entries (rowB follows colA as the row table follows the column table)
         }
     }
+    // the wave's count, converted once: an integer far below 2^24 in one lane and zeros in the others fold to the float the per-lane counts summed to
+    acc[27] = (tid & 63u) == 0u ? (float)n_ok : 0.0f;
     float *out = partials + ((unsigned)b * D.dp_stride + (unsigned)(D.atomic_sums ? p : p * D.dense_tiles + tile) * (unsigned)kDenseVals);
     dense_epilogue<true>(acc, red, out, D.atomic_sums ? 1 : D.publish ? 2 : 0);
 }

@@ -755,9 +755,9 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     if (D.walk_blocks) {
         const int bw = Wd / 8, bh = Hd / 8;
         const size_t band_blocks = (size_t)((bh + tiles - 1) / tiles) * bw;
-        if (band_blocks > 1024) D.walk_blocks = 0;                               // very large caches: row strips (a band's blocks are tested by 4 x 256 lanes)
+        if (band_blocks > (size_t)kMaxBandBlocks) D.walk_blocks = 0;                               // very large caches: row strips (a band's blocks are tested by 4 x 256 lanes)
         else {
-            blist_bytes = 32 + sizeof(uint32_t) * band_blocks;
+            blist_bytes = 32 * (size_t)(bw + bh) + 32 + sizeof(uint32_t) * band_blocks;      // hull entries of the block columns and rows, wave totals, the list
             if (ws->tune.block_skip) {                                          // (off: every block is walked)
                 if (Z.block_ranges) D.block_ranges = reinterpret_cast<const float2 *>(Z.block_ranges);      // part of the caller's / the pool's frame cache
                 else if (!Z.frame_slot) {                                       // not given: one pass over the frames per solve

@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "btba_device.hpp"
+#include "btba_hull.hpp"
 
 namespace btba {
 
@@ -1025,75 +1026,10 @@ __device__ __forceinline__ float pinhole_lut_entry(const SolveDims &D, int e)
     return is_x ? D.zn_ki[0] * c + D.zn_ki[2] : D.zn_ki[5] * c + D.zn_ki[6];
 }
 
-// Is the 8 x 8 block (bxl, byg) of the source frame PROVABLY without a pixel that lands in the target image?  A block's pixels with a
-// usable depth lie in the frustum segment spanned by the block's extreme rays and its depth range [zlo, zhi] (k_block_ranges, clipped to
-// depth_min .. depth_max); the relative pose maps the segment to a convex polytope whose vertices are the 8 transformed corners, and while
-// every corner has q.z > 0 the projection (u, v) of any point inside lies within the corners' [min, max] in u and in v (a ratio of affine
-// functions is quasi-linear on a convex set where the denominator is positive).  If that range misses the image by more than a margin --
-// 0.01 pixel, three orders of magnitude above the rounding differences between this evaluation and the per-pixel one -- no pixel of the
-// block can pass the in-image test of SolverBundlingDenseUtil.h:91-94 and the block contributes exactly nothing, as in the reference.
-// Blocks without any usable depth go the same way.  (lut: the pinhole_lut_entry table; R, t: the relative pose.)
-__device__ __forceinline__ bool block_is_live(const SolveDims &D, const float (&R)[9], const float (&t)[3], float2 zr, int bxl, int byg)
-{
-    zr.x = fmaxf(zr.x, D.depth_min); zr.y = fminf(zr.y, D.depth_max);      // usable depths: depth_min < z < depth_max
-    bool live = zr.x <= zr.y;
-    if (live) {
-        // the block's extreme rays: column / row terms of its first and last column / row (the table entries, evaluated in place)
-        const float xa = pinhole_lut_entry(D, 8 * bxl), xb = pinhole_lut_entry(D, 8 * bxl + 7);
-        const float ya = pinhole_lut_entry(D, D.width + 8 * byg), yb = pinhole_lut_entry(D, D.width + 8 * byg + 7);
-        float ulo = INFINITY, uhi = -INFINITY, vlo = INFINITY, vhi = -INFINITY, zq = INFINITY;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float x = (k & 1) ? xb : xa, y = (k & 2) ? yb : ya;
-            const float rx = R[0] * x + R[1] * y + R[2], ry = R[3] * x + R[4] * y + R[5], rz = R[6] * x + R[7] * y + R[8];
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const float d = e ? zr.y : zr.x;
-                const float qx = rx * d + t[0], qy = ry * d + t[1], qz = rz * d + t[2];
-                const float rq = fast_rcp(qz);
-                const float u = qx * D.fx * rq + D.cx, v = qy * D.fy * rq + D.cy;
-                ulo = fminf(ulo, u); uhi = fmaxf(uhi, u); vlo = fminf(vlo, v); vhi = fmaxf(vhi, v); zq = fminf(zq, qz);
-            }
-        }
-        const float m = 0.01f;
-        const bool outside = (uhi < -0.5f - m) | (ulo > (float)D.width - 0.5f + m) | (vhi < -0.5f - m) | (vlo > (float)D.height - 0.5f + m);
-        live = !(zq > 1e-3f && outside);          // NaN anywhere: comparisons false, the block stays
-    }
-    return live;
-}
+constexpr int kMaxBandBlocks = 1024;      // blocks of one band of the block walk: above it solve_enqueue falls back to row strips (the band's index arithmetic below relies on it)
 
-// The same test from the workgroup's ROTATED-RAY tables (colA[x] = R[:, 0] lx(x), rowB[y] = R[:, 1] ly(y) + R[:, 2], filled for the pixel loop anyway) and
-// without a division.  A point q = d r + t of the block's hull, q.z > 0, projects left of the image by more than the margin m iff
-//     fx q.x / q.z + cx < -0.5 - m   <=>   fx q.x + (cx + 0.5 + m) q.z < 0   <=>   d alpha_L(r) + beta_L < 0,   alpha_L = fx r.x + c_L r.z,  beta_L = fx t.x + c_L t.z,
-// a LINEAR form in d for a fixed ray, so over the block's depth range it peaks at one of the two ends; likewise for the other three image edges.  The
-// block is outside iff one of the four forms keeps its sign over all 4 corner rays x 2 depths: per ray 3 adds, 2 + 4 multiply-adds for the alphas, 8 products
-// and 8 min / max instead of 2 x (9 multiply-adds, a reciprocal, 4 operations for (u, v) and 5 min / max) -- and no table entries recomputed per lane.
-// 220 -> ~120 instructions of a workgroup's ~400-instruction prologue.  Same margin (0.01 pixel), same verdicts up to rounding far inside it.
-__device__ __forceinline__ bool block_is_live_planes(const SolveDims &D, const float4 *colA, const float4 *rowB, const float (&t)[3], float2 zr, int bxl, int byg)
-{
-    zr.x = fmaxf(zr.x, D.depth_min); zr.y = fminf(zr.y, D.depth_max);      // usable depths: depth_min < z < depth_max
-    bool live = zr.x <= zr.y;
-    if (live) {
-        const float4 ca = colA[8 * bxl], cb = colA[8 * bxl + 7], ra = rowB[8 * byg], rb = rowB[8 * byg + 7];
-        const float m = 0.01f;
-        const float cL = D.cx + 0.5f + m, cR = D.cx - ((float)D.width - 0.5f + m), cT = D.cy + 0.5f + m, cB = D.cy - ((float)D.height - 0.5f + m);
-        float maxL = -INFINITY, minR = INFINITY, maxT = -INFINITY, minB = INFINITY, zq = INFINITY;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float4 cx4 = (k & 1) ? cb : ca, ry4 = (k & 2) ? rb : ra;
-            const float rx = cx4.x + ry4.x, ry = cx4.y + ry4.y, rz = cx4.z + ry4.z;
-            const float fxrx = rx * D.fx, fyry = ry * D.fy;
-            const float aL = fxrx + cL * rz, aR = fxrx + cR * rz, aT = fyry + cT * rz, aB = fyry + cB * rz;
-            maxL = fmaxf(maxL, fmaxf(aL * zr.x, aL * zr.y)); minR = fminf(minR, fminf(aR * zr.x, aR * zr.y));
-            maxT = fmaxf(maxT, fmaxf(aT * zr.x, aT * zr.y)); minB = fminf(minB, fminf(aB * zr.x, aB * zr.y));
-            zq = fminf(zq, fminf(rz * zr.x, rz * zr.y));
-        }
-        const float bL = D.fx * t[0] + cL * t[2], bR = D.fx * t[0] + cR * t[2], bT = D.fy * t[1] + cT * t[2], bB = D.fy * t[1] + cB * t[2];
-        const bool outside = (maxL + bL < 0.0f) | (minR + bR > 0.0f) | (maxT + bT < 0.0f) | (minB + bB > 0.0f);
-        live = !((zq + t[2] > 1e-3f) && outside);         // a corner at or behind the camera plane: the block stays
-    }
-    return live;
-}
+// (The dead-block test of the block walk -- is an 8 x 8 block of the source frame PROVABLY without a pixel that lands in the target image? -- is
+// btba_hull.hpp: plain C++ that the host compiles too.)
 
 // (target, source, dense pair) of work position q: computed where the work order is the closed form (the default pair policies), read from
 // the work table otherwise.  q is wave-uniform: scalar arithmetic / a scalar load.
@@ -1143,11 +1079,12 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
     const int bw = D.width >> 3, bh = D.height >> 3;
     const int rows_per = (bh + D.dense_tiles - 1) / D.dense_tiles;
     const int r0 = min(bh, rows_per * tile), r1 = min(bh, rows_per * (tile + 1));
-    const int nb = (WALK == 2) ? (r1 - r0) * bw : 0;      // blocks of this band (the host keeps it <= 4 x 256)
+    const int nb = (WALK == 2) ? (r1 - r0) * bw : 0;      // blocks of this band (the host keeps it <= kMaxBandBlocks)
     const float2 *rng = (WALK == 2 && D.block_ranges) ? D.block_ranges + slot_s * (size_t)(bw * bh) + (size_t)r0 * bw : nullptr;
     const float2 zr0 = (rng && (int)tid < nb) ? rng[tid] : make_float2(0.0f, 0.0f);
     const float2 zr1 = (rng && (int)tid + kBlock < nb) ? rng[tid + kBlock] : make_float2(0.0f, 0.0f);      // a one-tile band of a 160 x 120 cache holds 300 blocks: both ranges of a lane in the SAME round of loads
                                                                                                            // (bands of more than 512 blocks fetch the rest in the compaction loop)
+    const int lane_c = (int)tid & 63, wave_c = __builtin_amdgcn_readfirstlane((int)tid >> 6);
     const Mat4 Tij = mat_mul(Tinv_i, T_j);                // source camera -> target camera
     PinholeCtx C;
 #pragma unroll
@@ -1169,31 +1106,57 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         else rowB[e - D.width] = make_float4(C.R[1] * l + C.R[2], C.R[4] * l + C.R[5], C.R[7] * l + C.R[8], 0.0f);
     }
     if (tid >= 64 && tid < 64 + 36) red[4 * kDenseVals + kDenseVals + 4 + ((int)tid - 64)] = m_stage;
-    int *hdr = reinterpret_cast<int *>(rowB + D.height);                  // [0 .. 8) wave totals of the list compaction (two blocks per lane and pass: [0 .. 4) first halves, [4 .. 8) second)
+    // behind the tables: the hull entries of the dead-block test (one per block column and block row, 8 floats apart), the wave totals of the list compaction
+    // ([0 .. 8): two blocks per lane and pass, [0 .. 4) first halves, [4 .. 8) second), the list of live blocks
+    float *hull = reinterpret_cast<float *>(rowB + D.height);
+    const int n_ent = bw + bh;
+    int *hdr = reinterpret_cast<int *>(hull + 8 * n_ent);
     unsigned *blist = reinterpret_cast<unsigned *>(hdr + 8);
     int n_live = 0;
     if (WALK == 2) {
-        // Blocks that are provably dead (block_is_live_planes: 90 % of the dead ones at c3) are removed BEFORE the walk; the live ones are compacted
+        // Blocks that are provably dead (btba_hull.hpp: 90 % of the dead ones at c3) are removed BEFORE the walk; the live ones are compacted
         // into an ordered list in LDS (ballot + mbcnt, block order: deterministic) that the four waves share round-robin.
-        __syncthreads();                                      // the ray tables are read by the test
-        const int lane_c = (int)tid & 63, wave_c = __builtin_amdgcn_readfirstlane((int)tid >> 6);
+        // The test is SEPARABLE: per block column and block row five extremes of the edge forms (35 entries for a 160 x 120 cache, one lane each, filled by the
+        // last wave -- the first one has the second half of a 300-block band to test); a block's verdict is then two 20-byte LDS reads and ~25 operations,
+        // where the corner-by-corner evaluation of the forms took ~120 and made wave 0, with two blocks per lane, the slowest of the prologue.
+        namespace H = btba_hull;
+        const H::HullForms F = H::hull_forms(D.fx, D.fy, D.cx, D.cy, D.width, D.height);
+        const H::HullBias hb = H::hull_bias(F, C.t);
+        if (rng) {
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+            for (int e = (int)tid - (kBlock - 64); e >= 0 && e < n_ent; e += 64) {      // block column e, or block row e - bw, from its first and last pixel's back-projection terms
+                const bool row = e >= bw;
+                const int px = row ? D.width + 8 * (e - bw) : 8 * e;
+                const H::HullEntry h = H::hull_entry(C.R, F, row, pinhole_lut_entry(D, px), pinhole_lut_entry(D, px + 7));
+                *reinterpret_cast<float4 *>(hull + 8 * e) = make_float4(h.lmax, h.rmin, h.tmax, h.bmin);
+                hull[8 * e + 4] = h.zmin;
+            }
+        }
+        __syncthreads();                                      // the entries are read by the test
+        const float inv_bw = fast_rcp((float)bw);             // block row of a block index: idx < kMaxBandBlocks, so the product's error, at most (1024 / bw) 3 2^-23, is far below the margin 0.5 / bw
         // Two blocks per lane and pass (idx, idx + 256): every band of a 160 x 120 cache -- 300 blocks at one tile -- is tested and compacted in ONE pass,
-        // one exchange of wave totals, two barriers (round 4: two passes of 256, the second with a fresh round of range loads in front of it and two more
-        // barriers: ~2 of a one-tile item's 9 us of set-up).  The list keeps its order -- blocks 0 .. 255 of the pass, then 256 .. 511 -- so the walk
+        // one exchange of wave totals and two barriers behind the one in front of the test: three in all (before round 5: two passes of 256, the second with a
+        // fresh round of range loads in front of it and two more barriers).  The list keeps its order -- blocks 0 .. 255 of the pass, then 256 .. 511 -- so the walk
         // and every sum are what they were.
+        auto is_live = [&](const float2 &zr, int bxl, int byg) {
+            const float *ce = hull + 8 * bxl, *re = hull + 8 * (bw + byg);
+            const float4 c4 = *reinterpret_cast<const float4 *>(ce), r4 = *reinterpret_cast<const float4 *>(re);
+            const H::HullEntry hc = { c4.x, c4.y, c4.z, c4.w, ce[4] }, hr = { r4.x, r4.y, r4.z, r4.w, re[4] };
+            return H::hull_block_live(hc, hr, hb, zr.x, zr.y, D.depth_min, D.depth_max);
+        };
         for (int c0 = 0; c0 < nb; c0 += 2 * kBlock) {
             const int idx0 = c0 + (int)tid, idx1 = idx0 + kBlock;
             bool live0 = false, live1 = false;
             unsigned code0 = 0, code1 = 0;
             if (idx0 < nb) {
-                const int byl = idx0 / bw, bxl = idx0 - byl * bw, byg = r0 + byl;
+                const int byl = (int)(((float)idx0 + 0.5f) * inv_bw), bxl = idx0 - byl * bw, byg = r0 + byl;
                 code0 = ((unsigned)byg << 16) | (unsigned)bxl;
-                live0 = rng ? block_is_live_planes(D, colA, rowB, C.t, c0 ? rng[idx0] : zr0, bxl, byg) : true;
+                live0 = rng ? is_live(c0 ? rng[idx0] : zr0, bxl, byg) : true;
             }
             if (idx1 < nb) {
-                const int byl = idx1 / bw, bxl = idx1 - byl * bw, byg = r0 + byl;
+                const int byl = (int)(((float)idx1 + 0.5f) * inv_bw), bxl = idx1 - byl * bw, byg = r0 + byl;
                 code1 = ((unsigned)byg << 16) | (unsigned)bxl;
-                live1 = rng ? block_is_live_planes(D, colA, rowB, C.t, c0 ? rng[idx1] : zr1, bxl, byg) : true;
+                live1 = rng ? is_live(c0 ? rng[idx1] : zr1, bxl, byg) : true;
             }
             const unsigned long long bal0 = __builtin_amdgcn_ballot_w64(live0), bal1 = __builtin_amdgcn_ballot_w64(live1);
             if (lane_c == 0) { hdr[wave_c] = __popcll(bal0); hdr[4 + wave_c] = __popcll(bal1); }

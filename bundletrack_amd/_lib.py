@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "btba_matrices_to_poses", "btba_poses_to_matrices",
     "btba_process_depth", "btba_depth_to_normals", "btba_ingest_params_default", "btba_ingest_frames",
      "btba_vos_params_default", "btba_vos_sample_frames", "btba_vos_first_labels", "btba_vos_propagate", "btba_vos_masks", "btba_vos_inputs",
+    "btba_vos_net_config_default", "btba_vos_net_layer_count", "btba_vos_net_model_create", "btba_vos_net_model_destroy", "btba_vos_net_out_size", "btba_vos_features",
     "btba_build_cache_zn", "btba_pack_zn", "btba_solve_batch_zn", "btba_zn_block_ranges", "btba_zn_valid_lists", "btba_solve_batch_zn_aux", "btba_pack_correspondences24",
     "btba_match_params_default", "btba_match_capacity", "btba_match_pairs",
     "btba_lfnet_params_default", "btba_lfnet_heatmaps", "btba_lfnet_select", "btba_lfnet_crops", "btba_lfnet_keypoints",
@@ -94,6 +95,16 @@ class VosParams(C.Structure):
     """btba_vos_params (include/btba.h)."""
     _fields_ = [("ref_num", C.c_int32), ("range", C.c_int32), ("sigma_dense", C.c_float), ("sigma_sparse", C.c_float), ("temperature", C.c_float),
                 ("continuous_frames", C.c_int32), ("sparse_after", C.c_int32)]
+
+
+class VosNetConfig(C.Structure):
+    """btba_vos_net_config (include/btba.h)."""
+    _fields_ = [("block", C.c_int32), ("layers", C.c_int32 * 4), ("bn_eps", C.c_float)]
+
+
+class VosNetLayer(C.Structure):
+    """btba_vos_net_layer (include/btba.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("weight", "bn_weight", "bn_bias", "running_mean", "running_var")]
 
 
 class LfnetParams(C.Structure):
@@ -228,6 +239,7 @@ def build(force: bool = False, verbose: bool = False, out: str | None = None, ex
 HOST_DRIVER = os.path.join(_ROOT, "tests", "cpp", "host_driver")
 LFNET_DESC_DRIVER = os.path.join(_ROOT, "tests", "cpp", "liblfnet_desc_driver.so")
 LFNET_DET_DRIVER = os.path.join(_ROOT, "tests", "cpp", "liblfnet_det_driver.so")
+VOS_NET_DRIVER = os.path.join(_ROOT, "tests", "cpp", "libvos_net_driver.so")
 
 
 def build_driver(name: str, shared: bool = True, force: bool = False, verbose: bool = False) -> str:
@@ -251,9 +263,10 @@ def build_driver(name: str, shared: bool = True, force: bool = False, verbose: b
 
 
 def build_host_cpp(force: bool = False, verbose: bool = False) -> str:
-    """Compile the C++ host layer's test program (tests/cpp/host_driver) and the two LF-Net nets' ctypes drivers."""
+    """Compile the C++ host layer's test program (tests/cpp/host_driver) and the three nets' ctypes drivers."""
     build_driver("lfnet_desc_driver", force=force, verbose=verbose)
     build_driver("lfnet_det_driver", force=force, verbose=verbose)
+    build_driver("vos_net_driver", force=force, verbose=verbose)
     return build_driver("host_driver", shared=False, force=force, verbose=verbose)
 
 
@@ -357,6 +370,14 @@ def lib() -> C.CDLL:
         L.btba_lfnet_desc_model_destroy.argtypes = [C.c_void_p]
         L.btba_lfnet_desc_model_destroy.restype = None
         L.btba_lfnet_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_vos_net_config_default.argtypes = [C.POINTER(VosNetConfig)]
+        L.btba_vos_net_config_default.restype = None
+        L.btba_vos_net_layer_count.argtypes = [C.POINTER(VosNetConfig)]
+        L.btba_vos_net_model_create.argtypes = [C.c_void_p, C.POINTER(VosNetConfig), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.btba_vos_net_model_destroy.argtypes = [C.c_void_p]
+        L.btba_vos_net_model_destroy.restype = None
+        L.btba_vos_net_out_size.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.btba_vos_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.btba_lfnet_det_config_default.argtypes = [C.POINTER(LfnetDetConfig)]
         L.btba_lfnet_det_config_default.restype = None
         L.btba_lfnet_det_scales.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p]
@@ -455,6 +476,19 @@ def ingest_params(**kw) -> IngestParams:
 def vos_params(**kw) -> VosParams:
     """btba_vos_params_default with fields overridden by keyword."""
     return _params(VosParams, "btba_vos_params_default", kw)
+
+
+def vos_net_config(**kw) -> VosNetConfig:
+    """btba_vos_net_config_default with fields overridden by keyword; layers: a sequence of four block counts."""
+    layers = kw.pop("layers", None)
+    p = _params(VosNetConfig, "btba_vos_net_config_default", kw)
+    if layers is not None:
+        layers = [int(v) for v in layers]
+        if len(layers) != 4:
+            raise ValueError("four block counts")
+        for i in range(4):
+            p.layers[i] = layers[i]
+    return p
 
 
 def lfnet_params(**kw) -> LfnetParams:

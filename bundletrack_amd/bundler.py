@@ -246,7 +246,7 @@ class Bundler:
     """Bundler::processNewFrame (src/Bundler.cpp:52-183) from the point where a frame has depth, normals and features --
     or, for a frame that carries only `depth_code_gpu` (and `bgr_gpu`), from its images: Bundler.ingest then makes depth_gpu,
     normal_gpu and color_gpu first (ingest.ingest_frames, what Frame's constructor does).  With a `segmenter` (the video
-    segmentation's backbone, a callable) and a `mask_propagator` (vos.MaskPropagator) a frame with `bgr_gpu` and no `mask_gpu` gets
+    segmentation's backbone, a callable: the caller's torch model, or btba_vos_features as vos_net.VosBackbone) and a `mask_propagator` (vos.MaskPropagator) a frame with `bgr_gpu` and no `mask_gpu` gets
     its mask from the propagation (Bundler.propagate_mask); off by default.  Then the segmentation by its mask when `mask_gpu` is set (segmentation.apply_masks on `mask_workspace` or the optimiser's
     workspace; the ROI gate then sees the real ROI), feature detection when a `detector` is given (Bundler.detect: the
     detector's input and the keypoints' way back on the GPU, the detector itself a callable; an exception from it marks the

@@ -941,6 +941,31 @@ LfnetDetector::ScoreFn LfnetScoreNet::asScoreNet(std::vector<float *> score_dev,
     };
 }
 
+btba_vos_net_config vosNetConfig()
+{
+    btba_vos_net_config c;
+    btba_vos_net_config_default(&c);
+    return c;
+}
+
+VosBackbone::VosBackbone(btba_workspace *ws, const btba_vos_net_config &config, const std::vector<btba_vos_net_layer> &layers)
+    : ws_(ws), config_(config)
+{
+    const int rc = btba_vos_net_model_create(ws, &config, layers.data(), (int)layers.size(), &model_);
+    if (rc != BTBA_OK) throw Error(rc, "btba_vos_net_model_create");
+}
+
+void VosBackbone::features(int n_frames, int H, int W, const float *rgb_dev, float *features_out_dev) const
+{
+    const int rc = btba_vos_features(ws_, model_, n_frames, H, W, rgb_dev, features_out_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_vos_features");
+}
+
+Bundler::SegmentFn VosBackbone::asSegmenter(int H, int W) const
+{
+    return [this, H, W](const float *rgb_dev, float *features_out_dev) { features(1, H, W, rgb_dev, features_out_dev); };
+}
+
 void DetectorFeatureManager::detectFeature(const std::shared_ptr<Frame> &frame)              // FeatureManager.cpp:811-908
 {
     prepareDetectorInputs(ws_, { frame }, bgr_, gray_, out_size_);

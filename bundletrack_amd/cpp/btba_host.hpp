@@ -470,8 +470,8 @@ public:
     int n_ba_calls = 0;
     Window last_window;                                             // what the last optimizeGPU marshalled
     btba_workspace *mask_ws = nullptr;                              // the caller's workspace for the segmentation (not owned)
-    // The video segmentation's backbone: normalised RGB float [3][H][W] on the device -> features float [C][Hd][Wd] written to
-    // features_out_dev.  With it and a mask_propagator set (both off by default) a frame with _bgr_gpu and no _mask_gpu gets its mask
+    // The video segmentation's backbone (the caller's own model, or VosBackbone::asSegmenter on btba_vos_features): normalised RGB float
+    // [3][H][W] on the device -> features float [C][Hd][Wd] written to features_out_dev.  With it and a mask_propagator set (both off by default) a frame with _bgr_gpu and no _mask_gpu gets its mask
     // from the propagation; a frame that brings its mask while the propagator is empty is the annotated first frame.  rgb_dev is the
     // caller's float [3][H][W] buffer the normalised image goes to.
     using SegmentFn = std::function<void(const float *rgb_dev, float *features_out_dev)>;
@@ -488,6 +488,28 @@ public:
 private:
     OptimizeFn optimize_;
     std::unique_ptr<OptimizerGpu> own_opt_;                         // created at the first BA call when no OptimizeFn was given
+};
+
+// The video segmentation's backbone (modeling/network.py::VOSNet in eval mode) on btba_vos_features; the rules are in include/btba.h.
+btba_vos_net_config vosNetConfig();                                              // btba_vos_net_config_default
+// A model on a workspace (created from host arrays in PyTorch's layouts, one record per convolution in the forward order of
+// include/btba.h; destroyed with the object; move-only).  features() takes rgb_dev float [n][3][H][W] to features_out_dev float
+// [n][256][Hd][Wd], asynchronously on the workspace stream.  asSegmenter gives the Bundler::SegmentFn for frames of H x W.
+class VosBackbone {
+public:
+    VosBackbone(btba_workspace *ws, const btba_vos_net_config &config, const std::vector<btba_vos_net_layer> &layers);
+    VosBackbone(const VosBackbone &) = delete;
+    VosBackbone &operator=(const VosBackbone &) = delete;
+    VosBackbone(VosBackbone &&o) noexcept : ws_(o.ws_), config_(o.config_), model_(o.model_) { o.model_ = nullptr; }
+    ~VosBackbone() { btba_vos_net_model_destroy(model_); }
+    const btba_vos_net_config &config() const { return config_; }
+    const btba_vos_net_model *model() const { return model_; }
+    void features(int n_frames, int H, int W, const float *rgb_dev, float *features_out_dev) const;
+    Bundler::SegmentFn asSegmenter(int H, int W) const;
+private:
+    btba_workspace *ws_;
+    btba_vos_net_config config_;
+    btba_vos_net_model *model_ = nullptr;
 };
 
 // Eigen's inverse() for a general 4x4, computed in double (used for the pose files)

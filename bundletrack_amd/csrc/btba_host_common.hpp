@@ -198,6 +198,7 @@ struct btba_workspace {
     DevBuf lfnet;                                           // btba_lfnet_*: per-map moments, peak flags, the compacted peak list
     DevBuf lfnet_desc;                                      // btba_lfnet_descriptors: two buffers of a chunk's widest layer
     DevBuf lfnet_det;                                       // btba_lfnet_scores: the residual stream and conv1's output of a pass, NHWC
+    DevBuf vos_net;                                         // btba_vos_features: the four NHWC activation buffers of a pass
     DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;

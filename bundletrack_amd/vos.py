@@ -3,8 +3,8 @@
 Mirrors transductive-vos.pytorch/run_video.py around its backbone: rgb_normalize, prepare_first_frame, lib/predict.py::predict with
 sample_frames and the Gaussian motion model, the one-hot history entry and the upsampled arg-max mask.  The reference forms an
 [n_ref * HW, HW] similarity matrix and two [HW, HW] weight tables per video; here predict is one fused pass with an online softmax
-(btba_vos.hpp) and neither exists.  The backbone stays with the caller: a callable from normalize_inputs' output to features
-[C, Hd, Wd].  The exact rules are in include/btba.h."""
+(btba_vos.hpp) and neither exists.  The backbone is a callable from normalize_inputs' output to features [C, Hd, Wd]: the caller's
+torch model, or btba_vos_features (vos_net.VosBackbone).  The exact rules are in include/btba.h."""
 from __future__ import annotations
 
 import ctypes as C

@@ -585,8 +585,9 @@ BTBA_API int btba_ingest_frames(btba_workspace *ws, const btba_ingest_params *pa
 /* ---- mask propagation (where a frame's object mask comes from) ---------------------------------------------------
  * Replaces transductive-vos.pytorch/run_video.py around its backbone: rgb_normalize (:81,113-114), prepare_first_frame (:68-82),
  * lib/predict.py::predict with sample_frames and get_spatial_weight (:11-59, :62-78, :118-134), the one-hot history entry (:145)
- * and the upsampled arg-max mask (:151-155).  The backbone (a torch model) stays with the caller: it maps btba_vos_inputs' output to
- * features float [C][Hd][Wd], Hd = ceil(H / 8), Wd = ceil(W / 8).  The mask btba_vos_masks writes is what btba_apply_masks takes.
+ * and the upsampled arg-max mask (:151-155).  The backbone is the caller's torch model or btba_vos_features (below): it maps
+ * btba_vos_inputs' output to features float [C][Hd][Wd], Hd = ceil(H / 8), Wd = ceil(W / 8).  The mask btba_vos_masks writes is what
+ * btba_apply_masks takes.
  *
  * btba_vos_sample_frames (host only; no GPU, no workspace): the history indices predict reads for target frame frame_idx >= 1
  * (frame 0 is the annotated one) and how many of them, counted from the end, take sigma_dense:
@@ -654,6 +655,70 @@ BTBA_API int btba_vos_propagate(btba_workspace *ws, const btba_vos_params *param
                                 float *const *onehot_out_dev);
 BTBA_API int btba_vos_masks(btba_workspace *ws, int d, int Hd, int Wd, int H, int W, const float *pred_dev, uint8_t *mask_out_dev);
 BTBA_API int btba_vos_inputs(btba_workspace *ws, int n_frames, int H, int W, const uint8_t *const *bgr_dev, float *rgb_out_dev);
+
+/* ---- the segmentation backbone (between btba_vos_inputs and btba_vos_propagate) ---------------------------------------
+ * transductive-vos.pytorch/modeling/network.py::VOSNet on modeling/backbone/resnet.py with model.eval(), as run_video.py:167-180
+ * runs it: rgb float [n][3][H][W] (what btba_vos_inputs writes) -> features float [n][256][Hd][Wd], Hd = ceil(H / 8), Wd = ceil(W / 8)
+ * (what btba_vos_propagate takes).  fp32 operands with fp32 accumulation throughout; no reduced precision.
+ *
+ * The net:
+ *   stem          conv 7 x 7, stride 2, pad 3, 3 -> 64, no bias; batch norm; relu; max pool 3 x 3, stride 2, pad 1 (padding never
+ *                 wins: torch pads with -inf).
+ *   layer1 .. 4   layers[s] blocks of planes 64 / 128 / 256 / 256 with strides 1 / 2 / 1 / 1 (layer4 is NOT torchvision's: 256 planes
+ *                 at stride 1).  Only a layer's first block carries its stride; it has a downsample (conv 1 x 1 with that stride,
+ *                 batch norm) on the shortcut where the stride is not 1 or the width changes.
+ *   bottleneck    conv 1 x 1 -> bn -> relu -> conv 3 x 3 (stride, pad 1) -> bn -> relu -> conv 1 x 1 (to 4 x planes) -> bn, + shortcut, relu.
+ *   basic         conv 3 x 3 (stride, pad 1) -> bn -> relu -> conv 3 x 3 (pad 1) -> bn, + shortcut, relu.
+ *   tail          bottleneck nets only: adjust_dim, conv 1 x 1, 1024 -> 256, no bias; bn256; no relu.  A basic net ends at layer4.
+ *   batch norm    inference mode, eps = bn_eps: scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale,
+ *                 in fp64 on the host, rounded once; y = conv * scale + shift in fp32 (one fmaf), then the shortcut is added, then relu.
+ *   convolution   a tap outside the image contributes 0.  Output size (in + 2 pad - k) / stride + 1, integer division.
+ *   summation     every convolution output element is ONE fp32 fmaf chain over k = (ky, kx, c_in), in that order with c_in fastest,
+ *                 from 0 (v_mfma_f32_32x32x2_f32 behind the stem, fmaf in the stem): no split of K.  The order does not depend on
+ *                 the grid position, the batch, the frame's place in it or the pass, so a frame gives the same bits alone, anywhere
+ *                 in a batch and in any pass.
+ * The widths are the reference's.  resnet18 is block 0 with layers 2, 2, 2, 2; resnet50 block 1 with 3, 4, 6, 3 (the default, as
+ * run_video.py's); resnet101 block 1 with 3, 4, 23, 3.
+ *
+ * Weights: n_layers records of host arrays in PyTorch's own layouts, weight [C_out][C_in][k][k] and four [C_out] arrays, in forward
+ * order: the stem (backbone.0, backbone.1); for layer s = 1 .. 4 (backbone.{3 + s}) and each of its blocks in turn conv1 + bn1,
+ * conv2 + bn2, for a bottleneck conv3 + bn3, and where the block has one downsample.0 + downsample.1; for a bottleneck net last
+ * adjust_dim + bn256.  btba_vos_net_layer_count gives n_layers for a configuration (-1 for a bad one).
+ * btba_vos_net_model_create checks the configuration and every array, re-lays each weight to [K][C_out] once, folds the batch norms
+ * and uploads.  It is the one call here that allocates and waits.  A model belongs to the workspace it was created with and must be
+ * destroyed before it.
+ * btba_vos_features: asynchronous on the workspace stream, no host wait, no allocation once the workspace scratch has grown.  Frames
+ * are worked in passes of at most BTBA_VOS_NET_PASS_PIXELS input pixels (a larger single frame is a pass of its own): the scratch is
+ * four NHWC buffers, each of the widest layer's output per frame of a pass (64 ceil(H / 2) ceil(W / 2) floats behind the stem or 256
+ * ceil(H / 4) ceil(W / 4) behind a bottleneck layer1, whichever is larger: about 16 H W).  n_frames == 0 is success without a launch; the pointers may then be NULL.
+ * BTBA_EINVAL, decided before any GPU work.  create: NULL ws, config, layers or out; block not 0 or 1; layers[i] outside 1 ..
+ * BTBA_VOS_NET_MAX_BLOCKS; bn_eps not finite or < 0; n_layers not btba_vos_net_layer_count(config); a NULL array in a record; a
+ * non-finite value; running_var + bn_eps <= 0.  features: NULL ws or model; n_frames < 0; H or W outside 1 .. BTBA_VOS_NET_MAX_SIZE;
+ * with n_frames > 0 a NULL pointer or one not aligned to 16 bytes; a model created with another workspace.  out_size: NULL outputs,
+ * H or W outside 1 .. BTBA_VOS_NET_MAX_SIZE. */
+#define BTBA_VOS_NET_BASIC 0
+#define BTBA_VOS_NET_BOTTLENECK 1
+#define BTBA_VOS_NET_MAX_BLOCKS 64
+#define BTBA_VOS_NET_MAX_SIZE 4096
+#define BTBA_VOS_NET_PASS_PIXELS (1 << 20)
+typedef struct btba_vos_net_config {
+    int32_t block;                   /* 1: 0 BasicBlock, 1 Bottleneck */
+    int32_t layers[4];               /* 3, 4, 6, 3: blocks of layer1 .. layer4 */
+    float bn_eps;                    /* 1e-5 */
+} btba_vos_net_config;
+typedef struct btba_vos_net_layer {
+    const float *weight;             /* the convolution's, [C_out][C_in][k][k] */
+    const float *bn_weight, *bn_bias, *running_mean, *running_var;   /* the batch norm's behind it, [C_out] each */
+} btba_vos_net_layer;
+typedef struct btba_vos_net_model btba_vos_net_model;
+BTBA_API void btba_vos_net_config_default(btba_vos_net_config *c);
+BTBA_API int btba_vos_net_layer_count(const btba_vos_net_config *config);
+BTBA_API int btba_vos_net_model_create(btba_workspace *ws, const btba_vos_net_config *config, const btba_vos_net_layer *layers, int n_layers,
+                                       btba_vos_net_model **out);
+BTBA_API void btba_vos_net_model_destroy(btba_vos_net_model *model);
+BTBA_API int btba_vos_net_out_size(int H, int W, int32_t *Hd, int32_t *Wd);
+BTBA_API int btba_vos_features(btba_workspace *ws, const btba_vos_net_model *model, int n_frames, int H, int W, const float *rgb_dev,
+                               float *features_out_dev);
 
 /* ---- foreground-mask segmentation (the first step of every frame) ------------------------------------------------
  * Replaces Frame::segmentationByMaskFile minus the PNG read (src/Frame.cpp:236-373, called first by Bundler::processNewFrame,

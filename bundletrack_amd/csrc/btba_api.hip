@@ -745,27 +745,24 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     }
     if (Z.frame_slot && B != 1) return BTBA_EINVAL;
     D.frame_slot = Z.frame_slot;
-    // block walk of the pinhole sweep: per-block depth ranges for its dead-block test, and the LDS it needs for the list of live blocks
-    size_t blist_bytes = 0;
+    // block walk of the pinhole sweep: per-block depth ranges for its dead-block test
     if (!(zn_layout == 1 && use_dense && !compaction)) D.walk_blocks = 0;
     // where the sparse items go in the fused launch: all of them at the END when the dense items are the long, VALU-bound walks over full
     // frames (c3 x 32: 176.4 -> 170.5 us per launch, gpurun_out/r03_24: they fill the launch's drain); interleaved when the dense items are
     // the short list walks of object-masked frames (49.7 interleaved against 53.3 us)
     D.sparse_tail_256 = ws->tune.sparse_tail_256 >= 0 ? ws->tune.sparse_tail_256 : ((use_dense && !compaction) ? 256 : 0);
-    if (D.walk_blocks) {
+    // the dynamic LDS of a dense item on the compact cache (btba_sweep_layout.hpp, which the kernels carve their pointers out of): coordinate look-up tables, the
+    // pinhole sweep's ray tables, the block walk's hull entries, wave totals and list of live blocks
+    const int band_blocks = D.walk_blocks ? ((Hd / 8 + tiles - 1) / tiles) * (Wd / 8) : 0;
+    const SweepLayout sweep_lds(Wd, Hd, band_blocks, D.walk_blocks ? kSweepLdsBlocks : zn_layout == 1 ? kSweepLdsStrips : kSweepLdsGeneralK);
+    if (!sweep_lds.block_walk) D.walk_blocks = 0;                               // very large caches: row strips (a band's blocks are tested by 4 x 256 lanes)
+    if (D.walk_blocks && ws->tune.block_skip) {                                 // (off: every block is walked)
         const int bw = Wd / 8, bh = Hd / 8;
-        const size_t band_blocks = (size_t)((bh + tiles - 1) / tiles) * bw;
-        if (band_blocks > (size_t)kMaxBandBlocks) D.walk_blocks = 0;                               // very large caches: row strips (a band's blocks are tested by 4 x 256 lanes)
-        else {
-            blist_bytes = 32 * (size_t)(bw + bh) + 32 + sizeof(uint32_t) * band_blocks;      // hull entries of the block columns and rows, wave totals, the list
-            if (ws->tune.block_skip) {                                          // (off: every block is walked)
-                if (Z.block_ranges) D.block_ranges = reinterpret_cast<const float2 *>(Z.block_ranges);      // part of the caller's / the pool's frame cache
-                else if (!Z.frame_slot) {                                       // not given: one pass over the frames per solve
-                    if ((rc = ws->block_ranges.ensure(sizeof(float2) * (size_t)B * N * bw * bh))) return rc;
-                    k_block_ranges<<<dim3((unsigned)((bw * bh + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)(B * N)), kBlock, 0, ws->stream>>>(Wd, Hd, reinterpret_cast<const float4 *>(Z.zn), nullptr, ws->block_ranges.as<float2>());
-                    D.block_ranges = ws->block_ranges.as<float2>();
-                }
-            }
+        if (Z.block_ranges) D.block_ranges = reinterpret_cast<const float2 *>(Z.block_ranges);      // part of the caller's / the pool's frame cache
+        else if (!Z.frame_slot) {                                               // not given: one pass over the frames per solve
+            if ((rc = ws->block_ranges.ensure(sizeof(float2) * (size_t)B * N * bw * bh))) return rc;
+            k_block_ranges<<<dim3((unsigned)((bw * bh + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)(B * N)), kBlock, 0, ws->stream>>>(Wd, Hd, reinterpret_cast<const float4 *>(Z.zn), nullptr, ws->block_ranges.as<float2>());
+            D.block_ranges = ws->block_ranges.as<float2>();
         }
     }
     // Software pipelining across instances: the batch is split in two halves on two streams, so one half's
@@ -795,7 +792,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     }
     const size_t pairsum_floats = lds_pairs / sizeof(float);
     S.chain_iterations = 0;
-    const size_t lut_bytes = sizeof(float) * (size_t)((Wd + Hd + 3) & ~3) + (zn_layout == 1 ? sizeof(float4) * (size_t)(Wd + Hd) : 0) + blist_bytes + (size_t)ws->tune.debug_lds_pad;         // coordinate look-up tables of the compact dense sweep (+ its list of live blocks)
+    const size_t lut_bytes = sweep_lds.total + (size_t)ws->tune.debug_lds_pad;
     if (chain) {
         // ONE launch: 8 XCD sequences x n_gn iterations x (instances of the XCD) x (sweep items + 1 solve item)
         const size_t chain_lds = std::max(lut_bytes, sizeof(float) * SolveLayout(N, D.n_dense_pairs, true, true).total);

@@ -20,7 +20,7 @@
 //
 // This file holds what all of them share (SolveDims, the frame caches) and the sweeps; the system solves are in
 // btba_solve_general.hpp (k_system_solve, k_big_reduce, k_big_assemble), btba_solve_small.hpp and btba_solve_mid.hpp, the chained
-// launch (k_chain) in btba_chain.hpp.
+// launch (k_chain) in btba_chain.hpp.  The dynamic-LDS layout of a dense item on the compact cache is btba_sweep_layout.hpp (shared with the host).
 //
 // Summation is deterministic (fixed DPP tree inside a wave, fixed order across waves, tiles and
 // pairs); the reference uses float atomics (SURVEY.md section 5 "race detection").
@@ -36,6 +36,7 @@
 #include <stdint.h>
 #include "btba_device.hpp"
 #include "btba_hull.hpp"
+#include "btba_sweep_layout.hpp"
 
 namespace btba {
 
@@ -113,27 +114,24 @@ __device__ __forceinline__ size_t frame_slot_of(const SolveDims &D, size_t f) { 
 
 __device__ __forceinline__ int pair_index(int i, int j, int n) { return i * n - i * (i + 1) / 2 + (j - i - 1); }
 
-__device__ __forceinline__ Mat4 load_mat4(const float *p)
+__device__ __forceinline__ Mat4 mat4_rows(const float4 &a, const float4 &b, const float4 &c, const float4 &d)
 {
     Mat4 m;
-    const float4 *q = reinterpret_cast<const float4 *>(p);
-    float4 a = q[0], b = q[1], c = q[2], d = q[3];
     m.m[0] = a.x; m.m[1] = a.y; m.m[2] = a.z; m.m[3] = a.w;
     m.m[4] = b.x; m.m[5] = b.y; m.m[6] = b.z; m.m[7] = b.w;
     m.m[8] = c.x; m.m[9] = c.y; m.m[10] = c.z; m.m[11] = c.w;
     m.m[12] = d.x; m.m[13] = d.y; m.m[14] = d.z; m.m[15] = d.w;
     return m;
 }
+__device__ __forceinline__ Mat4 load_mat4(const float *p)
+{
+    const float4 *q = reinterpret_cast<const float4 *>(p);
+    return mat4_rows(q[0], q[1], q[2], q[3]);
+}
 // the same through a constant-address-space pointer (wave-uniform address: four s_load_dwordx4)
 __device__ __forceinline__ Mat4 load_mat4_uniform(const float *p)
 {
-    Mat4 m;
-    const float4 a = ld_const_f4(p), b = ld_const_f4(p + 4), c = ld_const_f4(p + 8), d = ld_const_f4(p + 12);
-    m.m[0] = a.x; m.m[1] = a.y; m.m[2] = a.z; m.m[3] = a.w;
-    m.m[4] = b.x; m.m[5] = b.y; m.m[6] = b.z; m.m[7] = b.w;
-    m.m[8] = c.x; m.m[9] = c.y; m.m[10] = c.z; m.m[11] = c.w;
-    m.m[12] = d.x; m.m[13] = d.y; m.m[14] = d.z; m.m[15] = d.w;
-    return m;
+    return mat4_rows(ld_const_f4(p), ld_const_f4(p + 4), ld_const_f4(p + 8), ld_const_f4(p + 12));
 }
 __device__ __forceinline__ void store_mat4(float *p, const Mat4 &m)
 {
@@ -223,18 +221,16 @@ __global__ void __launch_bounds__(kBlock) k_build_cache(int W, int H, int Wd, in
 // operations (no contraction) where it is consumed gives bit-identical camera-space points while halving the
 // bytes and the load instructions of the dense sweep (one 16-byte load per tap instead of two).
 // Camera-space point of a cached pixel from its depth.  General intrinsics: the cache builder's arithmetic, term by
-// term (cx, cy = (float) full-resolution column / row of the cached pixel).  SIMPLE (zero skew, affine last row -- every
-// pinhole K): x = K^-1[0][0] (xi d) + K^-1[0][2] d = d (K^-1[0][0] xi + K^-1[0][2]) with the bracket tabulated per
-// column (cx) / row (cy): three multiplies per point instead of nine operations; differs from the builder's rounding
-// sequence by at most 1 ulp per coordinate.
-template <bool SIMPLE>
+// term (cx, cy = (float) full-resolution column / row of the cached pixel).  (Zero skew and an affine last row -- every
+// pinhole K -- take dense_block_pinhole instead: x = K^-1[0][0] (xi d) + K^-1[0][2] d = d (K^-1[0][0] xi + K^-1[0][2]) with the
+// bracket tabulated per column / row, pinhole_lut_entry: three multiplies per point instead of nine operations; differs from the
+// builder's rounding sequence by at most 1 ulp per coordinate.)
 __device__ __forceinline__ float3 zn_backproject(const float *ki, float cx, float cy, float d)
 {
 #pragma clang fp contract(off)
     // (double)d >= 0.1  <=>  d >= 0.1f  (0.1f is the smallest float above 0.1); below it the reference stores zeros,
     // and with d := 0 every product below is an exact zero as well, so one select replaces three.
     d = (d >= 0.1f) ? d : 0.0f;
-    if (SIMPLE) return make_float3(cx * d, cy * d, ki[15] * d);
     const float vx = cx * d, vy = cy * d;
     return make_float3(ki[0] * vx + ki[1] * vy + ki[2] * d + ki[3] * d, ki[4] * vx + ki[5] * vy + ki[6] * d + ki[7] * d,
                        ki[12] * vx + ki[13] * vy + ki[14] * d + ki[15] * d);
@@ -675,19 +671,24 @@ __device__ __forceinline__ int tri21(int r, int c) { if (r > c) { const int t = 
 // off the single-workgroup critical path of k_system_solve (it was 8.4 k of its 55 k cycles).
 // M of the congruence (6 x 6, from the target frame's pose), staged in LDS by 36 threads at the START of a dense workgroup: its global
 // loads are then off the tail of the workgroup (the epilogue used to wait a memory round trip for them)
-__device__ __forceinline__ void dense_stage_M(float *red, const float *__restrict__ T_target)
+// In two halves -- the entry of thread `tid` from the pose, and its store -- so that an item can issue the load with its other prologue loads and store
+// behind whatever it does meanwhile (dense_block_pinhole: the table fill); dense_block and dense_block_zn call them back to back.
+__device__ __forceinline__ float dense_M_load(unsigned tid, const float *__restrict__ T_target)
 {
-    float *Mt = red + 4 * kDenseVals + kDenseVals + 4;
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + 36) {
-        const int e = (int)threadIdx.x - 64, r = e / 6, c = e % 6;
-        float v;
+    float v = 0.0f;
+    if (tid >= 64 && tid < 64 + 36) {
+        const int e = (int)tid - 64, r = e / 6, c = e % 6;
         if (r < 3) v = (c < 3) ? T_target[4 * r + c] : 0.0f;
         else {
             const int q = r - 3, qa = (q + 1) % 3, qb = (q + 2) % 3;     // ([t]x R)[q][c] = t[qa] R[qb][c] - t[qb] R[qa][c]
             v = (c < 3) ? T_target[4 * qa + 3] * T_target[4 * qb + c] - T_target[4 * qb + 3] * T_target[4 * qa + c] : T_target[4 * q + (c - 3)];
         }
-        Mt[e] = v;
     }
+    return v;
+}
+__device__ __forceinline__ void dense_M_store(unsigned tid, float *red, float v)
+{
+    if (tid >= 64 && tid < 64 + 36) red[4 * kDenseVals + kDenseVals + 4 + ((int)tid - 64)] = v;
 }
 
 // FLIPPED: the sums were accumulated with a+ = D a, res+ = -res (dense_block_pinhole): S = D S+ D negates the nine entries that couple a
@@ -751,6 +752,31 @@ __device__ __forceinline__ void dense_epilogue(float (&acc)[kDenseVals], float *
     }
 }
 
+// where the workgroup of (dense pair p, tile, instance b) puts its record, and how (store_sum's mode)
+__device__ __forceinline__ float *dense_record_out(const SolveDims &D, float *__restrict__ partials, int p, int tile, int b) { return partials + ((unsigned)b * D.dp_stride + (unsigned)(D.atomic_sums ? p : p * D.dense_tiles + tile) * (unsigned)kDenseVals); }
+__device__ __forceinline__ int dense_record_mode(const SolveDims &D) { return D.atomic_sums ? 1 : D.publish ? 2 : 0; }
+
+// (tile, pair, instance) of position L of the dense grids: tile fastest, then pair, then instance
+__device__ __forceinline__ void dense_grid_decode(const SolveDims &D, unsigned L, int &tile, int &p, int &b)
+{
+    tile = (int)(L % (unsigned)D.dense_tiles);
+    p = (int)((L / (unsigned)D.dense_tiles) % (unsigned)D.n_dense_pairs);
+    b = (int)(L / ((unsigned)D.dense_tiles * (unsigned)D.n_dense_pairs));
+}
+
+// the context of pixel_geom / pixel_accumulate for target fi, source fj of the instance whose poses start at T + pb
+__device__ __forceinline__ DenseCtx dense_ctx(const SolveDims &D, const float *__restrict__ T, const float *__restrict__ Tinv, unsigned pb, int fi, int fj, const float4 *cam_t, const float4 *nrm_t)
+{
+    DenseCtx C;
+    C.Tij = mat_mul(load_mat4(Tinv + pb + 16 * fi), load_mat4(T + pb + 16 * fj));      // source camera -> target camera
+    C.cam_t = cam_t; C.nrm_t = nrm_t;
+    C.fx = D.fx; C.fy = D.fy; C.cx = D.cx; C.cy = D.cy; C.depth_min = D.depth_min; C.depth_max = D.depth_max;
+    C.normal_thresh = D.normal_thresh; C.dist2_thresh = D.dist_thresh * D.dist_thresh;
+    C.delta = D.robust_delta; C.delta2 = D.robust_delta * D.robust_delta; C.w_dense = D.w_dense;
+    C.W = D.width; C.H = D.height;
+    return C;
+}
+
 // 1-D grid of dense_tiles * Pd * B workgroups (XCD-remapped).  Lane = consecutive source pixel (coalesced
 // float4 loads of the source camPos / normal); two pixels per lane per trip, sixteen target-tap gathers in
 // flight; the taps stay in L1/L2 because neighbouring source pixels project to neighbouring target pixels.
@@ -761,14 +787,8 @@ __device__ __forceinline__ void dense_block(const SolveDims &D, const float4 *__
     const int fi = ij.x, fj = ij.y;                       // fi = target, fj = source
     const size_t fb = (size_t)b * D.n_frames;
     const unsigned pb = (unsigned)b * (unsigned)D.pose_stride;
-    dense_stage_M(red, T + pb + 16 * fi);
-    DenseCtx C;
-    C.Tij = mat_mul(load_mat4(Tinv + pb + 16 * fi), load_mat4(T + pb + 16 * fj));      // source camera -> target camera
-    C.cam_t = campos + (fb + fi) * (size_t)D.npix; C.nrm_t = normals + (fb + fi) * (size_t)D.npix;
-    C.fx = D.fx; C.fy = D.fy; C.cx = D.cx; C.cy = D.cy; C.depth_min = D.depth_min; C.depth_max = D.depth_max;
-    C.normal_thresh = D.normal_thresh; C.dist2_thresh = D.dist_thresh * D.dist_thresh;
-    C.delta = D.robust_delta; C.delta2 = D.robust_delta * D.robust_delta; C.w_dense = D.w_dense;
-    C.W = D.width; C.H = D.height;
+    dense_M_store(threadIdx.x, red, dense_M_load(threadIdx.x, T + pb + 16 * fi));
+    const DenseCtx C = dense_ctx(D, T, Tinv, pb, fi, fj, campos + (fb + fi) * (size_t)D.npix, normals + (fb + fi) * (size_t)D.npix);
     const float4 *cam_s = campos + (fb + fj) * (size_t)D.npix, *nrm_s = normals + (fb + fj) * (size_t)D.npix;
     const int per = (D.npix + D.dense_tiles - 1) / D.dense_tiles;
     const int lo = min(D.npix, per * tile), hi = min(D.npix, per * (tile + 1));
@@ -795,8 +815,7 @@ __device__ __forceinline__ void dense_block(const SolveDims &D, const float4 *__
             pixel_accumulate(C, g, c00, c10, c01, c11, n00, n10, n01, n11, acc);
         }
     }
-    float *out = partials + ((unsigned)b * D.dp_stride + (unsigned)(D.atomic_sums ? p : p * D.dense_tiles + tile) * (unsigned)kDenseVals);
-    dense_epilogue(acc, red, out, D.atomic_sums ? 1 : D.publish ? 2 : 0);
+    dense_epilogue(acc, red, dense_record_out(D, partials, p, tile, b), dense_record_mode(D));
 }
 
 // ---- per-block depth ranges of the compact cache ------------------------------------------------------------------
@@ -883,36 +902,28 @@ __global__ void __launch_bounds__(1024) k_valid_lists(int npix, const float4 *__
 }
 
 // The same sweep on the compact cache: ONE 16-byte load per source pixel and per tap (5 loads instead of 10),
-// camera-space points re-derived from z with the cache builder's exact arithmetic (zn_backproject).
-template <bool SIMPLE, bool LISTS>
+// camera-space points re-derived from z with the cache builder's exact arithmetic (zn_backproject).  General intrinsics only (skew, or a projective
+// last row): every pinhole case is dense_block_pinhole's.
+template <bool LISTS>
 __device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 *__restrict__ zn, const int2 ij,
                                                const float *__restrict__ T, const float *__restrict__ Tinv,
                                                float *__restrict__ partials, int tile, int p, int b, float *red,
                                                const uint32_t *__restrict__ valid_lists, const int *__restrict__ valid_counts, float *lut)
 {
-    // lut[0 .. Wd) = (float) full-res column of cache column x, lut[Wd .. Wd+Hd) the same for rows (SIMPLE: already
-    // folded with the inverse intrinsics): the per-coordinate arithmetic becomes one LDS read
-    for (int e = (int)threadIdx.x; e < D.width + D.height; e += kBlock) {
-        const bool is_x = e < D.width;
-        const float c = (float)(is_x ? zn_src_coord(e, D.zn_scale_w) : zn_src_coord(e - D.width, D.zn_scale_h));
-        lut[e] = SIMPLE ? (is_x ? D.zn_ki[0] * c + D.zn_ki[2] : D.zn_ki[5] * c + D.zn_ki[6]) : c;      // see zn_backproject
-    }
+    // lut[0 .. Wd) = (float) full-res column of cache column x, lut[Wd .. Wd+Hd) the same for rows: the per-coordinate
+    // arithmetic becomes one LDS read
+    for (int e = (int)threadIdx.x; e < D.width + D.height; e += kBlock)
+        lut[e] = (float)(e < D.width ? zn_src_coord(e, D.zn_scale_w) : zn_src_coord(e - D.width, D.zn_scale_h));
     __syncthreads();
     const float *lut_x = lut, *lut_y = lut + D.width;
     const int fi = ij.x, fj = ij.y;                       // fi = target, fj = source
     const size_t fb = (size_t)b * D.n_frames;
     const unsigned pb = (unsigned)b * (unsigned)D.pose_stride;
-    dense_stage_M(red, T + pb + 16 * fi);
-    DenseCtx C;
-    C.Tij = mat_mul(load_mat4(Tinv + pb + 16 * fi), load_mat4(T + pb + 16 * fj));
+    dense_M_store(threadIdx.x, red, dense_M_load(threadIdx.x, T + pb + 16 * fi));
+    DenseCtx C = dense_ctx(D, T, Tinv, pb, fi, fj, nullptr, nullptr);
     // the relative pose is the same in every lane: keep it in scalar registers (12 VGPRs back)
 #pragma unroll
     for (int e = 0; e < 12; e++) C.Tij.m[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, C.Tij.m[e])));
-    C.cam_t = nullptr; C.nrm_t = nullptr;
-    C.fx = D.fx; C.fy = D.fy; C.cx = D.cx; C.cy = D.cy; C.depth_min = D.depth_min; C.depth_max = D.depth_max;
-    C.normal_thresh = D.normal_thresh; C.dist2_thresh = D.dist_thresh * D.dist_thresh;
-    C.delta = D.robust_delta; C.delta2 = D.robust_delta * D.robust_delta; C.w_dense = D.w_dense;
-    C.W = D.width; C.H = D.height;
     // wave-uniform by construction; readfirstlane tells the compiler, so the frame bases live in SGPRs and the tap
     // gathers use the scalar-base + 32-bit-offset addressing form
     const size_t slot_t = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fi));
@@ -926,9 +937,7 @@ __device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 
     const int per = (n_src + D.dense_tiles - 1) / D.dense_tiles;
     const int lo = min(n_src, per * tile), hi = min(n_src, per * (tile + 1));
     const float inv_w = 1.0f / (float)D.width;
-    float acc[kDenseVals];
-#pragma unroll
-    for (int k = 0; k < kDenseVals; k++) acc[k] = 0.0f;
+    float acc[kDenseVals] = {};
 
     int t = lo + (int)threadIdx.x;
     int s_n = (t < hi) ? (LISTS ? (int)list[t] : t) : 0;
@@ -951,7 +960,7 @@ __device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 
             py += ((py + 1) * D.width <= s) ? 1 : 0;
             px = s - py * D.width;
         }
-        const float3 cp = zn_backproject<SIMPLE>(D.zn_ki, lut_x[px], lut_y[py], zs.x);
+        const float3 cp = zn_backproject(D.zn_ki, lut_x[px], lut_y[py], zs.x);
         const PixelGeom g = pixel_geom(C, make_float4(cp.x, cp.y, cp.z, 1.0f), make_float4(zs.y, zs.z, zs.w, 0.0f));
         if (__builtin_amdgcn_ballot_w64(g.valid) == 0ull) continue;
         // 32-bit byte offsets from a scalar base: one shift per tap instead of a 64-bit shift-add (a frame is far below 4 GB)
@@ -959,17 +968,16 @@ __device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 
         const float4 z00 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i00 << 4)), z10 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i10 << 4));
         const float4 z01 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i01 << 4)), z11 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i11 << 4));
         const float xia = lut_x[g.xa], xib = lut_x[g.xb], yia = lut_y[g.ya], yib = lut_y[g.yb];
-        const float3 c00 = zn_backproject<SIMPLE>(D.zn_ki, xia, yia, z00.x), c10 = zn_backproject<SIMPLE>(D.zn_ki, xib, yia, z10.x);
-        const float3 c01 = zn_backproject<SIMPLE>(D.zn_ki, xia, yib, z01.x), c11 = zn_backproject<SIMPLE>(D.zn_ki, xib, yib, z11.x);
+        const float3 c00 = zn_backproject(D.zn_ki, xia, yia, z00.x), c10 = zn_backproject(D.zn_ki, xib, yia, z10.x);
+        const float3 c01 = zn_backproject(D.zn_ki, xia, yib, z01.x), c11 = zn_backproject(D.zn_ki, xib, yib, z11.x);
         pixel_accumulate(C, g, make_float4(c00.x, c00.y, c00.z, 1.f), make_float4(c10.x, c10.y, c10.z, 1.f), make_float4(c01.x, c01.y, c01.z, 1.f), make_float4(c11.x, c11.y, c11.z, 1.f),
                          make_float4(z00.y, z00.z, z00.w, 0.f), make_float4(z10.y, z10.z, z10.w, 0.f), make_float4(z01.y, z01.z, z01.w, 0.f), make_float4(z11.y, z11.z, z11.w, 0.f), acc);
     }
-    float *out = partials + ((unsigned)b * D.dp_stride + (unsigned)(D.atomic_sums ? p : p * D.dense_tiles + tile) * (unsigned)kDenseVals);
-    dense_epilogue(acc, red, out, D.atomic_sums ? 1 : D.publish ? 2 : 0);
+    dense_epilogue(acc, red, dense_record_out(D, partials, p, tile, b), dense_record_mode(D));
 }
 
 // ---- the dense sweep for pinhole intrinsics on the GATED compact cache --------------------------------------------
-// Same arithmetic per accepted pixel as dense_block_zn<true, .>, re-shaped around what the VALU of gfx950 actually charges
+// Same arithmetic per accepted pixel as the general sweep's (dense_block_zn, with the back-projection bracket tabulated: see zn_backproject), re-shaped around what the VALU of gfx950 actually charges
 // (scripts/valu_calibrate.hip, profiles/r02/valu_calibration.md): a wave64 fp32 mul / add / fma with VGPR sources issues in
 // 2 cycles, but v_cmp*, v_cndmask*, v_cvt*, v_floor, v_min / v_max, v_lshlrev, every VOP3 integer op (v_lshl_add_u32,
 // v_mul_lo_u32, ...) and ANY VALU op with an SGPR source take 4, transcendentals 8.  The old loop spent 71 of its 222
@@ -995,6 +1003,14 @@ struct PinholeCtx {
     float fx, fy, cx, cy, wm1, hm1, wm2, hm2, w16, normal_thresh, dist2_thresh, wdelta, w_dense, ybase4;
     unsigned row16;                   // bytes per cache row
     unsigned zmin_bits, zrange_bits;  // depth_min < z < depth_max  <=>  bits(z) - (bits(depth_min) + 1) < zrange_bits (unsigned)
+    // what the phases of dense_block_pinhole share beside the per-pixel constants above
+    unsigned tid; int p;              // item_tid(); dense pair of the item
+    size_t slot_t, slot_s;            // cache slots of the target and the source frame (scalar registers)
+    int bw, bh, r0, nb;               // block walk: blocks per row and column of the cache, first block row and block count of this item's band
+    const float2 *rng; float2 zr0, zr1;      // block walk: the band's block ranges (nullptr: no block is skipped); those of blocks tid and tid + kBlock, loaded with the poses
+    float *lut; float4 *colA; float *hull; int *hdr; unsigned *blist;      // dynamic LDS (SweepLayout): back-projection terms, rotated rays (colA, rowB behind it), hull entries, the compaction's wave totals, live blocks
+    const float4 *zn_s; const char *tap_row0, *tap_row1;      // the source frame; the target frame's first and second row
+    float lut_addr_f, ybase4_abs;     // LDS byte addresses of the column and the row table, as floats
 };
 
 // 16 bytes at a byte offset, with the constant part of the address as the load's immediate offset (base + zext(byte_off) + IMM in 64 bits: a 32-bit
@@ -1018,15 +1034,13 @@ __device__ __forceinline__ float clamp0_s(float a, float bound) { float r; asm("
 __device__ __forceinline__ float sgpr(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 
 // column / row term of the back-projection of cache column / row e (e >= width: row e - width): K^-1[0][0] x_full(e) + K^-1[0][2] resp.
-// K^-1[1][1] y_full + K^-1[1][2] -- the cache builder's nearest-neighbour source coordinate, zn_backproject<true>'s bracket
+// K^-1[1][1] y_full + K^-1[1][2] -- the cache builder's nearest-neighbour source coordinate, the bracket of zn_backproject's comment
 __device__ __forceinline__ float pinhole_lut_entry(const SolveDims &D, int e)
 {
     const bool is_x = e < D.width;
     const float c = (float)(is_x ? zn_src_coord(e, D.zn_scale_w) : zn_src_coord(e - D.width, D.zn_scale_h));
     return is_x ? D.zn_ki[0] * c + D.zn_ki[2] : D.zn_ki[5] * c + D.zn_ki[6];
 }
-
-constexpr int kMaxBandBlocks = 1024;      // blocks of one band of the block walk: above it solve_enqueue falls back to row strips (the band's index arithmetic below relies on it)
 
 // (The dead-block test of the block walk -- is an 8 x 8 block of the source frame PROVABLY without a pixel that lands in the target image? -- is
 // btba_hull.hpp: plain C++ that the host compiles too.)
@@ -1048,88 +1062,92 @@ __device__ __forceinline__ void dense_work_item(const SolveDims &D, int q, int &
 }
 
 // ---- the dense sweep for pinhole intrinsics on the GATED compact cache --------------------------------------------
-// (the arithmetic per accepted pixel is dense_block_zn<true, .>'s; the shape is what the VALU of gfx950 charges for, see above)
-template <int WALK>     // 0: 64-pixel row strips   1: the source frame's valid-pixel list   2: 8 x 8 pixel blocks per wave (cache width and height multiples of 8)
-__device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const float4 *__restrict__ zn, int q,
-                                                    const float *__restrict__ T, const float *__restrict__ Tinv,
-                                                    float *__restrict__ partials, int tile, int b, float *red,
-                                                    const uint32_t *__restrict__ valid_lists, const int *__restrict__ valid_counts, float *lut)
+// (the arithmetic per accepted pixel is that of dense_block_zn with the back-projection bracket tabulated; the shape is what the VALU of gfx950 charges for, see above)
+// The phases of a pinhole item, in the order dense_block_pinhole runs them.  WALK: 0 64-pixel row strips, 1 the source frame's valid-pixel list,
+// 2 8 x 8 pixel blocks per wave (cache width and height multiples of 8).
+
+// Phase 1, item and poses.  The prologue is ONE round of memory loads, every address a function of the workgroup's grid position: the item (computed, or one
+// scalar load), the two poses (scalar loads: the previous launch wrote them), the target pose for M, the band's block ranges.
+// (Round 2: work table -> poses / ranges -> hull test -> list, four dependent round trips, 7.2 of a workgroup's 39 us.)
+// Returns this thread's entry of M of the epilogue's congruence (dense_M_load), to be stored behind the table fill.
+template <int WALK>
+__device__ __forceinline__ float pinhole_item_and_poses(const SolveDims &D, PinholeCtx &C, int q, const float *__restrict__ T, const float *__restrict__ Tinv, int tile, int b)
 {
-    const unsigned tid = item_tid();
-    // The prologue is ONE round of memory loads, every address a function of the workgroup's grid position: the item (computed, or one
-    // scalar load), the two poses (scalar loads: the previous launch wrote them), the target pose for M, the band's block ranges.
-    // (Round 2: work table -> poses / ranges -> hull test -> list, four dependent round trips, 7.2 of a workgroup's 39 us.)
-    int fi, fj, p;                                        // fi = target, fj = source
-    dense_work_item(D, q, fi, fj, p);
+    C.tid = item_tid();
+    int fi, fj;                                           // fi = target, fj = source
+    dense_work_item(D, q, fi, fj, C.p);
     const size_t fb = (size_t)b * D.n_frames;
-    const size_t slot_t = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fi));
-    const size_t slot_s = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fj));
+    C.slot_t = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fi));
+    C.slot_s = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fj));
     const unsigned pb = (unsigned)b * (unsigned)D.pose_stride;
     const Mat4 Tinv_i = load_mat4_uniform(Tinv + pb + 16 * fi), T_j = load_mat4_uniform(T + pb + 16 * fj);
-    float m_stage = 0.0f;                                 // M of the epilogue's congruence, from the target frame's pose (see dense_stage_M)
-    if (tid >= 64 && tid < 64 + 36) {
-        const float *T_target = T + pb + 16 * fi;
-        const int e = (int)tid - 64, r = e / 6, c = e % 6;
-        if (r < 3) m_stage = (c < 3) ? T_target[4 * r + c] : 0.0f;
-        else {
-            const int qq = r - 3, qa = (qq + 1) % 3, qb = (qq + 2) % 3;     // ([t]x R)[q][c] = t[qa] R[qb][c] - t[qb] R[qa][c]
-            m_stage = (c < 3) ? T_target[4 * qa + 3] * T_target[4 * qb + c] - T_target[4 * qb + 3] * T_target[4 * qa + c] : T_target[4 * qq + (c - 3)];
-        }
-    }
-    const int bw = D.width >> 3, bh = D.height >> 3;
-    const int rows_per = (bh + D.dense_tiles - 1) / D.dense_tiles;
-    const int r0 = min(bh, rows_per * tile), r1 = min(bh, rows_per * (tile + 1));
-    const int nb = (WALK == 2) ? (r1 - r0) * bw : 0;      // blocks of this band (the host keeps it <= kMaxBandBlocks)
-    const float2 *rng = (WALK == 2 && D.block_ranges) ? D.block_ranges + slot_s * (size_t)(bw * bh) + (size_t)r0 * bw : nullptr;
-    const float2 zr0 = (rng && (int)tid < nb) ? rng[tid] : make_float2(0.0f, 0.0f);
-    const float2 zr1 = (rng && (int)tid + kBlock < nb) ? rng[tid + kBlock] : make_float2(0.0f, 0.0f);      // a one-tile band of a 160 x 120 cache holds 300 blocks: both ranges of a lane in the SAME round of loads
+    const float m_stage = dense_M_load(C.tid, T + pb + 16 * fi);
+    C.bw = D.width >> 3; C.bh = D.height >> 3;
+    const int rows_per = (C.bh + D.dense_tiles - 1) / D.dense_tiles;
+    const int r1 = min(C.bh, rows_per * (tile + 1));
+    C.r0 = min(C.bh, rows_per * tile);
+    C.nb = (WALK == 2) ? (r1 - C.r0) * C.bw : 0;          // blocks of this band (the host keeps it <= kMaxBandBlocks)
+    C.rng = (WALK == 2 && D.block_ranges) ? D.block_ranges + C.slot_s * (size_t)(C.bw * C.bh) + (size_t)C.r0 * C.bw : nullptr;
+    C.zr0 = (C.rng && (int)C.tid < C.nb) ? C.rng[C.tid] : make_float2(0.0f, 0.0f);
+    C.zr1 = (C.rng && (int)C.tid + kBlock < C.nb) ? C.rng[C.tid + kBlock] : make_float2(0.0f, 0.0f);      // a one-tile band of a 160 x 120 cache holds 300 blocks: both ranges of a lane in the SAME round of loads
                                                                                                            // (bands of more than 512 blocks fetch the rest in the compaction loop)
-    const int lane_c = (int)tid & 63, wave_c = __builtin_amdgcn_readfirstlane((int)tid >> 6);
     const Mat4 Tij = mat_mul(Tinv_i, T_j);                // source camera -> target camera
-    PinholeCtx C;
 #pragma unroll
     for (int r = 0; r < 3; r++) {
 #pragma unroll
         for (int c = 0; c < 3; c++) C.R[3 * r + c] = sgpr(Tij.m[4 * r + c]);
         C.t[r] = sgpr(Tij.m[4 * r + 3]);
     }
-    // tables in LDS: lut[0 .. Wd) = K^-1[0][0] x_full(x) + K^-1[0][2] per cache column, lut[Wd .. Wd+Hd) the same for rows (the taps' back-projection),
-    // and the ROTATED RAYS: the transformed point of source pixel (x, y) with depth d is q = d (R (lx, ly, 1)) + t = d (colA[x] + rowB[y]) + t with
-    // colA[x] = R[:, 0] lx(x), rowB[y] = R[:, 1] ly(y) + R[:, 2] -- two 16-byte LDS reads, 3 adds and 3 FMAs per pixel instead of 2 reads,
-    // 2 multiplies and 12 operations with a scalar-register operand (which issue at half rate, profiles/r02/valu_calibration.md).  One pass.
-    float4 *colA = reinterpret_cast<float4 *>(lut + ((D.width + D.height + 3) & ~3));
-    float4 *rowB = colA + D.width;
-    for (int e = (int)tid; e < D.width + D.height; e += kBlock) {
+    return m_stage;
+}
+
+// Phase 2, table fill.  Tables in LDS: lut[0 .. Wd) = K^-1[0][0] x_full(x) + K^-1[0][2] per cache column, lut[Wd .. Wd+Hd) the same for rows (the taps' back-projection),
+// and the ROTATED RAYS: the transformed point of source pixel (x, y) with depth d is q = d (R (lx, ly, 1)) + t = d (colA[x] + rowB[y]) + t with
+// colA[x] = R[:, 0] lx(x), rowB[y] = R[:, 1] ly(y) + R[:, 2] -- two 16-byte LDS reads, 3 adds and 3 FMAs per pixel instead of 2 reads,
+// 2 multiplies and 12 operations with a scalar-register operand (which issue at half rate, profiles/r02/valu_calibration.md).  One pass.
+// Behind the tables (SweepLayout): the hull entries of the dead-block test (one per block column and block row, 8 floats apart), the wave totals of the list compaction
+// ([0 .. 8): two blocks per lane and pass, [0 .. 4) first halves, [4 .. 8) second), the list of live blocks.
+template <int WALK>
+__device__ __forceinline__ void pinhole_fill_tables(const SolveDims &D, PinholeCtx &C, float *lut)
+{
+    const SweepLayout L(D.width, D.height, 0, WALK == 2 ? kSweepLdsBlocks : kSweepLdsStrips);      // (no offset depends on the band's size: it only ends the list)
+    char *lds = reinterpret_cast<char *>(lut);
+    C.lut = lut; C.colA = reinterpret_cast<float4 *>(lds + L.colA);
+    C.hull = reinterpret_cast<float *>(lds + L.hull); C.hdr = reinterpret_cast<int *>(lds + L.hdr); C.blist = reinterpret_cast<unsigned *>(lds + L.blist);
+    for (int e = (int)C.tid; e < D.width + D.height; e += kBlock) {
         const float l = pinhole_lut_entry(D, e);
-        lut[e] = l;
-        if (e < D.width) colA[e] = make_float4(C.R[0] * l, C.R[3] * l, C.R[6] * l, 0.0f);
-        else rowB[e - D.width] = make_float4(C.R[1] * l + C.R[2], C.R[4] * l + C.R[5], C.R[7] * l + C.R[8], 0.0f);
+        C.lut[e] = l;
+        // rowB follows colA as the row terms follow the column terms in lut: entry e of both tables is colA[e]
+        if (e < D.width) C.colA[e] = make_float4(C.R[0] * l, C.R[3] * l, C.R[6] * l, 0.0f);
+        else C.colA[e] = make_float4(C.R[1] * l + C.R[2], C.R[4] * l + C.R[5], C.R[7] * l + C.R[8], 0.0f);
     }
-    if (tid >= 64 && tid < 64 + 36) red[4 * kDenseVals + kDenseVals + 4 + ((int)tid - 64)] = m_stage;
-    // behind the tables: the hull entries of the dead-block test (one per block column and block row, 8 floats apart), the wave totals of the list compaction
-    // ([0 .. 8): two blocks per lane and pass, [0 .. 4) first halves, [4 .. 8) second), the list of live blocks
-    float *hull = reinterpret_cast<float *>(rowB + D.height);
-    const int n_ent = bw + bh;
-    int *hdr = reinterpret_cast<int *>(hull + 8 * n_ent);
-    unsigned *blist = reinterpret_cast<unsigned *>(hdr + 8);
+}
+
+// Phase 3, the list of live blocks (WALK 2; the other walks only meet the barrier behind the tables).  Returns the number of list entries.
+// Blocks that are provably dead (btba_hull.hpp: 90 % of the dead ones at c3) are removed BEFORE the walk; the live ones are compacted
+// into an ordered list in LDS (ballot + mbcnt, block order: deterministic) that the four waves share round-robin.
+// The test is SEPARABLE: per block column and block row five extremes of the edge forms (35 entries for a 160 x 120 cache, one lane each, filled by the
+// last wave -- the first one has the second half of a 300-block band to test); a block's verdict is then two 20-byte LDS reads and ~25 operations,
+// where the corner-by-corner evaluation of the forms took ~120 and made wave 0, with two blocks per lane, the slowest of the prologue.
+template <int WALK>
+__device__ __forceinline__ int pinhole_live_blocks(const SolveDims &D, const PinholeCtx &C)
+{
     int n_live = 0;
     if (WALK == 2) {
-        // Blocks that are provably dead (btba_hull.hpp: 90 % of the dead ones at c3) are removed BEFORE the walk; the live ones are compacted
-        // into an ordered list in LDS (ballot + mbcnt, block order: deterministic) that the four waves share round-robin.
-        // The test is SEPARABLE: per block column and block row five extremes of the edge forms (35 entries for a 160 x 120 cache, one lane each, filled by the
-        // last wave -- the first one has the second half of a 300-block band to test); a block's verdict is then two 20-byte LDS reads and ~25 operations,
-        // where the corner-by-corner evaluation of the forms took ~120 and made wave 0, with two blocks per lane, the slowest of the prologue.
+        const unsigned tid = C.tid;
+        const int bw = C.bw, nb = C.nb, r0 = C.r0, n_ent = C.bw + C.bh;
+        const int lane_c = (int)tid & 63, wave_c = __builtin_amdgcn_readfirstlane((int)tid >> 6);
         namespace H = btba_hull;
         const H::HullForms F = H::hull_forms(D.fx, D.fy, D.cx, D.cy, D.width, D.height);
         const H::HullBias hb = H::hull_bias(F, C.t);
-        if (rng) {
+        if (C.rng) {
 #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
             for (int e = (int)tid - (kBlock - 64); e >= 0 && e < n_ent; e += 64) {      // block column e, or block row e - bw, from its first and last pixel's back-projection terms
                 const bool row = e >= bw;
                 const int px = row ? D.width + 8 * (e - bw) : 8 * e;
                 const H::HullEntry h = H::hull_entry(C.R, F, row, pinhole_lut_entry(D, px), pinhole_lut_entry(D, px + 7));
-                *reinterpret_cast<float4 *>(hull + 8 * e) = make_float4(h.lmax, h.rmin, h.tmax, h.bmin);
-                hull[8 * e + 4] = h.zmin;
+                *reinterpret_cast<float4 *>(C.hull + 8 * e) = make_float4(h.lmax, h.rmin, h.tmax, h.bmin);
+                C.hull[8 * e + 4] = h.zmin;
             }
         }
         __syncthreads();                                      // the entries are read by the test
@@ -1139,7 +1157,7 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
         // fresh round of range loads in front of it and two more barriers).  The list keeps its order -- blocks 0 .. 255 of the pass, then 256 .. 511 -- so the walk
         // and every sum are what they were.
         auto is_live = [&](const float2 &zr, int bxl, int byg) {
-            const float *ce = hull + 8 * bxl, *re = hull + 8 * (bw + byg);
+            const float *ce = C.hull + 8 * bxl, *re = C.hull + 8 * (bw + byg);
             const float4 c4 = *reinterpret_cast<const float4 *>(ce), r4 = *reinterpret_cast<const float4 *>(re);
             const H::HullEntry hc = { c4.x, c4.y, c4.z, c4.w, ce[4] }, hr = { r4.x, r4.y, r4.z, r4.w, re[4] };
             return H::hull_block_live(hc, hr, hb, zr.x, zr.y, D.depth_min, D.depth_max);
@@ -1148,35 +1166,39 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
             const int idx0 = c0 + (int)tid, idx1 = idx0 + kBlock;
             bool live0 = false, live1 = false;
             unsigned code0 = 0, code1 = 0;
-            if (idx0 < nb) {
-                const int byl = (int)(((float)idx0 + 0.5f) * inv_bw), bxl = idx0 - byl * bw, byg = r0 + byl;
-                code0 = ((unsigned)byg << 16) | (unsigned)bxl;
-                live0 = rng ? is_live(c0 ? rng[idx0] : zr0, bxl, byg) : true;
-            }
-            if (idx1 < nb) {
-                const int byl = (int)(((float)idx1 + 0.5f) * inv_bw), bxl = idx1 - byl * bw, byg = r0 + byl;
-                code1 = ((unsigned)byg << 16) | (unsigned)bxl;
-                live1 = rng ? is_live(c0 ? rng[idx1] : zr1, bxl, byg) : true;
-            }
+            auto test = [&](int idx, const float2 &zr, unsigned &code, bool &live) {
+                if (idx >= nb) return;
+                const int byl = (int)(((float)idx + 0.5f) * inv_bw), bxl = idx - byl * bw, byg = r0 + byl;
+                code = ((unsigned)byg << 16) | (unsigned)bxl;
+                live = C.rng ? is_live(c0 ? C.rng[idx] : zr, bxl, byg) : true;
+            };
+            test(idx0, C.zr0, code0, live0);
+            test(idx1, C.zr1, code1, live1);
             const unsigned long long bal0 = __builtin_amdgcn_ballot_w64(live0), bal1 = __builtin_amdgcn_ballot_w64(live1);
-            if (lane_c == 0) { hdr[wave_c] = __popcll(bal0); hdr[4 + wave_c] = __popcll(bal1); }
+            if (lane_c == 0) { C.hdr[wave_c] = __popcll(bal0); C.hdr[4 + wave_c] = __popcll(bal1); }
             __syncthreads();
             int base0 = n_live, total0 = 0, base1 = 0, total1 = 0;
 #pragma unroll
             for (int w = 0; w < kBlock / 64; w++) {
-                const int t0 = hdr[w], t1 = hdr[4 + w];
+                const int t0 = C.hdr[w], t1 = C.hdr[4 + w];
                 if (w < wave_c) { base0 += t0; base1 += t1; }
                 total0 += t0; total1 += t1;
             }
             base1 += n_live + total0;
             const int before0 = __builtin_amdgcn_mbcnt_hi((unsigned)(bal0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal0, 0));
             const int before1 = __builtin_amdgcn_mbcnt_hi((unsigned)(bal1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal1, 0));
-            if (live0) blist[base0 + before0] = code0;
-            if (live1) blist[base1 + before1] = code1;
+            if (live0) C.blist[base0 + before0] = code0;
+            if (live1) C.blist[base1 + before1] = code1;
             n_live += total0 + total1;
             __syncthreads();
         }
     } else __syncthreads();
+    return n_live;
+}
+
+// Phase 4, the per-pixel constants of the walk.
+__device__ __forceinline__ void pinhole_walk_constants(const SolveDims &D, PinholeCtx &C, const float4 *__restrict__ zn)
+{
     C.fx = D.fx; C.fy = D.fy; C.cx = D.cx; C.cy = D.cy;
     // the clamp bounds come from the host: a float the kernel makes itself (v_cvt_f32_i32) lives in a VGPR for the whole loop; as kernel arguments
     // they are scalar operands of clamp0_s / min_raw_s
@@ -1186,199 +1208,223 @@ __device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const fl
     C.normal_thresh = D.normal_thresh; C.dist2_thresh = D.dist2_thresh;
     C.wdelta = D.w_dense * D.robust_delta; C.w_dense = D.w_dense;
     C.zmin_bits = __float_as_uint(D.depth_min) + 1u; C.zrange_bits = __float_as_uint(D.depth_max) - __float_as_uint(D.depth_min) - 1u;
-    const float4 *zn_t = zn + slot_t * (size_t)D.npix, *zn_s = zn + slot_s * (size_t)D.npix;
-    constexpr bool LISTS = (WALK == 1);
-    float acc[kDenseVals];
-#pragma unroll
-    for (int k = 0; k < kDenseVals; k++) acc[k] = 0.0f;
-    int n_ok = 0;                                         // accepted pixels of this WAVE (scalar register); joins the record as acc[27] behind the walk
+    C.zn_s = zn + C.slot_s * (size_t)D.npix;
+    C.tap_row0 = reinterpret_cast<const char *>(zn + C.slot_t * (size_t)D.npix); C.tap_row1 = C.tap_row0 + C.row16;
+    C.lut_addr_f = (float)lds_address(C.lut); C.ybase4_abs = C.ybase4 + C.lut_addr_f;
+}
 
-    const char *tap_row0 = reinterpret_cast<const char *>(zn_t), *tap_row1 = tap_row0 + C.row16;
-    const float lut_addr_f = (float)lds_address(lut), ybase4_abs = C.ybase4 + lut_addr_f;
-    // one source pixel: zs = its (gated depth, normal), ox / oy = LDS byte offsets of its column / row entries in the ray tables (from colA)
-    auto pixel = [&](const float4 &zs, unsigned ox, unsigned oy) {
-        // source pixel -> camera space (gated depth: 0 where invalid), depth-range test on the bit pattern
-        const float d = zs.x;
-        const bool src_ok = (__float_as_uint(d) - C.zmin_bits) < C.zrange_bits;
-        // transform the point, project
-        const float4 ra = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(colA) + ox), rb = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(colA) + oy);
-        const float qx = (ra.x + rb.x) * d + C.t[0], qy = (ra.y + rb.y) * d + C.t[1], qz = (ra.z + rb.z) * d + C.t[2];
-        const float rqz = fast_rcp(qz);
-        // (u, v through the compiler's own FMAs, not fma_nd: an inline-asm consumer directly behind v_rcp_f32 is invisible to the hazard recognizer, which then
-        // does not insert the wait state gfx950 needs between a transcendental and a VALU use of its result -- a round-6 build that did so read a stale
-        // reciprocal now and then: non-deterministic poses, 2e-4 off, caught by tests/test_cpp_bundler.py and scripts/r06/determinism.py)
-        const float u = qx * C.fx * rqz + C.cx, v = qy * C.fy * rqz + C.cy;
-        const float uc = clamp0_s(u, C.wm1), vc = clamp0_s(v, C.hm1);      // NaN -> 0: addresses stay in the frame
-        const bool valid = src_ok & (fabsf(u - uc) < 0.5f) & (fabsf(v - vc) < 0.5f);
-        // (the wave's mask of `valid`, AND-ed from the ballots of the single tests: see ok_mask below)
-        const unsigned long long valid_mask = __builtin_amdgcn_ballot_w64(src_ok) & __builtin_amdgcn_ballot_w64(fabsf(u - uc) < 0.5f) & __builtin_amdgcn_ballot_w64(fabsf(v - vc) < 0.5f);
-        if (valid_mask == 0ull) return;
-        // rotate the normal (only the waves that go on need it: half of the block trips end above)
-        const float nqx = C.R[0] * zs.y + C.R[1] * zs.z + C.R[2] * zs.w;
-        const float nqy = C.R[3] * zs.y + C.R[4] * zs.z + C.R[5] * zs.w;
-        const float nqz = C.R[6] * zs.y + C.R[7] * zs.z + C.R[8] * zs.w;
-        // taps (x0, x0 + 1) x (y0, y0 + 1) with x0 = min(floor(uc), W - 2): at the right / bottom edge (uc = W - 1) the weights are (0, 1)
-        // instead of (1, -) -- the same blend, and the four taps are always the 2 x 2 block at ONE computed address
-        const float fx0 = min_raw_s(floorf(uc), C.wm2), fy0 = min_raw_s(floorf(vc), C.hm2);
-        const float alpha = uc - fx0, beta = vc - fy0;
-        // one computed byte offset for the 2 x 2 block: the second row's base is a scalar add (wave-uniform), the + 16 the load's immediate offset field
-        const unsigned o00 = (unsigned)(fy0 * C.w16 + 16.0f * fx0);                             // byte offset, fp32-exact below 2^24
-        // Lanes that already failed the in-image / source-depth tests (8.8 % in the trips that go on, clustered along block edges: profiles/r06/sweep_census.json) issue no
-        // taps.  The texture addresser's service time per gather is exposed almost in full (profiles/r06/bound_probes.json: one more 16-byte gather per trip = +13.4 us
-        // per launch, linear) and it skips idle quads (profiles/r06/taps_exec.json: same bits, -1.5 % on the launch).  The registers of those lanes stay undefined
-        // and are never used: `ok` contains `valid`, and nothing behind `ok` runs for a rejected lane.
-        float4 z00, z10, z01, z11;
+// One source pixel: zs = its (gated depth, normal), ox / oy = LDS byte offsets of its column / row entries in the ray tables (from colA).
+// acc: the lane's 27 sums; n_ok: accepted pixels of this WAVE (scalar register), which joins the record as acc[27] behind the walk.
+__device__ __forceinline__ void pinhole_pixel(const PinholeCtx &C, const float4 &zs, unsigned ox, unsigned oy, float (&acc)[kDenseVals], int &n_ok)
+{
+    // source pixel -> camera space (gated depth: 0 where invalid), depth-range test on the bit pattern
+    const float d = zs.x;
+    const bool src_ok = (__float_as_uint(d) - C.zmin_bits) < C.zrange_bits;
+    // transform the point, project
+    const float4 ra = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(C.colA) + ox), rb = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(C.colA) + oy);
+    const float qx = (ra.x + rb.x) * d + C.t[0], qy = (ra.y + rb.y) * d + C.t[1], qz = (ra.z + rb.z) * d + C.t[2];
+    const float rqz = fast_rcp(qz);
+    // (u, v through the compiler's own FMAs, not fma_nd: an inline-asm consumer directly behind v_rcp_f32 is invisible to the hazard recognizer, which then
+    // does not insert the wait state gfx950 needs between a transcendental and a VALU use of its result -- a round-6 build that did so read a stale
+    // reciprocal now and then: non-deterministic poses, 2e-4 off, caught by tests/test_cpp_bundler.py and scripts/r06/determinism.py)
+    const float u = qx * C.fx * rqz + C.cx, v = qy * C.fy * rqz + C.cy;
+    const float uc = clamp0_s(u, C.wm1), vc = clamp0_s(v, C.hm1);      // NaN -> 0: addresses stay in the frame
+    const bool valid = src_ok & (fabsf(u - uc) < 0.5f) & (fabsf(v - vc) < 0.5f);
+    // (the wave's mask of `valid`, AND-ed from the ballots of the single tests: see ok_mask below)
+    const unsigned long long valid_mask = __builtin_amdgcn_ballot_w64(src_ok) & __builtin_amdgcn_ballot_w64(fabsf(u - uc) < 0.5f) & __builtin_amdgcn_ballot_w64(fabsf(v - vc) < 0.5f);
+    if (valid_mask == 0ull) return;
+    // rotate the normal (only the waves that go on need it: half of the block trips end above)
+    const float nqx = C.R[0] * zs.y + C.R[1] * zs.z + C.R[2] * zs.w;
+    const float nqy = C.R[3] * zs.y + C.R[4] * zs.z + C.R[5] * zs.w;
+    const float nqz = C.R[6] * zs.y + C.R[7] * zs.z + C.R[8] * zs.w;
+    // taps (x0, x0 + 1) x (y0, y0 + 1) with x0 = min(floor(uc), W - 2): at the right / bottom edge (uc = W - 1) the weights are (0, 1)
+    // instead of (1, -) -- the same blend, and the four taps are always the 2 x 2 block at ONE computed address
+    const float fx0 = min_raw_s(floorf(uc), C.wm2), fy0 = min_raw_s(floorf(vc), C.hm2);
+    const float alpha = uc - fx0, beta = vc - fy0;
+    // one computed byte offset for the 2 x 2 block: the second row's base is a scalar add (wave-uniform), the + 16 the load's immediate offset field
+    const unsigned o00 = (unsigned)(fy0 * C.w16 + 16.0f * fx0);                             // byte offset, fp32-exact below 2^24
+    // Lanes that already failed the in-image / source-depth tests (8.8 % in the trips that go on, clustered along block edges: profiles/r06/sweep_census.json) issue no
+    // taps.  The texture addresser's service time per gather is exposed almost in full (profiles/r06/bound_probes.json: one more 16-byte gather per trip = +13.4 us
+    // per launch, linear) and it skips idle quads (profiles/r06/taps_exec.json: same bits, -1.5 % on the launch).  The registers of those lanes stay undefined
+    // and are never used: `ok` contains `valid`, and nothing behind `ok` runs for a rejected lane.
+    float4 z00, z10, z01, z11;
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wconditional-uninitialized"
-        if (valid) { z00 = gather16_imm<0>(tap_row0, o00); z10 = gather16_imm<16>(tap_row0, o00); z01 = gather16_imm<0>(tap_row1, o00); z11 = gather16_imm<16>(tap_row1, o00); }
+    if (valid) { z00 = gather16_imm<0>(C.tap_row0, o00); z10 = gather16_imm<16>(C.tap_row0, o00); z01 = gather16_imm<0>(C.tap_row1, o00); z11 = gather16_imm<16>(C.tap_row1, o00); }
 #pragma clang diagnostic pop
-        const float2 xi2 = lds_f32x2_abs((unsigned)(4.0f * fx0 + lut_addr_f)), yi2 = lds_f32x2_abs((unsigned)(4.0f * fy0 + ybase4_abs));
-        const float a0 = 1.0f - alpha, b0 = 1.0f - beta;
-        // blend of the taps' camera-space points (x = column term * z, y = row term * z, z = gated depth) and normals; the
-        // column / row terms are shared by the taps of a column / row, so they multiply the partial sums:
-        //     cix = xi2.x (t00 + t01) + xi2.y (t10 + t11),  ciy = yi2.x (t00 + t10) + yi2.y (t01 + t11),  ciz = (t00 + t01) + (t10 + t11),  t = c z
-        //     ni  = c00 z00.n + c10 z10.n + c01 z01.n + c11 z11.n
-        // written out as the fused multiply-adds the compiler contracts these expressions to (x y + z w -> fma(x, y, z w), left to right --
-        // the bits of every build since round 1), each as fma_nd: 13 of the 20 were v_fmac whose two multiplicands happened to sit in VGPRs
-        // of the same parity, which issue at half rate (26 of a trip's ~400 issue cycles).
-        const float c00 = b0 * a0, c10 = b0 * alpha, c01 = beta * a0, c11 = beta * alpha;
-        const float t10 = c10 * z10.x, t01 = c01 * z01.x, t11 = c11 * z11.x;
-        const float s0x = fma_nd(c00, z00.x, t01), s0y = fma_nd(c00, z00.x, t10);       // t00 + t01, t00 + t10
-        const float s1x = fma_nd(c10, z10.x, t11), s1y = fma_nd(c01, z01.x, t11);       // t10 + t11, t01 + t11
-        const float cix = fma_nd(xi2.x, s0x, xi2.y * s1x);
-        const float ciy = fma_nd(yi2.x, s0y, yi2.y * s1y);
-        const float ciz = s0x + s1x;
-        const float nix = fma_nd(c11, z11.y, fma_nd(c01, z01.y, fma_nd(c00, z00.y, c10 * z10.y)));
-        const float niy = fma_nd(c11, z11.z, fma_nd(c01, z01.z, fma_nd(c00, z00.z, c10 * z10.z)));
-        const float niz = fma_nd(c11, z11.w, fma_nd(c01, z01.w, fma_nd(c00, z00.w, c10 * z10.w)));
-        const float dx = qx - cix, dy = qy - ciy, dz = qz - ciz;
-        const float dist2 = fma_nd(dz, dz, fma_nd(dx, dx, dy * dy));
-        const float dn = fma_nd(nqz, niz, fma_nd(nqx, nix, nqy * niy));
-        // the accept mask of the wave, AND-ed from the ballots of the single tests (a ballot of one comparison is the comparison's own scalar result; the
-        // ballot of a combined flag is lowered through a select and a second compare)
-        const unsigned long long ok_mask = valid_mask & __builtin_amdgcn_ballot_w64((__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits)
-                                         & __builtin_amdgcn_ballot_w64(dn >= C.normal_thresh) & __builtin_amdgcn_ballot_w64(dist2 <= C.dist2_thresh);
-        // Rejected pixels contribute NOTHING: the count is a popcount of the wave's accept mask in a scalar register, and the residual, the weight, the row
-        // and the 27 accumulates run under the exec mask of `ok` like the taps above.  A sum that is not added to equals the sum that got + 0.0f (the
-        // accumulators start at + 0.0f and so never hold - 0.0f), so every sum keeps its bits; a rejected lane's blend -- undefined taps, a NaN or inf target
-        // normal -- is never read past `ok`.
-        n_ok += __popcll(ok_mask);
-        if (__builtin_amdgcn_inverse_ballot_w64(ok_mask)) {
-            // SIGNS: the row is accumulated as a+ = [n_i ; n_i x q] and the residual as res+ = (q - c_i) . n_i, i.e. a = D a+ with
-            // D = diag(-1, -1, -1, 1, 1, 1) and res = -res+ (SolverBundlingDenseUtil.h:78-110, LieDerivUtil.h:228-273).  Then S = D S+ D and
-            // g = -D g+ : exact sign changes of whole sums, applied once per workgroup in the epilogue instead of four negations per pixel.
-            const float res = fma_nd(dz, niz, fma_nd(dx, nix, dy * niy));
-            // Huber (SolverBundlingUtil.h:24-40) times the dense weight: rho' = 1 for e <= delta^2, delta / sqrt(e) above  <=>  min(1, delta rsq(e))
-            // (res = 0: rsq(0) = inf, min(inf, w) = w).
-            const float wgt = min_raw_s(C.wdelta * fast_rsq(res * res), C.w_dense);
-            const float a[6] = { nix, niy, niz, niy * qz - niz * qy, niz * qx - nix * qz, nix * qy - niy * qx };
-            int k = 0;
-            // acc += wa_r * a_c is a read-modify-write FMA: it issues at full rate only when its two multiplicands sit in VGPRs of
-            // different parity (profiles/r02/valu_calibration.md).  (wa_r, a_r) held as an aligned register PAIR puts every wa in an
-            // even and every a in an odd register, whatever the allocator does with the rest.
-            typedef float f2v __attribute__((ext_vector_type(2)));
-            f2v pr[6];
+    const float2 xi2 = lds_f32x2_abs((unsigned)(4.0f * fx0 + C.lut_addr_f)), yi2 = lds_f32x2_abs((unsigned)(4.0f * fy0 + C.ybase4_abs));
+    const float a0 = 1.0f - alpha, b0 = 1.0f - beta;
+    // blend of the taps' camera-space points (x = column term * z, y = row term * z, z = gated depth) and normals; the
+    // column / row terms are shared by the taps of a column / row, so they multiply the partial sums:
+    //     cix = xi2.x (t00 + t01) + xi2.y (t10 + t11),  ciy = yi2.x (t00 + t10) + yi2.y (t01 + t11),  ciz = (t00 + t01) + (t10 + t11),  t = c z
+    //     ni  = c00 z00.n + c10 z10.n + c01 z01.n + c11 z11.n
+    // written out as the fused multiply-adds the compiler contracts these expressions to (x y + z w -> fma(x, y, z w), left to right --
+    // the bits of every build since round 1), each as fma_nd: 13 of the 20 were v_fmac whose two multiplicands happened to sit in VGPRs
+    // of the same parity, which issue at half rate (26 of a trip's ~400 issue cycles).
+    const float c00 = b0 * a0, c10 = b0 * alpha, c01 = beta * a0, c11 = beta * alpha;
+    const float t10 = c10 * z10.x, t01 = c01 * z01.x, t11 = c11 * z11.x;
+    const float s0x = fma_nd(c00, z00.x, t01), s0y = fma_nd(c00, z00.x, t10);       // t00 + t01, t00 + t10
+    const float s1x = fma_nd(c10, z10.x, t11), s1y = fma_nd(c01, z01.x, t11);       // t10 + t11, t01 + t11
+    const float cix = fma_nd(xi2.x, s0x, xi2.y * s1x);
+    const float ciy = fma_nd(yi2.x, s0y, yi2.y * s1y);
+    const float ciz = s0x + s1x;
+    const float nix = fma_nd(c11, z11.y, fma_nd(c01, z01.y, fma_nd(c00, z00.y, c10 * z10.y)));
+    const float niy = fma_nd(c11, z11.z, fma_nd(c01, z01.z, fma_nd(c00, z00.z, c10 * z10.z)));
+    const float niz = fma_nd(c11, z11.w, fma_nd(c01, z01.w, fma_nd(c00, z00.w, c10 * z10.w)));
+    const float dx = qx - cix, dy = qy - ciy, dz = qz - ciz;
+    const float dist2 = fma_nd(dz, dz, fma_nd(dx, dx, dy * dy));
+    const float dn = fma_nd(nqz, niz, fma_nd(nqx, nix, nqy * niy));
+    // the accept mask of the wave, AND-ed from the ballots of the single tests (a ballot of one comparison is the comparison's own scalar result; the
+    // ballot of a combined flag is lowered through a select and a second compare)
+    const unsigned long long ok_mask = valid_mask & __builtin_amdgcn_ballot_w64((__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits)
+                                     & __builtin_amdgcn_ballot_w64(dn >= C.normal_thresh) & __builtin_amdgcn_ballot_w64(dist2 <= C.dist2_thresh);
+    // Rejected pixels contribute NOTHING: the count is a popcount of the wave's accept mask in a scalar register, and the residual, the weight, the row
+    // and the 27 accumulates run under the exec mask of `ok` like the taps above.  A sum that is not added to equals the sum that got + 0.0f (the
+    // accumulators start at + 0.0f and so never hold - 0.0f), so every sum keeps its bits; a rejected lane's blend -- undefined taps, a NaN or inf target
+    // normal -- is never read past `ok`.
+    n_ok += __popcll(ok_mask);
+    if (__builtin_amdgcn_inverse_ballot_w64(ok_mask)) {
+        // SIGNS: the row is accumulated as a+ = [n_i ; n_i x q] and the residual as res+ = (q - c_i) . n_i, i.e. a = D a+ with
+        // D = diag(-1, -1, -1, 1, 1, 1) and res = -res+ (SolverBundlingDenseUtil.h:78-110, LieDerivUtil.h:228-273).  Then S = D S+ D and
+        // g = -D g+ : exact sign changes of whole sums, applied once per workgroup in the epilogue instead of four negations per pixel.
+        const float res = fma_nd(dz, niz, fma_nd(dx, nix, dy * niy));
+        // Huber (SolverBundlingUtil.h:24-40) times the dense weight: rho' = 1 for e <= delta^2, delta / sqrt(e) above  <=>  min(1, delta rsq(e))
+        // (res = 0: rsq(0) = inf, min(inf, w) = w).
+        const float wgt = min_raw_s(C.wdelta * fast_rsq(res * res), C.w_dense);
+        const float a[6] = { nix, niy, niz, niy * qz - niz * qy, niz * qx - nix * qz, nix * qy - niy * qx };
+        int k = 0;
+        // acc += wa_r * a_c is a read-modify-write FMA: it issues at full rate only when its two multiplicands sit in VGPRs of
+        // different parity (profiles/r02/valu_calibration.md).  (wa_r, a_r) held as an aligned register PAIR puts every wa in an
+        // even and every a in an odd register, whatever the allocator does with the rest.
+        typedef float f2v __attribute__((ext_vector_type(2)));
+        f2v pr[6];
 #pragma unroll
-            for (int r = 0; r < 6; r++) { pr[r] = (f2v){ wgt * a[r], a[r] }; asm volatile("" : "+v"(pr[r])); }
-            f2v rr = (f2v){ wgt, res };
-            asm volatile("" : "+v"(rr));
+        for (int r = 0; r < 6; r++) { pr[r] = (f2v){ wgt * a[r], a[r] }; asm volatile("" : "+v"(pr[r])); }
+        f2v rr = (f2v){ wgt, res };
+        asm volatile("" : "+v"(rr));
 #pragma unroll
-            for (int r = 0; r < 6; r++) {
+        for (int r = 0; r < 6; r++) {
 #pragma unroll
-                for (int c = r; c < 6; c++) acc[k++] += pr[r].x * pr[c].y;
-                acc[21 + r] += pr[r].x * rr.y;
-            }
-        }
-    };
-
-    if (WALK == 2) {
-        // Waves walk 8 x 8 pixel blocks of this band of block rows; lane = (row, column) inside the block.  The region of a source
-        // frame that projects into the target is a compact blob, so whole blocks fall outside it (51 % of them at c3; 64 x 1 strips:
-        // 31 %), and a block's taps land in a compact patch of the target.  The list holds the blocks that are not provably dead.
-        const int lane = (int)tid & 63, wave = __builtin_amdgcn_readfirstlane((int)tid >> 6);
-        n_live = __builtin_amdgcn_readfirstlane(n_live);
-        if (D.live_blocks && tid == 0) atomicAdd(D.live_blocks, (unsigned long long)n_live);
-        const unsigned lx = (unsigned)lane & 7u, ly = (unsigned)lane >> 3;
-        const unsigned lane_px = ly * (unsigned)D.width + lx;          // pixel offset of the lane inside its block
-        const unsigned ox_l = 16u * lx, oy_l = 16u * ly + 16u * (unsigned)D.width;
-        unsigned lane_off16 = 16u * lane_px;
-        constexpr unsigned kBlockStep = 128u;            // 8 entries of 16 bytes
-        // This wave's blocks: list entries wave, wave + 4, ... -- nt of them.  While block i is worked on, block i + 1's pixels are in flight.
-        // The prefetch is UNCONDITIONAL (the last trip re-reads its own block): with a conditional one the number of loads in flight behind it
-        // depended on the path taken and the compiler had to wait for ALL of them (`s_waitcnt vmcnt(0)` right behind the prefetch it had just
-        // issued: the stream latency was paid in full on every trip, 2 % of the launch); now the wait for the current block's pixels is `vmcnt(1)`.
-        // (Reading the list entry one more trip ahead, so that the prefetch is issued from a scalar register without an LDS round trip in
-        // front of it: no change, r03 call 40.)
-        // Two trips per loop iteration with the two register sets swapping roles: a single-trip loop rotates (next -> current) through
-        // eight v_mov per trip, 5 % of its instructions.
-        const int nt = (n_live > wave) ? (n_live - wave + kBlock / 64 - 1) / (kBlock / 64) : 0;
-        // this wave's list entries ride in a register, 64 at a time (lane l: entry 64 c + l of the wave), and a trip takes its entry with v_readlane_b32:
-        // no LDS round trip (address move, ds_read, wait, readfirstlane) at the top of every trip
-        int list_chunk = 0;
-        unsigned list_reg = nt > 0 ? blist[wave + (kBlock / 64) * min(lane, nt - 1)] : 0u;
-        auto fetch = [&](int i, unsigned &code, float4 &zs) {
-            const int idx = min(i, nt - 1);
-            if ((idx >> 6) != list_chunk) { list_chunk = idx >> 6; list_reg = blist[wave + (kBlock / 64) * min(64 * list_chunk + lane, nt - 1)]; }
-            code = (unsigned)__builtin_amdgcn_readlane((int)list_reg, idx & 63);
-            // block base in the scalar address (wave-uniform), the lane's pixel inside the block as the constant vector offset: no vector add per trip
-            // (the lane offset goes through an opaque copy: seen as loop-invariant, `frame base + lane offset` is hoisted as a 64-bit VECTOR address and the block
-            // offset becomes a 64-bit vector add per trip)
-            asm volatile("" : "+v"(lane_off16));          // (in place: no copy)
-            zs = gather16_imm<0>(reinterpret_cast<const char *>(zn_s) + (size_t)(16u * ((code >> 16) * 8u * (unsigned)D.width + (code & 0xFFFFu) * 8u)), lane_off16);
-        };
-        auto work = [&](const float4 &zs, unsigned code) { pixel(zs, ox_l + kBlockStep * (code & 0xFFFFu), oy_l + kBlockStep * (code >> 16)); };
-        if (nt > 0) {
-            unsigned code_a, code_b = 0u;
-            float4 zs_a, zs_b = make_float4(0.f, 0.f, 0.f, 0.f);
-            fetch(0, code_a, zs_a);
-            for (int i = 0;;) {
-                fetch(i + 1, code_b, zs_b);
-                work(zs_a, code_a);
-                if (++i >= nt) break;
-                fetch(i + 1, code_a, zs_a);
-                work(zs_b, code_b);
-                if (++i >= nt) break;
-            }
-        }
-    } else {
-        const int n_src = LISTS ? valid_counts[slot_s] : D.npix;
-        const uint32_t *list = LISTS ? valid_lists + slot_s * (size_t)D.npix : nullptr;
-        const int per = (n_src + D.dense_tiles - 1) / D.dense_tiles;
-        const int lo = min(n_src, per * tile), hi = min(n_src, per * (tile + 1));
-        const float inv_w = 1.0f / (float)D.width;
-        int t = lo + (int)tid;
-        int s_n = (t < hi) ? (LISTS ? (int)list[t] : t) : 0;
-        // direct walk: LDS byte offsets of the pixel's column / row entries (row table behind the column table), advanced by
-        // one workgroup stride per trip
-        const unsigned w4 = 4u * (unsigned)D.width;
-        unsigned px4 = 4u * (unsigned)(s_n % D.width), py4 = 4u * (unsigned)(s_n / D.width) + w4;
-        const unsigned step_x4 = 4u * (unsigned)(kBlock % D.width), step_y4 = 4u * (unsigned)(kBlock / D.width);
-        float4 zs_n = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t < hi) zs_n = zn_s[s_n];
-        for (; t < hi; t += kBlock) {
-            const float4 zs = zs_n;
-            const int s = s_n;
-            // next pixel's stream loads, UNCONDITIONAL like the block walk's (the last trip re-reads the lane's last pixel): the wait for
-            // this trip's taps then does not have to cover a load that only some paths issue
-            const int tn = min(t + (int)kBlock, hi - 1);
-            s_n = LISTS ? (int)list[tn] : tn; zs_n = zn_s[s_n];
-            unsigned ox, oy;
-            if (!LISTS) {
-                ox = px4; oy = py4;
-                px4 += step_x4; py4 += step_y4;
-                if (px4 >= w4) { px4 -= w4; py4 += 4u; }
-            } else {
-                const float sf = (float)s;
-                const float pyf = floorf((sf + 0.5f) * inv_w);              // exact: the margin 0.5 / W is far above the rounding of the product
-                ox = (unsigned)(4.0f * (sf - pyf * (float)D.width)); oy = (unsigned)(4.0f * pyf + C.ybase4);
-            }
-            pixel(zs, 4u * ox, 4u * oy);                  // 4-byte table offsets -> 16-byte entries (rowB follows colA as the row table follows the column table)
+            for (int c = r; c < 6; c++) acc[k++] += pr[r].x * pr[c].y;
+            acc[21 + r] += pr[r].x * rr.y;
         }
     }
+}
+
+// Phase 5 (WALK 2).  Waves walk 8 x 8 pixel blocks of this band of block rows; lane = (row, column) inside the block.  The region of a source
+// frame that projects into the target is a compact blob, so whole blocks fall outside it (51 % of them at c3; 64 x 1 strips:
+// 31 %), and a block's taps land in a compact patch of the target.  The list holds the blocks that are not provably dead.
+__device__ __forceinline__ void walk_blocks(const SolveDims &D, const PinholeCtx &C, int n_live, float (&acc)[kDenseVals], int &n_ok)
+{
+    const int lane = (int)C.tid & 63, wave = __builtin_amdgcn_readfirstlane((int)C.tid >> 6);
+    n_live = __builtin_amdgcn_readfirstlane(n_live);
+    if (D.live_blocks && C.tid == 0) atomicAdd(D.live_blocks, (unsigned long long)n_live);
+    const unsigned lx = (unsigned)lane & 7u, ly = (unsigned)lane >> 3;
+    const unsigned lane_px = ly * (unsigned)D.width + lx;          // pixel offset of the lane inside its block
+    const unsigned ox_l = 16u * lx, oy_l = 16u * ly + 16u * (unsigned)D.width;
+    unsigned lane_off16 = 16u * lane_px;
+    constexpr unsigned kBlockStep = 128u;            // 8 entries of 16 bytes
+    // This wave's blocks: list entries wave, wave + 4, ... -- nt of them.  While block i is worked on, block i + 1's pixels are in flight.
+    // The prefetch is UNCONDITIONAL (the last trip re-reads its own block): with a conditional one the number of loads in flight behind it
+    // depended on the path taken and the compiler had to wait for ALL of them (`s_waitcnt vmcnt(0)` right behind the prefetch it had just
+    // issued: the stream latency was paid in full on every trip, 2 % of the launch); now the wait for the current block's pixels is `vmcnt(1)`.
+    // (Reading the list entry one more trip ahead, so that the prefetch is issued from a scalar register without an LDS round trip in
+    // front of it: no change, r03 call 40.)
+    // Two trips per loop iteration with the two register sets swapping roles: a single-trip loop rotates (next -> current) through
+    // eight v_mov per trip, 5 % of its instructions.
+    const int nt = (n_live > wave) ? (n_live - wave + kBlock / 64 - 1) / (kBlock / 64) : 0;
+    // this wave's list entries ride in a register, 64 at a time (lane l: entry 64 c + l of the wave), and a trip takes its entry with v_readlane_b32:
+    // no LDS round trip (address move, ds_read, wait, readfirstlane) at the top of every trip
+    int list_chunk = 0;
+    unsigned list_reg = nt > 0 ? C.blist[wave + (kBlock / 64) * min(lane, nt - 1)] : 0u;
+    auto fetch = [&](int i, unsigned &code, float4 &zs) {
+        const int idx = min(i, nt - 1);
+        if ((idx >> 6) != list_chunk) { list_chunk = idx >> 6; list_reg = C.blist[wave + (kBlock / 64) * min(64 * list_chunk + lane, nt - 1)]; }
+        code = (unsigned)__builtin_amdgcn_readlane((int)list_reg, idx & 63);
+        // block base in the scalar address (wave-uniform), the lane's pixel inside the block as the constant vector offset: no vector add per trip
+        // (the lane offset goes through an opaque copy: seen as loop-invariant, `frame base + lane offset` is hoisted as a 64-bit VECTOR address and the block
+        // offset becomes a 64-bit vector add per trip)
+        asm volatile("" : "+v"(lane_off16));          // (in place: no copy)
+        zs = gather16_imm<0>(reinterpret_cast<const char *>(C.zn_s) + (size_t)(16u * ((code >> 16) * 8u * (unsigned)D.width + (code & 0xFFFFu) * 8u)), lane_off16);
+    };
+    auto work = [&](const float4 &zs, unsigned code) { pinhole_pixel(C, zs, ox_l + kBlockStep * (code & 0xFFFFu), oy_l + kBlockStep * (code >> 16), acc, n_ok); };
+    if (nt > 0) {
+        unsigned code_a, code_b = 0u;
+        float4 zs_a, zs_b = make_float4(0.f, 0.f, 0.f, 0.f);
+        fetch(0, code_a, zs_a);
+        for (int i = 0;;) {
+            fetch(i + 1, code_b, zs_b);
+            work(zs_a, code_a);
+            if (++i >= nt) break;
+            fetch(i + 1, code_a, zs_a);
+            work(zs_b, code_b);
+            if (++i >= nt) break;
+        }
+    }
+}
+
+// Phase 5 (WALK 0 and 1): this tile's share of the source frame's pixels (LISTS: of its valid-pixel list), one pixel per lane and trip.
+template <bool LISTS>
+__device__ __forceinline__ void walk_strips(const SolveDims &D, const PinholeCtx &C, int tile, const uint32_t *__restrict__ valid_lists, const int *__restrict__ valid_counts, float (&acc)[kDenseVals], int &n_ok)
+{
+    const int n_src = LISTS ? valid_counts[C.slot_s] : D.npix;
+    const uint32_t *list = LISTS ? valid_lists + C.slot_s * (size_t)D.npix : nullptr;
+    const int per = (n_src + D.dense_tiles - 1) / D.dense_tiles;
+    const int lo = min(n_src, per * tile), hi = min(n_src, per * (tile + 1));
+    const float inv_w = 1.0f / (float)D.width;
+    int t = lo + (int)C.tid;
+    int s_n = (t < hi) ? (LISTS ? (int)list[t] : t) : 0;
+    // direct walk: LDS byte offsets of the pixel's column / row entries (row table behind the column table), advanced by
+    // one workgroup stride per trip
+    const unsigned w4 = 4u * (unsigned)D.width;
+    unsigned px4 = 4u * (unsigned)(s_n % D.width), py4 = 4u * (unsigned)(s_n / D.width) + w4;
+    const unsigned step_x4 = 4u * (unsigned)(kBlock % D.width), step_y4 = 4u * (unsigned)(kBlock / D.width);
+    float4 zs_n = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t < hi) zs_n = C.zn_s[s_n];
+    for (; t < hi; t += kBlock) {
+        const float4 zs = zs_n;
+        const int s = s_n;
+        // next pixel's stream loads, UNCONDITIONAL like the block walk's (the last trip re-reads the lane's last pixel): the wait for
+        // this trip's taps then does not have to cover a load that only some paths issue
+        const int tn = min(t + (int)kBlock, hi - 1);
+        s_n = LISTS ? (int)list[tn] : tn; zs_n = C.zn_s[s_n];
+        unsigned ox, oy;
+        if (!LISTS) {
+            ox = px4; oy = py4;
+            px4 += step_x4; py4 += step_y4;
+            if (px4 >= w4) { px4 -= w4; py4 += 4u; }
+        } else {
+            const float sf = (float)s;
+            const float pyf = floorf((sf + 0.5f) * inv_w);              // exact: the margin 0.5 / W is far above the rounding of the product
+            ox = (unsigned)(4.0f * (sf - pyf * (float)D.width)); oy = (unsigned)(4.0f * pyf + C.ybase4);
+        }
+        pinhole_pixel(C, zs, 4u * ox, 4u * oy, acc, n_ok);      // 4-byte table offsets -> 16-byte entries (rowB follows colA as the row table follows the column table)
+    }
+}
+
+// Phase 6, epilogue: the wave's count joins the sums, then the workgroup's record (dense_epilogue, with the signs of pinhole_pixel's row put right).
+__device__ __forceinline__ void pinhole_epilogue(const SolveDims &D, const PinholeCtx &C, float (&acc)[kDenseVals], int n_ok, float *red, float *__restrict__ partials, int tile, int b)
+{
     // the wave's count, converted once: an integer far below 2^24 in one lane and zeros in the others fold to the float the per-lane counts summed to
-    acc[27] = (tid & 63u) == 0u ? (float)n_ok : 0.0f;
-    float *out = partials + ((unsigned)b * D.dp_stride + (unsigned)(D.atomic_sums ? p : p * D.dense_tiles + tile) * (unsigned)kDenseVals);
-    dense_epilogue<true>(acc, red, out, D.atomic_sums ? 1 : D.publish ? 2 : 0);
+    acc[27] = (C.tid & 63u) == 0u ? (float)n_ok : 0.0f;
+    dense_epilogue<true>(acc, red, dense_record_out(D, partials, C.p, tile, b), dense_record_mode(D));
+}
+
+template <int WALK>
+__device__ __forceinline__ void dense_block_pinhole(const SolveDims &D, const float4 *__restrict__ zn, int q, const float *__restrict__ T, const float *__restrict__ Tinv, float *__restrict__ partials,
+                                                    int tile, int b, float *red, const uint32_t *__restrict__ valid_lists, const int *__restrict__ valid_counts, float *lut)
+{
+    PinholeCtx C;
+    const float m_stage = pinhole_item_and_poses<WALK>(D, C, q, T, Tinv, tile, b);
+    pinhole_fill_tables<WALK>(D, C, lut);
+    dense_M_store(C.tid, red, m_stage);
+    const int n_live = pinhole_live_blocks<WALK>(D, C);
+    pinhole_walk_constants(D, C, zn);
+    float acc[kDenseVals] = {};
+    int n_ok = 0;
+    if (WALK == 2) walk_blocks(D, C, n_live, acc, n_ok);
+    else walk_strips<WALK == 1>(D, C, tile, valid_lists, valid_counts, acc, n_ok);
+    pinhole_epilogue(D, C, acc, n_ok, red, partials, tile, b);
 }
 
 template <bool SIMPLE, bool LISTS>
@@ -1388,15 +1434,13 @@ __global__ void __launch_bounds__(kBlock, 5) k_dense_sweep_zn(SolveDims D, const
 {
     __shared__ float red[kRedFloats];
     extern __shared__ __attribute__((aligned(16))) float zn_lut[];        // (Wd + Hd) floats
-    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile = (int)(L % (unsigned)D.dense_tiles);
-    const int p = (int)((L / (unsigned)D.dense_tiles) % (unsigned)D.n_dense_pairs);
-    const int b = (int)(L / ((unsigned)D.dense_tiles * (unsigned)D.n_dense_pairs));
+    int tile, p, b;
+    dense_grid_decode(D, xcd_remap(blockIdx.x, gridDim.x), tile, p, b);
     // pinhole intrinsics: the same block as in the fused launch (same partial sums, bit for bit); `p` is then a WORK POSITION (dense_work_item)
     if (SIMPLE && LISTS) dense_block_pinhole<1>(D, zn, p, T, Tinv, partials, tile, b, red, valid_lists, valid_counts, zn_lut);
     else if (SIMPLE && D.walk_blocks) dense_block_pinhole<2>(D, zn, p, T, Tinv, partials, tile, b, red, valid_lists, valid_counts, zn_lut);
     else if (SIMPLE) dense_block_pinhole<0>(D, zn, p, T, Tinv, partials, tile, b, red, valid_lists, valid_counts, zn_lut);
-    else dense_block_zn<false, LISTS>(D, zn, dense_pairs[p], T, Tinv, partials, tile, p, b, red, valid_lists, valid_counts, zn_lut);
+    else dense_block_zn<LISTS>(D, zn, dense_pairs[p], T, Tinv, partials, tile, p, b, red, valid_lists, valid_counts, zn_lut);
 }
 
 // 1-D grid of dense_tiles * Pd * B workgroups (XCD-remapped).
@@ -1405,10 +1449,8 @@ __global__ void __launch_bounds__(kBlock, 3) k_dense_sweep(SolveDims D, const fl
                                                               float *__restrict__ partials)
 {
     __shared__ float red[kRedFloats];
-    const unsigned L = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile = (int)(L % (unsigned)D.dense_tiles);
-    const int p = (int)((L / (unsigned)D.dense_tiles) % (unsigned)D.n_dense_pairs);
-    const int b = (int)(L / ((unsigned)D.dense_tiles * (unsigned)D.n_dense_pairs));
+    int tile, p, b;
+    dense_grid_decode(D, xcd_remap(blockIdx.x, gridDim.x), tile, p, b);
     dense_block(D, campos, normals, dense_pairs[p], T, Tinv, partials, tile, p, b, red);
 }
 
@@ -1416,9 +1458,6 @@ __global__ void __launch_bounds__(kBlock, 3) k_dense_sweep(SolveDims D, const fl
 // n_s sparse workgroups (HBM-streaming) so the two overlap on every CU instead of running back to back.
 // Per XCD x (blocks g = 8 s + x, s = slot): a contiguous range of dense items (L2 locality, as in xcd_remap)
 // and every R_x-th slot a sparse item.
-#ifndef BTBA_FUSED_WAVES
-#define BTBA_FUSED_WAVES 3
-#endif
 template <int LAYOUT>   // 0: float4 camPos + float4 normals; compact cache: 1 zero-skew K, 2 general K, 3 / 4 the same walking valid-pixel lists
 __device__ __forceinline__ void fused_item(const SolveDims &D, unsigned n_d, unsigned n_s, unsigned g,
                                            const float4 *__restrict__ campos, const float4 *__restrict__ normals,
@@ -1468,8 +1507,8 @@ __device__ __forceinline__ void fused_item(const SolveDims &D, unsigned n_d, uns
             const int2 ij = make_int2(w.x, w.y);
             p = w.z;
             if (LAYOUT == 0) dense_block(D, campos, normals, ij, T, Tinv, dense_partials, tile, p, b, red);
-            else if (LAYOUT == 2) dense_block_zn<false, false>(D, campos, ij, T, Tinv, dense_partials, tile, p, b, red, valid_lists, valid_counts, zn_lut);
-            else dense_block_zn<false, true>(D, campos, ij, T, Tinv, dense_partials, tile, p, b, red, valid_lists, valid_counts, zn_lut);
+            else if (LAYOUT == 2) dense_block_zn<false>(D, campos, ij, T, Tinv, dense_partials, tile, p, b, red, valid_lists, valid_counts, zn_lut);
+            else dense_block_zn<true>(D, campos, ij, T, Tinv, dense_partials, tile, p, b, red, valid_lists, valid_counts, zn_lut);
         }
     }
 }

@@ -12,7 +12,7 @@ from bundletrack_amd import _lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "hip", "btba_probe.hip")
 SO = os.path.join(HERE, "hip", "libbtba_probe.so")
-DEPS = [SRC] + [os.path.join(_lib.SRC_DIR, h) for h in ("btba_device.hpp", "btba_svd3.hpp", "btba_solve_phases.hpp", "btba_kernels.hpp")] + [os.path.abspath(_lib.__file__)]
+DEPS = [SRC] + [os.path.join(_lib.SRC_DIR, h) for h in ("btba_device.hpp", "btba_svd3.hpp", "btba_solve_phases.hpp", "btba_kernels.hpp", "btba_sweep_layout.hpp")] + [os.path.abspath(_lib.__file__)]
 
 # name -> argument types (device pointers as c_void_p); every launcher returns the hipError_t
 SIGNATURES = {

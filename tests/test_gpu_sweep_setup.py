@@ -1,7 +1,8 @@
 """The SET-UP of a dense block-walk item: the separable dead-block test (bundletrack_amd/csrc/btba_hull.hpp) and the list of live blocks built from it.
 
 Three frames of one smooth surface, one instance, the three pairs (target 0, source 1), (0, 2), (1, 2); caches of 16 x 16 (4 blocks), 24 x 16, 72 x 40
-(45 blocks: not a multiple of 64) and one 160 x 120 window (300 blocks: both blocks of a lane).  Frame 1 is moved so that the overlap blob crosses the
+(45 blocks: not a multiple of 64), one 160 x 120 window (300 blocks: both blocks of a lane) and one of 208 x 168 (546 blocks at one tile: the list compaction's
+SECOND pass, which fetches its block ranges inside the loop, handles blocks 512 .. 545 -- less than a wave, a partial ballot).  Frame 1 is moved so that the overlap blob crosses the
 right, left, bottom and top image edge in turn (9.3 cache pixels: one column / row of blocks falls out of the target), frame 2 half as far.  Further:
   sideways  frame 1 turned by 0.9 rad: every block of its pairs lies far outside the target, every corner in front of it -- all dead, records all zeros
   behind    frame 1 turned by 180 degrees: every corner behind the camera plane -- all blocks stay, nothing is accepted, records all zeros
@@ -33,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAIRS = R.PAIRS_FWD
 Z0 = 0.8
 SHIFT = 9.3                     # cache pixels
-SIZES = {"16x16": (16, 16), "24x16": (24, 16), "72x40": (72, 40), "160x120": (160, 120)}
+SIZES = {"16x16": (16, 16), "24x16": (24, 16), "72x40": (72, 40), "160x120": (160, 120), "208x168": (208, 168)}
 _scenes = {}
 
 
@@ -168,9 +169,7 @@ CASES = [(s, c) for s in ("16x16", "24x16", "72x40") for c in ("right", "left", 
         [("72x40", "sideways"), ("72x40", "behind"), ("72x40", "nodepth"), ("160x120", "right"), ("160x120", "top")]
 
 
-@pytest.mark.parametrize("tiles", [1, 2])
-@pytest.mark.parametrize("size,case", CASES, ids=[f"{s}-{c}" for s, c in CASES])
-def test_block_list_set_up(gpu, gamma_d, hull, size, case, tiles):
+def check_block_list_set_up(gpu, gamma_d, hull, size, case, tiles):
     sc = make_scene(size, case)
     WD, HD = SIZES[size]
     nblocks = (WD // 8) * (HD // 8)
@@ -192,6 +191,19 @@ def test_block_list_set_up(gpu, gamma_d, hull, size, case, tiles):
     if case == "nodepth":
         assert host[0] == 0 and host[2] == nblocks and np.all(recs[0] == 0.0) and np.all(recs[2] == 0.0)
     check_records(recs, reference(gpu, sc), gamma_d, f"{size} {case} tiles {tiles}")
+
+
+@pytest.mark.parametrize("tiles", [1, 2])
+@pytest.mark.parametrize("size,case", CASES, ids=[f"{s}-{c}" for s, c in CASES])
+def test_block_list_set_up(gpu, gamma_d, hull, size, case, tiles):
+    check_block_list_set_up(gpu, gamma_d, hull, size, case, tiles)
+
+
+@pytest.mark.parametrize("case", ["right", "top"])
+def test_block_list_second_compaction_pass(gpu, gamma_d, hull, case):
+    """A band of 513 .. 1024 blocks (208 x 168 at one tile: 546) takes two passes of the list compaction; the second one reads its ranges in the loop."""
+    assert 512 < (SIZES["208x168"][0] // 8) * (SIZES["208x168"][1] // 8) <= 1024
+    check_block_list_set_up(gpu, gamma_d, hull, "208x168", case, 1)
 
 
 def test_masked_list_walk_is_untouched(gpu, gamma_d):

@@ -218,6 +218,7 @@ __global__ void __launch_bounds__(64) k_prepare_strided(int total, int n_frames,
     matrix_to_pose(M, rot, trans);
     float *o = x + (size_t)b * x_stride + 6 * f;
     o[0] = rot[0]; o[1] = rot[1]; o[2] = rot[2]; o[3] = trans[0]; o[4] = trans[1]; o[5] = trans[2];
+    se3_opaque(rot, trans);                                        // (as k_prepare: Exp of the pose as a kernel that starts from the stored x forms it)
     const Mat4 E = pose_to_matrix(rot, trans);
     store_mat4(T + (size_t)b * pose_stride + 16 * f, E);
     store_mat4(Tinv + (size_t)b * pose_stride + 16 * f, mat_inverse(E));

@@ -142,6 +142,18 @@ __device__ __forceinline__ void store_mat4(float *p, const Mat4 &m)
     q[3] = make_float4(m.m[12], m.m[13], m.m[14], m.m[15]);
 }
 
+// The compiler forgets where a pose came from.  A kernel that takes Log and then Exp of its result otherwise shares subexpressions between the two
+// (|rot|^2 and what hangs on it) and contracts them into other fused multiply-adds than a kernel that starts from the stored pose: the first
+// iterate's T then differed from k_poses_to_matrices' Exp of the stored x by an ulp in all entries of about one frame in seventeen
+// (tests/test_gpu_solve_stages.py found it: the assembly of iterate 0, fed the seam's matrices, was 4 x its bar out in that frame's blocks).
+// With it, the assembly of iterate 0 meets its bars from btba_matrices_to_poses / btba_poses_to_matrices' (x, T, Tinv) of the same matrices
+// (0.03 ... 0.74 of them).  No test compares the bits: the first T is not in the trace record, and how two kernels contract the same
+// expressions is the compiler's choice.
+__device__ __forceinline__ void se3_opaque(float (&rot)[3], float (&trans)[3])
+{
+    asm volatile("" : "+v"(rot[0]), "+v"(rot[1]), "+v"(rot[2]), "+v"(trans[0]), "+v"(trans[1]), "+v"(trans[2]));
+}
+
 // ---- prepare: Log of the input matrices, then Exp and inverse (SBA.cu:71-79, SolverBundling.cu:890-897)
 // keep_T (developer / experiment builds only, tests/tools/reference_order_experiment.py): the incoming matrix IS the first iterate's T -- no Exp(Log(.)) through
 // the device's libm in between --, so that an experiment can start this path and the oracle from bit-identical matrices
@@ -154,6 +166,7 @@ __global__ void __launch_bounds__(64) k_prepare(int total, const float *__restri
     matrix_to_pose(M, rot, trans);
     if (x) { float *o = x + 6 * (size_t)idx; o[0] = rot[0]; o[1] = rot[1]; o[2] = rot[2]; o[3] = trans[0]; o[4] = trans[1]; o[5] = trans[2]; }
     if (T || Tinv) {
+        se3_opaque(rot, trans);
         Mat4 E = pose_to_matrix(rot, trans);
 #if defined(BTBA_DEV_EXPERIMENTS) || defined(BTBA_REFERENCE_ORDER)
         if (keep_T) E = M;

@@ -211,8 +211,15 @@ def sparse_system(corr, T, prm=None):
                 sM[6 * k:6 * k + 3] += rh.sum()
                 sM[6 * k + 3:6 * k + 6] += (rh[:, None] * sq(Wa[sel])).sum(0)
         Ji, Jj, Ai, Aj = _jblk(wi), _jblk(wj), _jblk(Wi, True), _jblk(Wj, True)
-        for (a_, b_) in sorted(set(zip(ci.tolist(), cj.tolist()))):
-            sel = (ci == a_) & (cj == b_)
+        # one frame pair after the other, each pair's entries in their order of appearance (a stable sort: the same terms in the same order
+        # as a mask per pair, without a pass over all entries per pair)
+        key = ci * N + cj
+        order = np.argsort(key, kind="stable")
+        keys, starts = np.unique(key[order], return_index=True)
+        ends = np.append(starts[1:], order.size)
+        for kk, s0, s1 in zip(keys.tolist(), starts.tolist(), ends.tolist()):
+            a_, b_ = divmod(kk, N)
+            sel = order[s0:s1]
             for (M_, Ja, Jb, sg) in ((A, Ji, Jj, 1.0), (sA, Ai, Aj, -1.0)):
                 if a_ > 0:
                     M_[6 * a_:6 * a_ + 6, 6 * a_:6 * a_ + 6] += ws * np.einsum("nka,nkb->ab", Ja[sel], Ja[sel])
@@ -458,25 +465,28 @@ def sparse_normalised(rhs, precond, A, sp):
     return e_r, e_p, e_A
 
 
-def oracle_sparse_floor(corr, poses):
-    """(rhs, precond, A) normalised errors of the fp32 CPU oracle's first linearisation (feature term only) against the fp64 system at the
+def oracle_sparse_floor(corr, poses, n_gn=1):
+    """(rhs, precond, A) normalised errors of the fp32 CPU oracle's first n_gn linearisations (feature term only) against the fp64 system at the
     oracle's own matrices.  The oracle applies J^T J matrix-free, so its A is read off column by column with unit vectors (sparse_apply)."""
     from oracle import oracle as O
     N = poses.shape[0]
-    T, _ = oracle_matrices(poses)
-    sp = sparse_system(corr, T)
     clean = corr.copy()
     clean["pos_i"][corr["imgIdx_i"] == 0xFFFFFFFF] = 0
     worst = np.zeros(3)
+    zero = np.zeros((N, 2, 2, 4), np.float32)
     for mode in (0, 1):
-        prm = O.default_params(n_gn_iters=1, weight_dense_depth=0.0, accum_mode=mode)
-        tr = O.solve(np.zeros((N, 2, 2, 4), np.float32), np.zeros((N, 2, 2, 4), np.float32), np.array([1, 1, 0, 0], np.float32), clean, poses, params=prm)
-        A = np.zeros((6 * N, 6 * N))
-        for k in range(6, 6 * N):                      # column k in [trans, rot] order; sparse_apply speaks (rot, trans)
-            e = np.zeros(6 * N, np.float32)
-            e[k] = 1
-            col = O.sparse_apply(clean, T, to_rot_trans(e), params=prm).astype(np.float64)
-            A[:, k] = np.concatenate([col[:, 3:], col[:, :3]], 1).reshape(-1)
-        A[:6] = 0
-        worst = np.maximum(worst, sparse_normalised(tr.rhs[0], tr.precond[0], A, sp))
+        prm = O.default_params(n_gn_iters=n_gn, weight_dense_depth=0.0, accum_mode=mode)
+        tr = O.solve(zero, zero, np.array([1, 1, 0, 0], np.float32), clean, poses, params=prm)
+        T, _ = oracle_matrices(poses)
+        for it in range(n_gn):
+            sp = sparse_system(corr, T)
+            A = np.zeros((6 * N, 6 * N))
+            for k in range(6, 6 * N):                      # column k in [trans, rot] order; sparse_apply speaks (rot, trans)
+                e = np.zeros(6 * N, np.float32)
+                e[k] = 1
+                col = O.sparse_apply(clean, T, to_rot_trans(e), params=prm).astype(np.float64)
+                A[:, k] = np.concatenate([col[:, 3:], col[:, :3]], 1).reshape(-1)
+            A[:6] = 0
+            worst = np.maximum(worst, sparse_normalised(tr.rhs[it], tr.precond[it], A, sp))
+            T = tr.T_after[it]
     return tuple(float(w) for w in worst)

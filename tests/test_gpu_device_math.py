@@ -15,11 +15,9 @@ import pytest
 
 import device_probe
 import se3_ref as R
+from shared_checks import A_FAST, A_IEEE, B_FAST, B_IEEE, F32, FAST_VS_IEEE_ULPS, _bound, _ulp      # one copy, shared with test_gpu_solve_stages.py
 
 pytestmark = pytest.mark.gpu
-
-F32 = np.float32
-A_IEEE, B_IEEE, A_FAST, B_FAST, FAST_VS_IEEE_ULPS = 2.0, 4.0, 4.0, 8.0, 8.0
 
 
 @pytest.fixture(scope="module")
@@ -42,10 +40,6 @@ def _empty(*shape, dtype=None):
 def _call(fn, *args):
     rc = fn(*[a.data_ptr() if hasattr(a, "data_ptr") else a for a in args])
     assert rc == 0, f"{fn.__name__}: hipError {rc}"
-
-
-def _ulp(x):
-    return np.spacing(np.abs(np.asarray(x, np.float64)).astype(F32)).astype(np.float64)
 
 
 def _bits(a):
@@ -96,25 +90,6 @@ def _se3_cases(seed=3):
     rot = np.asarray(rot, F32)
     trans = (_axes(rng, len(rot)) * 10.0 ** rng.uniform(-3, 1, (len(rot), 1))).astype(F32)
     return np.array(labels), rot, trans
-
-
-def _bound(stats, labels, name, dev, ora, truth, scale, A, B):
-    """assert |dev - truth| <= A |ora - truth| + B ulp(scale) per component; record the worst ratio per branch"""
-    dev, ora, truth = (np.asarray(v, np.float64) for v in (dev, ora, truth))
-    u = _ulp(scale)
-    while u.ndim < dev.ndim:
-        u = u[..., None]
-    e_dev, e_ora = np.abs(dev - truth), np.abs(ora - truth)
-    ratio = (e_dev / (A * e_ora + B * u)).reshape(len(dev), -1).max(1)
-    ulps = (e_dev / u).reshape(len(dev), -1).max(1)
-    for lab in np.unique(labels):
-        m = labels == lab
-        key = (name, lab)
-        r, q = float(ratio[m].max()), float(ulps[m].max())
-        old = stats.get(key, (0.0, 0.0))
-        stats[key] = (max(old[0], r), max(old[1], q))
-    bad = np.nonzero(~(ratio <= 1.0))[0]
-    return [(name, labels[i], i, float(ratio[i])) for i in bad]
 
 
 def _print_stats(title, stats):

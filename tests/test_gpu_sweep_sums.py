@@ -15,6 +15,7 @@ import pytest
 
 import sweep_ref as R
 from bundletrack_amd import _lib
+from shared_checks import device_matrices
 
 pytestmark = pytest.mark.gpu
 FACTOR = 4.0
@@ -40,18 +41,6 @@ def gamma_d(oracle):
     fS, fg, per = R.oracle_dense_floor()
     print(f"\ndense: fp32 oracle floor S {fS:.3e} g {fg:.3e} -> bars {FACTOR * fS:.3e} / {FACTOR * fg:.3e}; per scene {per}")
     return FACTOR * fS, FACTOR * fg
-
-
-def device_matrices(g, poses):
-    """T = Exp(Log(pose)) and its inverse as k_prepare forms them (the same device functions behind the library's SE(3) seams)."""
-    n = poses.shape[0]
-    P_d = g.torch.from_numpy(np.ascontiguousarray(poses, np.float32).reshape(n, 16)).to(g.dev)
-    x_d, T_d, Ti_d = g.torch.zeros((n, 6), device=g.dev), g.torch.zeros((n, 16), device=g.dev), g.torch.zeros((n, 16), device=g.dev)
-    L = _lib.lib()
-    _lib.check(L.btba_matrices_to_poses(g.ws.handle, n, P_d.data_ptr(), x_d.data_ptr()), "m2p")
-    _lib.check(L.btba_poses_to_matrices(g.ws.handle, n, x_d.data_ptr(), T_d.data_ptr(), Ti_d.data_ptr()), "p2m")
-    g.ws.sync()
-    return T_d.cpu().numpy().reshape(n, 4, 4), Ti_d.cpu().numpy().reshape(n, 4, 4)
 
 
 def refs_of(g, name, pairs):

@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "btba_mappoints_create", "btba_mappoints_destroy", "btba_mappoints_register_frame", "btba_mappoints_forget_frame", "btba_mappoints_export",
     "btba_corres_params_default", "btba_corres_chain_capacity", "btba_corres_chain",
     "btba_window_layout", "btba_marshal_windows", "btba_procrustes_pairs",
+    "btba_linearize_batch_zn_aux", "btba_pose_covariances",
 ]
 
 # btba_match (include/btba.h): one descriptor match, 40 bytes
@@ -429,6 +430,9 @@ def lib() -> C.CDLL:
                                            C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_procrustes_pairs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_linearize_batch_zn_aux.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ZnAux),
+                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_pose_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

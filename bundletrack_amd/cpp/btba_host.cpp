@@ -280,6 +280,28 @@ void procrustesPairs(btba_workspace *ws, const btba_match *matches_dev, int64_t 
             for (int c = 0; c < 4; c++) poses[e](r, c) = out[16 * e + 4 * r + c];
 }
 
+void linearizeBatchZn(btba_workspace *ws, const btba_params &params, int n_instances, int n_frames, int H, int W, const Matrix3f &K, const float *zn_dev,
+                      const btba_zn_aux *aux, const btba_entryj *corr_dev, int64_t corr_stride, const uint32_t *pair_offsets_dev, uint32_t max_corr_per_pair,
+                      const std::vector<std::pair<int32_t, int32_t>> &dense_pairs, const float *poses_dev, float *info_dev, float *rhs_dev)
+{
+    float Kr[9];                                                  // row-major, as the C ABI takes it
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Kr[3 * r + c] = K(r, c);
+    std::vector<int32_t> dp;
+    for (const auto &p : dense_pairs) { dp.push_back(p.first); dp.push_back(p.second); }
+    const int rc = btba_linearize_batch_zn_aux(ws, &params, n_instances, n_frames, H, W, Kr, zn_dev, aux, corr_dev, corr_stride, pair_offsets_dev,
+                                               max_corr_per_pair, dp.empty() ? nullptr : dp.data(), (int)dense_pairs.size(), poses_dev, info_dev, rhs_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_linearize_batch_zn_aux");
+}
+
+void poseCovariances(btba_workspace *ws, int n_instances, int n_frames, const float *info_dev, double *cov_blocks_dev, int32_t *status_dev,
+                     double *cov_full_dev, double *pivot_ratio_dev)
+{
+    const int64_t na = 6 * ((int64_t)n_frames - 1);
+    const int rc = btba_pose_covariances(ws, n_instances, n_frames, info_dev, na * na, cov_blocks_dev, cov_full_dev, pivot_ratio_dev, status_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_pose_covariances");
+}
+
 double vocapAuc(const std::vector<double> &errors, double max_threshold)
 {
     const size_t n = errors.size();

@@ -235,6 +235,17 @@ void marshalWindows(btba_workspace *ws, int n_windows, int n_frames, const btba_
 void procrustesPairs(btba_workspace *ws, const btba_match *matches_dev, int64_t n_records, const std::vector<std::pair<int32_t, int32_t>> &segments,
                      const std::vector<Matrix4f> &posesA, const std::vector<Matrix4f> &posesB, std::vector<Matrix4f> &poses, std::vector<float> &err);
 
+// Pose covariances (include/btba.h, "pose covariances"): thin wrappers over the C ABI, all pointers device pointers, both asynchronous on the
+// workspace stream.  linearizeBatchZn: the arguments of btba_solve_batch_zn_aux with const poses -> info_dev float [n_instances][na][na]
+// (na = 6 (n_frames - 1), the public (rot, trans) order) and, unless null, rhs_dev float [n_instances][n_frames - 1][6]; dense_pairs empty: the
+// pair policy's default list.  poseCovariances: info (contiguous instances) -> cov_blocks_dev double [n_instances][n_frames][6][6],
+// status_dev int32 [n_instances] and, unless null, cov_full_dev double [n_instances][na][na] and pivot_ratio_dev double [n_instances].
+void linearizeBatchZn(btba_workspace *ws, const btba_params &params, int n_instances, int n_frames, int H, int W, const Matrix3f &K, const float *zn_dev,
+                      const btba_zn_aux *aux, const btba_entryj *corr_dev, int64_t corr_stride, const uint32_t *pair_offsets_dev, uint32_t max_corr_per_pair,
+                      const std::vector<std::pair<int32_t, int32_t>> &dense_pairs, const float *poses_dev, float *info_dev, float *rhs_dev = nullptr);
+void poseCovariances(btba_workspace *ws, int n_instances, int n_frames, const float *info_dev, double *cov_blocks_dev, int32_t *status_dev,
+                     double *cov_full_dev = nullptr, double *pivot_ratio_dev = nullptr);
+
 // VOCap (eval_ycbineoat.py:54-81) in closed form, the same arithmetic as bundletrack_amd/evaluation.py::vocap_auc: the area under
 // the accuracy-vs-threshold curve on [0, max_threshold] over max_threshold (0 without errors below the threshold).
 double vocapAuc(const std::vector<double> &errors, double max_threshold = 0.1);

@@ -200,6 +200,8 @@ struct btba_workspace {
     DevBuf lfnet_det;                                       // btba_lfnet_scores: the residual stream and conv1's output of a pass, NHWC
     DevBuf vos_net;                                         // btba_vos_features: the four NHWC activation buffers of a pass
     DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
+    DevBuf marginals;                                       // btba_linearize_batch_zn_aux: the copy of the poses and the record of its one traced iterate
+    bool marginals_attr_set = false;
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;

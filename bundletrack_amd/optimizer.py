@@ -427,6 +427,33 @@ class BatchSolver:
         self._last_layout = (L, N, npd if self.params.weight_dense_depth > 0 else 0)
         return tr
 
+    def linearize_zn(self, zn, H, W, K, corr_dev, pair_offsets_dev, max_corr_per_pair, poses_dev, dense_pairs=None, aux=None, corr_stride=None, rhs=False):
+        """The solver's system at poses_dev (btba_linearize_batch_zn_aux): the arguments of solve_zn, poses_dev is only read.  Returns info, CUDA
+        float32 [B, na, na] with na = 6 (N - 1) -- the Gauss-Newton matrix of frames 1 .. N - 1 in the public (rot, trans) order -- and with
+        rhs=True (info, rhs [B, N - 1, 6]).  Uses the scalar weights: BtbaError (BTBA_EINVAL) while set_iteration_weights is in force.  Asynchronous."""
+        torch = _torch()
+        B, N = int(zn.shape[0]), int(zn.shape[1])
+        na = 6 * (N - 1)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        stride = corr_dev.shape[1] if corr_dev is not None else int(corr_stride or 0)
+        dp = None
+        if dense_pairs is not None:
+            dp = np.ascontiguousarray(dense_pairs, np.int32).reshape(-1, 2)
+        info = torch.empty((B, na, na), dtype=torch.float32, device=zn.device)
+        rhs_t = torch.empty((B, N - 1, 6), dtype=torch.float32, device=zn.device) if rhs else None
+        za = None
+        if aux:
+            za = _lib.ZnAux(_dev_ptr(aux.get("block_ranges"), "block_ranges"), _dev_ptr(aux.get("valid_lists"), "valid_lists"), _dev_ptr(aux.get("valid_counts"), "valid_counts"),
+                            _dev_ptr(aux.get("corr24"), "corr24"))
+        rc = lib().btba_linearize_batch_zn_aux(
+            self.ws.handle, C.byref(self.params), B, N, int(H), int(W), Kf.ctypes.data, _dev_ptr(zn, "zn"), C.byref(za) if za is not None else None,
+            _dev_ptr(corr_dev, "corr_dev"), stride,
+            _dev_ptr(pair_offsets_dev, "pair_offsets_dev"), int(max_corr_per_pair),
+            dp.ctypes.data if dp is not None else None, dp.shape[0] if dp is not None else 0,
+            _dev_ptr(poses_dev, "poses_dev"), _dev_ptr(info, "info"), _dev_ptr(rhs_t, "rhs"))
+        check(rc, "btba_linearize_batch_zn_aux")
+        return (info, rhs_t) if rhs else info
+
     def trace_view(self, tr) -> TraceView:
         L, N, npd = self._last_layout
         self.ws.sync()

@@ -1314,6 +1314,61 @@ BTBA_API int btba_procrustes_pairs(btba_workspace *ws, int device_resident, int 
                                    const int32_t *segments, const float *posesA, const float *posesB,
                                    float *pose_out, float *err_out, double *moments_out);
 
+/* ---- pose covariances: how well a window constrains the poses a solve returns ----------------------------
+ * Two calls, usually made after btba_solve_batch_zn(_aux) on the poses it returned.
+ *
+ * btba_linearize_batch_zn_aux -- the solver's system at the caller's poses.  The arguments of btba_solve_batch_zn_aux, except that
+ * poses_dev is const and never written, there is no trace, and there are two outputs:
+ *   info_dev : float [n_instances][na][na], na = 6 (n_frames - 1) -- the Gauss-Newton matrix J^T W J the solve's first iterate would
+ *              assemble at these poses, frame 0 (fixed) without rows and columns
+ *   rhs_dev  : NULL, or float [n_instances][n_frames - 1][6] -- its right-hand side -J^T W r; the norm is the first-order optimality measure
+ * The unknowns are in the public order of btba_matrices_to_poses: per frame (rot, trans), rows 0-2 in radians, rows 3-5 in metres.  They
+ * describe the LEFT perturbation the solver applies, x_k <- Log(Exp(delta_k) Exp(x_k)).  Both outputs are, bit for bit, what a traced solve
+ * (BTBA_FLAG_TRACE) with n_gn_iters = 1 from the same poses and parameters records: info is the record's A without frame 0's rows and columns
+ * and with each frame's halves swapped from the record's [trans, rot] order, rhs the record's rhs of frames 1 .. n_frames - 1.
+ * WHAT THE MATRIX IS: the sparse (correspondence) share carries weight_sparse and NO Huber weight on the left-hand side (as in the reference's
+ * solver, the robust weight enters its right-hand side only); the dense share is Huber-weighted and carries weight_dense_depth; a dense pair listed
+ * only in the reversed direction (target > source) contributes to both frames' diagonal blocks and carries no cross block.  Its inverse is
+ * therefore the inverse of the solver's Gauss-Newton matrix, NOT a calibrated covariance: a caller scales it by a residual variance of its own.
+ * The scalar weight_sparse / weight_dense_depth are used; n_gn_iters, n_pcg_iters and BTBA_FLAG_TRACE are ignored; every window the solve serves
+ * (2 .. BTBA_MAX_FRAMES frames) is served, through whichever solve kernel the dispatch picks for it.  Asynchronous on the workspace stream; scratch
+ * (a copy of the poses, one trace record per instance) is grow-only in the workspace; a later solve on the workspace returns the bits it
+ * returns without this call, and btba_collect_stats keeps reporting the last solve.
+ * BTBA_EINVAL before any GPU work: NULL ws, params, poses_dev or info_dev, n_instances < 1, n_frames outside 2 .. BTBA_MAX_FRAMES, a per-iteration
+ * weight array set (weights_sparse_per_iter / weights_dense_per_iter); otherwise what btba_solve_batch_zn_aux returns for a traced solve
+ * (BTBA_REDUCE_ATOMIC is BTBA_EINVAL: the trace is defined on the reproducible sums).
+ *
+ * btba_pose_covariances -- the batched fp64 inverse of that matrix (or of any symmetric positive definite fp32 matrix in the same layout).
+ *   info_dev        : float, instance b at info_dev + b * info_stride, [na][na] row-major; the LOWER triangle is read
+ *   info_stride     : floats per instance, >= na * na
+ *   cov_blocks_dev  : double [n_instances][n_frames][6][6] -- each frame's marginal 6 x 6 block of the inverse, (rot, trans); frame 0: zeros
+ *   cov_full_dev    : NULL, or double [n_instances][na][na] -- the whole inverse
+ *   pivot_ratio_dev : NULL, or double [n_instances] -- min_j d_j / H_jj over the Cholesky pivots d_j: 1 for a diagonal matrix, towards 0 as
+ *                     some unknown becomes determined by the others; the cheap conditioning figure a tracker can threshold
+ *   status_dev      : int32 [n_instances] -- 0: the factorisation completed; 1 + j: unknown j (public order) is the first whose pivot d_j is
+ *                     not > 0 or not finite.  All covariance outputs of that instance are then quiet NaNs and its pivot_ratio is 0; the
+ *                     other instances are not affected.  A frame that nothing constrains has a zero block and an exactly zero pivot.
+ * One workgroup per instance: the matrix is widened to fp64 into LDS as a packed lower triangle, factorised H = L L^T over the unknowns in
+ * their public order, L inverted in place, Sigma = L^-T L^-1 -- IEEE fp64 throughout (fused multiply-add, correctly rounded division and square
+ * root), no atomics, every sum in an order fixed by the window size alone: an instance yields the same bits at any batch position and in
+ * any batch size, cov_full is symmetric bit for bit and cov_blocks are its diagonal blocks bit for bit.
+ * Windows of 2 .. BTBA_MAX_FRAMES_LDS (31) frames are served: at 31 frames the packed triangle takes 130 320 of a compute unit's 163 840
+ * bytes of LDS; a larger window is BTBA_EINVAL.  Asynchronous on the workspace stream; all pointers are device pointers.
+ * BTBA_EINVAL before any GPU work: NULL ws, info_dev, cov_blocks_dev or status_dev, n_instances < 1, n_frames outside
+ * 2 .. BTBA_MAX_FRAMES_LDS, info_stride < na * na, a misaligned pointer. */
+BTBA_API int btba_linearize_batch_zn_aux(btba_workspace *ws, const btba_params *params, int n_instances, int n_frames,
+                                         int H, int W, const float *K_rowmajor, const float *zn_dev, const btba_zn_aux *aux,
+                                         const btba_entryj *corr_dev, int64_t corr_stride,
+                                         const uint32_t *pair_offsets_dev, uint32_t max_corr_per_pair,
+                                         const int32_t *dense_pairs, int n_dense_pairs, const float *poses_dev,
+                                         float *info_dev, float *rhs_dev);
+BTBA_API int btba_pose_covariances(btba_workspace *ws, int n_instances, int n_frames,
+                                   const float *info_dev, int64_t info_stride /* floats per instance, >= na*na */,
+                                   double *cov_blocks_dev  /* [n_instances][n_frames][6][6]; frame 0: zeros */,
+                                   double *cov_full_dev    /* NULL or [n_instances][na][na] */,
+                                   double *pivot_ratio_dev /* NULL or [n_instances] */,
+                                   int32_t *status_dev     /* [n_instances] */);
+
 #ifdef __cplusplus
 }
 #endif

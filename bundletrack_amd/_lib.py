@@ -54,8 +54,17 @@ EXPORTED_SYMBOLS = [
     "btba_mappoints_create", "btba_mappoints_destroy", "btba_mappoints_register_frame", "btba_mappoints_forget_frame", "btba_mappoints_export",
     "btba_corres_params_default", "btba_corres_chain_capacity", "btba_corres_chain",
     "btba_window_layout", "btba_marshal_windows", "btba_procrustes_pairs",
-    "btba_linearize_batch_zn_aux", "btba_pose_covariances",
+    "btba_linearize_batch_zn_aux", "btba_pose_covariances", "btba_objective_batch_zn_aux",
 ]
+
+# btba_objective_pair / btba_objective_total (include/btba.h): 40 and 64 bytes
+OBJECTIVE_PAIR_DTYPE = np.dtype(
+    [("sum_sq", "<f8"), ("sum_rho", "<f8"), ("max_abs", "<f8"), ("count", "<i4"), ("n_outlier", "<i4"), ("worst", "<i4"), ("reserved", "<i4")]
+)
+OBJECTIVE_TOTAL_DTYPE = np.dtype(
+    [("objective", "<f8"), ("sparse_rho", "<f8"), ("dense_rho", "<f8"), ("sparse_sq", "<f8"), ("dense_wsq", "<f8"),
+     ("n_sparse", "<i8"), ("n_dense", "<i8"), ("n_residuals", "<i8")]
+)
 
 # btba_match (include/btba.h): one descriptor match, 40 bytes
 MATCH_DTYPE = np.dtype(
@@ -433,6 +442,8 @@ def lib() -> C.CDLL:
         L.btba_linearize_batch_zn_aux.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ZnAux),
                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_pose_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_objective_batch_zn_aux.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ZnAux),
+                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

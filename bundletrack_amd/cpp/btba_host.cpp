@@ -302,6 +302,27 @@ void poseCovariances(btba_workspace *ws, int n_instances, int n_frames, const fl
     if (rc != BTBA_OK) throw Error(rc, "btba_pose_covariances");
 }
 
+void objectiveBatchZn(btba_workspace *ws, const btba_params &params, int n_instances, int n_frames, int H, int W, const Matrix3f &K, const float *zn_dev,
+                      const btba_zn_aux *aux, const btba_entryj *corr_dev, int64_t corr_stride, const uint32_t *pair_offsets_dev, uint32_t max_corr_per_pair,
+                      const std::vector<std::pair<int32_t, int32_t>> &dense_pairs, const float *poses_dev, btba_objective_total *total_dev,
+                      btba_objective_pair *sparse_dev, btba_objective_pair *dense_dev)
+{
+    float Kr[9];                                                  // row-major, as the C ABI takes it
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Kr[3 * r + c] = K(r, c);
+    std::vector<int32_t> dp;
+    for (const auto &p : dense_pairs) { dp.push_back(p.first); dp.push_back(p.second); }
+    const int rc = btba_objective_batch_zn_aux(ws, &params, n_instances, n_frames, H, W, Kr, zn_dev, aux, corr_dev, corr_stride, pair_offsets_dev,
+                                               max_corr_per_pair, dp.empty() ? nullptr : dp.data(), (int)dense_pairs.size(), poses_dev, total_dev, sparse_dev, dense_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_objective_batch_zn_aux");
+}
+
+double residualVariance(const btba_objective_total &total, int n_frames)
+{
+    const double dof = (double)total.n_residuals - 6.0 * (double)(n_frames - 1);
+    return dof > 0.0 ? total.objective / dof : std::numeric_limits<double>::quiet_NaN();
+}
+
 double vocapAuc(const std::vector<double> &errors, double max_threshold)
 {
     const size_t n = errors.size();

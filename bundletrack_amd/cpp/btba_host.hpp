@@ -246,6 +246,16 @@ void linearizeBatchZn(btba_workspace *ws, const btba_params &params, int n_insta
 void poseCovariances(btba_workspace *ws, int n_instances, int n_frames, const float *info_dev, double *cov_blocks_dev, int32_t *status_dev,
                      double *cov_full_dev = nullptr, double *pivot_ratio_dev = nullptr);
 
+// Objective report (include/btba.h, "objective report"): the arguments of linearizeBatchZn -> total_dev btba_objective_total [n_instances] and,
+// unless null, sparse_dev btba_objective_pair [n_instances][n_frames (n_frames - 1) / 2] and dense_dev [n_instances][dense pairs]; asynchronous.
+// residualVariance: objective / (n_residuals - 6 (n_frames - 1)) of a total copied to the host, NaN where that is not positive -- what scales the
+// covariances of poseCovariances.
+void objectiveBatchZn(btba_workspace *ws, const btba_params &params, int n_instances, int n_frames, int H, int W, const Matrix3f &K, const float *zn_dev,
+                      const btba_zn_aux *aux, const btba_entryj *corr_dev, int64_t corr_stride, const uint32_t *pair_offsets_dev, uint32_t max_corr_per_pair,
+                      const std::vector<std::pair<int32_t, int32_t>> &dense_pairs, const float *poses_dev, btba_objective_total *total_dev,
+                      btba_objective_pair *sparse_dev = nullptr, btba_objective_pair *dense_dev = nullptr);
+double residualVariance(const btba_objective_total &total, int n_frames);
+
 // VOCap (eval_ycbineoat.py:54-81) in closed form, the same arithmetic as bundletrack_amd/evaluation.py::vocap_auc: the area under
 // the accuracy-vs-threshold curve on [0, max_threshold] over max_threshold (0 without errors below the threshold).
 double vocapAuc(const std::vector<double> &errors, double max_threshold = 0.1);

@@ -12,6 +12,7 @@
 
 #include "btba_host_common.hpp"
 #include "btba_kernels.hpp"
+#include "btba_objective.hpp"
 #include "btba_solve_general.hpp"
 #include "btba_chain.hpp"
 #include "btba_solve_small.hpp"
@@ -389,6 +390,79 @@ static int pick_tiles(const btba_params *prm, int B, int Pd, int npix, bool list
     return want;
 }
 
+// The dense pair list of a solve: the caller's explicit (target, source) list, or every i < j as (target i, source j).  BTBA_EINVAL for a frame
+// outside the window, a pair of a frame with itself, or a repeated pair.
+static int dense_pair_list(int N, const int32_t *dense_pairs, int Pd_in, std::vector<int32_t> &pairs)
+{
+    pairs.clear();
+    if (dense_pairs && Pd_in >= 0) pairs.assign(dense_pairs, dense_pairs + 2 * (size_t)Pd_in);
+    else for (int i = 0; i < N; i++) for (int j = i + 1; j < N; j++) { pairs.push_back(i); pairs.push_back(j); }
+    for (size_t k = 0; k < pairs.size(); k += 2)
+        if (pairs[k] < 0 || pairs[k] >= N || pairs[k + 1] < 0 || pairs[k + 1] >= N || pairs[k] == pairs[k + 1]) return BTBA_EINVAL;
+    if (dense_pairs && Pd_in >= 0) {
+        // an explicit list may name a pair in both directions, but not the same (target, source) twice: the system's diagonal blocks would
+        // count it twice and the one-pass off-diagonal assembly once (the reference's own list never repeats a pair, SolverBundling.cu:17-47)
+        std::vector<char> seen((size_t)N * N, 0);
+        for (size_t k = 0; k < pairs.size(); k += 2) {
+            char &c = seen[(size_t)pairs[k] * N + pairs[k + 1]];
+            if (c) return BTBA_EINVAL;
+            c = 1;
+        }
+    }
+    return BTBA_OK;
+}
+
+// The workspace's device table of that list, rebuilt (with one stream synchronisation) only when the list or the window size changes:
+// [Pd x (target, source)] [N+1 adjacency offsets] [2 Pd adjacency entries = pair << 1 | is_source],
+// adjacency of a frame listed in pair order (fixed summation order)
+static int dense_pair_table(btba_workspace *ws, int N, const std::vector<int32_t> &pairs)
+{
+    const int Pd = (int)(pairs.size() / 2);
+    if (Pd == 0 || (pairs == ws->dense_pairs_host && ws->dense_pairs_frames == N)) return BTBA_OK;
+    int rc;
+    std::vector<int32_t> tab(pairs);
+    std::vector<int32_t> off(N + 1, 0);
+    for (int q = 0; q < Pd; q++) { off[pairs[2 * q] + 1]++; off[pairs[2 * q + 1] + 1]++; }
+    for (int k = 0; k < N; k++) off[k + 1] += off[k];
+    std::vector<int32_t> adj(2 * (size_t)Pd), cur(off.begin(), off.end() - 1);
+    for (int q = 0; q < Pd; q++) { adj[cur[pairs[2 * q]]++] = (q << 1); adj[cur[pairs[2 * q + 1]]++] = (q << 1) | 1; }
+    tab.insert(tab.end(), off.begin(), off.end());
+    tab.insert(tab.end(), adj.begin(), adj.end());
+    // canonical pair (i < j) -> the dense pair listed as (target i, source j), the one whose cross block the system keeps (-1: none)
+    std::vector<int32_t> first_listed((size_t)N * N, -1);
+    for (int q = Pd - 1; q >= 0; q--) first_listed[(size_t)pairs[2 * q] * N + pairs[2 * q + 1]] = q;
+    for (int i = 0; i < N; i++) for (int j = i + 1; j < N; j++) tab.push_back(first_listed[(size_t)i * N + j]);
+    // work order of the fused sweep's dense items: frames close in the window overlap most (keyframes are in temporal order), so
+    // pairs sorted by |i - j| put the long workgroups first and the short ones at the end of the launch, where they drain quickly
+    std::vector<int32_t> order(Pd);
+    for (int q = 0; q < Pd; q++) order[q] = q;
+    if (ws->tune.dense_order) std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b2) { return std::abs(pairs[2 * a] - pairs[2 * a + 1]) < std::abs(pairs[2 * b2] - pairs[2 * b2 + 1]); });
+    // is that order the closed form the pinhole sweeps can compute for themselves?  (all pairs by ascending |i - j|, then ascending
+    // lower frame, every pair's index = its canonical index, target = the lower (1) or the higher (2) frame throughout)
+    ws->work_formula = 0;
+    if (Pd == N * (N - 1) / 2) {
+        for (int form = 1; form <= 2 && !ws->work_formula; form++) {
+            bool same = true;
+            int q = 0;
+            for (int d = 1; d < N && same; d++)
+                for (int i = 0; i + d < N && same; i++, q++) {
+                    const int pc = pair_index(N, (uint32_t)i, (uint32_t)(i + d));
+                    same = order[q] == pc && pairs[2 * pc] == (form == 1 ? i : i + d) && pairs[2 * pc + 1] == (form == 1 ? i + d : i);
+                }
+            if (same) ws->work_formula = form;
+        }
+    }
+    while (tab.size() % 4) tab.push_back(0);           // 16-byte entries
+    ws->dense_work_offset = tab.size();
+    for (int q = 0; q < Pd; q++) { tab.push_back(pairs[2 * order[q]]); tab.push_back(pairs[2 * order[q] + 1]); tab.push_back(order[q]); tab.push_back(0); }
+    if ((rc = ws->dense_pairs.ensure(sizeof(int32_t) * tab.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(ws->dense_pairs.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, ws->stream));
+    HIP_TRY(hipStreamSynchronize(ws->stream));         // `tab` is a local; the copy must land before it dies
+    ws->dense_pairs_host = pairs;
+    ws->dense_pairs_frames = N;
+    return BTBA_OK;
+}
+
 struct ZnSpec {      // compact cache + the full-res geometry it encodes
     const float *zn = nullptr; int H = 0, W = 0; const float *K = nullptr;
     const int *frame_slot = nullptr;                       // persistent cache: device int[N], frame -> pool slot (B == 1 only)
@@ -434,22 +508,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     const bool use_sparse = any_sparse_weight && corr && pair_offsets && max_corr_per_pair > 0;
     // dense pair list
     std::vector<int32_t> pairs;
-    if (any_dense_weight) {
-        if (dense_pairs && Pd_in >= 0) pairs.assign(dense_pairs, dense_pairs + 2 * (size_t)Pd_in);
-        else for (int i = 0; i < N; i++) for (int j = i + 1; j < N; j++) { pairs.push_back(i); pairs.push_back(j); }
-        for (size_t k = 0; k < pairs.size(); k += 2)
-            if (pairs[k] < 0 || pairs[k] >= N || pairs[k + 1] < 0 || pairs[k + 1] >= N || pairs[k] == pairs[k + 1]) return BTBA_EINVAL;
-        if (dense_pairs && Pd_in >= 0) {
-            // an explicit list may name a pair in both directions, but not the same (target, source) twice: the system's diagonal blocks would
-            // count it twice and the one-pass off-diagonal assembly once (the reference's own list never repeats a pair, SolverBundling.cu:17-47)
-            std::vector<char> seen((size_t)N * N, 0);
-            for (size_t k = 0; k < pairs.size(); k += 2) {
-                char &c = seen[(size_t)pairs[k] * N + pairs[k + 1]];
-                if (c) return BTBA_EINVAL;
-                c = 1;
-            }
-        }
-    }
+    if (any_dense_weight) { if (int prc = dense_pair_list(N, dense_pairs, Pd_in, pairs)) return prc; }
     const int Pd = (int)(pairs.size() / 2);
     const bool use_zn = Z.zn != nullptr;
     const bool use_dense = Pd > 0 && ((campos && normals) || use_zn);      // Pd == 0: "no overlapping images", SolverBundling.cu:280-283
@@ -475,50 +534,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     if ((rc = ws->Tinv.ensure(sizeof(float) * 16 * (size_t)B * N))) return rc;
     if ((rc = ws->sparse_part.ensure(sizeof(float) * (size_t)B * P * chunks * kSparseVals))) return rc;
     if ((rc = ws->dense_part.ensure(sizeof(float) * (size_t)B * (Pd > 0 ? Pd : 1) * tiles * kDenseVals))) return rc;
-    // device table: [Pd x (target, source)] [N+1 adjacency offsets] [2 Pd adjacency entries = pair << 1 | is_source],
-    // adjacency of a frame listed in pair order (fixed summation order)
-    if (Pd > 0 && (pairs != ws->dense_pairs_host || ws->dense_pairs_frames != N)) {
-        std::vector<int32_t> tab(pairs);
-        std::vector<int32_t> off(N + 1, 0);
-        for (int q = 0; q < Pd; q++) { off[pairs[2 * q] + 1]++; off[pairs[2 * q + 1] + 1]++; }
-        for (int k = 0; k < N; k++) off[k + 1] += off[k];
-        std::vector<int32_t> adj(2 * (size_t)Pd), cur(off.begin(), off.end() - 1);
-        for (int q = 0; q < Pd; q++) { adj[cur[pairs[2 * q]]++] = (q << 1); adj[cur[pairs[2 * q + 1]]++] = (q << 1) | 1; }
-        tab.insert(tab.end(), off.begin(), off.end());
-        tab.insert(tab.end(), adj.begin(), adj.end());
-        // canonical pair (i < j) -> the dense pair listed as (target i, source j), the one whose cross block the system keeps (-1: none)
-        std::vector<int32_t> first_listed((size_t)N * N, -1);
-        for (int q = Pd - 1; q >= 0; q--) first_listed[(size_t)pairs[2 * q] * N + pairs[2 * q + 1]] = q;
-        for (int i = 0; i < N; i++) for (int j = i + 1; j < N; j++) tab.push_back(first_listed[(size_t)i * N + j]);
-        // work order of the fused sweep's dense items: frames close in the window overlap most (keyframes are in temporal order), so
-        // pairs sorted by |i - j| put the long workgroups first and the short ones at the end of the launch, where they drain quickly
-        std::vector<int32_t> order(Pd);
-        for (int q = 0; q < Pd; q++) order[q] = q;
-        if (ws->tune.dense_order) std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b2) { return std::abs(pairs[2 * a] - pairs[2 * a + 1]) < std::abs(pairs[2 * b2] - pairs[2 * b2 + 1]); });
-        // is that order the closed form the pinhole sweeps can compute for themselves?  (all pairs by ascending |i - j|, then ascending
-        // lower frame, every pair's index = its canonical index, target = the lower (1) or the higher (2) frame throughout)
-        ws->work_formula = 0;
-        if (Pd == N * (N - 1) / 2) {
-            for (int form = 1; form <= 2 && !ws->work_formula; form++) {
-                bool same = true;
-                int q = 0;
-                for (int d = 1; d < N && same; d++)
-                    for (int i = 0; i + d < N && same; i++, q++) {
-                        const int pc = pair_index(N, (uint32_t)i, (uint32_t)(i + d));
-                        same = order[q] == pc && pairs[2 * pc] == (form == 1 ? i : i + d) && pairs[2 * pc + 1] == (form == 1 ? i + d : i);
-                    }
-                if (same) ws->work_formula = form;
-            }
-        }
-        while (tab.size() % 4) tab.push_back(0);           // 16-byte entries
-        ws->dense_work_offset = tab.size();
-        for (int q = 0; q < Pd; q++) { tab.push_back(pairs[2 * order[q]]); tab.push_back(pairs[2 * order[q] + 1]); tab.push_back(order[q]); tab.push_back(0); }
-        if ((rc = ws->dense_pairs.ensure(sizeof(int32_t) * tab.size()))) return rc;
-        HIP_TRY(hipMemcpyAsync(ws->dense_pairs.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, ws->stream));
-        HIP_TRY(hipStreamSynchronize(ws->stream));         // `tab` is a local; the copy must land before it dies
-        ws->dense_pairs_host = pairs;
-        ws->dense_pairs_frames = N;
-    }
+    if ((rc = dense_pair_table(ws, N, pairs))) return rc;
     // tables of k_system_solve that depend on the window size only: canonical pair p -> (i << 8 | j), then the 72
     // descriptors of the sparse 6x6 block entries (btba_solve_general.hpp: sparse_entry_descriptor)
     if (ws->solve_tab_frames != N) {
@@ -1698,3 +1714,71 @@ int btba_solve_batch_zn_aux(btba_workspace *ws, const btba_params *params, int n
 }
 
 }  // extern "C"
+
+// ---- objective report (btba_api_objective.hip checks the arguments; the launches live here, beside the sweeps whose device functions they call) ----
+int objective_enqueue(btba_workspace *ws, const ObjectiveCall &c)
+{
+    const btba_params *prm = c.prm;
+    const int B = c.B, N = c.N, Hd = c.Hd, Wd = c.Wd, P = N * (N - 1) / 2, npix = Hd * Wd;
+    const bool with_dense = prm->weight_dense_depth > 0.0f;
+    const bool with_sparse = prm->weight_sparse > 0.0f && c.corr && c.pair_offsets && c.max_corr_per_pair > 0;
+    // the dense pairs and their device table: the solve's
+    std::vector<int32_t> pairs;
+    if (int rc = dense_pair_list(N, c.dense_pairs, c.dense_pairs ? c.n_dense_pairs : -1, pairs)) return rc;
+    const int Pd_out = (int)(pairs.size() / 2), Pd = with_dense ? Pd_out : 0, Ps = with_sparse ? P : 0;
+    if (Pd > 0) { if (int rc = dense_pair_table(ws, N, pairs)) return rc; }
+    const ObjectiveLayout lay(B, N, npix, Pd, Ps, c.max_corr_per_pair);
+    if ((size_t)B * 16 * N >= ((size_t)1 << 31) || (size_t)lay.tiles * (size_t)std::max(Pd, 1) >= ((size_t)1 << 31) || B > 65535 || P > 65535) return BTBA_EINVAL;
+    if (int rc = ws->objective.ensure(lay.total)) return rc;
+    unsigned char *base = ws->objective.as<unsigned char>();
+    float *T = reinterpret_cast<float *>(base + lay.T), *Tinv = reinterpret_cast<float *>(base + lay.Tinv);
+    btba_objective_pair *dense_part = reinterpret_cast<btba_objective_pair *>(base + lay.dense), *sparse_part = reinterpret_cast<btba_objective_pair *>(base + lay.sparse);
+
+    float intr[4];
+    Mat4 Kinv;
+    scaled_intrinsics(c.H, c.W, Hd, Wd, c.K, intr, &Kinv);
+    // the fields of the solve's dimensions that the sweeps' device functions read (solve_enqueue fills them the same way)
+    SolveDims D{};
+    D.n_frames = N; D.n_pairs = P; D.n_dense_pairs = Pd;
+    D.npix = npix; D.width = Wd; D.height = Hd;
+    D.sparse_chunks = lay.chunks; D.dense_tiles = 1;
+    D.use_sparse = with_sparse; D.use_dense = Pd > 0;
+    D.fx = intr[0]; D.fy = intr[1]; D.cx = intr[2]; D.cy = intr[3];
+    D.robust_delta = prm->robust_delta; D.dist_thresh = prm->dense_dist_thresh; D.normal_thresh = prm->dense_normal_thresh;
+    D.dist2_thresh = prm->dense_dist_thresh * prm->dense_dist_thresh;
+    D.wm1 = (float)(Wd - 1); D.hm1 = (float)(Hd - 1); D.wm2 = (float)(Wd - 2); D.hm2 = (float)(Hd - 2);
+    D.depth_min = prm->depth_min; D.depth_max = prm->depth_max;
+    D.w_sparse = prm->weight_sparse; D.w_dense = prm->weight_dense_depth;
+    D.corr_stride = c.corr_stride; D.corr_nt_from = B; D.corr24 = c.corr24 ? 1 : 0;
+    D.pose_stride = 16 * N; D.x_stride = 6 * N;
+    if (Pd > 0) { D.dense_work = reinterpret_cast<const int4 *>(ws->dense_pairs.as<int32_t>() + ws->dense_work_offset); D.work_formula = ws->work_formula; }
+    for (int k = 0; k < 16; k++) D.zn_ki[k] = Kinv.m[k];
+    D.zn_scale_w = (float)(c.W - 1) / (float)(Wd - 1);
+    D.zn_scale_h = (float)(c.H - 1) / (float)(Hd - 1);
+    const float *ki = D.zn_ki;
+    D.zn_simple = (ki[1] == 0.f && ki[3] == 0.f && ki[4] == 0.f && ki[7] == 0.f && ki[12] == 0.f && ki[13] == 0.f && ki[14] == 0.f && ki[15] == 1.0f) ? 1 : 0;
+    const SweepLayout sweep_lds(Wd, Hd, 0, D.zn_simple ? kSweepLdsStrips : kSweepLdsGeneralK);
+    if (Pd > 0 && sweep_lds.total > 60 * 1024) return BTBA_EINVAL;      // (a cache of more than ~3 000 columns + rows)
+
+    const int total = B * N;
+    k_prepare<<<(total + 63) / 64, 64, 0, ws->stream>>>(total, c.poses, nullptr, T, Tinv, ws->tune.prepare_keep_T);
+    HIP_TRY(hipGetLastError());
+    if (Pd > 0) {
+        const dim3 grid((unsigned)(lay.tiles * Pd), (unsigned)B);
+        if (D.zn_simple) k_objective_dense_pinhole<<<grid, kObjectiveBlock, sweep_lds.total, ws->stream>>>(D, lay, reinterpret_cast<const float4 *>(c.zn), T, Tinv, dense_part);
+        else k_objective_dense_general<<<grid, kObjectiveBlock, sweep_lds.total, ws->stream>>>(D, lay, reinterpret_cast<const float4 *>(c.zn), T, Tinv, dense_part);
+        HIP_TRY(hipGetLastError());
+    }
+    if (Ps > 0) {
+        k_objective_sparse<<<dim3((unsigned)lay.chunks, (unsigned)P, (unsigned)B), kObjectiveBlock, 0, ws->stream>>>(D, lay, reinterpret_cast<const float4 *>(c.corr), c.pair_offsets, T, sparse_part);
+        HIP_TRY(hipGetLastError());
+    }
+    ObjectiveFoldArgs A{};
+    A.Pd_out = Pd_out; A.Pd = Pd; A.P_out = P; A.P = Ps;
+    A.w_sparse = with_sparse ? prm->weight_sparse : 0.0f; A.w_dense = with_dense ? prm->weight_dense_depth : 0.0f;
+    A.dense_partials = dense_part; A.sparse_partials = sparse_part; A.dense_folded = dense_part; A.sparse_folded = sparse_part;
+    A.dense_out = c.dense; A.sparse_out = c.sparse; A.total = c.total;
+    k_objective_fold<<<(unsigned)B, kObjectiveBlock, 0, ws->stream>>>(A, lay);
+    HIP_TRY(hipGetLastError());
+    return BTBA_OK;
+}

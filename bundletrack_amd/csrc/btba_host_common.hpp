@@ -202,6 +202,7 @@ struct btba_workspace {
     DevBuf window;                                          // btba_procrustes_pairs: segment table, moments, host-form poses and outputs
     DevBuf marginals;                                       // btba_linearize_batch_zn_aux: the copy of the poses and the record of its one traced iterate
     bool marginals_attr_set = false;
+    DevBuf objective;                                       // btba_objective_batch_zn_aux: the matrices of the caller's poses, the partial records of tiles and chunks
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;
@@ -232,6 +233,19 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
+
+// btba_objective_batch_zn_aux behind its argument checks (btba_api_objective.hip): the dense pair list and its device table as solve_enqueue derives
+// them, the scratch, k_prepare and the launches of btba_objective.hpp.  Defined in btba_api.hip, the one unit that holds the sweeps' device functions.
+struct ObjectiveCall {
+    const btba_params *prm;
+    int B, N, H, W, Hd, Wd;
+    const float *K, *zn, *poses;
+    const void *corr; bool corr24; int64_t corr_stride;     // nullptr: no sparse term
+    const uint32_t *pair_offsets; uint32_t max_corr_per_pair;
+    const int32_t *dense_pairs; int n_dense_pairs;          // host list, or nullptr: every i < j
+    btba_objective_total *total; btba_objective_pair *sparse, *dense;
+};
+int objective_enqueue(btba_workspace *ws, const ObjectiveCall &c);
 
 // What a model handle of either LF-Net net starts with: its workspace, that workspace's device and the arena's device copy.
 struct LfnetModelBase {

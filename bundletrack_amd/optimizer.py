@@ -454,6 +454,42 @@ class BatchSolver:
         check(rc, "btba_linearize_batch_zn_aux")
         return (info, rhs_t) if rhs else info
 
+    def objective_zn(self, zn, H, W, K, corr_dev, pair_offsets_dev, max_corr_per_pair, poses_dev, dense_pairs=None, aux=None, corr_stride=None, device=False):
+        """The solver's cost at poses_dev (btba_objective_batch_zn_aux): the arguments of linearize_zn, poses_dev is only read.  Returns
+        (total, sparse, dense), numpy structured views of btba_objective_total [B], btba_objective_pair [B, N (N - 1) / 2] and [B, Pd]
+        (_lib.OBJECTIVE_TOTAL_DTYPE / OBJECTIVE_PAIR_DTYPE); the call then synchronises.  device=True: the three CUDA uint8 tensors
+        ([B, 64], [B, P, 40], [B, Pd, 40]) instead, asynchronous.  Uses the scalar weights: BtbaError (BTBA_EINVAL) while set_iteration_weights
+        is in force."""
+        torch = _torch()
+        B, N = int(zn.shape[0]), int(zn.shape[1])
+        P = N * (N - 1) // 2
+        Kf = np.ascontiguousarray(K, np.float32).reshape(9)
+        stride = corr_dev.shape[1] if corr_dev is not None else int(corr_stride or 0)
+        dp = None
+        if dense_pairs is not None:
+            dp = np.ascontiguousarray(dense_pairs, np.int32).reshape(-1, 2)
+        Pd = dp.shape[0] if dp is not None else P
+        total = torch.empty((B, _lib.OBJECTIVE_TOTAL_DTYPE.itemsize), dtype=torch.uint8, device=zn.device)
+        sparse = torch.empty((B, P, _lib.OBJECTIVE_PAIR_DTYPE.itemsize), dtype=torch.uint8, device=zn.device)
+        dense = torch.empty((B, Pd, _lib.OBJECTIVE_PAIR_DTYPE.itemsize), dtype=torch.uint8, device=zn.device)
+        za = None
+        if aux:
+            za = _lib.ZnAux(_dev_ptr(aux.get("block_ranges"), "block_ranges"), _dev_ptr(aux.get("valid_lists"), "valid_lists"), _dev_ptr(aux.get("valid_counts"), "valid_counts"),
+                            _dev_ptr(aux.get("corr24"), "corr24"))
+        rc = lib().btba_objective_batch_zn_aux(
+            self.ws.handle, C.byref(self.params), B, N, int(H), int(W), Kf.ctypes.data, _dev_ptr(zn, "zn"), C.byref(za) if za is not None else None,
+            _dev_ptr(corr_dev, "corr_dev"), stride,
+            _dev_ptr(pair_offsets_dev, "pair_offsets_dev"), int(max_corr_per_pair),
+            dp.ctypes.data if dp is not None else None, dp.shape[0] if dp is not None else 0,
+            _dev_ptr(poses_dev, "poses_dev"), _dev_ptr(total, "total"), _dev_ptr(sparse, "sparse") if P else None, _dev_ptr(dense, "dense") if Pd else None)
+        check(rc, "btba_objective_batch_zn_aux")
+        if device:
+            return total, sparse, dense
+        self.ws.sync()
+        return (total.cpu().numpy().view(_lib.OBJECTIVE_TOTAL_DTYPE).reshape(B),
+                sparse.cpu().numpy().view(_lib.OBJECTIVE_PAIR_DTYPE).reshape(B, P),
+                dense.cpu().numpy().view(_lib.OBJECTIVE_PAIR_DTYPE).reshape(B, Pd))
+
     def trace_view(self, tr) -> TraceView:
         L, N, npd = self._last_layout
         self.ws.sync()

@@ -1369,6 +1369,54 @@ BTBA_API int btba_pose_covariances(btba_workspace *ws, int n_instances, int n_fr
                                    double *pivot_ratio_dev /* NULL or [n_instances] */,
                                    int32_t *status_dev     /* [n_instances] */);
 
+/* ---- objective report: the cost the solver descends, at given poses ------------------------------------------
+ * btba_objective_batch_zn_aux takes the arguments of btba_linearize_batch_zn_aux and returns, per instance, the value of
+ *     objective = weight_sparse * sum rho(||T_i pos_i - T_j pos_j||^2) + weight_dense_depth * sum rho(res^2)
+ * with rho the Huber loss (e inside the knee e <= robust_delta^2, 2 delta sqrt(e) - delta^2 beyond it) -- the function whose gradient along the
+ * solver's left perturbation is -2 x the right-hand side btba_linearize_batch_zn_aux returns --, and per correspondence segment and per dense
+ * pair how many terms there are, how many lie beyond the knee, and which one is worst.
+ * Evaluation is at the matrices a solve forms of these poses (Exp(Log(P)) and its inverse, in scratch; poses_dev is never written).  Each
+ * residual is computed in fp32 by the sweeps' own expressions: sparse r = T_i pos_i - T_j pos_j over the valid entries of a segment (EntryJ, or the
+ * 24-byte records of aux->corr24); dense res = (c_i - q) . n_i over the source pixels that pass the solver's gates (depth range, in-image
+ * projection, the clamped 2 x 2 tap blend, normal and distance thresholds), zero-skew and general K.  Everything behind the residual -- square,
+ * rho, weight, sums -- is IEEE fp64, no atomics, every sum in an order fixed by the cache size, the segment lengths and the window size: an
+ * instance gives the same bytes at any batch position and in any batch size.
+ * The dense pairs are those the solve derives from dense_pairs / n_dense_pairs (NULL: every i < j as (target i, source j)); record q belongs to
+ * listed pair q.  weight_dense_depth <= 0: no dense term is evaluated, as the solve builds no dense system then -- every dense record is zero with
+ * worst = -1; weight_sparse <= 0, no correspondences or max_corr_per_pair == 0: the same for the sparse records.
+ * BTBA_FLAG_COMPACTION is IGNORED: every pixel of the source frame is walked (aux's lists and block ranges are not read), which gives what a walk
+ * of the lists would give, a listed pixel being one with a depth.  n_gn_iters, n_pcg_iters, pair_policy, reduction_mode and the other flags are
+ * ignored as well.
+ * Asynchronous on the workspace stream; scratch (the matrices, one partial record per (pair, 1 024 pixels) and per (segment, 1 024 entries)) is
+ * grow-only in the workspace; btba_collect_stats keeps reporting the last solve, and a later solve returns the bits it returns without this call.
+ * BTBA_EINVAL before any GPU work: NULL ws, params, poses_dev or total_dev, n_instances < 1, n_frames outside 2 .. BTBA_MAX_FRAMES, a
+ * per-iteration weight array set, an output not aligned to 8 bytes; also what the solve refuses (NULL K or zn_dev, a cache below 2 x 2, an invalid or
+ * repeated dense pair).
+ * Not served: the float4 cache of btba_solve_batch and the btba_optimize_frames(_keyed) boundary.  The solve itself makes no use of the report. */
+typedef struct btba_objective_pair {      /* 40 bytes; one per (instance, pair) */
+    double  sum_sq;     /* sparse: sum ||r||^2.   dense: sum w res^2, w = min(1, delta / |res|) */
+    double  sum_rho;    /* sum rho(e), e = ||r||^2 or res^2 */
+    double  max_abs;    /* sparse: max over entries of max(|r.x|, |r.y|, |r.z|); dense: max |res|; 0 when count == 0 */
+    int32_t count;      /* valid entries of the segment / accepted pixels of the pair */
+    int32_t n_outlier;  /* of those, e > delta^2 */
+    int32_t worst;      /* entry index within the segment / source pixel index y * Wd + x that attains max_abs, the lowest on ties; -1 when count == 0 */
+    int32_t reserved;   /* 0 */
+} btba_objective_pair;
+typedef struct btba_objective_total {     /* 64 bytes; one per instance */
+    double  objective;  /* weight_sparse * sparse_rho + weight_dense_depth * dense_rho */
+    double  sparse_rho, dense_rho, sparse_sq, dense_wsq;   /* sums of the pair records in index order, unweighted */
+    int64_t n_sparse, n_dense;                             /* sums of the counts */
+    int64_t n_residuals;                                   /* 3 * n_sparse + n_dense */
+} btba_objective_total;
+BTBA_API int btba_objective_batch_zn_aux(btba_workspace *ws, const btba_params *params, int n_instances, int n_frames,
+                                         int H, int W, const float *K_rowmajor, const float *zn_dev, const btba_zn_aux *aux,
+                                         const btba_entryj *corr_dev, int64_t corr_stride,
+                                         const uint32_t *pair_offsets_dev, uint32_t max_corr_per_pair,
+                                         const int32_t *dense_pairs, int n_dense_pairs, const float *poses_dev,
+                                         btba_objective_total *total_dev  /* [n_instances] */,
+                                         btba_objective_pair *sparse_dev  /* NULL or [n_instances][n_frames (n_frames - 1) / 2] */,
+                                         btba_objective_pair *dense_dev   /* NULL or [n_instances][Pd], Pd = n_dense_pairs, or n_frames (n_frames - 1) / 2 without a list */);
+
 #ifdef __cplusplus
 }
 #endif

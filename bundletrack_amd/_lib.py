@@ -55,7 +55,9 @@ EXPORTED_SYMBOLS = [
     "btba_corres_params_default", "btba_corres_chain_capacity", "btba_corres_chain",
     "btba_window_layout", "btba_marshal_windows", "btba_procrustes_pairs",
     "btba_linearize_batch_zn_aux", "btba_pose_covariances", "btba_objective_batch_zn_aux",
+    "btba_fuse_params_default", "btba_fuse_layout", "btba_fuse_bounds", "btba_fuse_frames", "btba_voxel_downsample",
 ]
+FUSE_FRAME, FUSE_POINTS, FUSE_OVERFLOW, FUSE_MAX_VOXELS = 0, 1, 1, 1 << 24
 
 # btba_objective_pair / btba_objective_total (include/btba.h): 40 and 64 bytes
 OBJECTIVE_PAIR_DTYPE = np.dtype(
@@ -199,6 +201,17 @@ class TraceLayout(C.Structure):
 class CorresParams(C.Structure):
     """btba_corres_params (include/btba.h): the RANSAC settings of btba_corres_chain."""
     _fields_ = [("n_trials", C.c_int32), ("dist_thres", C.c_float), ("hypothesis", C.c_int32), ("pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class FuseParams(C.Structure):
+    """btba_fuse_params (include/btba.h)."""
+    _fields_ = [("leaf", C.c_float), ("min_points", C.c_int32), ("require_normals", C.c_int32), ("normalize_normals", C.c_int32)]
+
+
+class FuseSegment(C.Structure):
+    """btba_fuse_segment (include/btba.h): 104 bytes."""
+    _fields_ = [("kind", C.c_int32), ("instance", C.c_int32), ("n", C.c_int64), ("geom", C.c_void_p), ("normal", C.c_void_p),
+                ("colour", C.c_void_p), ("pose", C.c_float * 16)]
 
 
 class BtbaError(RuntimeError):
@@ -444,6 +457,12 @@ def lib() -> C.CDLL:
         L.btba_pose_covariances.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.btba_objective_batch_zn_aux.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ZnAux),
                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_fuse_params_default.argtypes = [C.POINTER(FuseParams)]
+        L.btba_fuse_params_default.restype = None
+        L.btba_fuse_layout.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.btba_fuse_bounds.argtypes = [C.c_void_p, C.POINTER(FuseParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.btba_fuse_frames.argtypes = [C.c_void_p, C.POINTER(FuseParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        L.btba_voxel_downsample.argtypes = [C.c_void_p, C.POINTER(FuseParams), C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 8
         _lib = L
     return _lib
 
@@ -538,6 +557,11 @@ def detector_params(**kw) -> DetectorParams:
 def nocs_params(**kw) -> NocsParams:
     """btba_nocs_params_default with fields overridden by keyword."""
     return _params(NocsParams, "btba_nocs_params_default", kw)
+
+
+def fuse_params(**kw) -> FuseParams:
+    """btba_fuse_params_default with fields overridden by keyword."""
+    return _params(FuseParams, "btba_fuse_params_default", kw)
 
 
 def declared_symbols() -> list[str]:

@@ -306,6 +306,16 @@ class Bundler:
     def keyframes(self):
         return self.memory.keyframes
 
+    def reconstruct(self, leaf=0.005, min_points=1):
+        """The object the session tracked: self.keyframes (their masked depth, normal and colour maps at their bundle-adjusted
+        pose_in_model) fused into one voxel-grid cloud on the optimiser's workspace (fusion.fuse_frames; an ObjectCloud of one instance).
+        Colour is fused when every keyframe has a colour map.  One host synchronisation: the data-derived box."""
+        from .fusion import frame_segment, fuse_frames
+        ws = getattr(self.opt, "workspace", None)
+        if ws is None:
+            raise RuntimeError("Bundler.reconstruct needs an optimizer with a workspace")
+        return fuse_frames(ws, [frame_segment(kf) for kf in self.keyframes], 1, self.K, leaf=leaf, min_points=min_points)
+
     def process_new_frame(self, frame: FrameRef) -> None:
         self.newframe = frame
         last = self.frames[-1] if self.frames else None

@@ -323,6 +323,68 @@ double residualVariance(const btba_objective_total &total, int n_frames)
     return dof > 0.0 ? total.objective / dof : std::numeric_limits<double>::quiet_NaN();
 }
 
+static btba_fuse_segment fuseSegment(int kind, int instance, const Matrix4f &pose, const void *geom, int64_t n, const void *normal, const void *colour)
+{
+    btba_fuse_segment s{};
+    s.kind = kind;
+    s.instance = instance;
+    s.n = n;
+    s.geom = geom;
+    s.normal = normal;
+    s.colour = colour;
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) s.pose[4 * r + c] = pose(r, c);          // row-major, as the C ABI takes it
+    return s;
+}
+
+btba_fuse_segment frameSegment(int instance, const Matrix4f &pose_in_model, const float *depth_gpu, const float4 *normal_gpu, const uchar4 *color_gpu)
+{
+    return fuseSegment(BTBA_FUSE_FRAME, instance, pose_in_model, depth_gpu, 0, normal_gpu, color_gpu);
+}
+
+btba_fuse_segment pointSegment(int instance, const Matrix4f &pose, const float4 *xyz_gpu, int64_t n, const float4 *normal_gpu, const uchar4 *color_gpu)
+{
+    return fuseSegment(BTBA_FUSE_POINTS, instance, pose, xyz_gpu, n, normal_gpu, color_gpu);
+}
+
+void fuseBounds(btba_workspace *ws, const btba_fuse_params &params, int n_instances, const std::vector<btba_fuse_segment> &segments, int H, int W,
+                const Matrix3f &K, int32_t *box_dev)
+{
+    float Kr[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Kr[3 * r + c] = K(r, c);
+    const int rc = btba_fuse_bounds(ws, &params, n_instances, (int)segments.size(), segments.data(), H, W, Kr, box_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_fuse_bounds");
+}
+
+void fuseFrames(btba_workspace *ws, const btba_fuse_params &params, int n_instances, const std::vector<btba_fuse_segment> &segments, int H, int W,
+                const Matrix3f &K, const std::vector<int32_t> &box, const ObjectCloudBuffers &out)
+{
+    if (box.size() != 6 * (size_t)std::max(n_instances, 0)) throw Error(BTBA_EINVAL, "fuseFrames: box");
+    float Kr[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Kr[3 * r + c] = K(r, c);
+    const int rc = btba_fuse_frames(ws, &params, n_instances, (int)segments.size(), segments.data(), H, W, Kr, box.data(), out.capacity,
+                                    reinterpret_cast<float *>(out.xyz), reinterpret_cast<float *>(out.normal), reinterpret_cast<uint8_t *>(out.colour),
+                                    out.count, out.lin, out.n_out, out.n_outside, out.status);
+    if (rc != BTBA_OK) throw Error(rc, "btba_fuse_frames");
+}
+
+void voxelDownsample(btba_workspace *ws, const btba_fuse_params &params, const std::vector<const float4 *> &xyz_gpu, const std::vector<int64_t> &n_points,
+                     const std::vector<int32_t> &box, const ObjectCloudBuffers &out, const std::vector<const float4 *> &normal_gpu,
+                     const std::vector<const uchar4 *> &color_gpu)
+{
+    const size_t B = xyz_gpu.size();
+    if (n_points.size() != B || box.size() != 6 * B || (!normal_gpu.empty() && normal_gpu.size() != B) || (!color_gpu.empty() && color_gpu.size() != B))
+        throw Error(BTBA_EINVAL, "voxelDownsample: one entry per instance");
+    const int rc = btba_voxel_downsample(ws, &params, (int)B, reinterpret_cast<const float *const *>(xyz_gpu.data()),
+                                         normal_gpu.empty() ? nullptr : reinterpret_cast<const float *const *>(normal_gpu.data()),
+                                         color_gpu.empty() ? nullptr : reinterpret_cast<const uint8_t *const *>(color_gpu.data()), n_points.data(), box.data(),
+                                         out.capacity, reinterpret_cast<float *>(out.xyz), reinterpret_cast<float *>(out.normal),
+                                         reinterpret_cast<uint8_t *>(out.colour), out.count, out.lin, out.n_out, out.n_outside, out.status);
+    if (rc != BTBA_OK) throw Error(rc, "btba_voxel_downsample");
+}
+
 double vocapAuc(const std::vector<double> &errors, double max_threshold)
 {
     const size_t n = errors.size();

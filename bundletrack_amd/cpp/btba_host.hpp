@@ -256,6 +256,29 @@ void objectiveBatchZn(btba_workspace *ws, const btba_params &params, int n_insta
                       btba_objective_pair *sparse_dev = nullptr, btba_objective_pair *dense_dev = nullptr);
 double residualVariance(const btba_objective_total &total, int n_frames);
 
+// Keyframe fusion and voxel-grid downsampling (include/btba.h, "keyframe fusion"): posed frames and point lists -> one voxel-grid cloud per
+// instance, Utils::downsamplePointCloud (Utils.cpp:134-140) included.  ObjectCloudBuffers: the caller's device outputs, `capacity` records per
+// instance; normal, colour, count and lin may be null.  fuseBounds writes VoxelGrid's data-derived box of every instance to device memory
+// (int32 [n_instances][6]); the caller copies it to the host and passes it as `box`.  All three are asynchronous on the workspace stream.
+struct ObjectCloudBuffers {
+    int capacity = 0;
+    float4 *xyz = nullptr, *normal = nullptr;
+    uchar4 *colour = nullptr;
+    uint32_t *count = nullptr;
+    int32_t *lin = nullptr;
+    int32_t *n_out = nullptr, *n_outside = nullptr, *status = nullptr;       // [n_instances] each
+};
+btba_fuse_segment frameSegment(int instance, const Matrix4f &pose_in_model, const float *depth_gpu, const float4 *normal_gpu, const uchar4 *color_gpu);
+btba_fuse_segment pointSegment(int instance, const Matrix4f &pose, const float4 *xyz_gpu, int64_t n, const float4 *normal_gpu = nullptr,
+                               const uchar4 *color_gpu = nullptr);
+void fuseBounds(btba_workspace *ws, const btba_fuse_params &params, int n_instances, const std::vector<btba_fuse_segment> &segments, int H, int W,
+                const Matrix3f &K, int32_t *box_dev);
+void fuseFrames(btba_workspace *ws, const btba_fuse_params &params, int n_instances, const std::vector<btba_fuse_segment> &segments, int H, int W,
+                const Matrix3f &K, const std::vector<int32_t> &box, const ObjectCloudBuffers &out);
+void voxelDownsample(btba_workspace *ws, const btba_fuse_params &params, const std::vector<const float4 *> &xyz_gpu, const std::vector<int64_t> &n_points,
+                     const std::vector<int32_t> &box, const ObjectCloudBuffers &out, const std::vector<const float4 *> &normal_gpu = {},
+                     const std::vector<const uchar4 *> &color_gpu = {});
+
 // VOCap (eval_ycbineoat.py:54-81) in closed form, the same arithmetic as bundletrack_amd/evaluation.py::vocap_auc: the area under
 // the accuracy-vs-threshold curve on [0, max_threshold] over max_threshold (0 without errors below the threshold).
 double vocapAuc(const std::vector<double> &errors, double max_threshold = 0.1);

@@ -203,6 +203,7 @@ struct btba_workspace {
     DevBuf marginals;                                       // btba_linearize_batch_zn_aux: the copy of the poses and the record of its one traced iterate
     bool marginals_attr_set = false;
     DevBuf objective;                                       // btba_objective_batch_zn_aux: the matrices of the caller's poses, the partial records of tiles and chunks
+    DevBuf fusion;                                          // btba_fuse_frames: the voxel planes (count, position, normal and colour sums), the compaction's block counts
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;

@@ -1417,6 +1417,104 @@ BTBA_API int btba_objective_batch_zn_aux(btba_workspace *ws, const btba_params *
                                          btba_objective_pair *sparse_dev  /* NULL or [n_instances][n_frames (n_frames - 1) / 2] */,
                                          btba_objective_pair *dense_dev   /* NULL or [n_instances][Pd], Pd = n_dense_pairs, or n_frames (n_frames - 1) / 2 without a list */);
 
+/* ---- keyframe fusion and voxel-grid downsampling: tracked frames to an object cloud --------------------------------
+ * btba_fuse_frames turns the posed keyframes a session ends with (Bundler's keyframes: depth, normal and colour maps already
+ * invalidated outside the mask by btba_apply_masks, and a bundle-adjusted pose_in_model) into ONE voxel-grid cloud per object, and
+ * is at the same time Utils::downsamplePointCloud (src/Utils.cpp:134-140: pcl::VoxelGrid; used for the model cloud at
+ * src/DataLoader.cpp:92 with leaf 0.015 and for drawProjectPoints at src/Utils.cpp:218 with leaf 0.01).  The voxel rule below is
+ * pcl::VoxelGrid::applyFilter's, RESTATED FROM PCL'S PUBLISHED HEADER AND UNVERIFIED AGAINST A PCL RUN (PCL is not available to this
+ * project).  Every rule is exact, so a CPU restatement (tests/fusion_ref.py) reproduces every output byte.
+ *
+ * A call serves n_instances independent objects.  Each owns the segments that name it (in any order) and one voxel box.
+ *   Frame segment (BTBA_FUSE_FRAME): geom = device float depth [H*W], normal = device float4 [H*W], colour = device uchar4 [H*W]
+ *     ((B, G, R, 0), Frame::updateColorGPU), pose = row-major 4 x 4 camera -> model (FrameRef.pose_in_model; row 3 is not read).  The
+ *     camera-space point of pixel (x, y) is btba_depth_to_normals' / btba_ingest_frames' xyz_out bit for bit (the same device
+ *     function, the same Kinv of K_rowmajor).  A pixel is dropped when its depth fails (double)d >= 0.1 and, with
+ *     params.require_normals, when its normal is exactly (0, 0, 0).  normal may be NULL only with require_normals = 0.
+ *   Point-list segment (BTBA_FUSE_POINTS): geom = device float4 xyz [n] (w is not read), normal = NULL or device float4 [n], colour =
+ *     NULL or device uchar4 [n].  A point with a non-finite coordinate is dropped (VoxelGrid's is_dense = false rule);
+ *     require_normals does not apply.  With the identity pose this is the plain downsamplePointCloud.
+ * Per surviving point, uncontracted fp32 in the order written:
+ *   1. p_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 and n_r = (T_r0 nx + T_r1 ny) + T_r2 nz.  A segment without a normal map gives n = 0; a
+ *      rotated normal with a component that is not below 2^16 in magnitude (or NaN) counts as (0, 0, 0).
+ *   2. voxel i_a = (int)floorf(p_a * inv_leaf) - min_b_a, inv_leaf = 1.0f / leaf formed once on the host in fp32.  The point is counted in
+ *      n_outside[instance] and dropped when some |p_a| is not below 2^16 m (NaN included) or some i_a lies outside 0 <= i_a < dims_a.
+ *   3. the voxel's count (uint32) grows by 1, its three position sums (int64) by llrint((double)p_a * 2^20) and its normal sums by
+ *      llrint((double)n_a * 2^20) (both exact up to the one rounding to nearest even), its three colour sums (uint32) by the
+ *      bytes x, y, z of the uchar4.  Integer atomicAdd on device memory; no float atomics.
+ * Output, per instance: the voxels with count >= min_points (VoxelGrid's setMinimumPointsNumberPerVoxel) in ascending linear index
+ * lin = ix + dims_x (iy + dims_y iz), VoxelGrid's order after its sort.  Record k of instance b sits at [b * capacity + k]:
+ *   xyz_out     float4: (float)((double)sum_a / 2^20 / count) per axis, w = 1
+ *   normal_out  float4: the mean normal formed the same way, w = 0; NOT renormalised (VoxelGrid averages every field) unless
+ *               params.normalize_normals: then n / sqrtf((nx nx + ny ny) + nz nz), (0, 0, 0) where that length is 0
+ *   colour_out  uchar4: (2 sum + count) / (2 count) per channel in integers, w = 0
+ *   count_out   uint32, lin_out int32
+ *   n_out[b]    the number of qualifying voxels EVEN WHEN IT EXCEEDS capacity; nothing is written at or past [b * capacity + capacity],
+ *               and status[b] then has BTBA_FUSE_OVERFLOW set (0 otherwise).  An instance without a surviving point gives n_out = 0.
+ * Because every sum is an integer, the result has the same bytes in any execution order, at any batch position, in any segment
+ * order and from run to run.  The sums are exact while a voxel receives fewer than 2^27 points (position), 2^24 (colour).
+ *
+ * The box (min_b[3], dims[3]) per instance is a HOST argument, so the fusion call needs no host synchronisation.  btba_fuse_bounds
+ * makes VoxelGrid's data-derived box on the device: over the same segments, min_b_a = min floorf(p_a * inv_leaf) and dims_a = max - min
+ * + 1 over the surviving points with every |p_a| below 2^16 (integer atomicMin / atomicMax), six int32 per instance; an instance
+ * without such a point gets six zeros.  The caller copies them to the host (its one synchronisation) and passes them on.
+ * btba_fuse_layout is host-only (no GPU, no workspace), in the family of btba_match_capacity and btba_window_layout: it validates
+ * the boxes (BTBA_EINVAL: a negative side, more than BTBA_FUSE_MAX_VOXELS voxels in the whole call) and returns every instance's first
+ * voxel, voxel_offsets_out [n_instances + 1] (NULL: not wanted), and the scratch the call will take, 64 bytes per voxel in
+ * structure-of-arrays planes plus the compaction's block counts.  The scratch itself is grow-only in the workspace, as
+ * btba_match_pairs' is: the caller passes none.
+ *
+ * btba_fuse_bounds and btba_fuse_frames are asynchronous on the workspace stream; segments go in chunks of BTBA_FUSE_CHUNK whose
+ * pointers, poses and boxes travel as kernel arguments, so no host memory is read after the call returns.  Planes that no output
+ * reads (normal sums without normal_out, colour sums without colour_out) are neither cleared nor accumulated.
+ * BTBA_EINVAL, decided before the first launch: NULL ws, params, segments (with n_segments > 0), box or a required output (xyz_out,
+ * n_out, n_outside, status; box_out_dev); n_instances < 1, n_segments < 0, capacity < 0, n_instances * capacity beyond 2^31 - 1; leaf
+ * not > 0, not finite or below 2^-14 m (inv_leaf would let the floor leave int32); min_points < 1; a segment with an unknown kind, an
+ * instance outside 0 .. n_instances - 1, a NULL geom (but for a point list with n = 0), n outside 0 .. 2^30 (point list); a frame segment with H < 1, W < 1, H * W >
+ * 2^30 or K_rowmajor NULL, or without a normal map under require_normals; geom of a point list, a normal map or a float4 output
+ * not 16-byte aligned, a depth, colour map, uchar4, count or lin output not 4-byte aligned; colour_out with a segment that has no colour
+ * map; a negative box side, |min_b_a| above 2^30, or more than BTBA_FUSE_MAX_VOXELS voxels.
+ * btba_voxel_downsample is btba_fuse_frames on one point-list segment per instance with the identity pose. */
+#define BTBA_FUSE_MAX_VOXELS (1 << 24)    /* voxels of one call, all instances together: 1 GiB of scratch */
+#define BTBA_FUSE_CHUNK 32                /* segments per launch */
+#define BTBA_FUSE_FRAME 0
+#define BTBA_FUSE_POINTS 1
+#define BTBA_FUSE_OVERFLOW 1              /* status bit: n_out exceeds capacity */
+typedef struct btba_fuse_params {
+    float leaf;                           /* voxel side in metres (default 0.005) */
+    int32_t min_points;                   /* 1 (default): points a voxel needs to be output */
+    int32_t require_normals;              /* 1 (default): frame pixels with a zero normal are dropped */
+    int32_t normalize_normals;            /* 0 (default): the mean normal as it is */
+} btba_fuse_params;
+typedef struct btba_fuse_segment {        /* 104 bytes, host memory */
+    int32_t kind;                         /* BTBA_FUSE_FRAME or BTBA_FUSE_POINTS */
+    int32_t instance;
+    int64_t n;                            /* points of a point list; not read for a frame (H * W) */
+    const void *geom;                     /* device: float depth [H*W], or float4 xyz [n] */
+    const void *normal;                   /* device float4, or NULL */
+    const void *colour;                   /* device uchar4, or NULL */
+    float pose[16];                       /* row-major camera -> model */
+} btba_fuse_segment;
+BTBA_API void btba_fuse_params_default(btba_fuse_params *p);
+BTBA_API int btba_fuse_layout(int n_instances, const int32_t *box /* host [n_instances][6] */, int64_t *voxel_offsets_out, int64_t *scratch_bytes_out);
+BTBA_API int btba_fuse_bounds(btba_workspace *ws, const btba_fuse_params *params, int n_instances, int n_segments,
+                              const btba_fuse_segment *segments, int H, int W, const float *K_rowmajor,
+                              int32_t *box_out_dev /* [n_instances][6] */);
+BTBA_API int btba_fuse_frames(btba_workspace *ws, const btba_fuse_params *params, int n_instances, int n_segments,
+                              const btba_fuse_segment *segments, int H, int W, const float *K_rowmajor,
+                              const int32_t *box /* host [n_instances][6] */, int capacity,
+                              float *xyz_out_dev      /* float4 [n_instances][capacity] */,
+                              float *normal_out_dev   /* NULL or float4 [n_instances][capacity] */,
+                              uint8_t *colour_out_dev /* NULL or uchar4 [n_instances][capacity] */,
+                              uint32_t *count_out_dev /* NULL or [n_instances][capacity] */,
+                              int32_t *lin_out_dev    /* NULL or [n_instances][capacity] */,
+                              int32_t *n_out_dev, int32_t *n_outside_dev, int32_t *status_dev /* [n_instances] each */);
+BTBA_API int btba_voxel_downsample(btba_workspace *ws, const btba_fuse_params *params, int n_instances,
+                                   const float *const *xyz_dev, const float *const *normal_dev /* NULL, or entries NULL */,
+                                   const uint8_t *const *colour_dev /* NULL, or entries NULL */, const int64_t *n_points,
+                                   const int32_t *box, int capacity, float *xyz_out_dev, float *normal_out_dev, uint8_t *colour_out_dev,
+                                   uint32_t *count_out_dev, int32_t *lin_out_dev, int32_t *n_out_dev, int32_t *n_outside_dev, int32_t *status_dev);
+
 #ifdef __cplusplus
 }
 #endif

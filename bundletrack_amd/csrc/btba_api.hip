@@ -463,6 +463,33 @@ static int dense_pair_table(btba_workspace *ws, int N, const std::vector<int32_t
     return BTBA_OK;
 }
 
+// The dimensions every sweep item reads that follow from the parameters, the window, the cache size and the intrinsics alone: what a pixel or an entry is
+// gated, weighted and addressed by.  intr: the cache's (fx, fy, cx, cy); H, W, K: the full-resolution geometry the compact cache encodes (K nullptr: no
+// compact cache).  Chunks and tiles, trace offsets, walk, lists and the launch's own fields are the caller's.
+static SolveDims sweep_dims(const btba_params *prm, int N, int Hd, int Wd, const float *intr, int H, int W, const float *K)
+{
+    SolveDims D{};
+    D.n_frames = N; D.n_pairs = N * (N - 1) / 2;
+    D.npix = Hd * Wd; D.width = Wd; D.height = Hd;
+    D.fx = intr[0]; D.fy = intr[1]; D.cx = intr[2]; D.cy = intr[3];
+    D.robust_delta = prm->robust_delta; D.dist_thresh = prm->dense_dist_thresh; D.normal_thresh = prm->dense_normal_thresh;
+    D.dist2_thresh = prm->dense_dist_thresh * prm->dense_dist_thresh;
+    D.wm1 = (float)(Wd - 1); D.hm1 = (float)(Hd - 1); D.wm2 = (float)(Wd - 2); D.hm2 = (float)(Hd - 2);
+    D.depth_min = prm->depth_min; D.depth_max = prm->depth_max;
+    D.w_sparse = prm->weight_sparse; D.w_dense = prm->weight_dense_depth;
+    D.pose_stride = 16 * N; D.x_stride = 6 * N;                      // instances back to back
+    if (K) {
+        float intr_chk[4]; Mat4 Kinv;
+        scaled_intrinsics(H, W, Hd, Wd, K, intr_chk, &Kinv);
+        for (int k = 0; k < 16; k++) D.zn_ki[k] = Kinv.m[k];
+        D.zn_scale_w = (float)(W - 1) / (float)(Wd - 1);
+        D.zn_scale_h = (float)(H - 1) / (float)(Hd - 1);
+        const float *ki = D.zn_ki;
+        D.zn_simple = (ki[1] == 0.f && ki[3] == 0.f && ki[4] == 0.f && ki[7] == 0.f && ki[12] == 0.f && ki[13] == 0.f && ki[14] == 0.f && ki[15] == 1.0f) ? 1 : 0;     // pinhole: z = d exactly
+    }
+    return D;
+}
+
 struct ZnSpec {      // compact cache + the full-res geometry it encodes
     const float *zn = nullptr; int H = 0, W = 0; const float *K = nullptr;
     const int *frame_slot = nullptr;                       // persistent cache: device int[N], frame -> pool slot (B == 1 only)
@@ -551,23 +578,16 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     const int32_t *d_adj_off = ws->dense_pairs.as<int32_t>() + 2 * (size_t)Pd;
     const int32_t *d_adj = d_adj_off + (N + 1);
 
-    SolveDims D{};
-    D.n_frames = N; D.n_pairs = P; D.n_dense_pairs = use_dense ? Pd : 0;
-    D.npix = npix; D.width = Wd; D.height = Hd;
+    if (use_zn && (!Z.K || Z.H < 2 || Z.W < 2)) return BTBA_EINVAL;
+    SolveDims D = sweep_dims(prm, N, Hd, Wd, intr, Z.H, Z.W, use_zn ? Z.K : nullptr);
+    D.n_dense_pairs = use_dense ? Pd : 0;
     D.sparse_chunks = chunks; D.dense_tiles = tiles; D.n_pcg = prm->n_pcg_iters;
     D.use_sparse = use_sparse; D.use_dense = use_dense;
-    D.fx = intr[0]; D.fy = intr[1]; D.cx = intr[2]; D.cy = intr[3];
-    D.robust_delta = prm->robust_delta; D.dist_thresh = prm->dense_dist_thresh; D.normal_thresh = prm->dense_normal_thresh;
-    D.dist2_thresh = prm->dense_dist_thresh * prm->dense_dist_thresh;
-    D.wm1 = (float)(Wd - 1); D.hm1 = (float)(Hd - 1); D.wm2 = (float)(Wd - 2); D.hm2 = (float)(Hd - 2);
-    D.depth_min = prm->depth_min; D.depth_max = prm->depth_max;
-    D.w_sparse = prm->weight_sparse; D.w_dense = prm->weight_dense_depth;
     D.corr_stride = corr_stride;
     D.corr_nt_from = B;                // plain loads unless decided otherwise below
     D.order_flag = order_flag;
     D.live_blocks = (ws->count_live && ws->live_blocks.p) ? ws->live_blocks.as<unsigned long long>() : nullptr;
-    D.pose_stride = 16 * N; D.x_stride = 6 * N;                      // instances back to back (the chained launch pads them, below)
-    D.sp_stride = (unsigned)((size_t)P * (atomic_sums ? 1 : chunks) * kSparseVals);
+    D.sp_stride = (unsigned)((size_t)P * (atomic_sums ? 1 : chunks) * kSparseVals);      // (the chained launch pads the strides, below)
     D.dp_stride = (unsigned)((size_t)(Pd > 0 ? Pd : 1) * (atomic_sums ? 1 : tiles) * kDenseVals);
     if ((size_t)B * std::max(D.sp_stride, D.dp_stride) >= ((size_t)1 << 32) || (size_t)B * 16 * N >= ((size_t)1 << 31)) return BTBA_EINVAL;      // the sweeps address an instance's poses and partials in 32 bits
     D.atomic_sums = atomic_sums ? 1 : 0;
@@ -578,19 +598,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     D.sparse_tail_256 = 0;             // set below, once the dense layout is known
     D.walk_blocks = (Wd % 8 == 0 && Hd % 8 == 0 && Wd + Hd <= 1024 && ws->tune.block_walk) ? 1 : 0;
     D.n_gn = prm->n_gn_iters;
-    int zn_layout = 0;
-    if (use_zn) {
-        if (!Z.K || Z.H < 2 || Z.W < 2) return BTBA_EINVAL;
-        float intr_chk[4];
-        Mat4 Kinv;
-        scaled_intrinsics(Z.H, Z.W, Hd, Wd, Z.K, intr_chk, &Kinv);
-        for (int k = 0; k < 16; k++) D.zn_ki[k] = Kinv.m[k];
-        D.zn_scale_w = (float)(Z.W - 1) / (float)(Wd - 1);
-        D.zn_scale_h = (float)(Z.H - 1) / (float)(Hd - 1);
-        const float *ki = D.zn_ki;
-        D.zn_simple = (ki[1] == 0.f && ki[3] == 0.f && ki[4] == 0.f && ki[7] == 0.f && ki[12] == 0.f && ki[13] == 0.f && ki[14] == 0.f && ki[15] == 1.0f) ? 1 : 0;     // pinhole: z = d exactly
-        zn_layout = D.zn_simple ? 1 : 2;
-    }
+    const int zn_layout = use_zn ? (D.zn_simple ? 1 : 2) : 0;
     D.trace_on = (trace != nullptr) && (prm->flags & BTBA_FLAG_TRACE);
     btba_trace_layout L;
     btba_trace_layout_get(N, D.n_dense_pairs, prm->n_pcg_iters, &L);
@@ -1735,28 +1743,14 @@ int objective_enqueue(btba_workspace *ws, const ObjectiveCall &c)
     btba_objective_pair *dense_part = reinterpret_cast<btba_objective_pair *>(base + lay.dense), *sparse_part = reinterpret_cast<btba_objective_pair *>(base + lay.sparse);
 
     float intr[4];
-    Mat4 Kinv;
-    scaled_intrinsics(c.H, c.W, Hd, Wd, c.K, intr, &Kinv);
-    // the fields of the solve's dimensions that the sweeps' device functions read (solve_enqueue fills them the same way)
-    SolveDims D{};
-    D.n_frames = N; D.n_pairs = P; D.n_dense_pairs = Pd;
-    D.npix = npix; D.width = Wd; D.height = Hd;
+    Mat4 Kinv_unused;
+    scaled_intrinsics(c.H, c.W, Hd, Wd, c.K, intr, &Kinv_unused);
+    SolveDims D = sweep_dims(prm, N, Hd, Wd, intr, c.H, c.W, c.K);
+    D.n_dense_pairs = Pd;
     D.sparse_chunks = lay.chunks; D.dense_tiles = 1;
     D.use_sparse = with_sparse; D.use_dense = Pd > 0;
-    D.fx = intr[0]; D.fy = intr[1]; D.cx = intr[2]; D.cy = intr[3];
-    D.robust_delta = prm->robust_delta; D.dist_thresh = prm->dense_dist_thresh; D.normal_thresh = prm->dense_normal_thresh;
-    D.dist2_thresh = prm->dense_dist_thresh * prm->dense_dist_thresh;
-    D.wm1 = (float)(Wd - 1); D.hm1 = (float)(Hd - 1); D.wm2 = (float)(Wd - 2); D.hm2 = (float)(Hd - 2);
-    D.depth_min = prm->depth_min; D.depth_max = prm->depth_max;
-    D.w_sparse = prm->weight_sparse; D.w_dense = prm->weight_dense_depth;
     D.corr_stride = c.corr_stride; D.corr_nt_from = B; D.corr24 = c.corr24 ? 1 : 0;
-    D.pose_stride = 16 * N; D.x_stride = 6 * N;
     if (Pd > 0) { D.dense_work = reinterpret_cast<const int4 *>(ws->dense_pairs.as<int32_t>() + ws->dense_work_offset); D.work_formula = ws->work_formula; }
-    for (int k = 0; k < 16; k++) D.zn_ki[k] = Kinv.m[k];
-    D.zn_scale_w = (float)(c.W - 1) / (float)(Wd - 1);
-    D.zn_scale_h = (float)(c.H - 1) / (float)(Hd - 1);
-    const float *ki = D.zn_ki;
-    D.zn_simple = (ki[1] == 0.f && ki[3] == 0.f && ki[4] == 0.f && ki[7] == 0.f && ki[12] == 0.f && ki[13] == 0.f && ki[14] == 0.f && ki[15] == 1.0f) ? 1 : 0;
     const SweepLayout sweep_lds(Wd, Hd, 0, D.zn_simple ? kSweepLdsStrips : kSweepLdsGeneralK);
     if (Pd > 0 && sweep_lds.total > 60 * 1024) return BTBA_EINVAL;      // (a cache of more than ~3 000 columns + rows)
 

@@ -307,6 +307,13 @@ __global__ void __launch_bounds__(kBlock) k_pack_zn(size_t total, const float4 *
 //            (pos_i.x, pos_i.y)[64], (pos_i.z, pos_j.x)[64], (pos_j.y, pos_j.z)[64] -- so that each of a wave's three 8-byte loads covers 512
 //            contiguous bytes: plain 24-byte records, three loads at stride 24, touch every cache line three times and measured SLOWER than
 //            EntryJ on the masked launch although they move a quarter less (52.0 vs 49.9 us, gpurun_out/r03_13).
+// the loaded words of one correspondence -> (valid, pos_i, pos_j): the one statement of both layouts (the sweep below, the objective report)
+struct SparseEntry { bool valid; float pix, piy, piz, pjx, pjy, pjz; };
+// EntryJ: q0 = (imgIdx_i, imgIdx_j, pos_i.x, pos_i.y)  q1 = (pos_i.z, pos_j.x, pos_j.y, pos_j.z); invalid <=> imgIdx_i = 0xFFFFFFFF (EntryJ::isValid)
+__device__ __forceinline__ SparseEntry sparse_entry_j(const float4 &q0, const float4 &q1) { return SparseEntry{ __float_as_uint(q0.x) != 0xFFFFFFFFu, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w }; }
+// C24: the three planes' words of the entry
+__device__ __forceinline__ SparseEntry sparse_entry_c24(const float2 &q0, const float2 &q1, const float2 &q2) { return SparseEntry{ __float_as_uint(q0.x) != 0xFFFFFFFFu, q0.x, q0.y, q1.x, q1.y, q2.x, q2.y }; }
+
 template <bool C24, bool NT>
 __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const float4 *__restrict__ corr, const uint32_t *__restrict__ pair_offsets,
                                                   const float *__restrict__ T, float *__restrict__ partials, int chunk, int p, int b, float *red)
@@ -332,10 +339,10 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
     // Otherwise an invalid / out-of-range slot contributes exact zeros (its payload may be anything, even NaN) through the selects in the two blocks behind
     // wave-uniform branches; with every entry valid those selects return their first operand, so both ways are the same arithmetic and the same bits.
     // (The empty asm keeps each block a branch: speculated, its selects would run on every trip again.)
-    auto accumulate = [&](const bool all_valid, bool valid, float pix, float piy, float piz, float pjx, float pjy, float pjz) {
+    auto accumulate = [&](const bool all_valid, bool valid, const SparseEntry &E) {
         float wix, wiy, wiz, wjx, wjy, wjz;
-        xform_point(Ti, pix, piy, piz, wix, wiy, wiz);
-        xform_point(Tj, pjx, pjy, pjz, wjx, wjy, wjz);
+        xform_point(Ti, E.pix, E.piy, E.piz, wix, wiy, wiz);
+        xform_point(Tj, E.pjx, E.pjy, E.pjz, wjx, wjy, wjz);
         if (!all_valid) {
             asm volatile("");
             wix = valid ? wix : 0.0f; wiy = valid ? wiy : 0.0f; wiz = valid ? wiz : 0.0f;
@@ -367,13 +374,12 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
         acc[41] += rho * (wjy * wjy + wjz * wjz); acc[42] += rho * (wjx * wjx + wjz * wjz); acc[43] += rho * (wjx * wjx + wjy * wjy);
     };
     // One trip's two correspondences.  The count is a popcount of the two valid masks (the ballots of single comparisons, AND-ed in scalar registers).
-    auto accumulate_pair = [&](bool valid_a, bool live_b, bool valid_b, float ax, float ay, float az, float aX, float aY, float aZ,
-                               float bx, float by, float bz, float bX, float bY, float bZ) {
-        const unsigned long long ma = __builtin_amdgcn_ballot_w64(valid_a), mb = __builtin_amdgcn_ballot_w64(live_b) & __builtin_amdgcn_ballot_w64(valid_b);
+    auto accumulate_pair = [&](const SparseEntry &A, bool live_b, const SparseEntry &B) {
+        const unsigned long long ma = __builtin_amdgcn_ballot_w64(A.valid), mb = __builtin_amdgcn_ballot_w64(live_b) & __builtin_amdgcn_ballot_w64(B.valid);
         n_valid += __popcll(ma) + __popcll(mb);
         const bool all_valid = (ma & mb) == ~0ull;
-        accumulate(all_valid, valid_a, ax, ay, az, aX, aY, aZ);
-        accumulate(all_valid, live_b && valid_b, bx, by, bz, bX, bY, bZ);
+        accumulate(all_valid, A.valid, A);
+        accumulate(all_valid, live_b && B.valid, B);
     };
     // two correspondences per lane per trip (entries e and e + 256: every load instruction of a wave covers consecutive entries), all of
     // their loads in flight together
@@ -387,8 +393,7 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
             const bool live2 = e2 < hi;
             const float2 *qa = cb + corr24_index(e_base + e), *qb = cb + corr24_index(e_base + (live2 ? e2 : e));
             const float2 a0 = ld_stream_f2<NT>(qa), a1 = ld_stream_f2<NT>(qa + 64), a2 = ld_stream_f2<NT>(qa + 128), b0 = ld_stream_f2<NT>(qb), b1 = ld_stream_f2<NT>(qb + 64), b2 = ld_stream_f2<NT>(qb + 128);
-            accumulate_pair(__float_as_uint(a0.x) != 0xFFFFFFFFu, live2, __float_as_uint(b0.x) != 0xFFFFFFFFu,
-                            a0.x, a0.y, a1.x, a1.y, a2.x, a2.y, b0.x, b0.y, b1.x, b1.y, b2.x, b2.y);
+            accumulate_pair(sparse_entry_c24(a0, a1, a2), live2, sparse_entry_c24(b0, b1, b2));
         }
     } else {
         const float4 *cb = corr + 2 * (size_t)b * D.corr_stride;
@@ -397,8 +402,7 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
         const size_t e_out = (size_t)D.corr_entry0 + (size_t)b * (size_t)D.corr_stride;
         // the entry's order check and re-layout (its sums: accumulate_pair)
         auto entry = [&](const float4 &q0, const float4 &q1, bool live, uint32_t e) {
-            // q0 = (imgIdx_i, imgIdx_j, pos_i.x, pos_i.y)  q1 = (pos_i.z, pos_j.x, pos_j.y, pos_j.z)
-            const bool valid = live && __float_as_uint(q0.x) != 0xFFFFFFFFu;      // EntryJ::isValid
+            const bool valid = live && sparse_entry_j(q0, q1).valid;
             misplaced |= valid & ((__float_as_uint(q0.x) != (uint32_t)fi) | (__float_as_uint(q0.y) != (uint32_t)fj));
             if (c24 && live) {
                 float2 *o = c24 + corr24_index(e_out + e);
@@ -414,8 +418,7 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
             const float4 a0 = ld_stream_f4<NT>(cb + 2 * (size_t)e), a1 = ld_stream_f4<NT>(cb + 2 * (size_t)e + 1), b0 = ld_stream_f4<NT>(cb + 2 * (size_t)e2c), b1 = ld_stream_f4<NT>(cb + 2 * (size_t)e2c + 1);
             entry(a0, a1, true, e);
             entry(b0, b1, live2, e2c);
-            accumulate_pair(__float_as_uint(a0.x) != 0xFFFFFFFFu, live2, __float_as_uint(b0.x) != 0xFFFFFFFFu,
-                            a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w);
+            accumulate_pair(sparse_entry_j(a0, a1), live2, sparse_entry_j(b0, b1));
         }
         if (D.order_flag && misplaced) atomicOr(D.order_flag, 1);
     }
@@ -560,32 +563,39 @@ __device__ __forceinline__ PixelGeom pixel_geom(const DenseCtx &C, const float4 
     return g;
 }
 
-__device__ __forceinline__ void pixel_accumulate(const DenseCtx &C, const PixelGeom &g,
-                                                 const float4 &c00, const float4 &c10, const float4 &c01, const float4 &c11,
-                                                 const float4 &n00, const float4 &n10, const float4 &n01, const float4 &n11,
-                                                 float (&acc)[kDenseVals])
+// stage 2: blend of the target taps, the gates and the residual.  ok contains g.valid; nothing here is masked yet.
+struct PixelBlend { float nix, niy, niz, dx, dy, dz, res; bool ok; };
+__device__ __forceinline__ PixelBlend pixel_blend(const DenseCtx &C, const PixelGeom &g, const float4 &c00, const float4 &c10, const float4 &c01, const float4 &c11,
+                                                  const float4 &n00, const float4 &n10, const float4 &n01, const float4 &n11)
 {
+    PixelBlend B;
     const float cix = g.c00 * c00.x + g.c10 * c10.x + g.c01 * c01.x + g.c11 * c11.x;
     const float ciy = g.c00 * c00.y + g.c10 * c10.y + g.c01 * c01.y + g.c11 * c11.y;
     const float ciz = g.c00 * c00.z + g.c10 * c10.z + g.c01 * c01.z + g.c11 * c11.z;
-    const float nix = g.c00 * n00.x + g.c10 * n10.x + g.c01 * n01.x + g.c11 * n11.x;
-    const float niy = g.c00 * n00.y + g.c10 * n10.y + g.c01 * n01.y + g.c11 * n11.y;
-    const float niz = g.c00 * n00.z + g.c10 * n10.z + g.c01 * n01.z + g.c11 * n11.z;
-    const float dx = g.qx - cix, dy = g.qy - ciy, dz = g.qz - ciz;
-    const float dist2 = dx * dx + dy * dy + dz * dz;
-    const float dn = g.nqx * nix + g.nqy * niy + g.nqz * niz;
+    B.nix = g.c00 * n00.x + g.c10 * n10.x + g.c01 * n01.x + g.c11 * n11.x;
+    B.niy = g.c00 * n00.y + g.c10 * n10.y + g.c01 * n01.y + g.c11 * n11.y;
+    B.niz = g.c00 * n00.z + g.c10 * n10.z + g.c01 * n01.z + g.c11 * n11.z;
+    B.dx = g.qx - cix; B.dy = g.qy - ciy; B.dz = g.qz - ciz;
+    const float dist2 = B.dx * B.dx + B.dy * B.dy + B.dz * B.dz;
+    const float dn = g.nqx * B.nix + g.nqy * B.niy + g.nqz * B.niz;
     // `&`, not `&&`: short-circuit evaluation turns into nested exec-mask branches with a block of zeroing moves on each
-    const bool ok = g.valid & (ciz > C.depth_min) & (ciz < C.depth_max) & (dn >= C.normal_thresh) & (dist2 <= C.dist2_thresh);
+    B.ok = g.valid & (ciz > C.depth_min) & (ciz < C.depth_max) & (dn >= C.normal_thresh) & (dist2 <= C.dist2_thresh);
+    B.res = -(B.dx * B.nix + B.dy * B.niy + B.dz * B.niz);
+    return B;
+}
+// stage 3: the pixel's row, weight and residual into the lane's sums
+__device__ __forceinline__ void pixel_sums(const DenseCtx &C, const PixelGeom &g, const PixelBlend &B, float (&acc)[kDenseVals])
+{
     // rejected pixels contribute exact zeros.  Bit masks, not `ok ? x : 0`: the compiler turns a run of such selects into
     // an exec-mask branch with a block of zeroing moves on the other path; AND-ing with 0 / ~0 stays straight-line and is
     // NaN-safe (0 * NaN would poison the sums if a target normal were not finite; q is finite whenever the poses are)
-    const unsigned keep = ok ? 0xFFFFFFFFu : 0u;
+    const unsigned keep = B.ok ? 0xFFFFFFFFu : 0u;
     auto masked = [keep](float x) { return __uint_as_float(__float_as_uint(x) & keep); };
-    const float res = masked(-(dx * nix + dy * niy + dz * niz));
+    const float res = masked(B.res);
     const float e = res * res;
     const float wgt = masked(C.w_dense * ((e <= C.delta2) ? 1.0f : C.delta * fast_rsq(e)));
     // camera-frame row a' = [-n_i ; n_i x q]
-    const float mx = masked(nix), my = masked(niy), mz = masked(niz);
+    const float mx = masked(B.nix), my = masked(B.niy), mz = masked(B.niz);
     const float a[6] = { -mx, -my, -mz, my * g.qz - mz * g.qy, mz * g.qx - mx * g.qz, mx * g.qy - my * g.qx };
     int k = 0;
 #pragma unroll
@@ -597,6 +607,10 @@ __device__ __forceinline__ void pixel_accumulate(const DenseCtx &C, const PixelG
     }
     acc[27] += masked(1.0f);
 }
+
+__device__ __forceinline__ void pixel_accumulate(const DenseCtx &C, const PixelGeom &g, const float4 &c00, const float4 &c10, const float4 &c01, const float4 &c11,
+                                                 const float4 &n00, const float4 &n10, const float4 &n01, const float4 &n11, float (&acc)[kDenseVals])
+{ pixel_sums(C, g, pixel_blend(C, g, c00, c10, c01, c11, n00, n10, n01, n11), acc); }
 
 #ifdef BTBA_REFERENCE_ORDER
 // ---- TEST-ONLY build (-DBTBA_REFERENCE_ORDER, never the product; speed irrelevant): one pixel of the dense term evaluated in the REFERENCE's order --
@@ -914,39 +928,65 @@ __global__ void __launch_bounds__(1024) k_valid_lists(int npix, const float4 *__
     if (threadIdx.x == 0) counts[f] = total;
 }
 
-// The same sweep on the compact cache: ONE 16-byte load per source pixel and per tap (5 loads instead of 10),
-// camera-space points re-derived from z with the cache builder's exact arithmetic (zn_backproject).  General intrinsics only (skew, or a projective
-// last row): every pinhole case is dense_block_pinhole's.
-template <bool LISTS>
-__device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 *__restrict__ zn, const int2 ij,
-                                               const float *__restrict__ T, const float *__restrict__ Tinv,
-                                               float *__restrict__ partials, int tile, int p, int b, float *red,
-                                               const uint32_t *__restrict__ valid_lists, const int *__restrict__ valid_counts, float *lut)
+// ---- the general-K sweep on the compact cache: ONE 16-byte load per source pixel and per tap (5 loads instead of 10), camera-space points re-derived from z with
+// the cache builder's exact arithmetic (zn_backproject).  General intrinsics only (skew, or a projective last row): every pinhole case is dense_block_pinhole's.
+// The set-up of an item and the stages of a pixel are shared with the objective report (btba_objective.hpp), like the pinhole stages below.
+struct ZnItem { DenseCtx C; const float *lut_x, *lut_y; const float4 *zn_t, *zn_s; size_t slot_s; };      // LDS tables (below); the target and the source frame; the source frame's cache slot
+// Item set-up, by the kBlock threads of the workgroup: target fi, source fj of instance b; lut = (Wd + Hd) floats of LDS.  Holds a barrier.
+__device__ __forceinline__ ZnItem zn_item_setup(const SolveDims &D, const float4 *__restrict__ zn, const float *__restrict__ T, const float *__restrict__ Tinv, int fi, int fj, int b, float *lut)
 {
     // lut[0 .. Wd) = (float) full-res column of cache column x, lut[Wd .. Wd+Hd) the same for rows: the per-coordinate
     // arithmetic becomes one LDS read
     for (int e = (int)threadIdx.x; e < D.width + D.height; e += kBlock)
         lut[e] = (float)(e < D.width ? zn_src_coord(e, D.zn_scale_w) : zn_src_coord(e - D.width, D.zn_scale_h));
     __syncthreads();
-    const float *lut_x = lut, *lut_y = lut + D.width;
-    const int fi = ij.x, fj = ij.y;                       // fi = target, fj = source
+    ZnItem I;
+    I.lut_x = lut; I.lut_y = lut + D.width;
     const size_t fb = (size_t)b * D.n_frames;
-    const unsigned pb = (unsigned)b * (unsigned)D.pose_stride;
-    dense_M_store(threadIdx.x, red, dense_M_load(threadIdx.x, T + pb + 16 * fi));
-    DenseCtx C = dense_ctx(D, T, Tinv, pb, fi, fj, nullptr, nullptr);
+    I.C = dense_ctx(D, T, Tinv, (unsigned)b * (unsigned)D.pose_stride, fi, fj, nullptr, nullptr);
     // the relative pose is the same in every lane: keep it in scalar registers (12 VGPRs back)
 #pragma unroll
-    for (int e = 0; e < 12; e++) C.Tij.m[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, C.Tij.m[e])));
+    for (int e = 0; e < 12; e++) I.C.Tij.m[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, I.C.Tij.m[e])));
     // wave-uniform by construction; readfirstlane tells the compiler, so the frame bases live in SGPRs and the tap
     // gathers use the scalar-base + 32-bit-offset addressing form
     const size_t slot_t = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fi));
-    const size_t slot_s = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fj));
-    const float4 *zn_t = zn + slot_t * (size_t)D.npix, *zn_s = zn + slot_s * (size_t)D.npix;
+    I.slot_s = (size_t)__builtin_amdgcn_readfirstlane((int)frame_slot_of(D, fb + fj));
+    I.zn_t = zn + slot_t * (size_t)D.npix; I.zn_s = zn + I.slot_s * (size_t)D.npix;
+    return I;
+}
+// stage 1: the source pixel (px, py) with cache entry zs, back-projected, through pixel_geom
+__device__ __forceinline__ PixelGeom zn_pixel_geom(const SolveDims &D, const ZnItem &I, int px, int py, const float4 &zs)
+{
+    const float3 cp = zn_backproject(D.zn_ki, I.lut_x[px], I.lut_y[py], zs.x);
+    return pixel_geom(I.C, make_float4(cp.x, cp.y, cp.z, 1.0f), make_float4(zs.y, zs.z, zs.w, 0.0f));
+}
+// stage 2: the four taps, back-projected, through pixel_blend (the tap indices of a rejected pixel are clamped into the frame all the same)
+__device__ __forceinline__ PixelBlend zn_pixel_blend(const SolveDims &D, const ZnItem &I, const PixelGeom &g)
+{
+    // 32-bit byte offsets from a scalar base: one shift per tap instead of a 64-bit shift-add (a frame is far below 4 GB)
+    const char *zt = reinterpret_cast<const char *>(I.zn_t);
+    const float4 z00 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i00 << 4)), z10 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i10 << 4));
+    const float4 z01 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i01 << 4)), z11 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i11 << 4));
+    const float xia = I.lut_x[g.xa], xib = I.lut_x[g.xb], yia = I.lut_y[g.ya], yib = I.lut_y[g.yb];
+    const float3 c00 = zn_backproject(D.zn_ki, xia, yia, z00.x), c10 = zn_backproject(D.zn_ki, xib, yia, z10.x);
+    const float3 c01 = zn_backproject(D.zn_ki, xia, yib, z01.x), c11 = zn_backproject(D.zn_ki, xib, yib, z11.x);
+    return pixel_blend(I.C, g, make_float4(c00.x, c00.y, c00.z, 1.f), make_float4(c10.x, c10.y, c10.z, 1.f), make_float4(c01.x, c01.y, c01.z, 1.f), make_float4(c11.x, c11.y, c11.z, 1.f),
+                       make_float4(z00.y, z00.z, z00.w, 0.f), make_float4(z10.y, z10.z, z10.w, 0.f), make_float4(z01.y, z01.z, z01.w, 0.f), make_float4(z11.y, z11.z, z11.w, 0.f));
+}
+
+template <bool LISTS>
+__device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 *__restrict__ zn, const int2 ij,
+                                               const float *__restrict__ T, const float *__restrict__ Tinv,
+                                               float *__restrict__ partials, int tile, int p, int b, float *red,
+                                               const uint32_t *__restrict__ valid_lists, const int *__restrict__ valid_counts, float *lut)
+{
+    const ZnItem I = zn_item_setup(D, zn, T, Tinv, ij.x, ij.y, b, lut);       // ij = (target, source)
+    dense_M_store(threadIdx.x, red, dense_M_load(threadIdx.x, T + (unsigned)b * (unsigned)D.pose_stride + 16 * ij.x));
     // LISTS: walk the source frame's ordered list of pixels that carry a depth (masked scenes: ~5 % of the image);
     // otherwise walk all pixels with incrementally advanced coordinates.  Two instantiations rather than one loop
     // with both: the kernel sits at the 96-VGPR / 5-waves-per-SIMD boundary and the merged loop measured 8 % slower.
-    const int n_src = LISTS ? valid_counts[slot_s] : D.npix;
-    const uint32_t *list = LISTS ? valid_lists + slot_s * (size_t)D.npix : nullptr;
+    const int n_src = LISTS ? valid_counts[I.slot_s] : D.npix;
+    const uint32_t *list = LISTS ? valid_lists + I.slot_s * (size_t)D.npix : nullptr;
     const int per = (n_src + D.dense_tiles - 1) / D.dense_tiles;
     const int lo = min(n_src, per * tile), hi = min(n_src, per * (tile + 1));
     const float inv_w = 1.0f / (float)D.width;
@@ -957,11 +997,11 @@ __device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 
     int px_i = s_n % D.width, py_i = s_n / D.width;             // incremental coordinates (direct walk only)
     const int step_x = kBlock % D.width, step_y = kBlock / D.width;
     float4 zs_n = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t < hi) zs_n = zn_s[s_n];
+    if (t < hi) zs_n = I.zn_s[s_n];
     for (; t < hi; t += kBlock) {
         const float4 zs = zs_n;
         const int s = s_n;
-        if (t + kBlock < hi) { s_n = LISTS ? (int)list[t + kBlock] : t + kBlock; zs_n = zn_s[s_n]; }      // next pixel's stream loads
+        if (t + kBlock < hi) { s_n = LISTS ? (int)list[t + kBlock] : t + kBlock; zs_n = I.zn_s[s_n]; }      // next pixel's stream loads
         int px, py;
         if (!LISTS) {
             px = px_i; py = py_i;
@@ -973,18 +1013,9 @@ __device__ __forceinline__ void dense_block_zn(const SolveDims &D, const float4 
             py += ((py + 1) * D.width <= s) ? 1 : 0;
             px = s - py * D.width;
         }
-        const float3 cp = zn_backproject(D.zn_ki, lut_x[px], lut_y[py], zs.x);
-        const PixelGeom g = pixel_geom(C, make_float4(cp.x, cp.y, cp.z, 1.0f), make_float4(zs.y, zs.z, zs.w, 0.0f));
+        const PixelGeom g = zn_pixel_geom(D, I, px, py, zs);
         if (__builtin_amdgcn_ballot_w64(g.valid) == 0ull) continue;
-        // 32-bit byte offsets from a scalar base: one shift per tap instead of a 64-bit shift-add (a frame is far below 4 GB)
-        const char *zt = reinterpret_cast<const char *>(zn_t);
-        const float4 z00 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i00 << 4)), z10 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i10 << 4));
-        const float4 z01 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i01 << 4)), z11 = *reinterpret_cast<const float4 *>(zt + ((unsigned)g.i11 << 4));
-        const float xia = lut_x[g.xa], xib = lut_x[g.xb], yia = lut_y[g.ya], yib = lut_y[g.yb];
-        const float3 c00 = zn_backproject(D.zn_ki, xia, yia, z00.x), c10 = zn_backproject(D.zn_ki, xib, yia, z10.x);
-        const float3 c01 = zn_backproject(D.zn_ki, xia, yib, z01.x), c11 = zn_backproject(D.zn_ki, xib, yib, z11.x);
-        pixel_accumulate(C, g, make_float4(c00.x, c00.y, c00.z, 1.f), make_float4(c10.x, c10.y, c10.z, 1.f), make_float4(c01.x, c01.y, c01.z, 1.f), make_float4(c11.x, c11.y, c11.z, 1.f),
-                         make_float4(z00.y, z00.z, z00.w, 0.f), make_float4(z10.y, z10.z, z10.w, 0.f), make_float4(z01.y, z01.z, z01.w, 0.f), make_float4(z11.y, z11.z, z11.w, 0.f), acc);
+        pixel_sums(I.C, g, zn_pixel_blend(D, I, g), acc);
     }
     dense_epilogue(acc, red, dense_record_out(D, partials, p, tile, b), dense_record_mode(D));
 }
@@ -1226,47 +1257,52 @@ __device__ __forceinline__ void pinhole_walk_constants(const SolveDims &D, Pinho
     C.lut_addr_f = (float)lds_address(C.lut); C.ybase4_abs = C.ybase4 + C.lut_addr_f;
 }
 
-// One source pixel: zs = its (gated depth, normal), ox / oy = LDS byte offsets of its column / row entries in the ray tables (from colA).
-// acc: the lane's 27 sums; n_ok: accepted pixels of this WAVE (scalar register), which joins the record as acc[27] behind the walk.
-__device__ __forceinline__ void pinhole_pixel(const PinholeCtx &C, const float4 &zs, unsigned ox, unsigned oy, float (&acc)[kDenseVals], int &n_ok)
+// ---- the stages of one source pixel, in the order they run.  pinhole_pixel accumulates the Jacobian sums behind them, the objective report
+// (btba_objective.hpp) its fp64 cost: both form the residual and the accept tests from these statements and no others.
+// Stage 1, project.  zs = the pixel's (gated depth, normal), ox / oy = LDS byte offsets of its column / row entries in the ray tables (from colA).
+// The three tests stay SINGLE comparisons: the sweep ballots each on its own (see pinhole_pixel), the report ANDs them.
+struct PinholeProj { float qx, qy, qz, uc, vc; bool src_ok, in_u, in_v; };
+__device__ __forceinline__ PinholeProj pinhole_project(const PinholeCtx &C, const float4 &zs, unsigned ox, unsigned oy)
 {
+    PinholeProj P;
     // source pixel -> camera space (gated depth: 0 where invalid), depth-range test on the bit pattern
     const float d = zs.x;
-    const bool src_ok = (__float_as_uint(d) - C.zmin_bits) < C.zrange_bits;
+    P.src_ok = (__float_as_uint(d) - C.zmin_bits) < C.zrange_bits;
     // transform the point, project
     const float4 ra = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(C.colA) + ox), rb = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(C.colA) + oy);
-    const float qx = (ra.x + rb.x) * d + C.t[0], qy = (ra.y + rb.y) * d + C.t[1], qz = (ra.z + rb.z) * d + C.t[2];
-    const float rqz = fast_rcp(qz);
+    P.qx = (ra.x + rb.x) * d + C.t[0]; P.qy = (ra.y + rb.y) * d + C.t[1]; P.qz = (ra.z + rb.z) * d + C.t[2];
+    const float rqz = fast_rcp(P.qz);
     // (u, v through the compiler's own FMAs, not fma_nd: an inline-asm consumer directly behind v_rcp_f32 is invisible to the hazard recognizer, which then
     // does not insert the wait state gfx950 needs between a transcendental and a VALU use of its result -- a round-6 build that did so read a stale
     // reciprocal now and then: non-deterministic poses, 2e-4 off, caught by tests/test_cpp_bundler.py and scripts/r06/determinism.py)
-    const float u = qx * C.fx * rqz + C.cx, v = qy * C.fy * rqz + C.cy;
-    const float uc = clamp0_s(u, C.wm1), vc = clamp0_s(v, C.hm1);      // NaN -> 0: addresses stay in the frame
-    const bool valid = src_ok & (fabsf(u - uc) < 0.5f) & (fabsf(v - vc) < 0.5f);
-    // (the wave's mask of `valid`, AND-ed from the ballots of the single tests: see ok_mask below)
-    const unsigned long long valid_mask = __builtin_amdgcn_ballot_w64(src_ok) & __builtin_amdgcn_ballot_w64(fabsf(u - uc) < 0.5f) & __builtin_amdgcn_ballot_w64(fabsf(v - vc) < 0.5f);
-    if (valid_mask == 0ull) return;
-    // rotate the normal (only the waves that go on need it: half of the block trips end above)
-    const float nqx = C.R[0] * zs.y + C.R[1] * zs.z + C.R[2] * zs.w;
-    const float nqy = C.R[3] * zs.y + C.R[4] * zs.z + C.R[5] * zs.w;
-    const float nqz = C.R[6] * zs.y + C.R[7] * zs.z + C.R[8] * zs.w;
-    // taps (x0, x0 + 1) x (y0, y0 + 1) with x0 = min(floor(uc), W - 2): at the right / bottom edge (uc = W - 1) the weights are (0, 1)
-    // instead of (1, -) -- the same blend, and the four taps are always the 2 x 2 block at ONE computed address
-    const float fx0 = min_raw_s(floorf(uc), C.wm2), fy0 = min_raw_s(floorf(vc), C.hm2);
-    const float alpha = uc - fx0, beta = vc - fy0;
+    const float u = P.qx * C.fx * rqz + C.cx, v = P.qy * C.fy * rqz + C.cy;
+    P.uc = clamp0_s(u, C.wm1); P.vc = clamp0_s(v, C.hm1);      // NaN -> 0: addresses stay in the frame
+    P.in_u = fabsf(u - P.uc) < 0.5f; P.in_v = fabsf(v - P.vc) < 0.5f;
+    return P;
+}
+// the source normal in the target camera
+__device__ __forceinline__ float3 pinhole_rotate_normal(const PinholeCtx &C, const float4 &zs) { return make_float3(C.R[0] * zs.y + C.R[1] * zs.z + C.R[2] * zs.w, C.R[3] * zs.y + C.R[4] * zs.z + C.R[5] * zs.w, C.R[6] * zs.y + C.R[7] * zs.z + C.R[8] * zs.w); }
+// Stage 2, taps: (x0, x0 + 1) x (y0, y0 + 1) with x0 = min(floor(uc), W - 2): at the right / bottom edge (uc = W - 1) the weights are (0, 1)
+// instead of (1, -) -- the same blend, and the four taps are always the 2 x 2 block at ONE computed address
+struct PinholeTaps { float fx0, fy0, alpha, beta; unsigned o00; };
+__device__ __forceinline__ PinholeTaps pinhole_taps(const PinholeCtx &C, const PinholeProj &P)
+{
+    PinholeTaps K;
+    K.fx0 = min_raw_s(floorf(P.uc), C.wm2); K.fy0 = min_raw_s(floorf(P.vc), C.hm2);
+    K.alpha = P.uc - K.fx0; K.beta = P.vc - K.fy0;
     // one computed byte offset for the 2 x 2 block: the second row's base is a scalar add (wave-uniform), the + 16 the load's immediate offset field
-    const unsigned o00 = (unsigned)(fy0 * C.w16 + 16.0f * fx0);                             // byte offset, fp32-exact below 2^24
-    // Lanes that already failed the in-image / source-depth tests (8.8 % in the trips that go on, clustered along block edges: profiles/r06/sweep_census.json) issue no
-    // taps.  The texture addresser's service time per gather is exposed almost in full (profiles/r06/bound_probes.json: one more 16-byte gather per trip = +13.4 us
-    // per launch, linear) and it skips idle quads (profiles/r06/taps_exec.json: same bits, -1.5 % on the launch).  The registers of those lanes stay undefined
-    // and are never used: `ok` contains `valid`, and nothing behind `ok` runs for a rejected lane.
-    float4 z00, z10, z01, z11;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wconditional-uninitialized"
-    if (valid) { z00 = gather16_imm<0>(C.tap_row0, o00); z10 = gather16_imm<16>(C.tap_row0, o00); z01 = gather16_imm<0>(C.tap_row1, o00); z11 = gather16_imm<16>(C.tap_row1, o00); }
-#pragma clang diagnostic pop
-    const float2 xi2 = lds_f32x2_abs((unsigned)(4.0f * fx0 + C.lut_addr_f)), yi2 = lds_f32x2_abs((unsigned)(4.0f * fy0 + C.ybase4_abs));
-    const float a0 = 1.0f - alpha, b0 = 1.0f - beta;
+    K.o00 = (unsigned)(K.fy0 * C.w16 + 16.0f * K.fx0);                                       // byte offset, fp32-exact below 2^24; 0 <= fx0 <= W - 2, 0 <= fy0 <= H - 2: inside the frame
+    return K;
+}
+__device__ __forceinline__ void pinhole_gather(const PinholeCtx &C, const PinholeTaps &K, float4 &z00, float4 &z10, float4 &z01, float4 &z11)
+{ z00 = gather16_imm<0>(C.tap_row0, K.o00); z10 = gather16_imm<16>(C.tap_row0, K.o00); z01 = gather16_imm<0>(C.tap_row1, K.o00); z11 = gather16_imm<16>(C.tap_row1, K.o00); }
+// Stage 3, blend: the target's normal n_i and q - c_i at the projection, and the three target tests (single comparisons, as in stage 1).  nq: the rotated source normal.
+struct PinholeBlend { float nix, niy, niz, dx, dy, dz; bool ciz_ok, dn_ok, dist_ok; };
+__device__ __forceinline__ PinholeBlend pinhole_blend(const PinholeCtx &C, const PinholeProj &P, const PinholeTaps &K, const float4 &z00, const float4 &z10, const float4 &z01, const float4 &z11, const float3 &nq)
+{
+    PinholeBlend B;
+    const float2 xi2 = lds_f32x2_abs((unsigned)(4.0f * K.fx0 + C.lut_addr_f)), yi2 = lds_f32x2_abs((unsigned)(4.0f * K.fy0 + C.ybase4_abs));
+    const float a0 = 1.0f - K.alpha, b0 = 1.0f - K.beta;
     // blend of the taps' camera-space points (x = column term * z, y = row term * z, z = gated depth) and normals; the
     // column / row terms are shared by the taps of a column / row, so they multiply the partial sums:
     //     cix = xi2.x (t00 + t01) + xi2.y (t10 + t11),  ciy = yi2.x (t00 + t10) + yi2.y (t01 + t11),  ciz = (t00 + t01) + (t10 + t11),  t = c z
@@ -1274,23 +1310,46 @@ __device__ __forceinline__ void pinhole_pixel(const PinholeCtx &C, const float4 
     // written out as the fused multiply-adds the compiler contracts these expressions to (x y + z w -> fma(x, y, z w), left to right --
     // the bits of every build since round 1), each as fma_nd: 13 of the 20 were v_fmac whose two multiplicands happened to sit in VGPRs
     // of the same parity, which issue at half rate (26 of a trip's ~400 issue cycles).
-    const float c00 = b0 * a0, c10 = b0 * alpha, c01 = beta * a0, c11 = beta * alpha;
+    const float c00 = b0 * a0, c10 = b0 * K.alpha, c01 = K.beta * a0, c11 = K.beta * K.alpha;
     const float t10 = c10 * z10.x, t01 = c01 * z01.x, t11 = c11 * z11.x;
     const float s0x = fma_nd(c00, z00.x, t01), s0y = fma_nd(c00, z00.x, t10);       // t00 + t01, t00 + t10
     const float s1x = fma_nd(c10, z10.x, t11), s1y = fma_nd(c01, z01.x, t11);       // t10 + t11, t01 + t11
     const float cix = fma_nd(xi2.x, s0x, xi2.y * s1x);
     const float ciy = fma_nd(yi2.x, s0y, yi2.y * s1y);
     const float ciz = s0x + s1x;
-    const float nix = fma_nd(c11, z11.y, fma_nd(c01, z01.y, fma_nd(c00, z00.y, c10 * z10.y)));
-    const float niy = fma_nd(c11, z11.z, fma_nd(c01, z01.z, fma_nd(c00, z00.z, c10 * z10.z)));
-    const float niz = fma_nd(c11, z11.w, fma_nd(c01, z01.w, fma_nd(c00, z00.w, c10 * z10.w)));
-    const float dx = qx - cix, dy = qy - ciy, dz = qz - ciz;
-    const float dist2 = fma_nd(dz, dz, fma_nd(dx, dx, dy * dy));
-    const float dn = fma_nd(nqz, niz, fma_nd(nqx, nix, nqy * niy));
+    B.nix = fma_nd(c11, z11.y, fma_nd(c01, z01.y, fma_nd(c00, z00.y, c10 * z10.y)));
+    B.niy = fma_nd(c11, z11.z, fma_nd(c01, z01.z, fma_nd(c00, z00.z, c10 * z10.z)));
+    B.niz = fma_nd(c11, z11.w, fma_nd(c01, z01.w, fma_nd(c00, z00.w, c10 * z10.w)));
+    B.dx = P.qx - cix; B.dy = P.qy - ciy; B.dz = P.qz - ciz;
+    const float dist2 = fma_nd(B.dz, B.dz, fma_nd(B.dx, B.dx, B.dy * B.dy));
+    const float dn = fma_nd(nq.z, B.niz, fma_nd(nq.x, B.nix, nq.y * B.niy));
+    B.ciz_ok = (__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits; B.dn_ok = dn >= C.normal_thresh; B.dist_ok = dist2 <= C.dist2_thresh;
+    return B;
+}
+// Stage 4, residual, with the sweep's sign: res+ = (q - c_i) . n_i = -res (SIGNS in pinhole_pixel)
+__device__ __forceinline__ float pinhole_residual(const PinholeBlend &B) { return fma_nd(B.dz, B.niz, fma_nd(B.dx, B.nix, B.dy * B.niy)); }
+
+// One source pixel of the sweep.  acc: the lane's 27 sums; n_ok: accepted pixels of this WAVE (scalar register), which joins the record as acc[27] behind the walk.
+__device__ __forceinline__ void pinhole_pixel(const PinholeCtx &C, const float4 &zs, unsigned ox, unsigned oy, float (&acc)[kDenseVals], int &n_ok)
+{
+    const PinholeProj P = pinhole_project(C, zs, ox, oy);
+    const bool valid = P.src_ok & P.in_u & P.in_v;
+    // (the wave's mask of `valid`, AND-ed from the ballots of the single tests: see ok_mask below)
+    const unsigned long long valid_mask = __builtin_amdgcn_ballot_w64(P.src_ok) & __builtin_amdgcn_ballot_w64(P.in_u) & __builtin_amdgcn_ballot_w64(P.in_v);
+    if (valid_mask == 0ull) return;
+    // rotate the normal (only the waves that go on need it: half of the block trips end above)
+    const float3 nq = pinhole_rotate_normal(C, zs);
+    const PinholeTaps K = pinhole_taps(C, P);
+    // Lanes that already failed the in-image / source-depth tests (8.8 % in the trips that go on, clustered along block edges: profiles/r06/sweep_census.json) issue no
+    // taps.  The texture addresser's service time per gather is exposed almost in full (profiles/r06/bound_probes.json: one more 16-byte gather per trip = +13.4 us
+    // per launch, linear) and it skips idle quads (profiles/r06/taps_exec.json: same bits, -1.5 % on the launch).  The registers of those lanes stay undefined
+    // and are never used: `ok` contains `valid`, and nothing behind `ok` runs for a rejected lane.
+    float4 z00, z10, z01, z11;
+    if (valid) pinhole_gather(C, K, z00, z10, z01, z11);
+    const PinholeBlend B = pinhole_blend(C, P, K, z00, z10, z01, z11, nq);
     // the accept mask of the wave, AND-ed from the ballots of the single tests (a ballot of one comparison is the comparison's own scalar result; the
     // ballot of a combined flag is lowered through a select and a second compare)
-    const unsigned long long ok_mask = valid_mask & __builtin_amdgcn_ballot_w64((__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits)
-                                     & __builtin_amdgcn_ballot_w64(dn >= C.normal_thresh) & __builtin_amdgcn_ballot_w64(dist2 <= C.dist2_thresh);
+    const unsigned long long ok_mask = valid_mask & __builtin_amdgcn_ballot_w64(B.ciz_ok) & __builtin_amdgcn_ballot_w64(B.dn_ok) & __builtin_amdgcn_ballot_w64(B.dist_ok);
     // Rejected pixels contribute NOTHING: the count is a popcount of the wave's accept mask in a scalar register, and the residual, the weight, the row
     // and the 27 accumulates run under the exec mask of `ok` like the taps above.  A sum that is not added to equals the sum that got + 0.0f (the
     // accumulators start at + 0.0f and so never hold - 0.0f), so every sum keeps its bits; a rejected lane's blend -- undefined taps, a NaN or inf target
@@ -1300,11 +1359,11 @@ __device__ __forceinline__ void pinhole_pixel(const PinholeCtx &C, const float4 
         // SIGNS: the row is accumulated as a+ = [n_i ; n_i x q] and the residual as res+ = (q - c_i) . n_i, i.e. a = D a+ with
         // D = diag(-1, -1, -1, 1, 1, 1) and res = -res+ (SolverBundlingDenseUtil.h:78-110, LieDerivUtil.h:228-273).  Then S = D S+ D and
         // g = -D g+ : exact sign changes of whole sums, applied once per workgroup in the epilogue instead of four negations per pixel.
-        const float res = fma_nd(dz, niz, fma_nd(dx, nix, dy * niy));
+        const float res = pinhole_residual(B);
         // Huber (SolverBundlingUtil.h:24-40) times the dense weight: rho' = 1 for e <= delta^2, delta / sqrt(e) above  <=>  min(1, delta rsq(e))
         // (res = 0: rsq(0) = inf, min(inf, w) = w).
         const float wgt = min_raw_s(C.wdelta * fast_rsq(res * res), C.w_dense);
-        const float a[6] = { nix, niy, niz, niy * qz - niz * qy, niz * qx - nix * qz, nix * qy - niy * qx };
+        const float a[6] = { B.nix, B.niy, B.niz, B.niy * P.qz - B.niz * P.qy, B.niz * P.qx - B.nix * P.qz, B.nix * P.qy - B.niy * P.qx };
         int k = 0;
         // acc += wa_r * a_c is a read-modify-write FMA: it issues at full rate only when its two multiplicands sit in VGPRs of
         // different parity (profiles/r02/valu_calibration.md).  (wa_r, a_r) held as an aligned register PAIR puts every wa in an

@@ -1,12 +1,12 @@
 // btba_objective.hpp -- the objective report (btba_objective_batch_zn_aux): the cost the Gauss-Newton loop descends, evaluated at given poses.
 //
 // Three sweeps and a fold, all on the matrices k_prepare makes of the caller's poses:
-//   k_objective_sparse          grid (chunks, P, B): chunk c of pair p's correspondence segment, r = T_i pos_i - T_j pos_j as the sparse sweep forms it
-//   k_objective_dense_pinhole   grid (tiles * Pd, B): 1 024 source pixels of a dense pair; the set-up phases of dense_block_pinhole<0> (item and poses, tables,
-//                               walk constants) and, per pixel, the gates, the clamped 2 x 2 tap blend and the residual of pinhole_pixel, expression by expression
-//   k_objective_dense_general   the same for a K with skew or a projective last row: dense_ctx, pixel_geom and the blend and gates of pixel_accumulate
+//   k_objective_sparse          grid (chunks, P, B): chunk c of pair p's correspondence segment, r = T_i pos_i - T_j pos_j from the sparse sweep's entry decode
+//   k_objective_dense_pinhole   grid (tiles * Pd, B): 1 024 source pixels of a dense pair; the set-up phases of dense_block_pinhole<0> and, per pixel, pinhole_pixel's stages
+//   k_objective_dense_general   the same for a K with skew or a projective last row: dense_block_zn's item set-up and pixel stages
 //   k_objective_fold            grid (B): tiles and chunks in index order into the pair records, the pair records in index order into the instance's totals
-// Every residual is fp32 as the sweeps compute it; everything behind it is IEEE fp64 with contraction off (a product of two fp32 values is exact in
+// Every residual and accept test is fp32 and the sweeps' own device function (btba_kernels.hpp), called, not written again: the sweep accumulates Jacobian
+// sums behind it, these kernels fp64 cost.  Everything behind it is IEEE fp64 with contraction off (a product of two fp32 values is exact in
 // fp64, so e = r.r and res^2 carry only the roundings of their additions).  No hull cull, no block lists, no valid-pixel lists: every pixel of the source
 // frame is walked -- this runs once per solve, not once per iterate.  No atomics: a lane sums its trips in ascending index order, a wave folds by a
 // butterfly (xor 1, 2, 4, 8, 16, 32: the wave reductions of btba_device.hpp are fp32 and sum onto lane 63; this is their fp64 counterpart with the result
@@ -25,7 +25,7 @@
 namespace btba {
 
 static_assert(sizeof(btba_objective_pair) == kObjectiveRecordBytes, "a partial record is a btba_objective_pair");
-static_assert(kObjectiveBlock == kBlock, "the pinhole set-up phases fill their tables with kBlock lanes");
+static_assert(kObjectiveBlock == kBlock, "the sweeps' set-up phases (pinhole tables, zn_item_setup) fill their tables with kBlock lanes");
 
 // what one lane, then one wave, then one workgroup has seen
 struct ObjectiveAcc {
@@ -137,65 +137,33 @@ __global__ void __launch_bounds__(kObjectiveBlock) k_objective_sparse(SolveDims 
     ObjectiveAcc acc = objective_acc_empty();
     const size_t e_base = (size_t)b * (size_t)D.corr_stride + seg0;
     for (uint32_t e = lo + tid; e < hi; e += kObjectiveBlock) {
-        float pix, piy, piz, pjx, pjy, pjz;
-        bool valid;
+        SparseEntry E;
         if (D.corr24) {
             const float2 *q = reinterpret_cast<const float2 *>(corr) + corr24_index(e_base + e);
-            const float2 a0 = q[0], a1 = q[64], a2 = q[128];
-            valid = __float_as_uint(a0.x) != 0xFFFFFFFFu;
-            pix = a0.x; piy = a0.y; piz = a1.x; pjx = a1.y; pjy = a2.x; pjz = a2.y;
-        } else {
-            const float4 a0 = corr[2 * (e_base + e)], a1 = corr[2 * (e_base + e) + 1];
-            valid = __float_as_uint(a0.x) != 0xFFFFFFFFu;      // EntryJ::isValid
-            pix = a0.z; piy = a0.w; piz = a1.x; pjx = a1.y; pjy = a1.z; pjz = a1.w;
-        }
-        if (!valid) continue;
+            E = sparse_entry_c24(q[0], q[64], q[128]);
+        } else E = sparse_entry_j(corr[2 * (e_base + e)], corr[2 * (e_base + e) + 1]);
+        if (!E.valid) continue;
         float wix, wiy, wiz, wjx, wjy, wjz;
-        xform_point(Ti, pix, piy, piz, wix, wiy, wiz);
-        xform_point(Tj, pjx, pjy, pjz, wjx, wjy, wjz);
+        xform_point(Ti, E.pix, E.piy, E.piz, wix, wiy, wiz);
+        xform_point(Tj, E.pjx, E.pjy, E.pjz, wjx, wjy, wjz);
         objective_add_sparse(acc, h, wix - wjx, wiy - wjy, wiz - wjz, (int)e);
     }
     objective_block_store(acc, red, partials + lay.sparse_record(D.n_pairs, b, p, chunk));
 }
 
 // ---- dense, pinhole K: grid (tiles * Pd, B) -------------------------------------------------------------------------------------------
-// One source pixel through pinhole_pixel's gates and blend.  Returns whether the solver accepts it; res = (c_i - q) . n_i.
+// One source pixel through the stages pinhole_pixel runs (btba_kernels.hpp), the single tests AND-ed per lane.  Returns whether the solver accepts it; res = (c_i - q) . n_i.
 __device__ __forceinline__ bool objective_pinhole_pixel(const PinholeCtx &C, const float4 &zs, unsigned ox, unsigned oy, float &res)
 {
-    const float d = zs.x;
-    const bool src_ok = (__float_as_uint(d) - C.zmin_bits) < C.zrange_bits;
-    const float4 ra = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(C.colA) + ox), rb = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(C.colA) + oy);
-    const float qx = (ra.x + rb.x) * d + C.t[0], qy = (ra.y + rb.y) * d + C.t[1], qz = (ra.z + rb.z) * d + C.t[2];
-    const float rqz = fast_rcp(qz);
-    const float u = qx * C.fx * rqz + C.cx, v = qy * C.fy * rqz + C.cy;
-    const float uc = clamp0_s(u, C.wm1), vc = clamp0_s(v, C.hm1);      // NaN -> 0: addresses stay in the frame
-    const bool valid = src_ok & (fabsf(u - uc) < 0.5f) & (fabsf(v - vc) < 0.5f);
-    if (!valid) return false;
-    const float nqx = C.R[0] * zs.y + C.R[1] * zs.z + C.R[2] * zs.w;
-    const float nqy = C.R[3] * zs.y + C.R[4] * zs.z + C.R[5] * zs.w;
-    const float nqz = C.R[6] * zs.y + C.R[7] * zs.z + C.R[8] * zs.w;
-    const float fx0 = min_raw_s(floorf(uc), C.wm2), fy0 = min_raw_s(floorf(vc), C.hm2);
-    const float alpha = uc - fx0, beta = vc - fy0;
-    const unsigned o00 = (unsigned)(fy0 * C.w16 + 16.0f * fx0);        // the 2 x 2 block at (fx0, fy0), 0 <= fx0 <= W - 2, 0 <= fy0 <= H - 2: inside the frame
-    const float4 z00 = gather16_imm<0>(C.tap_row0, o00), z10 = gather16_imm<16>(C.tap_row0, o00), z01 = gather16_imm<0>(C.tap_row1, o00), z11 = gather16_imm<16>(C.tap_row1, o00);
-    const float2 xi2 = lds_f32x2_abs((unsigned)(4.0f * fx0 + C.lut_addr_f)), yi2 = lds_f32x2_abs((unsigned)(4.0f * fy0 + C.ybase4_abs));
-    const float a0 = 1.0f - alpha, b0 = 1.0f - beta;
-    const float c00 = b0 * a0, c10 = b0 * alpha, c01 = beta * a0, c11 = beta * alpha;
-    const float t10 = c10 * z10.x, t01 = c01 * z01.x, t11 = c11 * z11.x;
-    const float s0x = fma_nd(c00, z00.x, t01), s0y = fma_nd(c00, z00.x, t10);
-    const float s1x = fma_nd(c10, z10.x, t11), s1y = fma_nd(c01, z01.x, t11);
-    const float cix = fma_nd(xi2.x, s0x, xi2.y * s1x);
-    const float ciy = fma_nd(yi2.x, s0y, yi2.y * s1y);
-    const float ciz = s0x + s1x;
-    const float nix = fma_nd(c11, z11.y, fma_nd(c01, z01.y, fma_nd(c00, z00.y, c10 * z10.y)));
-    const float niy = fma_nd(c11, z11.z, fma_nd(c01, z01.z, fma_nd(c00, z00.z, c10 * z10.z)));
-    const float niz = fma_nd(c11, z11.w, fma_nd(c01, z01.w, fma_nd(c00, z00.w, c10 * z10.w)));
-    const float dx = qx - cix, dy = qy - ciy, dz = qz - ciz;
-    const float dist2 = fma_nd(dz, dz, fma_nd(dx, dx, dy * dy));
-    const float dn = fma_nd(nqz, niz, fma_nd(nqx, nix, nqy * niy));
-    const bool ok = ((__float_as_uint(ciz) - C.zmin_bits) < C.zrange_bits) & (dn >= C.normal_thresh) & (dist2 <= C.dist2_thresh);
-    res = -fma_nd(dz, niz, fma_nd(dx, nix, dy * niy));      // pinhole_pixel keeps (q - c_i) . n_i and puts the sign right once per workgroup
-    return ok;
+    const PinholeProj P = pinhole_project(C, zs, ox, oy);
+    if (!(P.src_ok & P.in_u & P.in_v)) return false;
+    const float3 nq = pinhole_rotate_normal(C, zs);
+    const PinholeTaps K = pinhole_taps(C, P);
+    float4 z00, z10, z01, z11;
+    pinhole_gather(C, K, z00, z10, z01, z11);
+    const PinholeBlend B = pinhole_blend(C, P, K, z00, z10, z01, z11, nq);
+    res = -pinhole_residual(B);                             // pinhole_pixel keeps (q - c_i) . n_i and puts the sign right once per workgroup
+    return B.ciz_ok & B.dn_ok & B.dist_ok;
 }
 
 // D: the solve's dimensions with dense_tiles = 1 (the set-up phases then see one band, which the strip walk ignores); blockIdx.x = tile + tiles * work position
@@ -229,44 +197,19 @@ __global__ void __launch_bounds__(kObjectiveBlock) k_objective_dense_general(Sol
     __shared__ ObjectiveAcc red[kObjectiveBlock / 64];
     extern __shared__ __attribute__((aligned(16))) float objective_lds[];      // SweepLayout(Wd, Hd, 0, kSweepLdsGeneralK): (Wd + Hd) floats
     const int tile = (int)(blockIdx.x % (unsigned)lay.tiles), q = (int)(blockIdx.x / (unsigned)lay.tiles), b = blockIdx.y;
-    float *lut = objective_lds;
-    for (int e = (int)threadIdx.x; e < D.width + D.height; e += kObjectiveBlock)
-        lut[e] = (float)(e < D.width ? zn_src_coord(e, D.zn_scale_w) : zn_src_coord(e - D.width, D.zn_scale_h));
-    __syncthreads();
-    const float *lut_x = lut, *lut_y = lut + D.width;
     const int4 item = D.dense_work[q];                    // (target, source, dense pair, -)
-    const int fi = item.x, fj = item.y, p = item.z;
-    const size_t fb = (size_t)b * D.n_frames;
-    const unsigned pb = (unsigned)b * (unsigned)D.pose_stride;
-    const DenseCtx C = dense_ctx(D, T, Tinv, pb, fi, fj, nullptr, nullptr);
-    const float4 *zn_t = zn + frame_slot_of(D, fb + fi) * (size_t)D.npix, *zn_s = zn + frame_slot_of(D, fb + fj) * (size_t)D.npix;
+    const ZnItem I = zn_item_setup(D, zn, T, Tinv, item.x, item.y, b, objective_lds);
     const ObjectiveHuber h = objective_huber(D.robust_delta);
     ObjectiveAcc acc = objective_acc_empty();
     const int lo = objective_tile_lo(D.npix, tile), hi = objective_tile_hi(D.npix, tile);
     for (int s = lo + (int)threadIdx.x; s < hi; s += kObjectiveBlock) {
         const int py = s / D.width, px = s - py * D.width;
-        const float4 zs = zn_s[s];
-        const float3 cp = zn_backproject(D.zn_ki, lut_x[px], lut_y[py], zs.x);
-        const PixelGeom g = pixel_geom(C, make_float4(cp.x, cp.y, cp.z, 1.0f), make_float4(zs.y, zs.z, zs.w, 0.0f));
-        if (!g.valid) continue;                           // (the tap indices of a rejected pixel are clamped into the frame all the same)
-        const float4 z00 = zn_t[g.i00], z10 = zn_t[g.i10], z01 = zn_t[g.i01], z11 = zn_t[g.i11];
-        const float xia = lut_x[g.xa], xib = lut_x[g.xb], yia = lut_y[g.ya], yib = lut_y[g.yb];
-        const float3 c00 = zn_backproject(D.zn_ki, xia, yia, z00.x), c10 = zn_backproject(D.zn_ki, xib, yia, z10.x);
-        const float3 c01 = zn_backproject(D.zn_ki, xia, yib, z01.x), c11 = zn_backproject(D.zn_ki, xib, yib, z11.x);
-        // the blend, the gates and the residual of pixel_accumulate
-        const float cix = g.c00 * c00.x + g.c10 * c10.x + g.c01 * c01.x + g.c11 * c11.x;
-        const float ciy = g.c00 * c00.y + g.c10 * c10.y + g.c01 * c01.y + g.c11 * c11.y;
-        const float ciz = g.c00 * c00.z + g.c10 * c10.z + g.c01 * c01.z + g.c11 * c11.z;
-        const float nix = g.c00 * z00.y + g.c10 * z10.y + g.c01 * z01.y + g.c11 * z11.y;
-        const float niy = g.c00 * z00.z + g.c10 * z10.z + g.c01 * z01.z + g.c11 * z11.z;
-        const float niz = g.c00 * z00.w + g.c10 * z10.w + g.c01 * z01.w + g.c11 * z11.w;
-        const float dx = g.qx - cix, dy = g.qy - ciy, dz = g.qz - ciz;
-        const float dist2 = dx * dx + dy * dy + dz * dz;
-        const float dn = g.nqx * nix + g.nqy * niy + g.nqz * niz;
-        const bool ok = (ciz > C.depth_min) & (ciz < C.depth_max) & (dn >= C.normal_thresh) & (dist2 <= C.dist2_thresh);
-        if (ok) objective_add_dense(acc, h, -(dx * nix + dy * niy + dz * niz), s);
+        const PixelGeom g = zn_pixel_geom(D, I, px, py, I.zn_s[s]);
+        if (!g.valid) continue;
+        const PixelBlend B = zn_pixel_blend(D, I, g);
+        if (B.ok) objective_add_dense(acc, h, B.res, s);
     }
-    objective_block_store(acc, red, partials + lay.dense_record(D.n_dense_pairs, b, p, tile));
+    objective_block_store(acc, red, partials + lay.dense_record(D.n_dense_pairs, b, item.z, tile));
 }
 
 // ---- fold: grid (B) ---------------------------------------------------------------------------------------------------------------

@@ -94,7 +94,7 @@ __device__ __forceinline__ void process_depth_tile(const DepthFilterParams &P, c
     // stages 2 and 3: the mean-gated bilateral filter, twice
     const float two_sd2 = 2.0f * P.sigma_d * P.sigma_d, two_sr2 = 2 * P.sigma_r * P.sigma_r;
     const float num_total = (float)((2 * rf + 1) * (2 * rf + 1));
-    const float inv_two_sr2 = 1.0f / two_sr2;             // (the reference divides per tap: one rounding of a term that is <= 0.5 and usually ~1e-15)
+    const float inv_two_sr2 = 1.0f / two_sr2;             // (the reference divides per tap: three more roundings of the range term, inside the tests' weight bar)
     for (int pass = 0; pass < 2; pass++) {
         const float *src = pass == 0 ? b1 : b0;
         float *dst = pass == 0 ? b0 : nullptr;
@@ -126,7 +126,13 @@ __device__ __forceinline__ void process_depth_tile(const DepthFilterParams &P, c
                             const float c = ctr[dy * LW + dx];
                             if (c >= 0.1f && fabsf(c - mean) <= 0.01f) {
                                 const float spatial = -(float)(dx * dx + dy * dy) / two_sd2;          // (compile-time dx, dy: hoisted out of the pixel loop)
-                                const float wgt = __expf(spatial - (centre - c) * (centre - c) * inv_two_sr2);       // arguments in [-(2 rf^2) / (2 sigma_d^2) - ..., 0]: no range handling needed
+                                // The argument is <= 0, so nothing overflows, but it is NOT bounded below: the gate bounds |c - mean|, not |centre - c|, and a
+                                // centre that is a hole (0) or a flyer among c ~ 0.7 puts the range term at 0.49 / (2 sigma_r^2) -- about -95 at
+                                // sigma_r = 0.05.  There exp is an fp32 denormal (~4e-42) and __expf (v_exp_f32) returns 0 below FLT_MIN: every weight
+                                // is 0, sw > 0 fails and the pixel stays 0 -- the hole is NOT filled.  The reference's build (-use_fast_math: __expf on
+                                // ex2.approx.ftz) flushes the same way; libm's expf keeps the denormals and fills the hole ("Frame
+                                // ingest"; tests/test_gpu_image_stages.py::test_underflow_case holds the device to one of the two, as a whole map).
+                                const float wgt = __expf(spatial - (centre - c) * (centre - c) * inv_two_sr2);
                                 sw += wgt;
                                 sum += wgt * c;
                             }

@@ -1,5 +1,6 @@
 """SURVEY.md 8(f) rank 3 -- Frame::processDepth and Frame::depthToCloudAndNormals: CPU pins of the oracle
-(not gpu) and HIP-vs-oracle parity (gpu)."""
+(not gpu) and HIP-vs-oracle parity (gpu).  The comparison with derived bars, tile-seam and special-value cases against an fp64
+reference is in image_ref.py, test_image_ref.py and test_gpu_image_stages.py."""
 import numpy as np
 import pytest
 

@@ -2,7 +2,8 @@
 and colour with the per-frame calls (btba_process_depth + btba_depth_to_normals on the numpy-decoded depth) for both stencil
 variants, across a launch chunk and with every optional table left out; float input against the CPU oracle at the per-frame
 kernel's own bar; the argument checks; the optimiser fed from ingested frames; and the Python Bundler's hook.  One module-scoped
-workspace."""
+workspace.  (Bit identity with the per-frame kernels compares two instantiations of one tile function; both are held to the fp64
+reference of image_ref.py in test_gpu_image_stages.py.)"""
 import ctypes as C
 import os
 

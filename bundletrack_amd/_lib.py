@@ -56,8 +56,20 @@ EXPORTED_SYMBOLS = [
     "btba_window_layout", "btba_marshal_windows", "btba_procrustes_pairs",
     "btba_linearize_batch_zn_aux", "btba_pose_covariances", "btba_objective_batch_zn_aux",
     "btba_fuse_params_default", "btba_fuse_layout", "btba_fuse_bounds", "btba_fuse_frames", "btba_voxel_downsample",
+    "btba_register_params_default", "btba_register_index", "btba_register_frames", "btba_register_associate",
 ]
 FUSE_FRAME, FUSE_POINTS, FUSE_OVERFLOW, FUSE_MAX_VOXELS = 0, 1, 1, 1 << 24
+REG_CONVERGED, REG_MAX_ITERS, REG_DEGENERATE, REG_TOO_FEW, REG_SKIPPED = 0, 1, 2, 3, 4
+REG_STATUS_NAMES = ("CONVERGED", "MAX_ITERS", "DEGENERATE", "TOO_FEW", "SKIPPED")
+
+# btba_register_iter / btba_register_result (include/btba.h): 344 and 32 bytes
+REGISTER_ITER_DTYPE = np.dtype(
+    [("n_valid", "<i4"), ("n_matched", "<i4"), ("n_beyond", "<i4"), ("status", "<i4"), ("cost", "<f8"), ("H", "<f8", (21,)), ("g", "<f8", (6,)),
+     ("xi", "<f8", (6,)), ("pivot_ratio", "<f8"), ("pose", "<f4", (12,))]
+)
+REGISTER_RESULT_DTYPE = np.dtype(
+    [("status", "<i4"), ("iters_done", "<i4"), ("n_valid", "<i4"), ("n_matched", "<i4"), ("n_beyond", "<i4"), ("reserved", "<i4"), ("cost", "<f8")]
+)
 
 # btba_objective_pair / btba_objective_total (include/btba.h): 40 and 64 bytes
 OBJECTIVE_PAIR_DTYPE = np.dtype(
@@ -212,6 +224,13 @@ class FuseSegment(C.Structure):
     """btba_fuse_segment (include/btba.h): 104 bytes."""
     _fields_ = [("kind", C.c_int32), ("instance", C.c_int32), ("n", C.c_int64), ("geom", C.c_void_p), ("normal", C.c_void_p),
                 ("colour", C.c_void_p), ("pose", C.c_float * 16)]
+
+
+class RegisterParams(C.Structure):
+    """btba_register_params (include/btba.h): 44 bytes."""
+    _fields_ = [("leaf", C.c_float), ("search_radius", C.c_int32), ("max_dist", C.c_float), ("min_cos", C.c_float), ("huber_delta", C.c_float),
+                ("n_iters", C.c_int32), ("eps_rot", C.c_float), ("eps_trans", C.c_float), ("min_matches", C.c_int32), ("require_normals", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class BtbaError(RuntimeError):
@@ -463,6 +482,13 @@ def lib() -> C.CDLL:
         L.btba_fuse_bounds.argtypes = [C.c_void_p, C.POINTER(FuseParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.btba_fuse_frames.argtypes = [C.c_void_p, C.POINTER(FuseParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.btba_voxel_downsample.argtypes = [C.c_void_p, C.POINTER(FuseParams), C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 8
+        L.btba_register_params_default.argtypes = [C.POINTER(RegisterParams)]
+        L.btba_register_params_default.restype = None
+        L.btba_register_index.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.btba_register_frames.argtypes = [C.c_void_p, C.POINTER(RegisterParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_int] + [C.c_void_p] * 6
+        L.btba_register_associate.argtypes = [C.c_void_p, C.POINTER(RegisterParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_int] + [C.c_void_p] * 4
         _lib = L
     return _lib
 
@@ -562,6 +588,11 @@ def nocs_params(**kw) -> NocsParams:
 def fuse_params(**kw) -> FuseParams:
     """btba_fuse_params_default with fields overridden by keyword."""
     return _params(FuseParams, "btba_fuse_params_default", kw)
+
+
+def register_params(**kw) -> RegisterParams:
+    """btba_register_params_default with fields overridden by keyword."""
+    return _params(RegisterParams, "btba_register_params_default", kw)
 
 
 def declared_symbols() -> list[str]:

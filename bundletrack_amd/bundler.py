@@ -306,15 +306,38 @@ class Bundler:
     def keyframes(self):
         return self.memory.keyframes
 
-    def reconstruct(self, leaf=0.005, min_points=1):
+    def reconstruct(self, leaf=0.005, min_points=1, normalize_normals=False, want_colour=None):
         """The object the session tracked: self.keyframes (their masked depth, normal and colour maps at their bundle-adjusted
         pose_in_model) fused into one voxel-grid cloud on the optimiser's workspace (fusion.fuse_frames; an ObjectCloud of one instance).
-        Colour is fused when every keyframe has a colour map.  One host synchronisation: the data-derived box."""
+        Colour is fused when every keyframe has a colour map (want_colour None).  normalize_normals: unit mean normals, what
+        register_to_model needs of its model.  One host synchronisation: the data-derived box."""
         from .fusion import frame_segment, fuse_frames
         ws = getattr(self.opt, "workspace", None)
         if ws is None:
             raise RuntimeError("Bundler.reconstruct needs an optimizer with a workspace")
-        return fuse_frames(ws, [frame_segment(kf) for kf in self.keyframes], 1, self.K, leaf=leaf, min_points=min_points)
+        return fuse_frames(ws, [frame_segment(kf) for kf in self.keyframes], 1, self.K, leaf=leaf, min_points=min_points,
+                           normalize_normals=normalize_normals, want_colour=want_colour)
+
+    def register_to_model(self, frames=None, cloud=None, **params):
+        """Point-to-plane registration of frames against the fused object (registration.register_frames): each frame's masked depth and
+        normal maps, from its current pose_in_model.  frames: a FrameRef or a list of them (default: the newest frame); cloud: an ObjectCloud
+        or a registration.ModelIndex (default: self.reconstruct(normalize_normals=True, want_colour=False)).  Returns the Registration -- refined poses,
+        status, fitness, rms -- and changes no state: whether to adopt a pose is the caller's decision.  n_iters=0 is the pose check."""
+        from .fusion import frame_segment
+        from .registration import register_frames
+        ws = getattr(self.opt, "workspace", None)
+        if ws is None:
+            raise RuntimeError("Bundler.register_to_model needs an optimizer with a workspace")
+        if frames is None:
+            frames = [self.frames[-1]] if self.frames else []
+        elif isinstance(frames, FrameRef):
+            frames = [frames]
+        if cloud is None:
+            cloud = self.reconstruct(normalize_normals=True, want_colour=False)
+        segments = [frame_segment(f) for f in frames]
+        for s in segments:
+            s.colour = None
+        return register_frames(ws, cloud, segments, self.K, **params)
 
     def process_new_frame(self, frame: FrameRef) -> None:
         self.newframe = frame

@@ -385,6 +385,27 @@ void voxelDownsample(btba_workspace *ws, const btba_fuse_params &params, const s
     if (rc != BTBA_OK) throw Error(rc, "btba_voxel_downsample");
 }
 
+void registerIndex(btba_workspace *ws, int n_instances, const std::vector<int32_t> &box, const ObjectCloudBuffers &cloud, int32_t *cell_index_dev)
+{
+    if (box.size() != 6 * (size_t)std::max(n_instances, 0)) throw Error(BTBA_EINVAL, "registerIndex: box");
+    const int rc = btba_register_index(ws, n_instances, box.data(), cloud.capacity, cloud.lin, cloud.n_out, cell_index_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_register_index");
+}
+
+void registerFrames(btba_workspace *ws, const btba_register_params &params, int n_instances, const std::vector<btba_fuse_segment> &items, int H, int W,
+                    const Matrix3f &K, const std::vector<int32_t> &box, const ObjectCloudBuffers &cloud, const int32_t *cell_index_dev, float *pose_out_dev,
+                    btba_register_result *result_dev, btba_register_iter *trace_dev)
+{
+    if (box.size() != 6 * (size_t)std::max(n_instances, 0)) throw Error(BTBA_EINVAL, "registerFrames: box");
+    float Kr[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Kr[3 * r + c] = K(r, c);
+    const int rc = btba_register_frames(ws, &params, n_instances, (int)items.size(), items.data(), H, W, Kr, box.data(), cloud.capacity,
+                                        reinterpret_cast<const float *>(cloud.xyz), reinterpret_cast<const float *>(cloud.normal), cell_index_dev, pose_out_dev,
+                                        result_dev, trace_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_register_frames");
+}
+
 double vocapAuc(const std::vector<double> &errors, double max_threshold)
 {
     const size_t n = errors.size();

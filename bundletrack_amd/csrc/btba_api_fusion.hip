@@ -5,9 +5,10 @@
 #include <algorithm>
 #include <limits>
 
-namespace {
+namespace btba_host {
 
-// Everything btba_fuse_bounds and btba_fuse_frames share: the checks of params and segments, decided before any HIP call.
+// Everything btba_fuse_bounds and btba_fuse_frames share (and btba_api_register.hip takes over): the checks of params and segments, decided
+// before any HIP call.
 bool fuse_segments_ok(const btba_fuse_params *prm, int n_instances, int n_segments, const btba_fuse_segment *seg, int H, int W, const float *K,
                       bool need_colour)
 {
@@ -29,6 +30,16 @@ bool fuse_segments_ok(const btba_fuse_params *prm, int n_instances, int n_segmen
     return true;
 }
 
+bool fuse_has_frames(int n_segments, const btba_fuse_segment *seg)
+{
+    for (int s = 0; s < n_segments; s++) if (seg[s].kind == BTBA_FUSE_FRAME) return true;
+    return false;
+}
+
+}  // namespace btba_host
+
+namespace {
+
 // chunk [s0, s0 + ns) of the segments as the kernels take it; the box and first voxel of each segment's instance when box is given.
 // Returns the largest element count of the chunk.
 int fuse_chunk(const btba_fuse_segment *seg, int s0, int ns, int H, int W, const int32_t *box, const int64_t *vox_off, FuseSegments &S)
@@ -49,12 +60,6 @@ int fuse_chunk(const btba_fuse_segment *seg, int s0, int ns, int H, int W, const
         n_max = std::max(n_max, S.n[z]);
     }
     return n_max;
-}
-
-bool fuse_has_frames(int n_segments, const btba_fuse_segment *seg)
-{
-    for (int s = 0; s < n_segments; s++) if (seg[s].kind == BTBA_FUSE_FRAME) return true;
-    return false;
 }
 
 constexpr int kFuseMaxGridX = 1024;                     // blocks per segment: the kernels stride over the rest

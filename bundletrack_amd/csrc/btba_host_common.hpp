@@ -204,6 +204,7 @@ struct btba_workspace {
     bool marginals_attr_set = false;
     DevBuf objective;                                       // btba_objective_batch_zn_aux: the matrices of the caller's poses, the partial records of tiles and chunks
     DevBuf fusion;                                          // btba_fuse_frames: the voxel planes (count, position, normal and colour sums), the compaction's block counts
+    DevBuf registration;                                    // btba_register_frames: the partial records, current poses and stop flags
     uint64_t ransac_u_seed = 0;
     std::vector<FrameSlot> pool_slots;
     int pool_H = 0, pool_W = 0, pool_npix = 0;
@@ -247,6 +248,13 @@ struct ObjectiveCall {
     btba_objective_total *total; btba_objective_pair *sparse, *dense;
 };
 int objective_enqueue(btba_workspace *ws, const ObjectiveCall &c);
+
+// The argument checks btba_fuse_bounds / btba_fuse_frames make of params and segments, and whether a segment is a frame (btba_api_fusion.hip);
+// btba_register_frames takes the same segments and refuses what fusion refuses.
+namespace btba_host {
+bool fuse_segments_ok(const btba_fuse_params *prm, int n_instances, int n_segments, const btba_fuse_segment *seg, int H, int W, const float *K, bool need_colour);
+bool fuse_has_frames(int n_segments, const btba_fuse_segment *seg);
+}
 
 // What a model handle of either LF-Net net starts with: its workspace, that workspace's device and the arena's device copy.
 struct LfnetModelBase {

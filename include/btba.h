@@ -1515,6 +1515,118 @@ BTBA_API int btba_voxel_downsample(btba_workspace *ws, const btba_fuse_params *p
                                    const int32_t *box, int capacity, float *xyz_out_dev, float *normal_out_dev, uint8_t *colour_out_dev,
                                    uint32_t *count_out_dev, int32_t *lin_out_dev, int32_t *n_out_dev, int32_t *n_outside_dev, int32_t *status_dev);
 
+/* ---- frame-to-model registration: point-to-plane ICP of frames against the fused cloud ---------------------------------
+ * btba_register_frames refines the camera -> model pose of many (frame or point list, model) items in one call: batched point-to-plane
+ * Gauss-Newton ICP against the voxel cloud btba_fuse_frames / btba_voxel_downsample made, used in place.  It is what brings a frame the
+ * tracker marked FAIL back against what the session has learned of the object; with n_iters = 0 it is the numeric half of a pose check
+ * (the points of a frame that lie on the model at a pose, and their point-to-plane error); its cost per matched point is the per-frame
+ * drift figure where no CAD model exists.  The reference has nothing of the kind (its _need_reinit is set and never read), so the
+ * rules below are this project's own; every decision is exact, so a CPU restatement (tests/register_ref.py) reproduces each of them, and
+ * every sum is fp64 in a fixed order.
+ *
+ * An item is a btba_fuse_segment: `instance` names the model, `pose` is the INITIAL camera -> model pose, colour is not read.  A model is
+ * the output of the fusion call for n_instances instances with its `capacity` stride: xyz_dev and normal_dev (float4 [n_instances][capacity],
+ * both required), the host box, and the cell index btba_register_index builds from lin_out and n_out.  Fuse the model with
+ * normalize_normals = 1: the registration does NOT renormalise the model normals, and the residual is a distance only along a unit normal.
+ *
+ * btba_register_index: cell_index_dev is a caller-owned int32 [V] (V and the instances' first voxels: btba_fuse_layout).  Every cell is set to
+ * -1, then cell_index[vox_off[b] + lin[b][k]] = k for k < min(n_out[b], capacity) (n_out is read on the device; a lin outside the
+ * instance's box is ignored).  Asynchronous; the index serves every later call on that cloud.
+ *
+ * Per Gauss-Newton iteration and item, at the item's current fp32 pose T (uncontracted fp32 in the order written, rules 1 - 4):
+ *   1. Points are taken and dropped exactly as btba_fuse_frames takes and drops them (the same device function): backprojection, (double)d
+ *      >= 0.1, a zero normal under require_normals, a non-finite list point.  q_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3; n'_r likewise from
+ *      the source normal (fusion's rule 1, its 2^16 clamp included).  n_valid counts the survivors.
+ *   2. Cell i_a = (int)floorf(q_a * inv_leaf) - min_b_a, inv_leaf = 1.0f / leaf formed once on the host.  No candidates when some |q_a| is not
+ *      below 2^16 (NaN included).  Candidates: the cells i + o, o in [-r, r]^3, r = search_radius, oz outermost and ox innermost (ascending
+ *      lin), each tested on its own against 0 <= . < dims (the centre may lie outside the box while neighbours lie inside), with a record
+ *      k = cell_index[.] in 0 .. capacity - 1.  d_a = q_a - m_a, d2 = (dx dx + dy dy) + dz dz.  The first candidate is taken; a later one
+ *      replaces it only when its d2 is strictly smaller, so a tie goes to the lowest lin.
+ *   3. Gates, after the selection: d2 <= max_dist^2 (the square formed once on the host in fp32); the model normal m_n not exactly (0, 0, 0);
+ *      and, when the segment has a normal map and min_cos > -1, (n'x mx + n'y my) + n'z mz >= min_cos.
+ *   4. r = (nx dx + ny dy) + nz dz with n = m_n, and the row a = (q x n, n) in the public (rot, trans) order, each cross term two products and
+ *      one subtraction: (qy nz - qz ny, qz nx - qx nz, qx ny - qy nx, nx, ny, nz).
+ *   5. In fp64, the factors promoted exactly: w = 1 when |r| <= huber_delta, else (double)delta / fabs((double)r) (such a point counts in
+ *      n_beyond); rho = r^2 inside the knee, 2 delta |r| - delta^2 outside; H_ab += w a_a a_b over the 21 entries of the lower triangle
+ *      (row-major: (a, b), b <= a, at a (a + 1) / 2 + b), g_a += w a_a r, cost += rho.  No float atomics: points 2048 k .. 2048 k + 2047 of a
+ *      segment are summed by one workgroup in a fixed tree and the workgroups' records in index order, so the sums have the same bytes at
+ *      any batch position, with any n_items, and from run to run.
+ *   6. Fewer than min_matches matched points: BTBA_REG_TOO_FEW.  Otherwise H xi = -g by Cholesky in IEEE fp64; pivot_ratio = min_j d_j / H_jj
+ *      over the pivots d_j, as btba_pose_covariances defines it, and 0 for a failed factorisation; a pivot that is not positive and finite is
+ *      BTBA_REG_DEGENERATE (xi = 0).  On TOO_FEW or DEGENERATE the pose stays as it is and the item stops.
+ *   7. T <- Exp(xi) T in fp64, xi = (omega, u): R = I + (sin t / t) K + ((1 - cos t) / t^2) K^2, V = I + ((1 - cos t) / t^2) K + ((t - sin t) /
+ *      t^3) K^2 with K = [omega]x, t = |omega|; below t = 1e-12, R = I + K and V = I + K / 2.  The fp32 pose is promoted, multiplied and its 12
+ *      entries are rounded to fp32 once.  There is NO re-orthonormalisation: 64 roundings move the rotation off SO(3) by about 1e-6.
+ *   8. |omega| < eps_rot and |u| < eps_trans (fp64; 0 disables a threshold's side, and with it the stop) ends the item BTBA_REG_CONVERGED after
+ *      the step.  A device-side flag makes every later launch skip a stopped item; its later trace entries are zero-filled with status
+ *      BTBA_REG_SKIPPED.  An item still running after n_iters ends BTBA_REG_MAX_ITERS.
+ * After the loop ONE more accumulation pass, without a solve, evaluates every item at its pose_out: the result's n_valid, n_matched, n_beyond
+ * and cost belong to pose_out.  A call with n_iters = 0 is therefore the pose check: pose_out = the initial pose, status BTBA_REG_TOO_FEW
+ * when n_matched < min_matches and BTBA_REG_MAX_ITERS otherwise, and its four evaluated fields equal, byte for byte, those of the call that
+ * produced that pose.  trace_dev (NULL or [n_items][n_iters]) records every iteration: the sums at the pose the iteration started from, the
+ * step, and the pose after it (status BTBA_REG_MAX_ITERS there means "stepped, still running").
+ *
+ * btba_register_associate runs rule 1 - 3 once at the segments' poses (the accumulate kernel's own device function) and writes per point of
+ * item i to match_out[i] ([H*W] or [n] int32 on the device; match_out itself is a host array): the matched record k, or -1 no candidate, -2
+ * beyond max_dist, -3 a zero model normal or a failed normal gate, -4 the point was dropped.
+ *
+ * All three calls are asynchronous on the workspace stream with no host synchronisation inside; items go in chunks of BTBA_FUSE_CHUNK as
+ * kernel arguments, so no host memory is read after a call returns.  The scratch (partial records, current poses, flags) is grow-only in
+ * the workspace.  BTBA_EINVAL, decided before the first launch: NULL ws, params, segments (n_items > 0), box, xyz_dev, normal_dev,
+ * cell_index_dev, pose_out_dev, result_dev (match_out or one of its entries with points; lin_dev, n_out_dev for the index); n_instances < 1,
+ * n_items < 0, capacity < 0 or n_instances * capacity beyond 2^31 - 1; search_radius outside 0 .. 2, n_iters outside 0 .. 64, max_dist or
+ * huber_delta not finite, max_dist < 0, huber_delta <= 0, min_cos NaN, eps_rot or eps_trans negative or NaN, min_matches < 0; a leaf, a
+ * segment or a box that btba_fuse_frames refuses (instance outside 0 .. n_instances - 1 among them); float4 arrays not 16-byte aligned, the
+ * cell index, lin, n_out, pose_out or a match array not 4-byte aligned, result_dev or trace_dev not 8-byte aligned; more than 2^22 blocks
+ * of 2048 points in one call. */
+#define BTBA_REG_CONVERGED 0
+#define BTBA_REG_MAX_ITERS 1
+#define BTBA_REG_DEGENERATE 2
+#define BTBA_REG_TOO_FEW 3
+#define BTBA_REG_SKIPPED 4                /* trace entries only: the item had stopped before this iteration */
+#define BTBA_REG_MAX_ITERATIONS 64
+typedef struct btba_register_params {     /* 44 bytes */
+    float leaf;                           /* the model's voxel side (no default: must equal the leaf the cloud was fused with) */
+    int32_t search_radius;                /* 1 (default; 0 .. 2): voxels searched around the point's cell, 1 = 27 cells */
+    float max_dist;                       /* 0.02 (default): |q - m| gate, the dense sweep's */
+    float min_cos;                        /* cos 45 deg (default): normal gate, the dense sweep's; <= -1 switches it off */
+    float huber_delta;                    /* 0.005 (default): Huber knee in metres */
+    int32_t n_iters;                      /* 10 (default; 0 .. 64): Gauss-Newton iterations */
+    float eps_rot, eps_trans;             /* 1e-5 rad, 1e-6 m (defaults): convergence thresholds, 0 disables */
+    int32_t min_matches;                  /* 6 (default) */
+    int32_t require_normals;              /* 1 (default, as fusion's): frame pixels with a zero normal are dropped */
+    int32_t reserved;                     /* 0 */
+} btba_register_params;
+typedef struct btba_register_iter {       /* 344 bytes */
+    int32_t n_valid, n_matched, n_beyond, status;
+    double cost;
+    double H[21];                         /* lower triangle, row-major */
+    double g[6];
+    double xi[6];                         /* (omega, u) */
+    double pivot_ratio;
+    float pose[12];                       /* rows 0 .. 2 of the pose after the step */
+} btba_register_iter;
+typedef struct btba_register_result {     /* 32 bytes */
+    int32_t status, iters_done;           /* iters_done: iterations that accumulated for the item, the one it stopped in included */
+    int32_t n_valid, n_matched, n_beyond, reserved;      /* at pose_out */
+    double cost;                          /* at pose_out */
+} btba_register_result;
+BTBA_API void btba_register_params_default(btba_register_params *p);
+BTBA_API int btba_register_index(btba_workspace *ws, int n_instances, const int32_t *box /* host [n_instances][6] */, int capacity,
+                                 const int32_t *lin_dev /* [n_instances][capacity] */, const int32_t *n_out_dev /* [n_instances] */,
+                                 int32_t *cell_index_dev /* [V] */);
+BTBA_API int btba_register_frames(btba_workspace *ws, const btba_register_params *params, int n_instances, int n_items,
+                                  const btba_fuse_segment *segments, int H, int W, const float *K_rowmajor,
+                                  const int32_t *box /* host [n_instances][6] */, int capacity,
+                                  const float *xyz_dev, const float *normal_dev /* float4 [n_instances][capacity] each */,
+                                  const int32_t *cell_index_dev, float *pose_out_dev /* [n_items][12] */,
+                                  btba_register_result *result_dev /* [n_items] */,
+                                  btba_register_iter *trace_dev /* NULL or [n_items][n_iters] */);
+BTBA_API int btba_register_associate(btba_workspace *ws, const btba_register_params *params, int n_instances, int n_items,
+                                     const btba_fuse_segment *segments, int H, int W, const float *K_rowmajor,
+                                     const int32_t *box, int capacity, const float *xyz_dev, const float *normal_dev,
+                                     const int32_t *cell_index_dev, int32_t *const *match_out /* host [n_items] of device int32 [H*W] or [n] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,6 @@
 #include "btba_kernels.hpp"
 #include "btba_objective.hpp"
 #include "btba_solve_general.hpp"
-#include "btba_chain.hpp"
 #include "btba_solve_small.hpp"
 #include "btba_solve_mid.hpp"
 
@@ -53,7 +52,7 @@ const char *btba_strerror(int status)
     case BTBA_EHIP: return "HIP runtime error (see btba_last_hip_error)";
     case BTBA_ENUMERIC: return "non-finite value in the output poses";
     case BTBA_ENOMEM: return "out of device memory";
-    case BTBA_ESCHED: return "a wait inside the chained launch timed out (workgroups did not start in grid order): the solve's poses are invalid; the workspace now solves unchained";
+    case BTBA_ESCHED: return "reserved: a scheduling failure of the retired chained launch (no longer returned)";
     default: return "unknown status";
     }
 }
@@ -76,7 +75,6 @@ static int workspace_create(btba_workspace **out, void *stream, bool use_given)
     btba_workspace *ws = new (std::nothrow) btba_workspace();
     if (!ws) return BTBA_ENOMEM;
     if (hipGetDevice(&ws->device) != hipSuccess) { delete ws; return BTBA_EHIP; }
-    if (hipDeviceGetAttribute(&ws->n_cus, hipDeviceAttributeMultiprocessorCount, ws->device) != hipSuccess) ws->n_cus = 0;
     {   // developer switches from the environment: here and nowhere else
         auto on = [](const char *name) { const char *e = std::getenv(name); return e && e[0] && e[0] != '0'; };
         btba_workspace::Tuning &t = ws->tune;
@@ -89,22 +87,15 @@ static int workspace_create(btba_workspace **out, void *stream, bool use_given)
         if (const char *e = std::getenv("BTBA_GROUPS")) t.overlap_groups = std::atoi(e);
         if (const char *e = std::getenv("BTBA_GROUP_PRIO")) t.overlap_equal_prio = e[0] == 'e';
         if (const char *e = std::getenv("BTBA_KEYED_CORR_MIN_BYTES")) t.keyed_corr_min_bytes = (size_t)std::strtoull(e, nullptr, 10);
-        if (const char *e = std::getenv("BTBA_CHAIN")) t.chain = std::max(-1, std::min(1, std::atoi(e)));
-        if (const char *e = std::getenv("BTBA_CHAIN_PERIOD")) t.chain_sparse_period = std::max(0, std::atoi(e));
         t.relayout = on("BTBA_RELAYOUT");
         t.solve_small = !on("BTBA_SOLVE_LEGACY");
         if (const char *e = std::getenv("BTBA_CORR_NT")) t.corr_nt = std::atoi(e);
         if (const char *e = std::getenv("BTBA_LLC_MB")) t.last_level_cache = (long long)std::atoll(e) << 20;
         if (const char *e = std::getenv("BTBA_CORR_NT_PARTIAL")) t.corr_nt_partial = std::atoi(e);
-        if (const char *e = std::getenv("BTBA_CHAIN_TIMEOUT_MS")) t.chain_timeout_ms = std::max(1, std::atoi(e));
 #if defined(BTBA_DEV_EXPERIMENTS) || defined(BTBA_REFERENCE_ORDER)
         t.prepare_keep_T = on("BTBA_PREPARE_KEEP_T") ? 1 : 0;
 #endif
-#ifdef BTBA_DEV_EXPERIMENTS      // developer builds only (scripts/chain_trace.py and the timing experiments of profiles/r04): these change schedules in ways a product build never does
-        if (const char *e = std::getenv("BTBA_CHAIN_GROUP")) t.chain_group = std::max(1, std::atoi(e));
-        if (const char *e = std::getenv("BTBA_CHAIN_TRACE_FILE")) t.chain_trace_file = e;
-        if (const char *e = std::getenv("BTBA_CHAIN_SOLVE_PRIO")) t.chain_solve_prio = std::max(0, std::min(3, std::atoi(e)));
-        if (const char *e = std::getenv("BTBA_CHAIN_DEBUG_SKIP")) t.chain_debug_skip = std::atoi(e);
+#ifdef BTBA_DEV_EXPERIMENTS      // developer builds only: this changes occupancy in ways a product build never does
         if (const char *e = std::getenv("BTBA_DEBUG_LDS_PAD")) t.debug_lds_pad = std::max(0, std::min(60000, std::atoi(e)));
 #endif
     }
@@ -126,7 +117,6 @@ void btba_workspace_destroy(btba_workspace *ws)
     (void)hipStreamSynchronize(ws->stream);
     for (auto &ep : ws->events) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (auto e : ws->event_pool) (void)hipEventDestroy(e);
-    if (ws->chain_error) (void)hipHostFree(ws->chain_error);
     for (auto st : ws->aux_streams) if (st) (void)hipStreamDestroy(st);
     if (ws->copy_stream) (void)hipStreamDestroy(ws->copy_stream);
     if (ws->ev_copy) (void)hipEventDestroy(ws->ev_copy);
@@ -158,9 +148,10 @@ int btba_workspace_set_option(btba_workspace *ws, int option, int64_t value)
         t.overlap_equal_prio = value != 0;
         break;
     case BTBA_OPT_KEYED_CORR_MIN_BYTES: if (value < 0) return BTBA_EINVAL; t.keyed_corr_min_bytes = (size_t)value; break;
-    case BTBA_OPT_CHAIN: if (value < -1 || value > 1) return BTBA_EINVAL; t.chain = (int)value; break;
-    case BTBA_OPT_CHAIN_SPARSE_PERIOD: if (value < 0 || value == 1 || value > 64) return BTBA_EINVAL; t.chain_sparse_period = (int)value; break;
-    case BTBA_OPT_CHAIN_TIMEOUT_MS: if (value < 1 || value > 60000) return BTBA_EINVAL; t.chain_timeout_ms = (int)value; break;
+    // retired with the chained launch: the ranges are still validated, nothing is stored
+    case BTBA_OPT_CHAIN: if (value < -1 || value > 1) return BTBA_EINVAL; break;
+    case BTBA_OPT_CHAIN_SPARSE_PERIOD: if (value < 0 || value == 1 || value > 64) return BTBA_EINVAL; break;
+    case BTBA_OPT_CHAIN_TIMEOUT_MS: if (value < 1 || value > 60000) return BTBA_EINVAL; break;
     case BTBA_OPT_RELAYOUT: t.relayout = value != 0; break;
     case BTBA_OPT_SOLVE_SMALL: t.solve_small = value != 0; break;
     case BTBA_OPT_CORR_NONTEMPORAL: if (value < -1 || value > 1) return BTBA_EINVAL; t.corr_nt = (int)value; break;
@@ -172,30 +163,9 @@ int btba_workspace_set_option(btba_workspace *ws, int option, int64_t value)
             HIP_TRY(hipMemsetAsync(ws->live_blocks.p, 0, sizeof(unsigned long long), ws->stream));
         }
         break;
-    case 1000:      // not part of the ABI.  64 = the watchdog's self-test (solve items never publish: the launch runs into the watchdog, the solve is REPORTED failed,
-                    // tests/test_gpu_chain.py); the timing experiments (other bits: sweep items that skip their waits, solve items that do nothing -- wrong poses
-                    // behind BTBA_OK) exist in developer builds only
-#ifdef BTBA_DEV_EXPERIMENTS
-        t.chain_debug_skip = (int)value; break;
-#else
-        if (value != 0 && value != 64) return BTBA_EINVAL;
-        t.chain_debug_skip = (int)value; break;
-#endif
     default: return BTBA_EINVAL;
     }
     return BTBA_OK;
-}
-
-// After a host synchronisation: did a wait inside a chained launch run into its watchdog?  The poses of that solve are then unusable; the
-// call reports BTBA_ESCHED once and the workspace solves unchained from then on.
-static int chain_check(btba_workspace *ws)
-{
-    if (!ws->chain_error || !*ws->chain_error) return BTBA_OK;
-    *ws->chain_error = 0;                                   // the stream has just been synchronised: the poison kernel of the failed launch has run
-    ws->chain_failed = true;
-    const bool already = ws->chain_reported;
-    ws->chain_reported = false;
-    return already ? BTBA_OK : BTBA_ESCHED;
 }
 
 int btba_workspace_live_blocks(btba_workspace *ws, uint64_t *blocks)
@@ -216,7 +186,7 @@ int btba_workspace_sync(btba_workspace *ws)
     DeviceGuard device_guard(ws);
     if (!ws) return BTBA_EINVAL;
     HIP_TRY(hipStreamSynchronize(ws->stream));
-    return chain_check(ws);
+    return BTBA_OK;
 }
 
 static int order_streams(btba_workspace *ws, hipStream_t from, hipStream_t to)
@@ -505,14 +475,6 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
 {
     if (!ws || !prm || B < 1 || N < 2 || Hd < 2 || Wd < 2 || !intr || !poses) return BTBA_EINVAL;
     if (prm->n_gn_iters < 1 || prm->n_pcg_iters < 0) return BTBA_EINVAL;   // MLIB_ASSERT, CUDASolverBundling.cpp:194
-    // A watchdog of an EARLIER chained launch fired and nobody has synchronised through the library since (a caller that orders its own stream with
-    // btba_workspace_signal_stream never passes btba_workspace_sync): report it now -- that solve's poses were poisoned with NaN by the kernel (k_chain),
-    // this and every later solve of the workspace runs unchained.
-    // The device-visible word stays SET here: this path has not synchronised the stream, and the poison kernel queued behind the failed launch may not
-    // have run yet -- clearing the word now would let it read 0 and leave that solve's garbage poses finite.  The word is cleared only behind a host
-    // synchronisation (chain_check); `chain_reported` latches that the caller has been told, chaining is off from here on (only chained launches queue
-    // poison kernels, so a sticky word cannot poison a later solve).
-    if (ws->chain_error && *ws->chain_error && !ws->chain_reported) { ws->chain_reported = true; ws->chain_failed = true; return BTBA_ESCHED; }
     if (prm->reduction_mode != BTBA_REDUCE_DETERMINISTIC && prm->reduction_mode != BTBA_REDUCE_ATOMIC) return BTBA_EINVAL;
     const bool atomic_sums = prm->reduction_mode == BTBA_REDUCE_ATOMIC;      // the reference's way of summing (float atomics, order not fixed)
     if (atomic_sums && trace) return BTBA_EINVAL;                            // the decision traces are defined on the reproducible sums
@@ -587,7 +549,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     D.corr_nt_from = B;                // plain loads unless decided otherwise below
     D.order_flag = order_flag;
     D.live_blocks = (ws->count_live && ws->live_blocks.p) ? ws->live_blocks.as<unsigned long long>() : nullptr;
-    D.sp_stride = (unsigned)((size_t)P * (atomic_sums ? 1 : chunks) * kSparseVals);      // (the chained launch pads the strides, below)
+    D.sp_stride = (unsigned)((size_t)P * (atomic_sums ? 1 : chunks) * kSparseVals);
     D.dp_stride = (unsigned)((size_t)(Pd > 0 ? Pd : 1) * (atomic_sums ? 1 : tiles) * kDenseVals);
     if ((size_t)B * std::max(D.sp_stride, D.dp_stride) >= ((size_t)1 << 32) || (size_t)B * 16 * N >= ((size_t)1 << 31)) return BTBA_EINVAL;      // the sweeps address an instance's poses and partials in 32 bits
     D.atomic_sums = atomic_sums ? 1 : 0;
@@ -610,8 +572,8 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     // windows (up to the reference's 85 frames) keep it in an L2-resident global scratch and run the multi-wave PCG
     // (the layout of k_system_solve's LDS: btba_solve_layout.hpp)
     const size_t lds_limit = 160 * 1024;
-    const bool a_global = sizeof(float) * SolveLayout(N, D.n_dense_pairs, false, false).total > lds_limit;
-    const size_t lds_core = sizeof(float) * SolveLayout(N, D.n_dense_pairs, a_global, false).total;
+    const bool a_global = sizeof(float) * SolveLayout(N, D.n_dense_pairs, false).total > lds_limit;
+    const size_t lds_core = sizeof(float) * SolveLayout(N, D.n_dense_pairs, a_global).total;
     const size_t lds_pairs = ((size_t)P * kSparseVals + (size_t)D.n_dense_pairs * kDenseVals) * sizeof(float);
     D.pairsum_in_lds = (lds_core + lds_pairs <= 64 * 1024) ? 1 : 0;   // keep two workgroups per CU when it fits
     if (!D.pairsum_in_lds && lds_core + lds_pairs <= lds_limit && B <= 256) D.pairsum_in_lds = 1;
@@ -637,7 +599,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     }
 
     // tracker-sized windows run k_solve_small (btba_solve_small.hpp) instead of k_system_solve: not in atomic mode (its records are accumulators
-    // the solve has to clear), not for the chained launch's last solve, and only while everything fits the CU's LDS
+    // the solve has to clear), and only while everything fits the CU's LDS
     const int small_cpl_v = small_cpl(N);
     const size_t small_lds = sizeof(float) * small_solve_lds_floats(N, D.n_dense_pairs, small_cpl_v);
     const bool small_solve = ws->tune.solve_small && N <= kSmallMaxFrames && !atomic_sums && !a_global && !D.pre_assembled && 2 * D.n_dense_pairs <= kSmallBlock && small_lds <= lds_limit;
@@ -672,19 +634,6 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
         HIP_TRY(hipMemsetAsync(ws->dense_part.p, 0, sizeof(float) * (size_t)B * (Pd > 0 ? Pd : 1) * kDenseVals, ws->stream));
     }
     const bool compaction = use_zn && use_dense && (prm->flags & BTBA_FLAG_COMPACTION);
-    // The chained launch (btba_chain.hpp: k_chain): all Gauss-Newton iterations in ONE launch, the system solves handed over inside it.
-    // Same sums in the same order as the plain schedule; taken for the batches it pays for and the configurations it is written for.
-    const int chain_lay = zn_layout == 1 ? (compaction ? 3 : 1) : 0;
-    // Only on request (BTBA_OPT_CHAIN = 1).  Measured at c3 x 32 on one box (profiles/r04/chain_experiments.json): the chained launch with two tiles
-    // per pair 1.280 ms per step against 1.306 ms for the plain schedule with two tiles -- and 1.247 ms for the plain schedule with ONE tile, which the
-    // chained launch cannot use (1.314 ms: its sparse items come in bursts behind every instance's dense items instead of closing the launch).
-    // Object-masked frames: 0.74 against 0.52 ms (their sweeps are shorter than an in-launch solve).  The library's own choice is the plain schedule.
-    // (only on a device that shows all 8 XCDs x 32 compute units -- the launch's forward progress rests on workgroup g running on XCD g % 8 in grid order;
-    // a partitioned device runs the plain schedule)
-    const bool chain = chain_lay != 0 && !ws->chain_failed && ws->n_cus == 256 && ws->tune.chain > 0 && use_sparse && use_dense && !wsi && !wdi
-                       && !trace && !atomic_sums && !a_global && !D.pre_assembled && N <= kChainMaxFrames && chunks <= kChainMaxParts && tiles <= kChainMaxParts
-                       && !(prm->flags & (BTBA_FLAG_NO_FUSE | BTBA_FLAG_OVERLAP)) && !Z.frame_slot
-                       && sizeof(float) * SolveLayout(N, D.n_dense_pairs, true, true).total <= kChainLdsBytes;      // (c3's 15 frames are the largest window whose solve fits a sweep workgroup's LDS share)
     // Fresh matches arrive as EntryJ (32 B, the wire format).  A solve reads them once per Gauss-Newton iteration; with BTBA_OPT_RELAYOUT the FIRST
     // iteration's sparse sweep writes 24-byte records as the entries pass by (SolveDims::corr24_out) and the other iterations stream those -- no separate
     // pack pass (btba_pack_correspondences24: 65 us + a launch at c3 x 32, 7 % of a step).  Measured (profiles/r04/relayout.json): the first launch's
@@ -692,7 +641,7 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     // 1.286 / 1.300 ms per step against 1.297 / 1.287 ms with EntryJ in every iteration on two boxes -- a wash, so it is OFF by default.
     // (not on object-masked frames walked through valid-pixel lists: their fused launch is short and latency-bound, and it measured FASTER on the
     // 32-byte entries -- 49.1 against 51.2 us, profiles/r03 -- before the re-layout's extra write in the first iteration: 454 k -> 402 k GN it/s with it)
-    const bool relayout = ws->tune.relayout && use_sparse && !corr24 && !pair_lens && !chain && prm->n_gn_iters >= 3 && !atomic_sums && !compaction
+    const bool relayout = ws->tune.relayout && use_sparse && !corr24 && !pair_lens && prm->n_gn_iters >= 3 && !atomic_sums && !compaction
                           && (size_t)B * (size_t)corr_stride * sizeof(btba_entryj) >= ((size_t)4 << 20);
     if (relayout) { if ((rc = ws->corr24_tmp.ensure(sizeof(float2) * 192 * (((size_t)B * (size_t)corr_stride + 63) / 64)))) return rc; }
     // Non-temporal correspondence loads (SolveDims::corr_nt).  Every iteration re-reads the batch's frames (dense items, through L2) and streams its
@@ -709,53 +658,10 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
         corr_nt_auto = (frames_bytes >= ws->tune.last_level_cache || corr_per_instance <= 0) ? 0 : (int)std::min<long long>(B, (ws->tune.last_level_cache - frames_bytes) / corr_per_instance);
     if (ws->tune.corr_nt_partial == 0 && corr_nt_auto < B) corr_nt_auto = 0;
     const int corr_nt_from = ws->tune.corr_nt >= 0 ? (ws->tune.corr_nt ? 0 : B) : corr_nt_auto;
-    ChainDims Cn{};
-    int plain_pairsum_in_lds = 0;
-    auto pad32 = [](size_t floats) { return (floats + 31) & ~(size_t)31; };      // whole 128-byte lines
-    if (chain) {
-        const int n_it = prm->n_gn_iters;
-        D.pose_stride = (int)pad32(16 * (size_t)N); D.x_stride = (int)pad32(6 * (size_t)N);
-        D.sp_stride = (unsigned)pad32((size_t)P * chunks * kSparseVals); D.dp_stride = (unsigned)pad32((size_t)Pd * tiles * kDenseVals);
-        D.publish = 1;
-        D.corr_nt_from = corr_nt_from;
-        plain_pairsum_in_lds = D.pairsum_in_lds;
-        D.pairsum_in_lds = 0;
-        Cn.last_solve_external = 1;
-        Cn.n_iter = n_it; Cn.n_inst = B; Cn.inst_per_xcd = (unsigned)((B + 7) / 8);
-        Cn.items_d = (unsigned)tiles * (unsigned)D.n_dense_pairs; Cn.items_s = (unsigned)chunks * (unsigned)P;
-        Cn.sparse_period = (unsigned)ws->tune.chain_sparse_period;
-        if (Cn.sparse_period >= 2u && Cn.sparse_period * Cn.items_s > Cn.items_d + Cn.items_s) Cn.sparse_period = (Cn.items_d + Cn.items_s) / Cn.items_s;      // all sparse items must find a slot
-        if (Cn.sparse_period < 2u) Cn.sparse_period = 0u;
-        Cn.group = (Cn.sparse_period == 0u && ws->tune.chain_group > 1 && Cn.inst_per_xcd % (unsigned)ws->tune.chain_group == 0u && B % 8 == 0) ? (unsigned)ws->tune.chain_group : 1u;
-        Cn.timeout_ticks = (long long)ws->tune.chain_timeout_ms * 100000ll;
-        Cn.solve_prio = ws->tune.chain_solve_prio;
-        Cn.debug_skip = ws->tune.chain_debug_skip;
-        if (Cn.debug_skip & 16) D.publish = 0;             // (timing experiment: plain record stores)
-        Cn.pose_ring = (size_t)B * D.pose_stride; Cn.x_ring = (size_t)B * D.x_stride;
-        Cn.sp_ring = (size_t)B * (size_t)D.sp_stride; Cn.dp_ring = (size_t)B * (size_t)D.dp_stride;
-        Cn.ps_size = pad32((size_t)D.n_dense_pairs * kDenseVals); Cn.A_size = pad32((n + 2) * ld);      // (global scratch: the reduced DENSE pair sums; the matrix before it is packed into LDS)
-        if ((rc = ws->x.ensure(sizeof(float) * (n_it + 1) * Cn.x_ring))) return rc;
-        if ((rc = ws->T.ensure(sizeof(float) * (n_it + 1) * Cn.pose_ring))) return rc;
-        if ((rc = ws->Tinv.ensure(sizeof(float) * (n_it + 1) * Cn.pose_ring))) return rc;
-        if ((rc = ws->sparse_part.ensure(sizeof(float) * n_it * Cn.sp_ring))) return rc;
-        if ((rc = ws->dense_part.ensure(sizeof(float) * n_it * Cn.dp_ring))) return rc;
-        if ((rc = ws->pairsum.ensure(sizeof(float) * (size_t)n_it * B * Cn.ps_size))) return rc;
-        if ((rc = ws->big_A.ensure(sizeof(float) * (size_t)n_it * B * Cn.A_size))) return rc;
-        const size_t sync_head = ((size_t)B * (n_it + 1) + 15) & ~(size_t)15;               // flags[B], arrivals[n_it][B], padded to a 64-byte line
-        const size_t sync_ints = sync_head + (size_t)16 * B * (n_it + 1);                  // ... published[n_it + 1][B][16]
-        if ((rc = ws->chain_sync.ensure(sizeof(int) * sync_ints))) return rc;
-        if (!ws->chain_error) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ws->chain_error), 64, hipHostMallocDefault));
-            *ws->chain_error = 0;
-        }
-        HIP_TRY(hipMemsetAsync(ws->chain_sync.p, 0, sizeof(int) * sync_ints, ws->stream));      // flags and arrival counters: zero before EVERY launch
-        Cn.flags = ws->chain_sync.as<int>(); Cn.arrivals = Cn.flags + B; Cn.published = Cn.flags + sync_head; Cn.error = ws->chain_error;
-    }
     // Log, Exp, inverse of the incoming matrices
     {
         const int total = B * N;
-        if (chain) k_prepare_strided<<<(total + 63) / 64, 64, 0, ws->stream>>>(total, N, D.pose_stride, D.x_stride, poses, ws->x.as<float>(), ws->T.as<float>(), ws->Tinv.as<float>());
-        else k_prepare<<<(total + 63) / 64, 64, 0, ws->stream>>>(total, poses, ws->x.as<float>(), ws->T.as<float>(), ws->Tinv.as<float>(), ws->tune.prepare_keep_T);
+        k_prepare<<<(total + 63) / 64, 64, 0, ws->stream>>>(total, poses, ws->x.as<float>(), ws->T.as<float>(), ws->Tinv.as<float>(), ws->tune.prepare_keep_T);
     }
     // per-frame valid-pixel lists for the compact dense sweep (once per solve; the frames do not change across iterations)
     const uint32_t *lists_base = Z.lists;
@@ -817,82 +723,6 @@ static int solve_enqueue(btba_workspace *ws, const btba_params *prm, int B, int 
     const size_t pairsum_floats = lds_pairs / sizeof(float);
     S.chain_iterations = 0;
     const size_t lut_bytes = sweep_lds.total + (size_t)ws->tune.debug_lds_pad;
-    if (chain) {
-        // ONE launch: 8 XCD sequences x n_gn iterations x (instances of the XCD) x (sweep items + 1 solve item)
-        const size_t chain_lds = std::max(lut_bytes, sizeof(float) * SolveLayout(N, D.n_dense_pairs, true, true).total);
-        const unsigned per_inst = Cn.items_d + Cn.items_s + 1u;
-        const unsigned grid = 8u * (unsigned)prm->n_gn_iters * Cn.inst_per_xcd * per_inst;
-        if (!ws->tune.chain_trace_file.empty()) {          // developer: timeline of the launch (scripts/chain_trace.py)
-            const size_t trace_bytes = 32 * (size_t)grid + 64 * (size_t)prm->n_gn_iters * B;
-            if ((rc = ws->chain_trace.ensure(trace_bytes))) return rc;
-            HIP_TRY(hipMemsetAsync(ws->chain_trace.p, 0, trace_bytes, ws->stream));
-            Cn.trace = ws->chain_trace.as<unsigned long long>();
-            Cn.stamps = Cn.trace + 4 * (size_t)grid;
-        }
-        const float4 *corr_c = reinterpret_cast<const float4 *>(corr);
-        size_t slot;
-        if (Cn.debug_skip & 32) {
-            // developer TIMING experiment: the chain kernel as a plain per-iteration sweep launch (its solve items return at once) followed by
-            // k_system_solve on ring slot 0 -- what the sweep items cost in THIS kernel binary without the in-launch schedule
-            ChainDims C1 = Cn;
-            C1.n_iter = 1; C1.debug_skip |= 8; C1.trace = nullptr; C1.stamps = nullptr;
-            const unsigned grid1 = 8u * Cn.inst_per_xcd * per_inst;
-            if ((rc = ws->pairsum.ensure(sizeof(float) * (size_t)B * ((size_t)P * kSparseVals + (size_t)D.n_dense_pairs * kDenseVals + 64)))) return rc;
-            for (int it = 0; it < prm->n_gn_iters; it++) {
-                if ((rc = time_begin(ws, timing, 0, &slot))) return rc;
-#define BTBA_CHAIN_ARGS1 D, C1, reinterpret_cast<const float4 *>(Z.zn), ws->T.as<float>(), ws->Tinv.as<float>(), ws->x.as<float>(), ws->dense_part.as<float>(), corr_c, pair_offsets, \
-                        ws->sparse_part.as<float>(), compaction ? lists_base : nullptr, compaction ? counts_base : nullptr, ws->dense_pairs.as<int2>(), d_adj_off, d_adj, ws->solve_tab.as<int>(), \
-                        ws->pairsum.as<float>(), ws->big_A.as<float>(), poses
-                if (chain_lay == 1) k_chain<1><<<dim3(grid1), kBlock, chain_lds, ws->stream>>>(BTBA_CHAIN_ARGS1);
-                else k_chain<3><<<dim3(grid1), kBlock, chain_lds, ws->stream>>>(BTBA_CHAIN_ARGS1);
-#undef BTBA_CHAIN_ARGS1
-                if ((rc = time_end(ws, slot))) return rc;
-                if ((rc = time_begin(ws, timing, 2, &slot))) return rc;
-                k_system_solve<false, false><<<B, kSolveBlock, lds_core, ws->stream>>>(D, it, ws->sparse_part.as<float>(), ws->dense_part.as<float>(), ws->dense_pairs.as<int2>(), d_adj_off, d_adj,
-                    ws->x.as<float>(), ws->T.as<float>(), ws->Tinv.as<float>(), ws->pairsum.as<float>(), nullptr, nullptr, it == prm->n_gn_iters - 1 ? poses : nullptr, ws->solve_tab.as<int>());
-                if ((rc = time_end(ws, slot))) return rc;
-            }
-            S.fused_sweeps = 1;
-        } else {
-        if ((rc = time_begin(ws, timing, 0, &slot))) return rc;
-#define BTBA_CHAIN_ARGS D, Cn, reinterpret_cast<const float4 *>(Z.zn), ws->T.as<float>(), ws->Tinv.as<float>(), ws->x.as<float>(), ws->dense_part.as<float>(), corr_c, pair_offsets, \
-                        ws->sparse_part.as<float>(), compaction ? lists_base : nullptr, compaction ? counts_base : nullptr, ws->dense_pairs.as<int2>(), d_adj_off, d_adj, ws->solve_tab.as<int>(), \
-                        ws->pairsum.as<float>(), ws->big_A.as<float>(), poses
-        if (chain_lay == 1) k_chain<1><<<dim3(grid), kBlock, chain_lds, ws->stream>>>(BTBA_CHAIN_ARGS);
-        else k_chain<3><<<dim3(grid), kBlock, chain_lds, ws->stream>>>(BTBA_CHAIN_ARGS);
-#undef BTBA_CHAIN_ARGS
-        if ((rc = time_end(ws, slot))) return rc;
-        if (Cn.last_solve_external) {
-            // the last iteration's system solve as its own launch on the last ring slot: the launch above has drained, 16 waves per instance
-            const int il = prm->n_gn_iters - 1;
-            SolveDims Dl = D;
-            Dl.pairsum_in_lds = plain_pairsum_in_lds; Dl.publish = 0;
-            if (!Dl.pairsum_in_lds) { if ((rc = ws->pairsum.ensure(std::max(sizeof(float) * (size_t)prm->n_gn_iters * B * Cn.ps_size, (size_t)B * lds_pairs + 16)))) return rc; }
-            if ((rc = time_begin(ws, timing, 2, &slot))) return rc;
-#define BTBA_LAST_SOLVE(LP) k_system_solve<LP, false><<<B, kSolveBlock, lds_bytes, ws->stream>>>(Dl, il, ws->sparse_part.as<float>() + il * Cn.sp_ring, ws->dense_part.as<float>() + il * Cn.dp_ring, \
-                ws->dense_pairs.as<int2>(), d_adj_off, d_adj, ws->x.as<float>() + il * Cn.x_ring, ws->T.as<float>() + il * Cn.pose_ring, ws->Tinv.as<float>() + il * Cn.pose_ring, \
-                ws->pairsum.as<float>(), nullptr, nullptr, poses, ws->solve_tab.as<int>())
-            if (Dl.pairsum_in_lds) BTBA_LAST_SOLVE(true); else BTBA_LAST_SOLVE(false);
-#undef BTBA_LAST_SOLVE
-            if ((rc = time_end(ws, slot))) return rc;
-        }
-        // a watchdog that fired inside the launch leaves poses nobody may use: NaN them on the device, so that a caller who never synchronises through
-        // the library (and so never sees BTBA_ESCHED from btba_workspace_sync) runs into its own finiteness checks / BTBA_ENUMERIC
-        k_chain_poison<<<(16 * B * N + 255) / 256, 256, 0, ws->stream>>>(Cn.error, poses, 16 * B * N);
-        S.chain_iterations = prm->n_gn_iters;
-        S.fused_sweeps = 1;
-        ws->chain_launches++;
-        if (Cn.trace) {
-            HIP_TRY(hipStreamSynchronize(ws->stream));
-            std::vector<unsigned long long> host(4 * (size_t)grid + 8 * (size_t)prm->n_gn_iters * B);
-            HIP_TRY(hipMemcpy(host.data(), ws->chain_trace.p, 8 * host.size(), hipMemcpyDeviceToHost));
-            if (FILE *f = std::fopen(ws->tune.chain_trace_file.c_str(), "wb")) {       // [0] = number of block records, then the records, then the solve items' phase stamps
-                const unsigned long long nrec = grid;
-                std::fwrite(&nrec, 8, 1, f); std::fwrite(host.data(), 8, host.size(), f); std::fclose(f);
-            }
-        }
-        }
-    } else
     for (int it = 0; it < prm->n_gn_iters; it++) {
         const bool timing_it = timing && (timed_iteration < 0 || timed_iteration == it);
         // this iteration's weights (parameters.weightSparse / weightDenseDepth / useDense of SolverBundling.cu:948-953)
@@ -1035,7 +865,7 @@ int btba_collect_stats(btba_workspace *ws, btba_stats *stats)
     if (stats) *stats = S;
     S.ms_dense_sweep = S.ms_sparse_sweep = S.ms_system_solve = S.ms_solve = S.ms_cache = 0.0f;
     S.n_dense_launches = S.n_sparse_launches = S.n_solve_launches = 0;
-    return chain_check(ws);
+    return BTBA_OK;
 }
 
 int btba_solve_batch(btba_workspace *ws, const btba_params *params, int n_instances, int n_frames, int Hd, int Wd, const float *intr,

@@ -1,6 +1,6 @@
 // btba_fusion.hpp -- keyframe fusion and voxel-grid downsampling (btba_fuse_bounds / btba_fuse_frames, include/btba.h): posed
 // keyframes (depth, normal and colour maps) and unorganised clouds -> one voxel-grid cloud per instance.  The cloud primitive is
-// Utils::downsamplePointCloud = pcl::VoxelGrid (src/Utils.cpp:134-140; restated from PCL's published header, unverified against a
+// Utils::downsamplePointCloud = pcl::VoxelGrid (src/Utils.cpp:134-140; restated from PCL's public header, unverified against a
 // PCL run: PCL is not available to this project).
 //
 // Segments travel in chunks of BTBA_FUSE_CHUNK as kernel arguments (as btba_ingest_frames' frames do), so an asynchronous call

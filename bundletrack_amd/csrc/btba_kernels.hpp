@@ -19,8 +19,8 @@
 //                            LDS, SE(3) update, next iterate's T and T^-1.
 //
 // This file holds what all of them share (SolveDims, the frame caches) and the sweeps; the system solves are in
-// btba_solve_general.hpp (k_system_solve, k_big_reduce, k_big_assemble), btba_solve_small.hpp and btba_solve_mid.hpp, the chained
-// launch (k_chain) in btba_chain.hpp.  The dynamic-LDS layout of a dense item on the compact cache is btba_sweep_layout.hpp (shared with the host).
+// btba_solve_general.hpp (k_system_solve, k_big_reduce, k_big_assemble), btba_solve_small.hpp and btba_solve_mid.hpp.  The dynamic-LDS
+// layout of a dense item on the compact cache is btba_sweep_layout.hpp (shared with the host).
 //
 // Summation is deterministic (fixed DPP tree inside a wave, fixed order across waves, tiles and
 // pairs); the reference uses float atomics (SURVEY.md section 5 "race detection").
@@ -96,15 +96,14 @@ struct SolveDims {
     int zn_simple;       // 1: zero skew and affine last row (ki[1]=ki[3]=ki[4]=ki[7]=ki[12]=ki[13]=ki[14]=0)
     // persistent frame cache: frame f of the solve lives in pool slot frame_slot[f] (nullptr: slot == f, contiguous cache)
     const int *frame_slot;
-    // floats per INSTANCE in the pose arrays (T, Tinv: >= 16 N), the state array (x: >= 6 N) and the sweep partials.  The plain launches keep
-    // the instances back to back; the chained launch (k_chain) pads every instance's region to whole 128-byte lines, so that no cache line is
-    // shared by two regions that different workgroups publish at different times.
+    // floats per INSTANCE in the pose arrays (T, Tinv: 16 N), the state array (x: 6 N) and the sweep partials: the instances lie back to back.
+    // (the two pose strides arrive as kernel arguments although they follow from N: computed in the kernels they measured +0.5 % on the fused
+    // sweep at c3 x 32, profiles/chain_removal/ab.json)
     int pose_stride, x_stride;
     unsigned sp_stride, dp_stride;      // (32-bit: an instance's partials are a few MB at most; 64-bit strides cost the short masked / sparse items ~100 scalar instructions)
     float2 *corr24_out;  // non-null (EntryJ sweeps only): the sweep also WRITES every entry it reads as a 24-byte record (corr24_index layout, entry index counted from
                          // corr_entry0 + b * corr_stride): the first iteration of a solve re-lays the caller's fresh EntryJ array out for the iterations that follow
     unsigned long long *live_blocks;   // non-null (BTBA_OPT_COUNT_LIVE, bench.py's roofline.executed): every block-walk workgroup adds the number of 8 x 8 blocks it walks
-    int publish;         // k_chain: sweep workgroups store their partial records write-through (agent scope) -- another workgroup of the SAME launch reads them
     int corr_nt_from;    // instances b >= corr_nt_from read their correspondences with NON-TEMPORAL loads: once a batch's frames + correspondences exceed the memory-side
                          // cache, the read-once stream otherwise evicts the frames the dense items re-read every iteration (btba_api.hip: corr_nt_auto); what still fits
                          // beside the frames -- the first instances' correspondences -- stays cached, and below the limit plain loads are faster for everything
@@ -424,7 +423,7 @@ __device__ __forceinline__ void sparse_block_impl(const SolveDims &D, const floa
     }
     acc[0] = (tid & 63u) == 0u ? (float)n_valid : 0.0f;         // an integer far below 2^24: the float the per-lane counts summed to
     float *out = partials + ((unsigned)b * D.sp_stride + (unsigned)(D.atomic_sums ? p : p * D.sparse_chunks + chunk) * (unsigned)kSparseVals);
-    block_reduce_store<kSparseVals, 4>(acc, red, out, D.atomic_sums ? 1 : D.publish ? 2 : 0);
+    block_reduce_store<kSparseVals, 4>(acc, red, out, D.atomic_sums ? 1 : 0);
 }
 __device__ __forceinline__ void sparse_block(const SolveDims &D, const float4 *__restrict__ corr, const uint32_t *__restrict__ pair_offsets,
                                              const float *__restrict__ T, float *__restrict__ partials, int chunk, int p, int b, float *red)
@@ -720,12 +719,10 @@ __device__ __forceinline__ void dense_M_store(unsigned tid, float *red, float v)
 
 // FLIPPED: the sums were accumulated with a+ = D a, res+ = -res (dense_block_pinhole): S = D S+ D negates the nine entries that couple a
 // translation row with a rotation row, g = -D g+ negates the three rotation entries -- exact.
-// mode: 0 store the record, 1 add it to the record with float atomics (BTBA_REDUCE_ATOMIC), 2 store it WRITE-THROUGH at agent scope (k_chain:
-// the record is read by another workgroup of the same launch, MI355X_MICROARCH.md "inter-workgroup visibility")
+// mode: 0 store the record, 1 add it to the record with float atomics (BTBA_REDUCE_ATOMIC)
 __device__ __forceinline__ void store_sum(float *p, float v, int mode)
 {
     if (mode == 1) unsafeAtomicAdd(p, v);
-    else if (mode == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *p = v;
 }
 template <bool FLIPPED = false>
@@ -781,7 +778,7 @@ __device__ __forceinline__ void dense_epilogue(float (&acc)[kDenseVals], float *
 
 // where the workgroup of (dense pair p, tile, instance b) puts its record, and how (store_sum's mode)
 __device__ __forceinline__ float *dense_record_out(const SolveDims &D, float *__restrict__ partials, int p, int tile, int b) { return partials + ((unsigned)b * D.dp_stride + (unsigned)(D.atomic_sums ? p : p * D.dense_tiles + tile) * (unsigned)kDenseVals); }
-__device__ __forceinline__ int dense_record_mode(const SolveDims &D) { return D.atomic_sums ? 1 : D.publish ? 2 : 0; }
+__device__ __forceinline__ int dense_record_mode(const SolveDims &D) { return D.atomic_sums ? 1 : 0; }
 
 // (tile, pair, instance) of position L of the dense grids: tile fastest, then pair, then instance
 __device__ __forceinline__ void dense_grid_decode(const SolveDims &D, unsigned L, int &tile, int &p, int &b)

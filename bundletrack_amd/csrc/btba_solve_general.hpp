@@ -1,16 +1,18 @@
 // btba_solve_general.hpp -- the general system solve: k_system_solve, with k_big_reduce and k_big_assemble in front of it on larger windows.
-// It runs windows of 32 to 85 frames, the atomic reduction mode, explicit dense pair lists with more than P pairs, every window when
-// BTBA_OPT_SOLVE_SMALL = 0, the last solve of a chained launch, and -- as system_solve_body<CHAIN> -- the solve items inside k_chain
-// (btba_chain.hpp), whose sums are pinned to this kernel's bit for bit.  One workgroup per instance walks
-//   reduce the sweep partials -> assemble A, b, M^-1 -> (chained: pack A's triangle) -> PCG -> update x, T, T^-1
+// It runs windows of 32 to 85 frames, the atomic reduction mode, explicit dense pair lists with more than P pairs, and every
+// window when BTBA_OPT_SOLVE_SMALL = 0.  One workgroup of kSolveBlock threads per instance walks
+//   reduce the sweep partials -> assemble A, b, M^-1 -> PCG -> update x, T, T^-1
 // each step a forced-inline function over one SolveCtx; the LDS layout is btba_solve_layout.hpp's, shared with the host.
+// The order of every sum in here is pinned: the decision traces (BTBA_FLAG_TRACE) are compared bit for bit across builds,
+// tests/test_gpu_solve_stages.py holds each stage to its fp64 reference, and test_small_solve_kernel_agrees_with_the_legacy_kernel holds
+// k_solve_small to this kernel.
 #pragma once
 #include "btba_kernels.hpp"
 #include "btba_solve_layout.hpp"
 
 namespace btba {
 
-static_assert(kLayoutSparseVals == kSparseVals, "btba_solve_layout.hpp sizes region R with the sparse record's length");
+static_assert(kLayoutSparseVals == kSparseVals, "btba_solve_layout.hpp carries the sparse record's length");
 
 // Linear form of a sparse 6x6 block entry ([trans, rot] order; J_k = [ I | -[w_k]x ]) from a pair's 44 moment sums:
 //   diagonal block of endpoint e (0 = i, 1 = j):  [[ n I, -[s]x ], [ [s]x, tr(M) I - M ]]
@@ -54,9 +56,6 @@ __device__ __forceinline__ float block_sum(float v, float *scratch)
     return t;
 }
 
-// p as a pointer that is LDS by type (the caller knows it is)
-__device__ __forceinline__ __attribute__((address_space(3))) float *as_lds(float *p) { return (__attribute__((address_space(3))) float *)p; }
-
 // ---- the assembly formulas, once: the workgroup (assemble, below) and k_big_assemble call them with their own slice counts and their
 // own homes of the pair sums (ps: sparse [P][44], pd: dense [Pd][28]) and tables (LDS there, global memory here) ----------------------
 
@@ -76,26 +75,21 @@ __device__ __forceinline__ float off_diag_entry(const SolveDims &D, const int *e
 }
 
 // Sum of the dense pair sums `off` of adjacency entries [qa, qb) of a frame, signed by the frame's role in the pair when `by_role`
-// (source frame: row_j = a;  target frame: row_i = -a).  BATCH = 8 (the chained solve: pd is the global scratch, an L2 round trip per
-// value): the loads of eight entries are issued before the first add -- the same values enter the same sum in the same order.
-template <int BATCH>
+// (source frame: row_j = a;  target frame: row_i = -a), in adjacency order.
 __device__ __forceinline__ float dense_adj_sum(const int *adj, const float *pd, int qa, int qb, int off, bool by_role)
 {
     float acc = 0.0f;
-    for (int q = qa; q < qb; q += BATCH) {
-        float v[BATCH];
-        int a[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; u++) { a[u] = adj[BATCH == 1 ? q : min(q + u, qb - 1)]; v[u] = pd[(size_t)(a[u] >> 1) * kDenseVals + off]; }
-#pragma unroll
-        for (int u = 0; u < BATCH; u++) if (BATCH == 1 || q + u < qb) acc += by_role ? ((a[u] & 1) ? v[u] : -v[u]) : v[u];
+    for (int q = qa; q < qb; q++) {
+        const int a = adj[q];
+        const float v = pd[(size_t)(a >> 1) * kDenseVals + off];
+        acc += by_role ? ((a & 1) ? v : -v) : v;
     }
     return acc;
 }
 
 // Slice s of PARTS of diagonal-block entry rc of frame k >= 1: the frame's partners m in [N s / PARTS, N (s + 1) / PARTS) and the same
 // share of its dense adjacency, each in fixed order.  The caller adds the PARTS slices with its shuffle tree.
-template <int PARTS, int BATCH>
+template <int PARTS>
 __device__ __forceinline__ float diag_entry_slice(const SolveDims &D, int N, int k, int rc, int s, const int *entry_lut, const float *ps, const float *pd,
                                                   const int *adj_off, const int *adj)
 {
@@ -116,13 +110,13 @@ __device__ __forceinline__ float diag_entry_slice(const SolveDims &D, int N, int
     }
     if (D.use_dense) {
         const int q0 = adj_off[k], nq = adj_off[k + 1] - q0;
-        v += dense_adj_sum<BATCH>(adj, pd, q0 + (nq * s) / PARTS, q0 + (nq * (s + 1)) / PARTS, tri21(rc / 6, rc % 6), false);
+        v += dense_adj_sum(adj, pd, q0 + (nq * s) / PARTS, q0 + (nq * (s + 1)) / PARTS, tri21(rc / 6, rc % 6), false);
     }
     return v;
 }
 
 // Slice s of PARTS of the right-hand side (rhs) and of the Jacobi diagonal (md) of unknown r of frame k >= 1
-template <int PARTS, int BATCH>
+template <int PARTS>
 __device__ __forceinline__ void rhs_jacobi_slice(const SolveDims &D, int N, int k, int r, int s, const float *ps, const float *pd, const int *adj_off, const int *adj,
                                                  float &rhs, float &md)
 {
@@ -142,7 +136,7 @@ __device__ __forceinline__ void rhs_jacobi_slice(const SolveDims &D, int N, int 
     }
     if (D.use_dense) {
         const int q0 = adj_off[k], nq = adj_off[k + 1] - q0;
-        rhs -= dense_adj_sum<BATCH>(adj, pd, q0 + (nq * s) / PARTS, q0 + (nq * (s + 1)) / PARTS, 21 + r, true);
+        rhs -= dense_adj_sum(adj, pd, q0 + (nq * s) / PARTS, q0 + (nq * (s + 1)) / PARTS, 21 + r, true);
     }
 }
 // M^-1 of an unknown from the summed Jacobi diagonal (frame 0 stays fixed)
@@ -238,7 +232,7 @@ __global__ void __launch_bounds__(256) k_big_assemble(SolveDims D, const float *
         const unsigned e = t >> 3, sub = t & 7u;
         const bool live = e < (unsigned)(N - 1) * 36u;
         const int k = live ? 1 + (int)(e / 36u) : 1, rc = live ? (int)(e % 36u) : 0;
-        float v = live ? diag_entry_slice<8, 1>(D, N, k, rc, (int)sub, entry_lut, ps, pd, adj_off, adj) : 0.0f;
+        float v = live ? diag_entry_slice<8>(D, N, k, rc, (int)sub, entry_lut, ps, pd, adj_off, adj) : 0.0f;
         v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
         if (live && sub == 0) A[(size_t)(6 * k + rc / 6) * ld + 6 * k + rc % 6] = v;
         return;
@@ -249,7 +243,7 @@ __global__ void __launch_bounds__(256) k_big_assemble(SolveDims D, const float *
         const bool live = e < (unsigned)n;
         const int k = live ? (int)e / 6 : 0, r = live ? (int)e % 6 : 0;
         float rhs = 0.0f, md = 0.0f;
-        if (live && k > 0) rhs_jacobi_slice<8, 1>(D, N, k, r, (int)sub, ps, pd, adj_off, adj, rhs, md);
+        if (live && k > 0) rhs_jacobi_slice<8>(D, N, k, r, (int)sub, ps, pd, adj_off, adj, rhs, md);
         rhs += __shfl_xor(rhs, 1, 64); md += __shfl_xor(md, 1, 64);
         rhs += __shfl_xor(rhs, 2, 64); md += __shfl_xor(md, 2, 64);
         rhs += __shfl_xor(rhs, 4, 64); md += __shfl_xor(md, 4, 64);
@@ -264,18 +258,14 @@ __global__ void __launch_bounds__(256) k_big_assemble(SolveDims D, const float *
     else if (t - 6u * ld < zero_fill_rest((unsigned)n, (unsigned)ld)) A[zero_fill_rest_index((int)(t - 6u * ld), n, ld)] = 0.0f;
 }
 
-// What one instance's system solve reads and writes, every pointer already at THIS instance.  The plain launch (k_system_solve) updates x, T
-// and T^-1 in place; the chained launch (k_chain) reads iterate `it` and writes iterate `it + 1` into the next slot of a ring, because the
-// sweep workgroups of other instances -- and of this instance's next iteration -- are running at the same time.
+// What one instance's system solve reads and writes, every pointer already at THIS instance.  x, T and T^-1 are updated in place.
 struct SolveIO {
     float *sparse_partials, *dense_partials;            // this iteration's sweep partials (not const: in BTBA_REDUCE_ATOMIC mode they are accumulators that the solve clears)
-    const float *x_in, *T_in;                           // this iterate
-    float *x_out, *T_out, *Tinv_out;                    // the next one
+    float *x, *T, *Tinv;                                // this iterate on entry, the next one on return (T^-1 is only written)
     float *poses_out;                                   // last iteration: the caller's pose buffer (or nullptr)
     float *pairsum_global;                              // reduced pair sums when they are not staged in LDS
-    float *A_scratch;                                   // A_GLOBAL / pre_assembled / CHAIN: A[n][ld], rhs[ld], prec[ld]
+    float *A_scratch;                                   // A_GLOBAL / pre_assembled: A[n][ld], rhs[ld], prec[ld]
     float *trace;                                       // this instance's trace records (or nullptr)
-    unsigned long long *stamps;                         // developer (scripts/chain_trace.py): 8 wall-clock stamps of the phases of this solve (or nullptr)
 };
 
 // What every phase of one solve works on: the dimensions, the calling lane, and the workgroup's pointers -- into the dynamic LDS (each
@@ -286,12 +276,11 @@ struct SolveCtx {
     int tid, N, n, ld;
     float *tr;                                  // this iteration's trace record (or nullptr)
     long long clk0;
-    float *A;                                   // the matrix: LDS, or the global scratch (A_GLOBAL, CHAIN); global layout per instance: A[n][ld], rhs[ld], prec[ld]
+    float *A;                                   // the matrix: LDS, or the global scratch (A_GLOBAL); global layout per instance: A[n][ld], rhs[ld], prec[ld]
     float *vb, *vM, *vp, *vAp, *vd, *scratch, *vT, *x_l;
     int *dense_pairs_l, *adj_off_l, *adj_l, *pair_ij_l, *cross_l, *entry_lut;
-    float *region_R;                            // CHAIN: the reduced SPARSE pair sums while the system is assembled, afterwards the packed matrix (pack_triangle)
     // reduced pair sums, sparse [P][44] and model-frame dense (S, g, count) [Pd][28]: in LDS when they fit (address space known at compile
-    // time -> ds_* instructions, not flat_*), otherwise in an L2-resident global scratch (K = 30; chained: the dense sums always)
+    // time -> ds_* instructions, not flat_*), otherwise in an L2-resident global scratch (K = 30)
     float *ps, *pd;
     __device__ __forceinline__ SolveCtx(const SolveDims &D_, const SolveIO &io_, int tid_, float *tr_, float *lds, const SolveLayout &L, bool a_in_global, float *ps_, float *pd_)
         : D(D_), io(io_), tid(tid_), N(D_.n_frames), n(6 * D_.n_frames), ld(L.ld), tr(tr_), clk0(tr_ ? (long long)clock64() : 0),
@@ -299,20 +288,18 @@ struct SolveCtx {
           scratch(lds + L.scratch), vT(lds + L.vT), x_l(lds + L.x),
           dense_pairs_l(reinterpret_cast<int *>(lds + L.dense_pairs)), adj_off_l(reinterpret_cast<int *>(lds + L.adj_off)), adj_l(reinterpret_cast<int *>(lds + L.adj)),
           pair_ij_l(reinterpret_cast<int *>(lds + L.pair_ij)), cross_l(reinterpret_cast<int *>(lds + L.cross)), entry_lut(reinterpret_cast<int *>(lds + L.entry_lut)),
-          region_R(lds + L.region_R), ps(ps_), pd(pd_) {}
+          ps(ps_), pd(pd_) {}
 };
 
-// clock stamp `slot` of the trace record (and, chained, of the developer's phase stamps), by lane 0
-template <bool CHAIN>
-__device__ __forceinline__ void solve_stamp(const SolveCtx &C, int slot)
+// clock stamp `slot` of the trace record, by lane 0
+__device__ __forceinline__ void trace_stamp(const SolveCtx &C, int slot)
 {
     if (C.tr && C.tid == 0) C.tr[C.D.tr_clk + slot] = (float)((long long)clock64() - C.clk0);
-    if (CHAIN && C.io.stamps && C.tid == 0) C.io.stamps[slot] = (unsigned long long)wall_clock64();
 }
 
 // ---- a pre-assembled system (larger windows): k_big_reduce + k_big_assemble have built A, the right-hand side and the Jacobi diagonal
 // in the global scratch; a matrix that fits LDS is loaded back for the one-wave PCG (coalesced, once)
-template <bool A_IN_GLOBAL, int NTHR>
+template <bool A_IN_GLOBAL>
 __device__ __forceinline__ void load_pre_assembled(const SolveCtx &C)
 {
     const int tid = C.tid, N = C.N, n = C.n, ld = C.ld;
@@ -321,12 +308,12 @@ __device__ __forceinline__ void load_pre_assembled(const SolveCtx &C)
     if (!A_IN_GLOBAL) {
         const float4 *src = reinterpret_cast<const float4 *>(Ag);
         float4 *dst = reinterpret_cast<float4 *>(C.A);
-        for (int e = tid; e < (n * ld) / 4; e += NTHR) dst[e] = src[e];
+        for (int e = tid; e < (n * ld) / 4; e += kSolveBlock) dst[e] = src[e];
     }
-    for (int e = tid; e < 16 * N; e += NTHR) C.vT[e] = C.io.T_in[e];
-    for (int e = tid; e < 6 * N; e += NTHR) C.x_l[e] = C.io.x_in[e];
-    for (int e = tid; e < n; e += NTHR) { C.vb[e] = rhs_g[e]; C.vM[e] = prec_g[e]; C.vd[e] = 0.0f; }
-    for (int e = n + tid; e < ld; e += NTHR) C.vp[e] = 0.0f;
+    for (int e = tid; e < 16 * N; e += kSolveBlock) C.vT[e] = C.io.T[e];
+    for (int e = tid; e < 6 * N; e += kSolveBlock) C.x_l[e] = C.io.x[e];
+    for (int e = tid; e < n; e += kSolveBlock) { C.vb[e] = rhs_g[e]; C.vM[e] = prec_g[e]; C.vd[e] = 0.0f; }
+    for (int e = n + tid; e < ld; e += kSolveBlock) C.vp[e] = 0.0f;
     __syncthreads();
 }
 
@@ -345,8 +332,8 @@ __device__ __forceinline__ GeneralStaged stage_load(const SolveCtx &C, const Sol
     const SolveDims &D = C.D;
     const int tid = C.tid, N = C.N, n_dp = D.n_dense_pairs, n_adj = D.use_dense ? 2 * D.n_dense_pairs : 0, n_ao = D.use_dense ? N + 1 : 0;
     GeneralStaged S;
-    S.T = tid < 16 * N ? C.io.T_in[tid] : 0.0f;
-    S.x = tid < 6 * N ? C.io.x_in[tid] : 0.0f;
+    S.T = tid < 16 * N ? C.io.T[tid] : 0.0f;
+    S.x = tid < 6 * N ? C.io.x[tid] : 0.0f;
     S.dp = tid < n_dp ? G.dense_pairs[tid] : make_int2(0, 0);
     S.ao = tid < n_ao ? G.adj_off[tid] : 0;
     S.adj = tid < n_adj ? G.adj[tid] : 0;
@@ -357,7 +344,6 @@ __device__ __forceinline__ GeneralStaged stage_load(const SolveCtx &C, const Sol
     return S;
 }
 // the staged values: first trip from the registers loaded above, the rest (windows beyond 64 frames / 1 024 pairs) by loops
-template <int NTHR>
 __device__ __forceinline__ void stage_store(const SolveCtx &C, const SolveTables &G, const GeneralStaged &S)
 {
     const SolveDims &D = C.D;
@@ -365,19 +351,19 @@ __device__ __forceinline__ void stage_store(const SolveCtx &C, const SolveTables
     const int *cross_tab = G.cross_tab(D);
     if (tid < 16 * N) C.vT[tid] = S.T;
     if (tid < 6 * N) C.x_l[tid] = S.x;
-    for (int e = tid + NTHR; e < 6 * N; e += NTHR) C.x_l[e] = C.io.x_in[e];
+    for (int e = tid + kSolveBlock; e < 6 * N; e += kSolveBlock) C.x_l[e] = C.io.x[e];
     if (tid < D.n_pairs) C.pair_ij_l[tid] = S.pij;
     if (tid < 288) C.entry_lut[tid] = S.lut;
-    for (int e = tid + NTHR; e < 288; e += NTHR) C.entry_lut[e] = G.solve_tab[D.n_pairs + e];
+    for (int e = tid + kSolveBlock; e < 288; e += kSolveBlock) C.entry_lut[e] = G.solve_tab[D.n_pairs + e];
     if (tid < D.n_pairs) C.cross_l[tid] = S.cross;
-    for (int e = tid + NTHR; e < D.n_pairs; e += NTHR) { C.pair_ij_l[e] = G.solve_tab[e]; C.cross_l[e] = D.use_dense ? cross_tab[e] : -1; }
+    for (int e = tid + kSolveBlock; e < D.n_pairs; e += kSolveBlock) { C.pair_ij_l[e] = G.solve_tab[e]; C.cross_l[e] = D.use_dense ? cross_tab[e] : -1; }
     if (tid < n_dp) { C.dense_pairs_l[2 * tid] = S.dp.x; C.dense_pairs_l[2 * tid + 1] = S.dp.y; }
     if (tid < n_ao) C.adj_off_l[tid] = S.ao;
-    for (int e = tid + NTHR; e < n_ao; e += NTHR) C.adj_off_l[e] = G.adj_off[e];
+    for (int e = tid + kSolveBlock; e < n_ao; e += kSolveBlock) C.adj_off_l[e] = G.adj_off[e];
     if (tid < n_adj) C.adj_l[tid] = S.adj;
-    for (int e = tid + NTHR; e < 16 * N; e += NTHR) C.vT[e] = C.io.T_in[e];
-    for (int e = tid + NTHR; e < n_dp; e += NTHR) { const int2 ij = G.dense_pairs[e]; C.dense_pairs_l[2 * e] = ij.x; C.dense_pairs_l[2 * e + 1] = ij.y; }
-    for (int e = tid + NTHR; e < n_adj; e += NTHR) C.adj_l[e] = G.adj[e];
+    for (int e = tid + kSolveBlock; e < 16 * N; e += kSolveBlock) C.vT[e] = C.io.T[e];
+    for (int e = tid + kSolveBlock; e < n_dp; e += kSolveBlock) { const int2 ij = G.dense_pairs[e]; C.dense_pairs_l[2 * e] = ij.x; C.dense_pairs_l[2 * e + 1] = ij.y; }
+    for (int e = tid + kSolveBlock; e < n_adj; e += kSolveBlock) C.adj_l[e] = G.adj[e];
 }
 
 // ---- phase A: fixed-order reduction of the sweep partials.
@@ -385,19 +371,19 @@ __device__ __forceinline__ void stage_store(const SolveCtx &C, const SolveTables
 // partials were written by other XCDs' workgroups, every load comes from the fabric side of this XCD's L2 at ~1-2 k
 // cycles, so the phase costs (number of dependent load rounds) x (that latency) -- 6 rounds at B = 1 (10 tiles,
 // 5 chunks) instead of the 14 of a 2-item x 4-partial scheme.  Sums in partial order (fixed), whatever the grouping.
-template <int VALS, int ITEMS, bool CHAIN, int NTHR>
+template <int VALS, int ITEMS>
 __device__ __forceinline__ void reduce_partials_scalar(const SolveCtx &C, float *src, float *dst, int n_items_pairs, int parts)
 {
     const SolveDims &D = C.D;
     const int tid = C.tid;
     const int total = n_items_pairs * VALS;
-    for (int e0 = tid; e0 < total; e0 += ITEMS * NTHR) {
+    for (int e0 = tid; e0 < total; e0 += ITEMS * kSolveBlock) {
         float *q[ITEMS];
         float sum[ITEMS];
         bool own[ITEMS];                                              // dead slots re-read the lane's first item (and must not clear it twice)
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
-            const int e = e0 + i * NTHR;
+            const int e = e0 + i * kSolveBlock;
             const int ec = e < total ? e : e0;
             own[i] = e < total;
             q[i] = src + (size_t)(ec / VALS) * parts * VALS + (ec % VALS);
@@ -423,18 +409,15 @@ __device__ __forceinline__ void reduce_partials_scalar(const SolveCtx &C, float 
             }
             c += width;
         };
-        if (!CHAIN) {                               // (the chained launch runs with <= 2 chunks / tiles: kChainMaxParts, checked by the host)
-            while (c + 8 <= parts) round(std::integral_constant<int, 8>{});
-            if (c + 4 <= parts) round(std::integral_constant<int, 4>{});
-        }
+        while (c + 8 <= parts) round(std::integral_constant<int, 8>{});
+        if (c + 4 <= parts) round(std::integral_constant<int, 4>{});
         if (c + 2 <= parts) round(std::integral_constant<int, 2>{});
         if (c < parts) round(std::integral_constant<int, 1>{});
 #pragma unroll
-        for (int i = 0; i < ITEMS; i++) { const int e = e0 + i * NTHR; if (e < total) dst[e] = sum[i]; }
+        for (int i = 0; i < ITEMS; i++) { const int e = e0 + i * kSolveBlock; if (e < total) dst[e] = sum[i]; }
     }
 }
 
-template <bool CHAIN, int NTHR>
 __device__ __forceinline__ void reduce_partials_general(const SolveCtx &C)
 {
     const SolveDims &D = C.D;
@@ -442,20 +425,19 @@ __device__ __forceinline__ void reduce_partials_general(const SolveCtx &C)
     float *ps = C.ps, *pd = C.pd;
     // items per lane per trip: one trip covers the c3 window (105 pairs: 4 620 sparse / 2 940 dense sums over 1 024 lanes).  (Reducing both kinds at
     // the same time on disjoint groups of waves -- one round of fabric-latency loads instead of two -- measured 0.5 us SLOWER per launch, r03 call 39.)
-    // (k_chain: 256 lanes under the sweep's 80-register budget and at most two partials per sum -- more items per lane, narrower rounds)
     // Batches big enough to fill the chip run with one or two partials per sum (pick_chunks, pick_tiles): 16-byte loads then, and ALL of a lane's loads --
-    // sparse and dense records -- issued before the first add: ONE round of fabric latency instead of the two (plain kernel: sparse, then dense) or four
-    // (256-lane chained solve) of the scalar scheme.  The same sums: 0 + first (+ second).  Chained solve 6.4 -> 4.5 us; plain kernel: see DESIGN.md 4.3.
-    if (!D.use_sparse) for (int e = tid; e < D.n_pairs * kSparseVals; e += NTHR) ps[e] = 0.0f;       // (read with weight 0)
-    if (CHAIN || (D.sparse_chunks <= 2 && D.dense_tiles <= 2 && !D.atomic_sums)) {
-        constexpr int kS4 = kSparseVals / 4, kD4 = kDenseVals / 4, kRounds = CHAIN ? 6 : 2;          // sums of four a lane holds per pass: 15 frames = 1 155 + 735 of them, 7.4 per lane of 256, 1.85 per lane of 1 024
+    // sparse and dense records -- issued before the first add: ONE round of fabric latency instead of the two (sparse, then dense) of the scalar
+    // scheme.  The same sums: 0 + first (+ second).  See DESIGN.md 4.3.
+    if (!D.use_sparse) for (int e = tid; e < D.n_pairs * kSparseVals; e += kSolveBlock) ps[e] = 0.0f;       // (read with weight 0)
+    if (D.sparse_chunks <= 2 && D.dense_tiles <= 2 && !D.atomic_sums) {
+        constexpr int kS4 = kSparseVals / 4, kD4 = kDenseVals / 4;          // 15 frames = 1 155 + 735 sums of four, 1.85 per lane: a lane holds two per pass
         const int ns4 = D.use_sparse ? D.n_pairs * kS4 : 0, nd4 = D.use_dense ? D.n_dense_pairs * kD4 : 0;
-        for (int e0 = tid; e0 < ns4 + nd4; e0 += kRounds * NTHR) {
-            float4 v0[kRounds], v1[kRounds];
-            bool two[kRounds];
+        for (int e0 = tid; e0 < ns4 + nd4; e0 += 2 * kSolveBlock) {
+            float4 v0[2], v1[2];
+            bool two[2];
 #pragma unroll
-            for (int u = 0; u < kRounds; u++) {
-                const int e = min(e0 + u * NTHR, ns4 + nd4 - 1);
+            for (int u = 0; u < 2; u++) {
+                const int e = min(e0 + u * kSolveBlock, ns4 + nd4 - 1);
                 const bool sp = e < ns4;
                 const int q = sp ? e : e - ns4, per = sp ? kS4 : kD4, parts = sp ? D.sparse_chunks : D.dense_tiles;
                 const int rec = q / per, k = q - rec * per;
@@ -465,29 +447,25 @@ __device__ __forceinline__ void reduce_partials_general(const SolveCtx &C)
                 v1[u] = src[two[u] ? per : 0];
             }
 #pragma unroll
-            for (int u = 0; u < kRounds; u++) {
-                const int e = e0 + u * NTHR;
+            for (int u = 0; u < 2; u++) {
+                const int e = e0 + u * kSolveBlock;
                 if (e >= ns4 + nd4) continue;
                 float4 sum = make_float4(0.0f + v0[u].x, 0.0f + v0[u].y, 0.0f + v0[u].z, 0.0f + v0[u].w);
                 if (two[u]) { sum.x += v1[u].x; sum.y += v1[u].y; sum.z += v1[u].z; sum.w += v1[u].w; }
-                // (four scalar stores: the plain kernel's LDS copy of the pair sums is not 16-byte aligned; two branches, not a selected pointer: ps and pd
-                // may live in different address spaces, and a select between them sends this compiler's backend into an illegal instruction.  Chained, ps is
-                // region R and is LDS BY TYPE: the optimiser otherwise merges the two branches' stores into one through a selected pointer all the same --
-                // flat stores, and three spilled registers under the sweep's 80-register budget)
+                // (four scalar stores: the LDS copy of the pair sums is not 16-byte aligned; two branches, not a selected pointer: ps and pd
+                // may live in different address spaces, and a select between them sends this compiler's backend into an illegal instruction)
                 auto put = [&](auto *dst) { dst[0] = sum.x; dst[1] = sum.y; dst[2] = sum.z; dst[3] = sum.w; };
                 if (e >= ns4) put(pd + 4 * (size_t)(e - ns4));
-                else if (CHAIN) put(as_lds(ps) + 4 * e);
                 else put(ps + 4 * (size_t)e);
             }
         }
     } else {
-        if (D.use_sparse) reduce_partials_scalar<kSparseVals, 5, CHAIN, NTHR>(C, C.io.sparse_partials, ps, D.n_pairs, D.sparse_chunks);
-        if (D.use_dense) reduce_partials_scalar<kDenseVals, 3, CHAIN, NTHR>(C, C.io.dense_partials, pd, D.n_dense_pairs, D.dense_tiles);
+        if (D.use_sparse) reduce_partials_scalar<kSparseVals, 5>(C, C.io.sparse_partials, ps, D.n_pairs, D.sparse_chunks);
+        if (D.use_dense) reduce_partials_scalar<kDenseVals, 3>(C, C.io.dense_partials, pd, D.n_dense_pairs, D.dense_tiles);
     }
 }
 
 // ---- phase B: the system from the reduced pair sums, by the workgroup (tables and sparse sums in LDS)
-template <bool CHAIN, int NTHR>
 __device__ __forceinline__ void assemble(const SolveCtx &C)
 {
     const SolveDims &D = C.D;
@@ -498,35 +476,7 @@ __device__ __forceinline__ void assemble(const SolveCtx &C)
     // dense pair listed as (target i, source j) for this canonical pair, if any (cross_l; a pair listed the other way round is erased
     // by the reference's FlipJtJ, duplicates of a pair in an explicit list are not supported -- documented): ONE pass, no
     // read-modify-write, no barrier before the diagonal blocks.
-    // CHAIN: the dense pair sums come from the global scratch -- an L2 round trip each, and a store to A between two of them keeps the compiler
-    // from issuing the next before the previous has returned (61 us for this phase, profiles/r04/chain_experiments.json).  So the loads of a
-    // batch of entries are issued first and consumed afterwards: the same values enter the same sums in the same order.
-    if (CHAIN) {
-        constexpr int kB = 4;                             // entries per lane and batch
-        const int total = D.n_pairs * 36;
-        for (int e0 = tid; e0 < total; e0 += kB * NTHR) {
-            int pp[kB], rcv[kB], ij[kB];
-            float dv[kB];
-            bool has[kB];
-#pragma unroll
-            for (int u = 0; u < kB; u++) {
-                const int e = e0 + u * NTHR, ec = min(e, total - 1);
-                pp[u] = ec / 36; rcv[u] = ec - 36 * pp[u];
-                const int pij = C.pair_ij_l[pp[u]];
-                ij[u] = (e < total && (pij >> 8) != 0) ? pij : 0;             // 0: nothing to do (beyond the end, or frame 0's rows / columns)
-                const int dp = ij[u] ? C.cross_l[pp[u]] : -1;
-                has[u] = dp >= 0;
-                dv[u] = has[u] ? pd[(size_t)dp * kDenseVals + tri21(rcv[u] / 6, rcv[u] % 6)] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < kB; u++) {
-                if (!ij[u]) continue;
-                const int rc = rcv[u], r = rc / 6, c = rc - 6 * r, i = ij[u] >> 8, j = ij[u] & 255;
-                A[(6 * j + c) * ld + 6 * i + r] = off_diag_entry(D, C.entry_lut, ps, pp[u], rc, has[u], dv[u]);       // (the lower-triangle copy is the one the packing reads)
-            }
-        }
-    } else
-    for (int e = tid; e < D.n_pairs * 36; e += NTHR) {
+    for (int e = tid; e < D.n_pairs * 36; e += kSolveBlock) {
         const int p = e / 36, rc = e - 36 * p, r = rc / 6, c = rc - 6 * r;
         const int pij = C.pair_ij_l[p];
         const int i = pij >> 8, j = pij & 255;
@@ -537,19 +487,19 @@ __device__ __forceinline__ void assemble(const SolveCtx &C)
         A[(6 * j + c) * ld + 6 * i + r] = v;
     }
     // Phase B2: diagonal blocks: TWO lanes per (frame k >= 1, entry), each sums half of the frame's pairs in fixed order
-    for (int t = tid; t < 2 * (N - 1) * 36; t += NTHR) {
+    for (int t = tid; t < 2 * (N - 1) * 36; t += kSolveBlock) {
         const int e = t >> 1, half = t & 1;
         const int k = 1 + e / 36, rc = e % 36;
-        float v = diag_entry_slice<2, CHAIN ? 8 : 1>(D, N, k, rc, half, C.entry_lut, ps, pd, C.adj_off_l, C.adj_l);
+        float v = diag_entry_slice<2>(D, N, k, rc, half, C.entry_lut, ps, pd, C.adj_off_l, C.adj_l);
         v += __shfl_xor(v, 1, 64);                       // partner lane = same entry, other half (t and t^1 share a wave)
         if (!half) A[(6 * k + rc / 6) * ld + 6 * k + rc % 6] = v;
     }
     // right-hand side and Jacobi diagonal: FOUR lanes per unknown, each sums a quarter of the frame's pairs
-    for (int t = tid; t < 4 * n; t += NTHR) {
+    for (int t = tid; t < 4 * n; t += kSolveBlock) {
         const int e = t >> 2, part = t & 3;
         const int k = e / 6, r = e % 6;
         float rhs = 0.0f, md = 0.0f;
-        if (k > 0) rhs_jacobi_slice<4, CHAIN ? 8 : 1>(D, N, k, r, part, ps, pd, C.adj_off_l, C.adj_l, rhs, md);
+        if (k > 0) rhs_jacobi_slice<4>(D, N, k, r, part, ps, pd, C.adj_off_l, C.adj_l, rhs, md);
         rhs += __shfl_xor(rhs, 1, 64); md += __shfl_xor(md, 1, 64);        // the four lanes of an unknown sit in one wave
         rhs += __shfl_xor(rhs, 2, 64); md += __shfl_xor(md, 2, 64);
         if (part == 0) {
@@ -558,49 +508,23 @@ __device__ __forceinline__ void assemble(const SolveCtx &C)
             C.vd[e] = 0.0f;
         }
     }
-    for (int e = n + tid; e < ld; e += NTHR) C.vp[e] = 0.0f;      // pad of p: read by the 16-byte mat-vec chunks
-    __syncthreads();
-}
-
-// ---- chained: the matrix into region R (the sparse pair sums are spent): entry (a, c), c <= a, of its non-zero (n - 6) x (n - 6) part at a (a + 1) / 2 + c.
-// A is symmetric bit for bit (off-diagonal blocks are one value for both positions; a diagonal block's entries (r, c) and (c, r) are the
-// same sums of the same values), so the packed lower triangle holds every value a row of the mat-vec reads.
-template <int NTHR>
-__device__ __forceinline__ void pack_triangle(const SolveCtx &C)
-{
-    const int tid = C.tid, ld = C.ld;
-    const int na = C.n - 6, n_tri = na * (na + 1) / 2;
-    for (int e0 = tid; e0 < n_tri; e0 += 8 * NTHR) {       // eight loads per lane in flight (the copy used to run one L2 round trip per element: 17 us)
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int e = min(e0 + u * NTHR, n_tri - 1);
-            int a = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);       // row of packed index e, fixed up for the rounding of the root
-            a -= (a * (a + 1) / 2 > e) ? 1 : 0;
-            a += ((a + 1) * (a + 2) / 2 <= e) ? 1 : 0;
-            const int c = e - a * (a + 1) / 2;
-            v[u] = C.A[(size_t)(6 + a) * ld + 6 + c];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) if (e0 + u * NTHR < n_tri) C.region_R[e0 + u * NTHR] = v[u];
-    }
+    for (int e = n + tid; e < ld; e += kSolveBlock) C.vp[e] = 0.0f;      // pad of p: read by the 16-byte mat-vec chunks
     __syncthreads();
 }
 
 // ---- trace: right-hand side and preconditioner in trace order -- (rot, trans); internal [trans, rot] -- and the matrix
-template <int NTHR>
 __device__ __forceinline__ void trace_general_system(const SolveCtx &C)
 {
     const SolveDims &D = C.D;
     const int n = C.n;
     float *tr = C.tr;
-    for (int e = C.tid; e < n; e += NTHR) {
+    for (int e = C.tid; e < n; e += kSolveBlock) {
         const int k = e / 6, r = e % 6;           // trace order (rot, trans); internal [trans, rot]
         const int o = k * 6 + (r < 3 ? r + 3 : r - 3);
         tr[D.tr_rhs + o] = C.vb[e];
         tr[D.tr_prec + o] = C.vM[e];
     }
-    for (int e = C.tid; e < n * n; e += NTHR) tr[D.tr_A + e] = C.A[(e / n) * C.ld + (e % n)];
+    for (int e = C.tid; e < n * n; e += kSolveBlock) tr[D.tr_A + e] = C.A[(e / n) * C.ld + (e % n)];
 }
 
 // ---- phase C: Jacobi-preconditioned CG, SolverBundling.cu:575-818 (frame 0 entries stay 0).
@@ -619,7 +543,7 @@ __device__ __forceinline__ void pcg_block(const SolveCtx &C)
     float r_ = live ? C.vb[row] : 0.0f, m_ = live ? C.vM[row] : 0.0f, d_ = 0.0f;
     float p_ = m_ * r_;
     if (live) vp[row] = p_;
-    float rz = block_sum(r_ * p_, C.scratch);          // (contains the barrier that publishes vp)
+    float rz = block_sum(r_ * p_, C.scratch);          // (contains the barrier that makes vp visible)
     for (int li = 0; li < D.n_pcg; li++) {
         float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
         if (live) {
@@ -646,44 +570,6 @@ __device__ __forceinline__ void pcg_block(const SolveCtx &C)
         __syncthreads();
     }
     if (live) C.vd[row] = d_;
-}
-
-// The matrix-vector product of a chained PCG step, by all four waves of the solve item (the matrix is the packed triangle in region R);
-// leaves A p in vAp.  All threads must call.
-// Row r of A p in the one-wave code (wave_matvec): four partial sums over the x, y, z, w lanes of its 16-byte chunks, fused multiply-adds
-// in chunk order, then (x + y) + (z + w).  Here lane pair (2 q, 2 q + 1) owns row 6 + q (frame 0's rows are zero: their product is
-// an exact +0), lane h of the pair runs the two sums of its half of every chunk, and one exchange adds the halves: the same
-// operations on the same operands in the same order.
-// The matrix is the packed triangle in region R: A[row][k] = L[a (a + 1) / 2 + c] for c <= a, L[c (c + 1) / 2 + a] above the diagonal
-// (a = row - 6, c = k - 6).  Columns 0 .. 5 (frame 0) and the pad columns hold exact zeros and zeros of p: skipped, their
-// fused multiply-adds leave the sums as they are.
-template <int NTHR>
-__device__ __forceinline__ void chain_matvec(const SolveCtx &C)
-{
-    const int tid = C.tid, n = C.n;
-    const float *vp = C.vp;
-    __syncthreads();                              // this step's p is in LDS
-    const int h = tid & 1, na = n - 6;
-    const float *L = C.region_R;
-    for (int pr = tid >> 1; pr < na; pr += NTHR >> 1) {
-        const int row = 6 + pr, a = pr, row_base = a * (a + 1) / 2;
-        float sa = 0.0f, sb = 0.0f;
-        // chunk cc covers columns 4 cc .. 4 cc + 3; this lane its columns k0 = 4 cc + 2 h and k0 + 1
-        int c0 = 4 + 2 * h - 6;                                 // active column of k0 in chunk 1 (chunk 0 lies inside frame 0's zero columns)
-        int tri0 = c0 * (c0 + 1) / 2, tri1 = (c0 + 1) * (c0 + 2) / 2;      // c (c + 1) / 2 of the two columns, advanced by 4 c + 10 per chunk
-        for (int k0 = 4 + 2 * h; k0 < n; k0 += 4) {
-            const float2 q = *reinterpret_cast<const float2 *>(vp + k0);
-            if (c0 >= 0) sa = __builtin_fmaf(L[c0 <= a ? row_base + c0 : tri0 + a], q.x, sa);
-            if (c0 + 1 >= 0 && c0 + 1 < na) sb = __builtin_fmaf(L[c0 + 1 <= a ? row_base + c0 + 1 : tri1 + a], q.y, sb);
-            tri0 += 4 * c0 + 10; tri1 += 4 * c0 + 14;
-            c0 += 4;
-        }
-        const float th = sa + sb;
-        const float ap = th + __shfl_xor(th, 1, 64);
-        if (h == 0) C.vAp[row] = ap;
-    }
-    if (tid < 6) C.vAp[tid] = 0.0f;
-    __syncthreads();
 }
 
 // The matrix-vector product of a one-wave PCG step on the LDS-resident matrix: rows lane + 64 j of A p into ap_[j].
@@ -732,21 +618,20 @@ _Pragma("unroll 4")
 // ROWS per lane: 2 up to 128 unknowns (windows of <= 21 frames: every tracker-size window), 4 up to 186 (N <= BTBA_MAX_FRAMES_LDS = 31).
 // One wave alone on its SIMD pays ~8 cycles per instruction, so the two dead rows of a 4-row loop cost real time (the sums only
 // ever add their exact zeros: same bits either way).
-// CHAIN: wave 0 runs this code as it stands, except that the matrix-vector product of a step is computed by all four waves (the
-// matrix is in the global scratch: two rounds of L2-latency loads spread over 256 lanes instead of 23 chunks x 2 rows on one wave);
-// all threads of the solve item call.  Otherwise wave 0 alone calls.
-template <int ROWS, bool CHAIN, int NTHR>
+// Wave 0 alone calls.  The `w0` tests below restate that: the compiler does not carry the caller's `tid < 64` into the loop, and lays the
+// scalar control flow out with a few instructions more without them.
+template <int ROWS>
 __device__ __forceinline__ void pcg_wave(const SolveCtx &C)
 {
     const SolveDims &D = C.D;
     const int tid = C.tid, n = C.n;
     // the caller's choice of ROWS: rows 0 and 1 of a lane of the 4-row version are always live.  NOT a mere hint: without it the compiler contracts one
-    // multiply-add of the 4-row version differently, and windows of 24 and 31 frames lose bit equality with the sums k_chain is pinned to
+    // multiply-add of the 4-row version differently, and traced windows of 24 and 31 frames lose bit equality with the traces of earlier builds
     __builtin_assume(n > 64 * (ROWS - 2));
     float *vp = C.vp, *tr = C.tr;
     const int lane = tid & 63;
-    const bool w0 = tid < 64;
     float r_[ROWS], m_[ROWS], p_[ROWS], d_[ROWS];
+    const bool w0 = tid < 64;
     float part = 0.0f, rz = 0.0f;
     if (w0) {
 #pragma unroll
@@ -764,13 +649,7 @@ __device__ __forceinline__ void pcg_wave(const SolveCtx &C)
         float ap_[ROWS];
 #pragma unroll
         for (int j = 0; j < ROWS; j++) ap_[j] = 0.0f;
-        if (CHAIN) {
-            chain_matvec<NTHR>(C);
-            if (w0) {
-#pragma unroll
-                for (int j = 0; j < ROWS; j++) ap_[j] = C.vAp[min(lane + 64 * j, n - 1)];
-            }
-        } else wave_matvec<ROWS>(C, lane, ap_);
+        wave_matvec<ROWS>(C, lane, ap_);
         if (!w0) continue;
         part = 0.0f;
 #pragma unroll
@@ -804,15 +683,14 @@ __device__ __forceinline__ void pcg_wave(const SolveCtx &C)
 }
 
 // ---- phase D: x_k <- Log(Exp(delta_k) Exp(x_k)); next iterate's T, T^-1  (SolverBundling.cu:805-815, 890-897)
-template <bool CHAIN, int NTHR>
 __device__ __forceinline__ void update_general(const SolveCtx &C)
 {
     const SolveDims &D = C.D;
     const SolveIO &io = C.io;
     const float *vd = C.vd;
     float *tr = C.tr;
-    for (int k = C.tid; k < C.N; k += NTHR) {
-        float *xk = (CHAIN ? io.x_out : const_cast<float *>(io.x_in)) + 6 * k;       // (in place unless chained: one base pointer less to keep)
+    for (int k = C.tid; k < C.N; k += kSolveBlock) {
+        float *xk = io.x + 6 * k;
         const float *xl = C.x_l + 6 * k;
         float rot[3] = { xl[0], xl[1], xl[2] }, trans[3] = { xl[3], xl[4], xl[5] };
         if (k > 0) {
@@ -821,11 +699,11 @@ __device__ __forceinline__ void update_general(const SolveCtx &C)
             const Mat4 Ck = load_mat4(C.vT + 16 * k);      // = Exp(x_k): this iterate's T, computed from the same x_k by the previous launch
             matrix_to_pose(mat_mul(U, Ck), rot, trans);
         }
-        if (k > 0 || CHAIN) { xk[0] = rot[0]; xk[1] = rot[1]; xk[2] = rot[2]; xk[3] = trans[0]; xk[4] = trans[1]; xk[5] = trans[2]; }      // (in place: frame 0 keeps its x)
+        if (k > 0) { xk[0] = rot[0]; xk[1] = rot[1]; xk[2] = rot[2]; xk[3] = trans[0]; xk[4] = trans[1]; xk[5] = trans[2]; }      // (frame 0 keeps its x)
         const Mat4 E = pose_to_matrix(rot, trans);
-        store_mat4((CHAIN ? io.T_out : const_cast<float *>(io.T_in)) + 16 * k, E);
+        store_mat4(io.T + 16 * k, E);
         if (io.poses_out) store_mat4(io.poses_out + 16 * k, E);      // last iterate: convertPosesToMatricesCU (SBA.cpp:115), no separate copy
-        store_mat4(io.Tinv_out + 16 * k, mat_inverse(E));
+        store_mat4(io.Tinv + 16 * k, mat_inverse(E));
         if (tr) {
             for (int q = 0; q < 3; q++) { tr[D.tr_x + 6 * k + q] = rot[q]; tr[D.tr_x + 6 * k + 3 + q] = trans[q]; }
             for (int q = 0; q < 16; q++) tr[D.tr_T + 16 * k + q] = E.m[q];
@@ -834,61 +712,50 @@ __device__ __forceinline__ void update_general(const SolveCtx &C)
     }
 }
 
-// The system solve of ONE instance by the calling workgroup (all of its threads must call; dynamic LDS: SolveLayout, plus (optionally)
-// the reduced pair sums behind it).
-//   CHAIN = false: k_system_solve's body, a workgroup of 1 024 threads, one-wave PCG on the LDS-resident matrix (or the 16-wave PCG of A_GLOBAL:
-//                  windows of more than BTBA_MAX_FRAMES_LDS frames, whose matrix does not fit the CU's LDS and lives in an L2-resident global scratch).
-//   CHAIN = true : the same sums in the same order run by a 256-thread workgroup of k_chain that shares its compute unit with five sweep
-//                  workgroups and may only use a sweep workgroup's share of the LDS: the matrix lives in an L2-resident global scratch, the
-//                  mat-vec of the PCG is spread over all four waves (two lanes per row, each the two partial sums of the one-wave version
-//                  that belong to its half of the 16-byte chunks), everything else of a PCG step is the one-wave code, bit for bit.
-// NTHR: the workgroup size, a compile-time constant: loop strides and bounds against it fold.
-template <bool LDS_PAIRS, bool A_GLOBAL, bool CHAIN, int NTHR>
+// The system solve of ONE instance by the calling workgroup of kSolveBlock threads (all of them must call; dynamic LDS: SolveLayout, plus
+// (optionally) the reduced pair sums behind it): one-wave PCG on the LDS-resident matrix, or the 16-wave PCG of A_GLOBAL -- windows of more than
+// BTBA_MAX_FRAMES_LDS frames, whose matrix does not fit the CU's LDS and lives in an L2-resident global scratch.
+template <bool LDS_PAIRS, bool A_GLOBAL>
 __device__ __forceinline__ void system_solve_body(const SolveDims &D, int iter, const int tid, float *lds, const SolveIO &io,
                                                   const int2 *__restrict__ dense_pairs, const int *__restrict__ adj_off, const int *__restrict__ adj,
                                                   const int *__restrict__ solve_tab)
 {
-    constexpr bool A_IN_GLOBAL = A_GLOBAL || CHAIN;
     const int N = D.n_frames, n = 6 * N;
-    const SolveLayout L(N, D.n_dense_pairs, A_IN_GLOBAL, CHAIN);
+    const SolveLayout L(N, D.n_dense_pairs, A_GLOBAL);
     float *tr = (D.trace_on && io.trace) ? io.trace + (size_t)iter * D.trace_record : nullptr;
-    float *ps = CHAIN ? lds + L.region_R : LDS_PAIRS ? lds + L.total : io.pairsum_global;
-    const SolveCtx C(D, io, tid, tr, lds, L, A_IN_GLOBAL, ps, CHAIN ? io.pairsum_global : ps + (size_t)D.n_pairs * kSparseVals);
+    float *ps = LDS_PAIRS ? lds + L.total : io.pairsum_global;
+    const SolveCtx C(D, io, tid, tr, lds, L, A_GLOBAL, ps, ps + (size_t)D.n_pairs * kSparseVals);
 
-    if (D.pre_assembled) load_pre_assembled<A_IN_GLOBAL, NTHR>(C);
+    if (D.pre_assembled) load_pre_assembled<A_GLOBAL>(C);
     else {
         const SolveTables G = { dense_pairs, adj_off, adj, solve_tab };
         const GeneralStaged staged = stage_load(C, G);
-        solve_stamp<CHAIN>(C, 6);
-        reduce_partials_general<CHAIN, NTHR>(C);
-        solve_stamp<CHAIN>(C, 7);
-        stage_store<NTHR>(C, G, staged);
+        trace_stamp(C, 6);
+        reduce_partials_general(C);
+        trace_stamp(C, 7);
+        stage_store(C, G, staged);
         // zero what the assembly does not write; every other entry is assigned by phase B (all canonical pairs with i >= 1, all diagonal blocks k >= 1)
-        // (the chained solve packs the non-zero part of the matrix and never reads the rest)
-        if (!CHAIN) {
-            for (int e = tid; e < 6 * L.ld; e += NTHR) C.A[e] = 0.0f;
-            for (int e = tid; e < (n - 6) * (6 + L.ld - n); e += NTHR) C.A[zero_fill_rest_index(e, n, L.ld)] = 0.0f;
-        }
+        for (int e = tid; e < 6 * L.ld; e += kSolveBlock) C.A[e] = 0.0f;
+        for (int e = tid; e < (n - 6) * (6 + L.ld - n); e += kSolveBlock) C.A[zero_fill_rest_index(e, n, L.ld)] = 0.0f;
         __syncthreads();
-        solve_stamp<CHAIN>(C, 0);
+        trace_stamp(C, 0);
         // (the camera-frame -> model-frame congruence of the dense pair sums is done by the sweep workgroups: dense_epilogue)
-        if (tr && D.use_dense) for (int e = tid; e < D.n_dense_pairs * kDenseVals; e += NTHR) tr[D.tr_dpair + e] = C.pd[e];
-        solve_stamp<CHAIN>(C, 1);
-        assemble<CHAIN, NTHR>(C);
+        if (tr && D.use_dense) for (int e = tid; e < D.n_dense_pairs * kDenseVals; e += kSolveBlock) tr[D.tr_dpair + e] = C.pd[e];
+        trace_stamp(C, 1);
+        assemble(C);
     }
-    solve_stamp<CHAIN>(C, 2);
-    if (CHAIN) pack_triangle<NTHR>(C);
-    if (tr) trace_general_system<NTHR>(C);
-    solve_stamp<CHAIN>(C, 5);
+    trace_stamp(C, 2);
+    if (tr) trace_general_system(C);
+    trace_stamp(C, 5);
     if (A_GLOBAL) pcg_block(C);
-    else if (CHAIN || tid < 64) { if (n <= 128) pcg_wave<2, CHAIN, NTHR>(C); else pcg_wave<4, CHAIN, NTHR>(C); }
+    else if (tid < 64) { if (n <= 128) pcg_wave<2>(C); else pcg_wave<4>(C); }
     __syncthreads();
-    solve_stamp<CHAIN>(C, 3);
-    update_general<CHAIN, NTHR>(C);
-    solve_stamp<CHAIN>(C, 4);
+    trace_stamp(C, 3);
+    update_general(C);
+    trace_stamp(C, 4);
 }
 
-// grid (B) x 1 024: one workgroup per instance, x / T / T^-1 updated in place.
+// grid (B) x kSolveBlock: one workgroup per instance, x / T / T^-1 updated in place.
 template <bool LDS_PAIRS, bool A_GLOBAL = false>
 __global__ void __launch_bounds__(kSolveBlock) k_system_solve(SolveDims D, int iter,
                                                         float *sparse_partials, float *dense_partials,
@@ -902,14 +769,13 @@ __global__ void __launch_bounds__(kSolveBlock) k_system_solve(SolveDims D, int i
     const int N = D.n_frames, n = 6 * N, ld = solve_row_floats(N);
     SolveIO io;
     io.sparse_partials = sparse_partials + b * D.sp_stride; io.dense_partials = dense_partials + b * D.dp_stride;
-    io.x_in = io.x_out = x + b * D.x_stride;
-    io.T_in = io.T_out = T + b * D.pose_stride; io.Tinv_out = Tinv + b * D.pose_stride;
+    io.x = x + b * D.x_stride;
+    io.T = T + b * D.pose_stride; io.Tinv = Tinv + b * D.pose_stride;
     io.poses_out = poses_out ? poses_out + 16 * b * N : nullptr;
     io.pairsum_global = pairsum_global ? pairsum_global + b * ((size_t)D.n_pairs * kSparseVals + (size_t)D.n_dense_pairs * kDenseVals) : nullptr;
     io.A_scratch = A_scratch ? A_scratch + b * (size_t)(n + 2) * ld : nullptr;
     io.trace = trace ? trace + b * (size_t)D.n_gn * D.trace_record : nullptr;
-    io.stamps = nullptr;
-    system_solve_body<LDS_PAIRS, A_GLOBAL, false, kSolveBlock>(D, iter, (int)threadIdx.x, lds, io, dense_pairs, adj_off, adj, solve_tab);
+    system_solve_body<LDS_PAIRS, A_GLOBAL>(D, iter, (int)threadIdx.x, lds, io, dense_pairs, adj_off, adj, solve_tab);
 }
 
 }  // namespace btba

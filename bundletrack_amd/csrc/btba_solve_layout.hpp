@@ -13,17 +13,13 @@
 namespace btba {
 
 constexpr int kLayoutSparseVals = 44;      // = kSparseVals (btba_kernels.hpp; asserted in btba_solve_general.hpp)
-constexpr size_t kChainLdsBytes = 26560;   // dynamic LDS of a k_chain workgroup: with the 736 static bytes a sixth of the compute unit's 160 KB -- six workgroups per CU, as k_fused_sweeps
-// floats of region R a chained solve needs behind its tables and vectors (system_solve_body<CHAIN>): the reduced sparse pair sums, then the packed matrix
-BTBA_LAYOUT_HD inline size_t chain_region_floats(int n_frames) { const size_t P = (size_t)n_frames * (n_frames - 1) / 2, na = 6 * (size_t)n_frames - 6; return P * kLayoutSparseVals > na * (na + 1) / 2 ? P * kLayoutSparseVals : na * (na + 1) / 2; }
 
 // row length of A and stride of the vectors: an odd multiple of 4 floats -- 16-byte rows, conflict-free ds_read_b128
 BTBA_LAYOUT_HD constexpr int solve_row_floats(int n_frames) { return 4 * (((6 * n_frames + 3) / 4) | 1); }
 
 // Offsets in floats from the start of the dynamic LDS (the int tables count one float per int).
-//   a_in_global: the matrix lives in a global scratch (windows beyond BTBA_MAX_FRAMES_LDS frames, and every chained solve), not in front of the vectors
-//   chain      : a solve item of k_chain -- region R follows the tables, and the total is what the chained launch asks for
-// The plain kernel's reduced pair sums, when the host stages them in LDS (SolveDims::pairsum_in_lds), start at `total` and are sized by the host.
+//   a_in_global: the matrix lives in a global scratch (windows beyond BTBA_MAX_FRAMES_LDS frames), not in front of the vectors
+// The reduced pair sums, when the host stages them in LDS (SolveDims::pairsum_in_lds), start at `total` and are sized by the host.
 struct SolveLayout {
     int ld;                         // solve_row_floats(N)
     int A;                          // A[n][ld] (nothing when a_in_global; its pad columns n..ld-1 stay 0)
@@ -38,15 +34,10 @@ struct SolveLayout {
     int entry_lut;
     int cross;                      // ints: canonical pair -> the dense pair whose cross block it carries (or -1): P, padded to 16 bytes
     int x;                          // this iterate's x (phase D would otherwise start with a fabric-latency load): 6 N floats, padded to 16 bytes
-    // CHAIN: a workgroup of k_chain owns a sweep workgroup's share of the LDS (a sixth of the compute unit's 160 KB).  What is left of it behind
-    // the tables and vectors -- region R, 16-byte aligned -- holds the reduced SPARSE pair sums while the system is assembled (two of their values
-    // go into every matrix entry per pair; the dense sums, one value per entry and pair, stay in the global scratch and are fetched in batches) and
-    // afterwards the assembled matrix, packed: the lower triangle of its (n - 6) x (n - 6) non-zero part.  The host checks that both fit (total).
-    int region_R;
     size_t rest_floats;             // everything but A
-    size_t total;                   // floats the launch asks for (without the plain kernel's staged pair sums)
+    size_t total;                   // floats the launch asks for (without the staged pair sums)
 
-    BTBA_LAYOUT_HD SolveLayout(int N, int Pd, bool a_in_global, bool chain)
+    BTBA_LAYOUT_HD SolveLayout(int N, int Pd, bool a_in_global)
     {
         const int n = 6 * N, P = N * (N - 1) / 2;
         ld = solve_row_floats(N);
@@ -62,9 +53,8 @@ struct SolveLayout {
         cross = entry_lut + 288;
         x = cross + ((P + 3) & ~3);
         const int end = x + ((n + 3) & ~3);
-        region_R = (end + 3) & ~3;
         rest_floats = (size_t)(end - vb);
-        total = chain ? rest_floats + 4 + chain_region_floats(N) : (size_t)end;      // (+ 4: region R's alignment)
+        total = (size_t)end;
     }
 };
 

@@ -8,10 +8,10 @@
 //   k_ransac_vote reads three floats per lane -- instead of 2 000 curand_init calls per pair, each of which walks jump matrices
 //   for its subsequence on the device (cuRAND's curand_init is the notoriously slow part of such kernels).
 //
-// cuRAND is CUDA-toolkit code (absent here); what follows implements its published XORWOW algorithm:
+// cuRAND is CUDA-toolkit code (absent here); what follows implements its documented XORWOW algorithm:
 //   recurrence  -- Marsaglia, "Xorshift RNGs" (2003), xorwow: t = v0 ^ (v0 >> 2); v0..v3 = v1..v4;
 //                  v4 = (v4 ^ (v4 << 4)) ^ (t ^ (t << 1)); d += 362437; output d + v4;
-//   curand_init -- scramble (seed) into (v, d) as curand_kernel.h does (restated from the published header, UNVERIFIED: see seeded()), then advance by subsequence * 2^67 steps (+ offset steps);
+//   curand_init -- scramble (seed) into (v, d) as curand_kernel.h does (restated from the public header, UNVERIFIED: see seeded()), then advance by subsequence * 2^67 steps (+ offset steps);
 //                  the five xorshift words evolve linearly over GF(2), so n steps are the 160 x 160 bit matrix A^n; the Weyl
 //                  counter d moves by 362437 * n, which is 0 mod 2^32 for n = k 2^67;
 //   uniform     -- x * 2^-32 + 2^-33 in fp32, in (0, 1].
@@ -107,11 +107,11 @@ inline uint32_t next(State &s)                               // curand(&state)
     s.d += 362437u;
     return s.d + s.v[4];
 }
-// Seed scrambling of curand_init, as published in curand_kernel.h (_curand_init_scratch): two salts XORed into the halves of the seed,
+// Seed scrambling of curand_init, as printed in curand_kernel.h (_curand_init_scratch): two salts XORed into the halves of the seed,
 // two odd multipliers, then Marsaglia's five initial words and his d combined with the products as  +, ^, +, ^, +  and  d + t1 + t0.
 // rocRAND's xorwow_engine (/opt/rocm/include/rocrand/rocrand_xorwow.h:113-122) is the same construction with four other constants, which
 // is what lets a third-party implementation pin the operators here (tests/test_oracle_xorwow.py builds rocRAND's engine on the host and
-// compares it with seeded(seed, kRocrandSeeding)).  The four cuRAND constants themselves rest on the published header alone:
+// compares it with seeded(seed, kRocrandSeeding)).  The four cuRAND constants themselves rest on the public header alone:
 // RESTATED, UNVERIFIED until a CUDA machine prints the rows INTEGRATION.md names.
 struct SeedConstants { uint32_t salt_lo, salt_hi, mul_lo, mul_hi; };
 constexpr SeedConstants kCurandSeeding = { 0xaad26b49u, 0xf7dcefddu, 1099087573u, 2591861531u };

@@ -3,7 +3,7 @@
 What a session ends with -- Bundler.keyframes, each with depth_gpu / normal_gpu / color_gpu and a bundle-adjusted pose_in_model --
 becomes one voxel-grid cloud per object; the same kernels are Utils::downsamplePointCloud (src/Utils.cpp:134-140, pcl::VoxelGrid) for
 any cloud.  Every voxel sum is an integer, so the output bytes do not depend on execution order, batch position or segment order.
-The exact rules are in include/btba.h ("keyframe fusion"); the voxel rule is restated from PCL's published header and unverified
+The exact rules are in include/btba.h ("keyframe fusion"); the voxel rule is restated from PCL's public header and unverified
 against a PCL run."""
 from __future__ import annotations
 

@@ -39,9 +39,7 @@ enum {
     BTBA_EHIP     = 2,   /* a HIP runtime call failed; btba_last_hip_error() has the hipError_t */
     BTBA_ENUMERIC = 3,   /* a non-finite value reached the output poses */
     BTBA_ENOMEM   = 4,
-    BTBA_ESCHED   = 5    /* a wait inside the chained launch ran into its watchdog (the device did not start the launch's workgroups in grid
-                            order): the poses of that solve are invalid.  Reported by the next call that synchronises with the host
-                            (btba_workspace_sync, btba_collect_stats); the workspace solves with the plain schedule from then on. */
+    BTBA_ESCHED   = 5    /* reserved: the retired chained launch's scheduling failure; no longer returned */
 };
 
 /* ---- wire formats ---------------------------------------------------------------------- */
@@ -160,8 +158,7 @@ typedef struct btba_stats {
     int32_t fused_sweeps;         /* 1: sparse + dense sweeps ran as ONE launch (timed as ms_dense_sweep) */
     int32_t cache_frames_built;   /* optimize_frames: frames cached in this call (n_frames unless keyed and already cached) */
     int32_t corr_pairs_uploaded;  /* optimize_frames: frame-pair segments that crossed PCIe in this call (all P unless BTBA_FLAG_KEYED_CORR) */
-    int32_t chain_iterations;     /* > 0: the solve ran as ONE chained launch carrying this many Gauss-Newton iterations (sweeps AND system solves);
-                                     it is timed as ms_dense_sweep / n_dense_launches, ms_system_solve stays 0 */
+    int32_t chain_iterations;     /* always 0: the chained launch was retired (kept for the struct's layout) */
 } btba_stats;
 
 /* Per-instance, per-GN-iteration trace record (floats), written when BTBA_FLAG_TRACE is set.
@@ -214,16 +211,9 @@ enum {
     BTBA_OPT_OVERLAP_EQUAL_PRIO   = 7,  /* 1: the groups' streams get equal priority (default 0: lowest for groups >= 1).        env BTBA_GROUP_PRIO=e   */
     BTBA_OPT_SPARSE_TAIL          = 9,  /* 0 .. 256: share (x / 256) of the sparse items that close the fused sweep instead of being interleaved (fills the launch's drain); -1 (default): 256 on full frames, 0 on object-masked ones. env BTBA_SPARSE_TAIL */
     BTBA_OPT_KEYED_CORR_MIN_BYTES = 8,  /* BTBA_FLAG_KEYED_CORR is ignored below this many bytes of correspondences (default 1 MiB). env of the same name */
-    BTBA_OPT_CHAIN                = 10, /* the chained launch: ALL Gauss-Newton iterations of a batch in one launch, every instance's system solve handed
-                                           over inside the launch while the other instances' sweeps run (btba_chain.hpp: k_chain).  0 (default) / -1: the
-                                           plain schedule (two launches per iteration) -- it measured faster once one tile per pair became the better
-                                           choice; 1: every batch the launch supports (pinhole compact cache, sparse + dense terms,
-                                           <= 15 frames, no trace, deterministic sums).  Same bits as the plain schedule with the same tile count AND BTBA_OPT_SOLVE_SMALL = 0 (the in-launch
-                                           solve items reproduce k_system_solve's sums); against the default plain schedule (k_solve_small: the same sums in another
-                                           order) the poses agree to the 1e-4 bar, not bit for bit.                                 env BTBA_CHAIN */
-    BTBA_OPT_CHAIN_SPARSE_PERIOD  = 11, /* chained launch: 0 (default) an instance's sparse items follow its dense items; R >= 2: every R-th item of an
-                                           instance is a sparse one.                                                               env BTBA_CHAIN_PERIOD */
-    BTBA_OPT_CHAIN_TIMEOUT_MS     = 12, /* watchdog of the waits inside the chained launch (default 500 ms): see BTBA_ESCHED.        env BTBA_CHAIN_TIMEOUT_MS */
+    BTBA_OPT_CHAIN                = 10, /* retired (the chained launch): -1 .. 1 is accepted and ignored, no launch supports the solve */
+    BTBA_OPT_CHAIN_SPARSE_PERIOD  = 11, /* retired: 0 or 2 .. 64 is accepted and ignored */
+    BTBA_OPT_CHAIN_TIMEOUT_MS     = 12, /* retired: 1 .. 60000 is accepted and ignored */
     BTBA_OPT_RELAYOUT             = 14, /* 1: a batch whose correspondences arrive as EntryJ (4 MiB or more, three iterations or more, full frames) is re-laid out to
                                            24-byte records BY ITS FIRST ITERATION'S SWEEP, and the other iterations stream those; 0 (default): every iteration reads
                                            EntryJ.  Same bits; measured a wash at c3 x 32 (the first launch's extra writes cost what the others save).  env BTBA_RELAYOUT */

@@ -10,9 +10,9 @@
 using btba::SolveLayout;
 
 static int failures = 0;
-static void fail(const char *what, int N, int Pd, bool a_in_global, bool chain)
+static void fail(const char *what, int N, int Pd, bool a_in_global)
 {
-    std::printf("FAILED %s: N = %d, Pd = %d, a_in_global = %d, chain = %d\n", what, N, Pd, (int)a_in_global, (int)chain);
+    std::printf("FAILED %s: N = %d, Pd = %d, a_in_global = %d\n", what, N, Pd, (int)a_in_global);
     failures++;
 }
 
@@ -25,20 +25,19 @@ int main()
         const int P = N * (N - 1) / 2, n = 6 * N;
         const int pds[4] = { 0, 1, P, 2 * P };
         for (int Pd : pds)
-            for (int variant = 0; variant < 3; variant++) {
-                const bool a_in_global = variant > 0, chain = variant == 2;
-                const SolveLayout L(N, Pd, a_in_global, chain);
+            for (int variant = 0; variant < 2; variant++) {
+                const bool a_in_global = variant > 0;
+                const SolveLayout L(N, Pd, a_in_global);
                 cases++;
                 const size_t ld = 4 * (size_t)(((n + 3) / 4) | 1);
-                if ((size_t)L.ld != ld || L.ld != btba::solve_row_floats(N)) fail("ld", N, Pd, a_in_global, chain);
+                if ((size_t)L.ld != ld || L.ld != btba::solve_row_floats(N)) fail("ld", N, Pd, a_in_global);
                 // the size of everything but the matrix, as the host used to write it out
                 const size_t rest = 6 * ld + 16 + 16 * (size_t)N + 4 * (size_t)Pd + (size_t)N + 1 + (size_t)P + 288 + round4((size_t)P) + round4(6 * (size_t)N);
-                if (L.rest_floats != rest) fail("rest_floats", N, Pd, a_in_global, chain);
+                if (L.rest_floats != rest) fail("rest_floats", N, Pd, a_in_global);
                 const size_t a_floats = a_in_global ? 0 : (size_t)n * ld;
-                if (!chain && L.total != a_floats + rest) fail("total (plain)", N, Pd, a_in_global, chain);
-                if (chain && L.total != rest + 4 + btba::chain_region_floats(N)) fail("total (chained)", N, Pd, a_in_global, chain);
+                if (L.total != a_floats + rest) fail("total", N, Pd, a_in_global);
                 // the regions in address order, with their sizes: each starts exactly where the one before it ends -- no overlap, and no gap that would move the
-                // footprint -- except region R, which may sit up to three floats later for its alignment; the last ends inside the total
+                // footprint; the last ends inside the total
                 struct Region { const char *name; size_t off, size; bool read16; } regions[] = {
                     { "A", (size_t)L.A, a_floats, true },                         // float4 rows (the one-wave mat-vec, the load of a pre-assembled matrix)
                     { "vb", (size_t)L.vb, ld, true }, { "vM", (size_t)L.vM, ld, true }, { "unused", (size_t)L.unused, ld, false },
@@ -53,26 +52,20 @@ int main()
                     { "entry_lut", (size_t)L.entry_lut, 288, false },
                     { "cross", (size_t)L.cross, round4((size_t)P), false },
                     { "x", (size_t)L.x, round4(6 * (size_t)N), false },
-                    { "region_R", (size_t)L.region_R, chain ? btba::chain_region_floats(N) : 0, chain },      // chained: the packed matrix, 16-byte stores of the reduced sums
                 };
                 size_t end = 0;
                 for (const Region &r : regions) {
                     if (r.size == 0) continue;                                            // (not part of this variant)
-                    const bool is_R = &r == &regions[sizeof(regions) / sizeof(regions[0]) - 1];
-                    if (r.off < end || r.off - end > (is_R ? 3u : 0u)) fail(r.name, N, Pd, a_in_global, chain);      // overlaps the region before it, or leaves a gap
-                    if (r.read16 && r.off % 4 != 0) fail(r.name, N, Pd, a_in_global, chain);      // not 16-byte aligned
+                    if (r.off != end) fail(r.name, N, Pd, a_in_global);      // overlaps the region before it, or leaves a gap
+                    if (r.read16 && r.off % 4 != 0) fail(r.name, N, Pd, a_in_global);      // not 16-byte aligned
                     end = r.off + r.size;
                 }
-                if (end > L.total) fail("end beyond total", N, Pd, a_in_global, chain);
-                if (L.ld % 8 != 4) fail("ld is not an odd multiple of 4", N, Pd, a_in_global, chain);
-                // the plain kernel's staged pair sums start at `total`: directly behind x
-                if (!chain && L.total != (size_t)L.x + round4(6 * (size_t)N)) fail("pair sums do not follow x", N, Pd, a_in_global, chain);
+                if (end > L.total) fail("end beyond total", N, Pd, a_in_global);
+                if (L.ld % 8 != 4) fail("ld is not an odd multiple of 4", N, Pd, a_in_global);
+                // the staged pair sums start at `total`: directly behind x
+                if (L.total != (size_t)L.x + round4(6 * (size_t)N)) fail("pair sums do not follow x", N, Pd, a_in_global);
             }
     }
-    // the chained launch's budget: a sweep workgroup's share of the LDS holds the solve of 15 frames with every canonical pair listed once, not of 16
-    const auto chain_bytes = [](int N) { return sizeof(float) * SolveLayout(N, N * (N - 1) / 2, true, true).total; };
-    if (!(chain_bytes(15) <= btba::kChainLdsBytes)) fail("chained budget refuses 15 frames", 15, 105, true, true);
-    if (!(chain_bytes(16) > btba::kChainLdsBytes)) fail("chained budget admits 16 frames", 16, 120, true, true);
     std::printf("checked %ld layouts\n", cases);
     return failures ? 1 : 0;
 }

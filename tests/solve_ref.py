@@ -410,7 +410,7 @@ def mid_solve_lds_floats(N, Pd):
 
 
 def general_solve_lds_floats(N, Pd):
-    """SolveLayout(N, Pd, a_in_global = false, chain = false).total (btba_solve_layout.hpp)."""
+    """SolveLayout(N, Pd, a_in_global = false).total (btba_solve_layout.hpp)."""
     n, P = 6 * N, N * (N - 1) // 2
     ld = 4 * (((n + 3) // 4) | 1)
     return n * ld + 6 * ld + 16 + 16 * N + 2 * Pd + (N + 1) + 2 * Pd + P + 288 + _r4(P) + _r4(n)

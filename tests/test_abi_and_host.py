@@ -171,7 +171,7 @@ def test_python_constants_match_the_header():
     assert len(opts) == 16 and all(getattr(_lib, "OPT_" + name) == v for name, v in opts.items())
     assert enums["BTBA_REDUCE_DETERMINISTIC"] == _lib.REDUCE_DETERMINISTIC and enums["BTBA_REDUCE_ATOMIC"] == _lib.REDUCE_ATOMIC
     assert 128 not in flags.values()                    # the bit that was BTBA_FLAG_FUSE stays without a meaning
-    assert C.sizeof(_lib.Stats) == 104      # (chain_iterations took the struct's tail padding)
+    assert C.sizeof(_lib.Stats) == 104      # (chain_iterations, kept for the layout and always 0, took the struct's tail padding)
 
 
 def test_counter_file_matches_the_committed_pmc_summaries():

@@ -4,4 +4,6 @@ OptimizerGpu::optimizeFrames boundary (see DESIGN.md).  The compute path is libb
 from . import _lib  # noqa: F401
 from ._lib import ENTRYJ_DTYPE, BtbaError, default_params  # noqa: F401
 
-__all__ = ["ENTRYJ_DTYPE", "BtbaError", "default_params"]
+from .keyframes import DeviceKeyframeMemory, KeyframeSession  # noqa: F401
+
+__all__ = ["ENTRYJ_DTYPE", "BtbaError", "default_params", "DeviceKeyframeMemory", "KeyframeSession"]

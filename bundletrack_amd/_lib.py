@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "btba_linearize_batch_zn_aux", "btba_pose_covariances", "btba_objective_batch_zn_aux",
     "btba_fuse_params_default", "btba_fuse_layout", "btba_fuse_bounds", "btba_fuse_frames", "btba_voxel_downsample",
     "btba_register_params_default", "btba_register_index", "btba_register_frames", "btba_register_associate",
+    "btba_keyframes_create", "btba_keyframes_destroy", "btba_keyframes_reset", "btba_keyframes_check_add", "btba_keyframes_select",
+    "btba_keyframes_writeback", "btba_keyframes_export", "btba_rotation_distances",
 ]
 FUSE_FRAME, FUSE_POINTS, FUSE_OVERFLOW, FUSE_MAX_VOXELS = 0, 1, 1, 1 << 24
 REG_CONVERGED, REG_MAX_ITERS, REG_DEGENERATE, REG_TOO_FEW, REG_SKIPPED = 0, 1, 2, 3, 4
@@ -490,6 +492,15 @@ def lib() -> C.CDLL:
                                            C.c_int] + [C.c_void_p] * 6
         L.btba_register_associate.argtypes = [C.c_void_p, C.POINTER(RegisterParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_int] + [C.c_void_p] * 4
+        L.btba_keyframes_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.btba_keyframes_destroy.argtypes = [C.c_void_p]
+        L.btba_keyframes_destroy.restype = None
+        L.btba_keyframes_reset.argtypes = [C.c_void_p, C.c_int]
+        L.btba_keyframes_check_add.argtypes = [C.c_void_p, C.c_float, C.c_int] + [C.c_void_p] * 7
+        L.btba_keyframes_select.argtypes = [C.c_void_p] * 11
+        L.btba_keyframes_writeback.argtypes = [C.c_void_p] * 5
+        L.btba_keyframes_export.argtypes = [C.c_void_p] * 6
+        L.btba_rotation_distances.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

@@ -271,7 +271,7 @@ class Bundler:
     def __init__(self, optimizer, feature_manager, K, H, W, *, window_size=2, max_BA_frames=15, min_rot_deg=10.0,
                  min_feat_num=0, min_fm_edges_newframe=5, pose_dir=None, persistent_frame_cache=False,
                  mask_largest_component_hull=False, mask_dilate=5, mask_workspace=None, detector=None, detector_out_size=400,
-                 device_window=False, segmenter=None, mask_propagator=None):
+                 device_window=False, segmenter=None, mask_propagator=None, memory=None):
         self.opt, self.fm = optimizer, feature_manager
         if (segmenter is None) != (mask_propagator is None):
             raise ValueError("Bundler: segmenter and mask_propagator go together")
@@ -289,7 +289,9 @@ class Bundler:
         self.K, self.H, self.W = np.asarray(K, np.float32), int(H), int(W)
         self.window_size = int(window_size)                        # bundle.window_size (config_ycbineoat.yml:26 ships 2)
         self.min_fm_edges_newframe = int(min_fm_edges_newframe)    # bundle.min_fm_edges_newframe
-        self.memory = KeyframeMemory(min_rot_deg=min_rot_deg, min_feat_num=min_feat_num, max_BA_frames=max_BA_frames)
+        # memory: anything with KeyframeMemory's interface (keyframes, check_and_add_keyframe, select_keyframes_for_ba), e.g. keyframes.KeyframeSession,
+        # built by the caller with its own gates; None (default): the host memory, as before
+        self.memory = memory if memory is not None else KeyframeMemory(min_rot_deg=min_rot_deg, min_feat_num=min_feat_num, max_BA_frames=max_BA_frames)
         self.frames: list = []                                     # _frames (deque)
         self.local_frames: list = []
         self.newframe = None

@@ -385,6 +385,65 @@ void voxelDownsample(btba_workspace *ws, const btba_fuse_params &params, const s
     if (rc != BTBA_OK) throw Error(rc, "btba_voxel_downsample");
 }
 
+DeviceKeyframeMemory::DeviceKeyframeMemory(btba_workspace *ws, int n_sessions, int capacity, int max_BA_frames, float min_rot_deg1, int min_feat_num1)
+    : min_rot_deg(min_rot_deg1), min_feat_num(min_feat_num1), n_sessions_(n_sessions), capacity_(capacity), max_BA_(max_BA_frames)
+{
+    const int rc = btba_keyframes_create(ws, n_sessions, capacity, max_BA_frames, &kf_);
+    if (rc != BTBA_OK) throw Error(rc, "btba_keyframes_create");
+}
+
+DeviceKeyframeMemory::~DeviceKeyframeMemory() { btba_keyframes_destroy(kf_); }
+
+DeviceKeyframeMemory::DeviceKeyframeMemory(DeviceKeyframeMemory &&o) noexcept
+    : min_rot_deg(o.min_rot_deg), min_feat_num(o.min_feat_num), kf_(o.kf_), n_sessions_(o.n_sessions_), capacity_(o.capacity_), max_BA_(o.max_BA_)
+{
+    o.kf_ = nullptr;
+}
+
+void DeviceKeyframeMemory::reset(int session)
+{
+    const int rc = btba_keyframes_reset(kf_, session);
+    if (rc != BTBA_OK) throw Error(rc, "btba_keyframes_reset");
+}
+
+void DeviceKeyframeMemory::checkAndAddKeyframes(const float *pose_dev, const int32_t *frame_id_dev, const uint64_t *frame_key_dev, const int32_t *status_other_dev,
+                                                const int32_t *n_keypts_dev, int32_t *added_out_dev, const int32_t *active_dev)
+{
+    const int rc = btba_keyframes_check_add(kf_, min_rot_deg, min_feat_num, active_dev, pose_dev, frame_id_dev, frame_key_dev, status_other_dev, n_keypts_dev,
+                                            added_out_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_keyframes_check_add");
+}
+
+void DeviceKeyframeMemory::selectKeyFramesForBA(const float *newpose_dev, const int32_t *new_frame_id_dev, const uint64_t *new_frame_key_dev,
+                                                const KeyframeWindows &out, const int32_t *active_dev)
+{
+    const int rc = btba_keyframes_select(kf_, active_dev, newpose_dev, new_frame_id_dev, new_frame_key_dev, out.n_window, out.slot, out.frame_id, out.frame_key,
+                                         out.pose, out.newframe_index);
+    if (rc != BTBA_OK) throw Error(rc, "btba_keyframes_select");
+}
+
+void DeviceKeyframeMemory::writeback(const int32_t *n_window_dev, const int32_t *window_slot_dev, const float *pose_dev, const int32_t *active_dev)
+{
+    const int rc = btba_keyframes_writeback(kf_, active_dev, n_window_dev, window_slot_dev, pose_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_keyframes_writeback");
+}
+
+KeyframePools DeviceKeyframeMemory::exportPools()
+{
+    KeyframePools p;
+    const size_t S = (size_t)n_sessions_, SC = S * (size_t)capacity_;
+    p.count.resize(S); p.overflow.resize(S); p.frame_id.resize(SC); p.frame_key.resize(SC); p.poses.resize(16 * SC);
+    const int rc = btba_keyframes_export(kf_, p.count.data(), p.overflow.data(), p.frame_id.data(), p.frame_key.data(), p.poses.data());
+    if (rc != BTBA_OK) throw Error(rc, "btba_keyframes_export");
+    return p;
+}
+
+void rotationDistances(btba_workspace *ws, int n, const float *A_dev, const float *B_dev, float *dist_out_dev)
+{
+    const int rc = btba_rotation_distances(ws, n, A_dev, B_dev, dist_out_dev);
+    if (rc != BTBA_OK) throw Error(rc, "btba_rotation_distances");
+}
+
 void registerIndex(btba_workspace *ws, int n_instances, const std::vector<int32_t> &box, const ObjectCloudBuffers &cloud, int32_t *cell_index_dev)
 {
     if (box.size() != 6 * (size_t)std::max(n_instances, 0)) throw Error(BTBA_EINVAL, "registerIndex: box");

@@ -288,6 +288,48 @@ void registerFrames(btba_workspace *ws, const btba_register_params &params, int 
                     const Matrix3f &K, const std::vector<int32_t> &box, const ObjectCloudBuffers &cloud, const int32_t *cell_index_dev, float *pose_out_dev,
                     btba_register_result *result_dev, btba_register_iter *trace_dev = nullptr);
 
+// The device keyframe memory (include/btba.h, "device keyframe memory"): checkAndAddKeyframe and selectKeyFramesForBA for n_sessions tracking
+// sessions at once, on device memory.  Owns the btba_keyframes handle, whose buffers free themselves; move-only.  Every per-session argument
+// is a device array [n_sessions], `active` (int32, nonzero = take part) may be null: all sessions.  All calls but exportPools are asynchronous
+// on the workspace stream.  rotationDistances is the memory's distance for n pose pairs (row-major 4 x 4 floats on the device).
+struct KeyframeWindows {                 // device outputs of select, rows ordered by frame id; the caller's memory
+    int32_t *n_window = nullptr;         // [S]
+    int32_t *slot = nullptr;             // [S][max_BA]: the pool slot, -1 for the new frame
+    int32_t *frame_id = nullptr;         // [S][max_BA]
+    uint64_t *frame_key = nullptr;       // [S][max_BA]
+    float *pose = nullptr;               // [S][max_BA][16]
+    int32_t *newframe_index = nullptr;   // [S]
+};
+struct KeyframePools {                   // host copy of the pools
+    std::vector<int32_t> count, overflow, frame_id;
+    std::vector<uint64_t> frame_key;
+    std::vector<float> poses;
+};
+class DeviceKeyframeMemory {
+public:
+    DeviceKeyframeMemory(btba_workspace *ws, int n_sessions, int capacity, int max_BA_frames, float min_rot_deg = 10.0f, int min_feat_num = 0);
+    ~DeviceKeyframeMemory();
+    DeviceKeyframeMemory(const DeviceKeyframeMemory &) = delete;
+    DeviceKeyframeMemory &operator=(const DeviceKeyframeMemory &) = delete;
+    DeviceKeyframeMemory(DeviceKeyframeMemory &&o) noexcept;
+    void reset(int session = -1);
+    void checkAndAddKeyframes(const float *pose_dev, const int32_t *frame_id_dev, const uint64_t *frame_key_dev, const int32_t *status_other_dev,
+                              const int32_t *n_keypts_dev, int32_t *added_out_dev, const int32_t *active_dev = nullptr);
+    void selectKeyFramesForBA(const float *newpose_dev, const int32_t *new_frame_id_dev, const uint64_t *new_frame_key_dev, const KeyframeWindows &out,
+                              const int32_t *active_dev = nullptr);
+    void writeback(const int32_t *n_window_dev, const int32_t *window_slot_dev, const float *pose_dev, const int32_t *active_dev = nullptr);
+    KeyframePools exportPools();
+    int n_sessions() const { return n_sessions_; }
+    int capacity() const { return capacity_; }
+    int max_BA_frames() const { return max_BA_; }
+    float min_rot_deg;
+    int min_feat_num;
+private:
+    btba_keyframes *kf_ = nullptr;
+    int n_sessions_ = 0, capacity_ = 0, max_BA_ = 0;
+};
+void rotationDistances(btba_workspace *ws, int n, const float *A_dev, const float *B_dev, float *dist_out_dev);
+
 // VOCap (eval_ycbineoat.py:54-81) in closed form, the same arithmetic as bundletrack_amd/evaluation.py::vocap_auc: the area under
 // the accuracy-vs-threshold curve on [0, max_threshold] over max_threshold (0 without errors below the threshold).
 double vocapAuc(const std::vector<double> &errors, double max_threshold = 0.1);

@@ -1617,6 +1617,55 @@ BTBA_API int btba_register_associate(btba_workspace *ws, const btba_register_par
                                      const int32_t *box, int capacity, const float *xyz_dev, const float *normal_dev,
                                      const int32_t *cell_index_dev, int32_t *const *match_out /* host [n_items] of device int32 [H*W] or [n] */);
 
+/* ---- device keyframe memory ---------------------------------------------------------------------------------------------------------
+ * The "memory" of the memory-augmented pose graph for many tracking sessions at once: Bundler::checkAndAddKeyframe and
+ * Bundler::selectKeyFramesForBA (Bundler.cpp:185-274) with Utils::rotationGeodesicDistance (Utils.cpp:42-47), on device memory.  Every
+ * call is asynchronous on the workspace stream (export alone synchronises), none uses atomics, and a session's bytes depend on that
+ * session alone: the same session gives the same bytes at any batch position and from run to run.
+ *
+ * The distance is acos(clamp((tr(R1 R2^T) - 1) / 2)): the trace and the clamp in the reference's own float arithmetic, the arc cosine by
+ * the memory's own function -- fp64 from IEEE-exact operations in a fixed order, rounded once to float -- so that the host compiler, numpy
+ * and the device give the same bits (bundletrack_amd/csrc/btba_keyframes_point.hpp; the C library's acosf differs from it by at most one
+ * float ulp).  btba_rotation_distances evaluates it for n pose pairs (row-major 4 x 4 floats, only the rotation blocks are read).
+ *
+ * btba_keyframes_create: n_sessions >= 1 pools of `capacity` >= 1 keyframes, n_sessions * capacity <= 2^24, max_BA_frames 2 .. 85; the
+ * select kernel's table (capacity * max_BA_frames floats and a little more) must fit 160 KB of LDS -- about 1024 keyframes at
+ * max_BA_frames <= 32.  Anything else is BTBA_EINVAL; nothing is ever truncated.  _destroy does not touch the workspace.  _reset empties one
+ * session's pool (or all: -1) and its overflow counter.
+ *
+ * Per-session arguments are device arrays [n_sessions]; active_dev (int32, nonzero = take part) may be NULL: all sessions.  An inactive
+ * session's state and outputs keep their bytes.
+ *   _check_add : one frame per session.  frame_id 0 always joins; any other frame needs status_other != 0, n_keypts >= min_feat_num and
+ *                (float)((double)(distance * 180) / pi) >= min_rot_deg against EVERY pool member.  added_out: 1 joined (the next slot), 0 not,
+ *                -1 would have joined a full pool -- overflow[s] is incremented and nothing is written.  frame_key_dev may be NULL (keys 0).
+ *   _select    : the window for a new frame that is not in the pool.  count + 1 <= max_BA_frames: every keyframe and the new frame.
+ *                Otherwise the new frame, slot 0, then in every round the slot with the SMALLEST cum_dist: the float sum of its distances
+ *                to the chosen set, summed over the chosen slots ascending and the new frame last; strict `<`, the lowest slot on ties.
+ *                Rows are ordered by frame id (on equal ids a pool slot before the new frame, lower slots first): window_slot_out
+ *                [S][max_BA] (-1: the new frame), window_frame_id_out, window_frame_key_out, window_pose_out [S][max_BA][16], n_window_out
+ *                [S] rows, newframe_index_out [S] the new frame's row.  Rows at and past n_window keep their bytes.
+ *   _writeback : pose_dev [S][max_BA][16] rows 0 .. n_window - 1 go to the pool slots window_slot names (Bundler.cpp:353-357); rows of the
+ *                new frame (-1) and slots outside the pool are skipped.
+ *   _export    : a synchronising host copy, for tests and host adapters: count_out, overflow_out [S], frame_id_out, frame_key_out [S][capacity],
+ *                pose_out [S][capacity][16]; any may be NULL.  Slots at and past count hold stale or zero bytes. */
+typedef struct btba_keyframes btba_keyframes;
+BTBA_API int btba_keyframes_create(btba_workspace *ws, int n_sessions, int capacity, int max_BA_frames, btba_keyframes **out);
+BTBA_API void btba_keyframes_destroy(btba_keyframes *kf);
+BTBA_API int btba_keyframes_reset(btba_keyframes *kf, int session /* -1: all */);
+BTBA_API int btba_keyframes_check_add(btba_keyframes *kf, float min_rot_deg, int min_feat_num, const int32_t *active_dev,
+                                      const float *pose_dev /* [S][16] */, const int32_t *frame_id_dev, const uint64_t *frame_key_dev,
+                                      const int32_t *status_other_dev, const int32_t *n_keypts_dev, int32_t *added_out_dev);
+BTBA_API int btba_keyframes_select(btba_keyframes *kf, const int32_t *active_dev, const float *newpose_dev /* [S][16] */,
+                                   const int32_t *new_frame_id_dev, const uint64_t *new_frame_key_dev, int32_t *n_window_out,
+                                   int32_t *window_slot_out, int32_t *window_frame_id_out, uint64_t *window_frame_key_out,
+                                   float *window_pose_out, int32_t *newframe_index_out);
+BTBA_API int btba_keyframes_writeback(btba_keyframes *kf, const int32_t *active_dev, const int32_t *n_window_dev,
+                                      const int32_t *window_slot_dev, const float *pose_dev /* [S][max_BA][16] */);
+BTBA_API int btba_keyframes_export(btba_keyframes *kf, int32_t *count_out, int32_t *overflow_out, int32_t *frame_id_out,
+                                   uint64_t *frame_key_out, float *pose_out);
+BTBA_API int btba_rotation_distances(btba_workspace *ws, int n, const float *A_dev, const float *B_dev /* [n][16] each */,
+                                     float *dist_out_dev /* [n] */);
+
 #ifdef __cplusplus
 }
 #endif

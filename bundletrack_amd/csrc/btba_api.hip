@@ -1347,7 +1347,7 @@ static int pool_resolve(btba_workspace *ws, int N, int H, int W, int Hd, int Wd,
     const bool same_geometry = ws->pool_H == H && ws->pool_W == W && ws->pool_npix == npix && ws->pool_downscale == downscale &&
                                std::memcmp(ws->pool_K, K, sizeof ws->pool_K) == 0;
     const size_t want_slots = std::max<size_t>(32, 2 * (size_t)N);
-    if (!same_geometry || ws->pool_slots.size() < (size_t)N) {
+    if (!same_geometry || ws->pool_slots.size() < want_slots) {      // (a pool that has to grow is re-allocated: every frame is cached again)
         const size_t cap = std::max(want_slots, ws->pool_slots.size());
         if ((rc = ws->pool_zn.ensure(sizeof(float) * 4 * cap * npix))) return rc;
         if ((rc = ws->pool_lists.ensure(sizeof(uint32_t) * cap * npix))) return rc;

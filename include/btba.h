@@ -273,7 +273,9 @@ BTBA_API int btba_optimize_frames(btba_workspace *ws, const btba_params *params,
  * of frame k that is stable across calls (the tracker's Frame::_id, Frame.h:61).  A frame whose (key, depth pointer,
  * normal pointer) was cached by an earlier call on the same workspace, with the same H, W, K and image_downscale, is
  * NOT cached again: its compact (z, n) pixels, its valid-pixel list and count stay in a pool slot of the workspace
- * (least-recently-used slots are recycled; pool = max(32, 2 n_frames) slots).  In a tracker only the new frame is
+ * (least-recently-used slots are recycled; pool = max(32, 2 n_frames) slots for the largest window so far: a window
+ * that needs more re-allocates the pool, and so does another H, W, K or image_downscale -- every frame is then cached
+ * again; which of several slots last used by the same call goes first is not specified).  In a tracker only the new frame is
  * built per call, the keyframes were cached when they were new -- the reference re-caches all K frames every call
  * (LossGPU.cu:74-78).  The caller must not modify a frame's device buffers while it is cached under the same key
  * (keyframes are immutable after Frame's constructor, Frame.cpp:107-149); btba_frame_cache_clear drops everything.
